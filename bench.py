@@ -7,7 +7,14 @@ Lookahead(RAdam) update, all in the HIP library.  Default workload = BASELINE.js
 get_model(dim=256, 2 squeeze + 2 conformer blocks, kernel_sizes=[11,5,3]) on B=256 clips per
 GPU, T=384 frames, F=224 features, bf16 storage / fp32 accumulate, inputs resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--config 2|4|5]
+  python bench.py --gpus N --steps K --warmup W [--config 2|4|5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes work of its own: the
+profiled step behind `roofline` / `kernels_ms`, the CPU baseline and, for N>1, the multi-GPU diagnostics.
+--dump-outputs DIR writes what the last timed step produced, from fixed seeded inputs (float32 .npy files, under 64 MB in all):
+loss.npy (the loss train_on_batch returns), weights.npy (the flat parameters it leaves, moving statistics included) and
+gradients.npy (the flat gradient of the trainable parameters).  An array longer than DUMP_MAX_ELEMS is written as the elements
+at a fixed seeded sample of indices, the same in every run of the same config (configs[3]'s 88 M parameters).
 
 N>1: run under `python -m torch.distributed.run --nproc-per-node N ...` (one rank per GPU over RCCL); when started WITHOUT
 that launcher, bench.py starts it itself as a child process and relays rank 0's JSON line and the exit code.  A mismatch
@@ -16,7 +23,7 @@ between --gpus and the ranks torch.distributed sees is an error, never a silent 
 --config 4: BASELINE configs[3] (d512, 6+6 blocks, 8 heads, T512) training throughput, B=512 per GPU.
 --config 5: BASELINE configs[4] (inference, B=1, T=384, fp16 storage, hipGraph replay): metric = latency per clip.
 
-Rank 0 prints ONE JSON line (contract in the task brief) with two extra objects:
+Rank 0 prints ONE JSON line; with --full it carries two extra objects:
   roofline      the dominant kernel family of the step, timed live with HIP events on the
                 launch stream (ishara_profile_*): algorithmic bytes per launch / avg duration
   cpu_baseline  the CPU oracle (oracle/ishara_oracle.py, a port — TensorFlow is not installed)
@@ -34,6 +41,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
 MFMA_PEAK_TFLOPS = 2500.0      # dense bf16 MFMA
+DUMP_MAX_ELEMS = 7_900_000     # per dumped array: weights + gradients stay under 64 MB of float32 together
 
 CONFIGS = {
     2: dict(kw=dict(dim=256, num_conv_squeeze_blocks=2, num_conv_conform_blocks=2, kernel_sizes=[11, 5, 3], num_conv_per_block=3,
@@ -140,6 +148,19 @@ def roofline_of(prof, cfg, frames_per_s):
     return fam, roof
 
 
+def dump_outputs(path: str, arrays) -> None:
+    """--dump-outputs: every device tensor of `arrays` as <path>/<name>.npy in float32, sampled as the module docstring says."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.float().cpu().numpy())
+
+
 def run_training(args):
     import numpy as np
     import torch
@@ -180,10 +201,12 @@ def run_training(args):
     dt_local = time.perf_counter() - t0
     dt = parallel.reduce_max(dt_local, device=dev)
     loss_v = float(loss.item())
+    if args.dump_outputs and rank == 0:            # before anything below runs another step; the replicas hold the same weights
+        dump_outputs(args.dump_outputs, {"loss": loss, "weights": model.params, "gradients": model.grads[:model.n_train]})
     # N > 1 diagnostics (outside the timed region, every rank takes part): each rank's own step time, the flat gradient all-reduce alone,
     # and the step without the exchange -> how much of the all-reduce the step exposes
     diag = None
-    if world > 1:
+    if args.full and world > 1:
         per_rank = torch.zeros(world, dtype=torch.float64, device=dev)
         per_rank[rank] = dt_local / args.steps * 1e3
         dist.all_reduce(per_rank)
@@ -202,24 +225,16 @@ def run_training(args):
                 "exposed_allreduce_ms": dt / args.steps * 1e3 - noar_ms, "diagnostic_steps": k}
 
     log(f"timed region done: {dt / args.steps * 1e3:.2f} ms/step")
-    # one more step with every launch bracketed by HIP events; EVERY rank runs it (the step contains the gradient
-    # all-reduce: a rank that skipped it would leave the others blocked in the collective), rank 0 reports
-    prof = model.profile_step(x, y)
-    parallel.barrier()
-    log("profile: " + json.dumps({k: round(v["ms"], 3) for k, v in (prof or {}).items()}))
+    if args.full:
+        # one more step with every launch bracketed by HIP events; EVERY rank runs it (the step contains the gradient
+        # all-reduce: a rank that skipped it would leave the others blocked in the collective), rank 0 reports
+        prof = model.profile_step(x, y)
+        parallel.barrier()
+        log("profile: " + json.dumps({k: round(v["ms"], 3) for k, v in (prof or {}).items()}))
     if rank != 0:
         return
     ms = dt / args.steps * 1e3
     value = world * B * T * args.steps / dt
-    fam, roof = roofline_of(prof, cfg, value / world)
-    # the profiled step brackets every launch with events and therefore runs the weight-gradient slab sums as launches of their own
-    # (`reduce_slabs(wgrad)`); in the timed steps they ride as extra workgroups of the next weight-gradient GEMM: kernels_ms is the
-    # non-deferred launch sequence and does not sum to ms_per_step
-    roof["profiled_path"] = "non-deferred slab sums (timed steps: deferred riders)"
-    if B == cfg["batch"] and args.dtype == "bf16":
-        roof["traffic"], roof["traffic_source"] = committed_traffic(fam, f"cfg{args.config}")
-    else:
-        roof["traffic_source"] = "not the profiled batch/dtype"
     out = {
         "metric": cfg["metric"], "value": value, "unit": "frames/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
@@ -229,11 +244,21 @@ def run_training(args):
                    "ranks_seen": dist.get_world_size() if world > 1 else 1, "backend": (dist.get_backend() if world > 1 else None),
                    "allreduce": ("bucketed+overlapped" if parallel.overlap_enabled() else "flat") if world > 1 else None,
                    "multi_gpu_diagnostics": diag},
-        "roofline": roof,
-        "kernels_ms": {k: round(v["ms"], 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
     }
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(cfg["kw"], 8 if args.config == 2 else 2, 12 if args.config == 2 else 3)
+    if args.full:
+        fam, roof = roofline_of(prof, cfg, value / world)
+        # the profiled step brackets every launch with events and therefore runs the weight-gradient slab sums as launches of their own
+        # (`reduce_slabs(wgrad)`); in the timed steps they ride as extra workgroups of the next weight-gradient GEMM: kernels_ms is the
+        # non-deferred launch sequence and does not sum to ms_per_step
+        roof["profiled_path"] = "non-deferred slab sums (timed steps: deferred riders)"
+        if B == cfg["batch"] and args.dtype == "bf16":
+            roof["traffic"], roof["traffic_source"] = committed_traffic(fam, f"cfg{args.config}")
+        else:
+            roof["traffic_source"] = "not the profiled batch/dtype"
+        out["roofline"] = roof
+        out["kernels_ms"] = {k: round(v["ms"], 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(cfg["kw"], 8 if args.config == 2 else 2, 12 if args.config == 2 else 3)
     print(json.dumps(out))
 
 
@@ -245,20 +270,27 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=[2, 4, 5], help="BASELINE.json config number (1-based): 2 = configs[1] (the metric's), 4 = d512 6+6 T512, 5 = B=1 inference latency")
     ap.add_argument("--batch", type=int, default=0, help="clips per GPU (weak scaling); 0 = the config's")
     ap.add_argument("--dtype", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also the profiled step (roofline, kernels_ms), the CPU baseline and the N>1 diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's loss, weights and gradients as DIR/<name>.npy")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_distributed(args))
     if args.config == 5:
         if args.gpus != 1:
             raise SystemExit("bench.py: --config 5 (B=1 inference latency) does not shard: replicas only, run it with --gpus 1")
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs covers the training configs (2, 4), not --config 5")
         from tools.bench_infer import run_inference_bench
         args.dtype = args.dtype or "f16"
+        args.no_cpu_baseline = args.no_cpu_baseline or not args.full
         print(json.dumps(run_inference_bench(args)))
         return
     args.dtype = args.dtype or "bf16"

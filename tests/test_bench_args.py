@@ -72,3 +72,24 @@ def test_traffic_is_quoted_only_for_the_measured_build(bench, tmp_path, monkeypa
     val, why = bench.committed_traffic("k", "cfg2")
     assert val == 5.0 and "not live" in why
     assert bench.committed_traffic("other", "cfg2")[0] is None
+
+
+def test_steps_must_be_positive(bench, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert "--steps" in str(e.value)
+
+
+def test_dumped_outputs_are_float32_and_large_arrays_a_fixed_sample(bench, tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    assert 2 * bench.DUMP_MAX_ELEMS * 4 + 1024 < 64e6          # weights + gradients (+ loss and headers) within the 64 MB budget
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    arrays = {"big": torch.arange(1000, dtype=torch.float32).reshape(10, 100), "small": torch.arange(50, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    big, small = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "small.npy")
+    assert big.dtype == small.dtype == np.float32
+    assert np.array_equal(small, np.arange(50)) and big.shape == (100,) and np.all(np.diff(big) > 0)
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))

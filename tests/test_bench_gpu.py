@@ -21,7 +21,7 @@ def _last_json(out: str):
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "32", "--no-cpu-baseline"], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "32", "--full", "--no-cpu-baseline"], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -30,15 +30,38 @@ def test_bench_single_gpu_line():
     assert rf["bound"] in ("hbm", "mfma") and 0 < rf["frac"] < 1 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9
 
 
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries no profiled-step or CPU figures; --dump-outputs writes the last timed step's loss, weights
+    and gradients in float32, and two runs with the same arguments write the same arrays (the training step is deterministic)."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "8", "--dump-outputs", str(tmp_path / run)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _last_json(r.stdout)
+        assert KEYS - {"roofline"} <= set(j) and not {"roofline", "kernels_ms", "cpu_baseline"} & set(j)
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["dtype"] == "bf16" and j["higher_is_better"] is True
+        d = {n: np.load(tmp_path / run / f"{n}.npy") for n in ("loss", "weights", "gradients")}
+        assert all(a.dtype == np.float32 for a in d.values())
+        assert d["loss"].shape == (1,) and float(d["loss"][0]) == np.float32(j["config"]["loss"])
+        assert d["weights"].shape == (j["config"]["params"],) and 0 < d["gradients"].size < d["weights"].size
+        assert np.isfinite(d["weights"]).all() and np.isfinite(d["gradients"]).all() and np.abs(d["gradients"]).max() > 0
+        dumps.append(d)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
 def test_bench_two_ranks_complete():
     env = dict(os.environ)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--no-cpu-baseline",
+           "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--full", "--no-cpu-baseline",
            "--backend", "gloo", "--share-gpu"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = _last_json(r.stdout)
     assert j["n_gpus"] == 2 and j["config"]["global_batch"] == 32 and j["value"] > 0 and "cpu_baseline" not in j
+    assert "roofline" in j and j["config"]["multi_gpu_diagnostics"]["diagnostic_steps"] >= 3
 
 
 def test_grad_buckets_cover_the_gradient_in_completion_order():

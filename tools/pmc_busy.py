@@ -26,7 +26,7 @@ for k, c in agg.items():
         if "SQ_ACTIVE_INST_VALU" in c: rec["valu_busy_frac"] = c["SQ_ACTIVE_INST_VALU"] / busy
         if "SQ_WAIT_INST_ANY" in c: rec["issue_stall_frac_of_wave_cycles"] = c["SQ_WAIT_INST_ANY"] / max(c.get("SQ_WAVE_CYCLES", 0.0), 1.0)
     out[k] = rec
-json.dump(dict(source_hash=source_hash(), note="rocprofv3 --pmc SQ pass over `python bench.py --steps 1 --warmup 0 --no-cpu-baseline`; raw counter sums per kernel; "
+json.dump(dict(source_hash=source_hash(), note="rocprofv3 --pmc SQ pass over `python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline`; raw counter sums per kernel; "
                "mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (4 SQ_BUSY_CU_CYCLES); valu_busy_frac = SQ_ACTIVE_INST_VALU / SQ_BUSY_CU_CYCLES", kernels=out), open(sys.argv[2], "w"), indent=1)
 top = sorted(out.items(), key=lambda kv: -kv[1]["counters"].get("SQ_WAVE_CYCLES", 0))[:14]
 for k, v in top:

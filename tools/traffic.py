@@ -38,7 +38,7 @@ def main():
         n = max(nf, nw, 1)
         out[k] = dict(launches=n, read_bytes_per_launch=2.0 * f * 1024 / n, write_bytes_per_launch=w * 1024 / n,
                       hbm_bytes_per_launch=(2.0 * f + w) * 1024 / n)
-    json.dump(dict(source_hash=source_hash(), note="rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over `python bench.py --steps 1 --warmup 0 --no-cpu-baseline`; "
+    json.dump(dict(source_hash=source_hash(), note="rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over `python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline`; "
                         "KiB units, FETCH_SIZE x2 (gfx950 wide-read correction)", kernels=out), open(sys.argv[3], "w"), indent=1)
     top = sorted(out.items(), key=lambda kv: -kv[1]["hbm_bytes_per_launch"] * kv[1]["launches"])[:8]
     for k, v in top:

@@ -144,6 +144,28 @@ int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, int32_t C, i
  * -> out [T,276].  One kernel, graph-capturable. */
 int ishara_preprocess(const float* raw, const int32_t* n_frames, int32_t max_frames, const float* mean, const float* stdv,
                       float* out, int32_t T, ishara_stream s);
+
+/* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
+ * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */
+typedef struct ishara_clip_aug {
+    int64_t offset;                 /* first frame of the clip in the store (frames of 124*3 f32) */
+    int32_t n;                      /* raw frame count */
+    int32_t L1;                     /* length after the time stretch (n when no stretch was drawn) */
+    int32_t shift;                  /* frame shift, -10..10; 0 when none was drawn */
+    int32_t L2;                     /* length after the shift: L1, or 0 for a drawn shift of 0 (the reference's [:0]) */
+    int32_t mirror;                 /* 1: swap the hands, negate x */
+    int32_t t0[3];                  /* finger-dropout windows [t0, t1) over the augmented frames */
+    int32_t t1[3];
+    int32_t fingers[3];             /* 21-bit finger mask per window (bit f zeroes landmarks 76+f and 97+f); 0 = no window */
+} ishara_clip_aug;
+/* feature layouts of the collated batch */
+enum { ISHARA_LAYOUT_FLAT = 0, ISHARA_LAYOUT_HANDS_LIPS_XY = 1 };
+/* ASLDataset.__getitem__ (data_loader.py:124-188) + collate for a batch, on device: raw [N_frames,124,3] f32 (16-byte aligned),
+ * clips [B] in device memory -> x [B,T,F] f32 (16-byte aligned), F = 372 (FLAT) or 224 (HANDS_LIPS_XY: landmarks 76-117 then
+ * 0-69, x and y).  Augment (stretch, shift, mirror, finger dropout), resample / pad to T, z-normalise per clip and coordinate
+ * over all T*124 values in fp64.  1 <= T <= 4096.  One kernel, graph-capturable, bit-identical from run to run. */
+int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
+                      float* x, ishara_stream s);
 /* tf.nn.ctc_loss alone: nll [B]; dlogits [B,T,C] may be NULL; ws = ishara_ctc_workspace_bytes. */
 int64_t ishara_ctc_workspace_bytes(int32_t B, int32_t T, int32_t L);
 int ishara_ctc_loss(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C,

@@ -32,6 +32,17 @@ class Config(C.Structure):
     ]
 
 
+class ClipAug(C.Structure):
+    """ishara_clip_aug: one clip's augmentation parameters for ishara_clip_batch (64 bytes, field order of the header)."""
+    _fields_ = [
+        ("offset", C.c_int64), ("n", C.c_int32), ("L1", C.c_int32), ("shift", C.c_int32), ("L2", C.c_int32),
+        ("mirror", C.c_int32), ("t0", C.c_int32 * 3), ("t1", C.c_int32 * 3), ("fingers", C.c_int32 * 3),
+    ]
+
+
+LAYOUT_FLAT, LAYOUT_HANDS_LIPS_XY = 0, 1
+
+
 # name -> (restype, argtypes); every symbol include/ishara_hip.h declares
 _P, _I32, _I64, _U32, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 SIGNATURES = {
@@ -63,6 +74,7 @@ SIGNATURES = {
     "ishara_profile_report": (C.c_int, [_P, C.c_char_p, _I32]),
     "ishara_greedy_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "ishara_preprocess": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _P]),
+    "ishara_clip_batch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "ishara_ctc_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_ctc_loss": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P]),
     "ishara_dropout_mask": (C.c_int, [_U32, _U32, _I32, _I32, _F, _P, _P]),

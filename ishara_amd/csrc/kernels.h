@@ -2,6 +2,7 @@
 // asynchronous on the given stream, allocates nothing and never synchronises.
 #pragma once
 #include "common.h"
+#include "../../include/ishara_hip.h"
 
 enum DType : int { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };       // DT_F16: forward (inference) kernels only
 static inline size_t dt_size(int dt) { return dt == DT_F32 ? 4 : 2; }
@@ -232,6 +233,9 @@ int launch_greedy_decode(const float* logits, int B, int T, int C, int blank, in
 
 // ---- inference preprocessing (preprocess.hip): raw [max_frames,276] (+ device clip length) -> [T,276]; mean/std [276] in OUTPUT order
 int launch_preprocess(const float* raw, const int* n_frames, int max_frames, const float* mean, const float* stdv, float* out, int T, hipStream_t s);
+// ---- training input batch (input_batch.hip): device store of raw clips + per-clip augmentation table -> x [B,T,F]
+#define CLIP_MAX_T 4096
+int launch_clip_batch(const float* raw, const ishara_clip_aug* clips, int B, int T, int layout, float* x, hipStream_t s);
 
 // ---- optimizer (optimizer.hip) -----------------------------------------------------------
 struct RAdamArgs { float lr, wd, beta1, beta2, eps, c1, c2, r_t; int rect; int sync; float slow_step; };

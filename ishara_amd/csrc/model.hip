@@ -1069,6 +1069,14 @@ extern "C" int ishara_preprocess(const float* raw, const int32_t* n_frames, int3
     if (max_frames <= 0 || max_frames > 8192) { ishara_set_error("ishara_preprocess: max_frames %d unsupported (1..8192)", max_frames); return -1; }
     return launch_preprocess(raw, n_frames, max_frames, mean, stdv, out, T, (hipStream_t)s);
 }
+extern "C" int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
+                                 float* x, ishara_stream s) {
+    if (B < 0 || T < 1 || T > CLIP_MAX_T) { ishara_set_error("ishara_clip_batch: B=%d T=%d unsupported (B >= 0, 1 <= T <= %d)", B, T, CLIP_MAX_T); return -1; }
+    if (layout != ISHARA_LAYOUT_FLAT && layout != ISHARA_LAYOUT_HANDS_LIPS_XY) { ishara_set_error("ishara_clip_batch: unknown layout %d", layout); return -1; }
+    if (B > 0 && (!clips || !x)) { ishara_set_error("ishara_clip_batch: null clips / x"); return -1; }
+    if (((uintptr_t)raw | (uintptr_t)x) % 16) { ishara_set_error("ishara_clip_batch: raw and x must be 16-byte aligned"); return -1; }
+    return launch_clip_batch(raw, clips, B, T, layout, x, (hipStream_t)s);
+}
 
 // ---- operator tests: dense
 static void op_shadow_layout(int dt, int K, int N, size_t& wt, int& ldt, size_t& wn, int& ldn, size_t& slab, size_t& total, int M) {

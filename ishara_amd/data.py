@@ -10,9 +10,11 @@ padded with 59 (conv-hybrid-model.ipynb c4:21-23)."""
 from __future__ import annotations
 
 import random
-from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
+from typing import Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
+
+from ._lib import ClipAug
 
 MAX_PHRASE_LENGTH = 64   # c1:33
 PAD_TOKEN_IDX = 59       # c1:5
@@ -132,3 +134,234 @@ class BatchAdapter:
                 yield torch.from_numpy(x).to(self.device), torch.from_numpy(y).to(self.device)
             else:
                 yield x, y
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Device-resident input pipeline: the raw clips live on the GPU (DeviceClipStore), the host only draws each clip's
+# augmentation parameters (draw_augmentation) into a 64-byte table row, and ONE kernel (ishara_clip_batch, csrc/input_batch.hip)
+# builds the normalised, collated batch.  apply_augmentations / pad_resize_normalize / collate / BatchAdapter above stay the
+# oracle of this path.
+
+class AugmentationDraw(NamedTuple):
+    """The parameters `apply_augmentations` draws for one clip.  `shift` is None when no shift was drawn; `L2 == 0` after a drawn
+    shift of 0 (the reference's `[:0]`).  `windows[i] = (t0, t1)` over the augmented frames, `fingers[i]` its 21-bit finger mask."""
+    n: int
+    L1: int
+    shift: Optional[int]
+    L2: int
+    mirror: int
+    windows: Tuple[Tuple[int, int], ...]
+    fingers: Tuple[int, ...]
+
+
+def draw_augmentation(n_frames: int, rng: random.Random) -> AugmentationDraw:
+    """Draw what `apply_augmentations` would apply to a clip of `n_frames` frames, making exactly its `rng` calls in its order and
+    touching no landmark data; raises ValueError where it raises (a dropout window on a clip shorter than 10 frames)."""
+    n = int(n_frames)
+    L1, shift, mirror, windows, fingers = n, None, 0, [], []
+    if rng.random() < 0.8:
+        L1 = int(n * rng.uniform(0.8, 1.2))
+    L2 = L1
+    if rng.random() < 0.5:
+        shift = rng.randint(-10, 10)
+        if shift == 0:
+            L2 = 0
+    if rng.random() < 0.5:
+        mirror = 1
+    if rng.random() < 0.5:
+        n_fingers, n_windows = rng.randint(2, 6), rng.randint(2, 3)
+        for _ in range(n_windows):
+            t0 = rng.randint(0, L2 - 10)
+            t1 = t0 + rng.randint(5, 10)
+            mask = 0
+            for _ in range(n_fingers):
+                mask |= 1 << rng.randint(0, 20)
+            windows.append((t0, t1))
+            fingers.append(mask)
+    return AugmentationDraw(n, L1, shift, L2, mirror, tuple(windows), tuple(fingers))
+
+
+def no_augmentation(n_frames: int) -> AugmentationDraw:
+    n = int(n_frames)
+    return AugmentationDraw(n, n, None, n, 0, (), ())
+
+
+def fill_clip_table(table: np.ndarray, offsets: np.ndarray, draws: Sequence[AugmentationDraw]) -> None:
+    """Write one `ishara_clip_aug` row per clip into `table` (a numpy view with the dtype of `_lib.ClipAug`)."""
+    b = len(draws)
+    table["offset"] = offsets
+    table["n"] = [d.n for d in draws]
+    table["L1"] = [d.L1 for d in draws]
+    table["shift"] = [d.shift or 0 for d in draws]
+    table["L2"] = [d.L2 for d in draws]
+    table["mirror"] = [d.mirror for d in draws]
+    win = np.zeros((b, 3, 3), np.int32)                 # t0, t1, fingers
+    for i, d in enumerate(draws):
+        for w, ((t0, t1), m) in enumerate(zip(d.windows, d.fingers)):
+            win[i, :, w] = (t0, t1, m)
+    table["t0"], table["t1"], table["fingers"] = win[:, 0], win[:, 1], win[:, 2]
+
+
+class ClipDataset:
+    """`ASLDataset.__getitem__` (data_loader.py:166-195) over in-memory raw clips: `(landmarks [n,124,3], phrase)` ->
+    `(pad_resize_normalize([apply_augmentations](landmarks), max_frames), phrase)`.  The host path, for `BatchAdapter`.
+    `rng` defaults to the `random` module (the reference's global draws)."""
+
+    def __init__(self, clips, max_frames: int = 384, augment: bool = False, rng=None):
+        self.clips, self.max_frames, self.augment = clips, max_frames, augment
+        self.rng = random if rng is None else rng
+
+    def __len__(self) -> int:
+        return len(self.clips)
+
+    def __getitem__(self, i):
+        lm, phrase = self.clips[i]
+        lm = np.asarray(lm, np.float32)
+        if self.augment:
+            lm = apply_augmentations(lm, self.rng)
+        return pad_resize_normalize(lm, self.max_frames), phrase
+
+
+CLIP_AUG_DTYPE = np.dtype(ClipAug)                 # one ishara_clip_aug row
+C_CLIP_AUG_BYTES = CLIP_AUG_DTYPE.itemsize        # 64
+_LAYOUT_IDS = {"flat": 0, "hands_lips_xy": 1}
+_LAYOUT_F = {"flat": 124 * 3, "hands_lips_xy": 224}
+
+
+def _require_gpu():
+    """The device pipeline has no CPU fallback: the library and a GPU are both required."""
+    from . import _lib
+    import torch
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.IsharaError("the device input pipeline needs a GPU (there is no CPU fallback)")
+    return lib
+
+
+class DeviceClipStore:
+    """The raw clips of a dataset, resident on the device for the whole run: `raw [N_frames,124,3]` f32 with int64 frame
+    `offsets` / `lengths` per clip (host copies, for the draws) and the padded phrases `[N,64]` int64 on the device.
+    `dataset_or_clips` is an indexable of `(landmarks [n,124,3], phrase)` — the reference's `_load_landmarks(idx)` and
+    `_encode_phrase`.  Clips are uploaded in chunks of at most `chunk_bytes` and joined once at the end (the device briefly holds
+    the store twice)."""
+
+    def __init__(self, dataset_or_clips, device="cuda:0", chunk_bytes: int = 256 << 20):
+        _require_gpu()
+        import torch
+        self.device = torch.device(device)
+        n_clips = len(dataset_or_clips)
+        offsets, lengths, phrases = np.zeros(n_clips, np.int64), np.zeros(n_clips, np.int64), []
+        chunks, pending, pending_bytes, total = [], [], 0, 0
+
+        def flush():
+            nonlocal pending, pending_bytes
+            if pending:
+                chunks.append(torch.from_numpy(np.concatenate(pending)).to(self.device))
+            pending, pending_bytes = [], 0
+
+        for i in range(n_clips):
+            lm, phrase = dataset_or_clips[i]
+            lm = np.ascontiguousarray(np.asarray(lm.numpy() if hasattr(lm, "numpy") else lm, np.float32))
+            if lm.ndim != 3 or lm.shape[1:] != (124, 3):
+                raise ValueError(f"clip {i}: landmarks must be [n,124,3], got {lm.shape}")
+            offsets[i], lengths[i] = total, lm.shape[0]
+            total += lm.shape[0]
+            phrases.append(pad_phrase(list(phrase)))
+            if lm.shape[0]:
+                pending.append(lm)
+                pending_bytes += lm.nbytes
+            if pending_bytes >= chunk_bytes:
+                flush()
+        flush()
+        if not chunks:                                   # no frames at all: a one-frame store keeps the pointer valid
+            chunks = [torch.zeros((1, 124, 3), dtype=torch.float32, device=self.device)]
+        self.raw = chunks[0] if len(chunks) == 1 else torch.cat(chunks)
+        del chunks
+        self.offsets, self.lengths = offsets, lengths
+        self.n_frames = total
+        self.phrases = torch.from_numpy(np.stack(phrases) if phrases else np.zeros((0, MAX_PHRASE_LENGTH), np.int64)).to(self.device)
+
+    def __len__(self) -> int:
+        return len(self.lengths)
+
+
+class DeviceBatchAdapter:
+    """Re-iterable stream of device batches `(x [B,T,F] f32, y [B,64] int64)` built by `ishara_clip_batch` from a
+    `DeviceClipStore`: the device twin of `BatchAdapter(ClipDataset(...))`.  It visits the clips in `BatchAdapter`'s order (the
+    same `np.random.default_rng(seed)` shuffle) and draws the augmentations per clip in batch order from `rng` (default
+    `random.Random(seed)`; pass the `random` module for the reference's global draws).  The per-clip table is written to pinned
+    memory, copied asynchronously and consumed by one kernel on the current stream; a pinned table is rewritten only after the
+    event of its previous copy has completed.  `shard=(rank, world)`: draw for the whole (global) batch, emit rank's slice."""
+
+    _SLOTS = 3
+
+    def __init__(self, store: DeviceClipStore, batch_size: int, T: int, layout: str = "hands_lips_xy", augment: bool = True,
+                 shuffle: bool = False, seed: int = 0, rng=None, drop_last: bool = False, shard: Optional[Tuple[int, int]] = None):
+        self._lib = _require_gpu()
+        if layout not in _LAYOUT_IDS:
+            raise ValueError(f"unknown layout {layout!r}")
+        if not 1 <= T <= 4096:
+            raise ValueError(f"T={T} unsupported (1..4096)")
+        self.store, self.batch_size, self.T, self.layout, self.augment = store, batch_size, T, layout, augment
+        self.shuffle, self.drop_last = shuffle, drop_last
+        self.rank, self.world = shard if shard is not None else (0, 1)
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f"shard {shard} out of range")
+        self.rng = random.Random(seed) if rng is None else rng
+        self._order_rng = np.random.default_rng(seed)
+        self._slots: List[tuple] = []
+        self._turn = 0
+
+    def __len__(self) -> int:
+        n = len(self.store)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        order = np.arange(len(self.store))
+        if self.shuffle:
+            self._order_rng.shuffle(order)
+        for i in range(0, len(order), self.batch_size):
+            idx = order[i:i + self.batch_size]
+            if self.drop_last and len(idx) < self.batch_size:
+                break
+            yield self.batch(idx)
+
+    def _slot(self):
+        """Next pinned table (+ its device copy) of the ring, once the copy of its previous use has completed."""
+        import torch
+        nbytes = self.batch_size * (C_CLIP_AUG_BYTES + 8)
+        if len(self._slots) < self._SLOTS:
+            host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            dev = torch.empty(nbytes, dtype=torch.uint8, device=self.store.device)
+            self._slots.append((host, dev, torch.cuda.Event()))
+        slot = self._slots[self._turn % len(self._slots)]
+        self._turn += 1
+        if not slot[2].query():
+            slot[2].synchronize()
+        return slot
+
+    def batch(self, idx) -> Tuple["torch.Tensor", "torch.Tensor"]:
+        """One device batch of the store's clips `idx` (draws for all of them, emits this rank's slice)."""
+        import ctypes
+        import torch
+        from . import _lib
+        idx = np.asarray(idx, np.int64)
+        lengths = self.store.lengths[idx]
+        draws = [draw_augmentation(n, self.rng) if self.augment else no_augmentation(n) for n in lengths]
+        lo, hi = len(idx) * self.rank // self.world, len(idx) * (self.rank + 1) // self.world
+        idx, draws = idx[lo:hi], draws[lo:hi]
+        b = len(idx)
+        host, dev, ev = self._slot()
+        hn = host.numpy()
+        tab = hn[:b * C_CLIP_AUG_BYTES].view(CLIP_AUG_DTYPE)
+        fill_clip_table(tab, self.store.offsets[idx], draws)
+        hn[b * C_CLIP_AUG_BYTES:b * (C_CLIP_AUG_BYTES + 8)].view(np.int64)[:] = idx
+        used = b * (C_CLIP_AUG_BYTES + 8)
+        dev[:used].copy_(host[:used], non_blocking=True)
+        ev.record()
+        x = torch.empty((b, self.T, _LAYOUT_F[self.layout]), dtype=torch.float32, device=self.store.device)
+        _lib.check(self._lib.ishara_clip_batch(_lib.ptr(self.store.raw), _lib.ptr(dev), b, self.T, _LAYOUT_IDS[self.layout],
+                                               _lib.ptr(x), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   "ishara_clip_batch")
+        y = self.store.phrases.index_select(0, dev[b * C_CLIP_AUG_BYTES:used].view(torch.int64))
+        return x, y

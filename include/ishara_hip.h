@@ -144,6 +144,17 @@ int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, int32_t C, i
  * -> out [T,276].  One kernel, graph-capturable. */
 int ishara_preprocess(const float* raw, const int32_t* n_frames, int32_t max_frames, const float* mean, const float* stdv,
                       float* out, int32_t T, ishara_stream s);
+/* The same for B ragged clips at once (the test-set loop of c18:5-7 runs one clip per call): raw [n_total,276] holds the clips back
+ * to back, clip b is rows [offsets[b], offsets[b+1]) of a device-resident int64 table [B+1] (an empty range is a valid, empty clip; rows
+ * past max_frames are ignored, as ishara_preprocess ignores them) -> out [B,T,276], each clip bit-identical to ishara_preprocess.  raw
+ * and out 16-byte aligned; 1 <= max_frames <= 8192, 1 <= T <= 4096.  One kernel, graph-capturable. */
+int ishara_preprocess_batch(const float* raw, int64_t n_total, const int64_t* offsets, int32_t B, int32_t max_frames,
+                            const float* mean, const float* stdv, float* out, int32_t T, ishara_stream s);
+/* Levenshtein.distance of c18:1-9 on the device: out_idx [B,T] / out_len [B] of ishara_greedy_decode, a decode shorter than 3
+ * replaced by the wrapper's constant phrase (c13:22-23); targets [B,L] int32 padded with 59 (PAD_TOKEN_IDX, c1:5), 1 <= L <= 64
+ * (MAX_PHRASE_LENGTH, c1:28) -> dist [B], tlen [B] (symbols before the first pad).  Integer-only, deterministic. */
+int ishara_edit_distance(const int32_t* out_idx, const int32_t* out_len, int32_t B, int32_t T, const int32_t* targets, int32_t L,
+                         int32_t* dist, int32_t* tlen, ishara_stream s);
 
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */

@@ -233,6 +233,12 @@ int launch_greedy_decode(const float* logits, int B, int T, int C, int blank, in
 
 // ---- inference preprocessing (preprocess.hip): raw [max_frames,276] (+ device clip length) -> [T,276]; mean/std [276] in OUTPUT order
 int launch_preprocess(const float* raw, const int* n_frames, int max_frames, const float* mean, const float* stdv, float* out, int T, hipStream_t s);
+// batched ragged form: raw [N_total,276] packed clips, offsets [B+1] int64 (device) -> out [B,T,276]; both buffers 16-byte aligned
+int launch_preprocess_batch(const float* raw, int64_t n_total, const int64_t* offsets, int B, int max_frames, const float* mean, const float* stdv,
+                            float* out, int T, hipStream_t s);
+// ---- test-set scoring (score.hip): edit distance of greedy decodes (len < 3 -> fallback phrase) to pad-59 targets [B,L], L <= 64
+#define SCORE_MAX_L 64
+int launch_edit_distance(const int* out_idx, const int* out_len, int B, int T, const int* targets, int L, int* dist, int* tlen, hipStream_t s);
 // ---- training input batch (input_batch.hip): device store of raw clips + per-clip augmentation table -> x [B,T,F]
 #define CLIP_MAX_T 4096
 int launch_clip_batch(const float* raw, const ishara_clip_aug* clips, int B, int T, int layout, float* x, hipStream_t s);

@@ -1069,6 +1069,22 @@ extern "C" int ishara_preprocess(const float* raw, const int32_t* n_frames, int3
     if (max_frames <= 0 || max_frames > 8192) { ishara_set_error("ishara_preprocess: max_frames %d unsupported (1..8192)", max_frames); return -1; }
     return launch_preprocess(raw, n_frames, max_frames, mean, stdv, out, T, (hipStream_t)s);
 }
+extern "C" int ishara_preprocess_batch(const float* raw, int64_t n_total, const int64_t* offsets, int32_t B, int32_t max_frames,
+                                       const float* mean, const float* stdv, float* out, int32_t T, ishara_stream s) {
+    if (max_frames <= 0 || max_frames > 8192) { ishara_set_error("ishara_preprocess_batch: max_frames %d unsupported (1..8192)", max_frames); return -1; }
+    if (B < 0 || B > 65535 || T < 1 || T > 4096) { ishara_set_error("ishara_preprocess_batch: B=%d T=%d unsupported (0 <= B <= 65535, 1 <= T <= 4096)", B, T); return -1; }
+    if (n_total < 0) { ishara_set_error("ishara_preprocess_batch: n_total %lld < 0", (long long)n_total); return -1; }
+    if (B > 0 && (!offsets || !mean || !stdv || !out || (n_total > 0 && !raw))) { ishara_set_error("ishara_preprocess_batch: null raw / offsets / mean / stdv / out"); return -1; }
+    if (((uintptr_t)raw | (uintptr_t)out) % 16) { ishara_set_error("ishara_preprocess_batch: raw and out must be 16-byte aligned"); return -1; }
+    return launch_preprocess_batch(raw, n_total, offsets, B, max_frames, mean, stdv, out, T, (hipStream_t)s);
+}
+extern "C" int ishara_edit_distance(const int32_t* out_idx, const int32_t* out_len, int32_t B, int32_t T, const int32_t* targets, int32_t L,
+                                    int32_t* dist, int32_t* tlen, ishara_stream s) {
+    if (L < 1 || L > SCORE_MAX_L) { ishara_set_error("ishara_edit_distance: target length L=%d unsupported (1..%d: one wavefront lane per target symbol)", L, SCORE_MAX_L); return -1; }
+    if (B < 0 || T < 1 || T > 4096) { ishara_set_error("ishara_edit_distance: B=%d T=%d unsupported (B >= 0, 1 <= T <= 4096)", B, T); return -1; }
+    if (B > 0 && (!out_idx || !out_len || !targets || !dist || !tlen)) { ishara_set_error("ishara_edit_distance: null argument"); return -1; }
+    return launch_edit_distance(out_idx, out_len, B, T, targets, L, dist, tlen, (hipStream_t)s);
+}
 extern "C" int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
                                  float* x, ishara_stream s) {
     if (B < 0 || T < 1 || T > CLIP_MAX_T) { ishara_set_error("ishara_clip_batch: B=%d T=%d unsupported (B >= 0, 1 <= T <= %d)", B, T, CLIP_MAX_T); return -1; }

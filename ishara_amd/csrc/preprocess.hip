@@ -12,6 +12,30 @@
 __device__ __constant__ int pp_out0[5] = {0, 40, 61, 82, 87};
 __device__ __constant__ int pp_src0[5] = {52, 0, 21, 47, 42};
 
+// Output element (t, c) of one clip: n raw frames, sh[0..m) the kept frames' indices in order, ratio = m / Tn (1 when m == 0).
+// Shared by preprocess_kernel and preprocess_batch_kernel, so that both compute every element with the same operations.
+__device__ __forceinline__ float pp_value(const float* __restrict__ raw, const int* sh, int n, int m, int Tn, float ratio, int t, int c,
+                                          const float* __restrict__ mean, const float* __restrict__ stdv) {
+    const int lm = c / 3, axis = c - lm * 3;
+    int part = 0;
+#pragma unroll
+    for (int p = 1; p < 5; ++p) if (lm >= pp_out0[p]) part = p;
+    const int col = axis * PP_LM + pp_src0[part] + (lm - pp_out0[part]);
+    float v;
+    if (n == 0) v = t == 0 ? 0.f : __builtin_nanf("");     // empty clip -> ONE all-zero frame, NaN padded (c13:11, c3:3-4)
+    else if (m < Tn) v = t < m ? raw[(size_t)sh[t] * PP_COLS + col] : __builtin_nanf("");       // NaN pad (c3:3-4)
+    else {                                                 // tf.image.resize bilinear, half-pixel centres (c3:6)
+        float src = ((float)t + 0.5f) * ratio - 0.5f;
+        src = src < 0.f ? 0.f : src;
+        int i0 = (int)floorf(src); i0 = i0 > m - 1 ? m - 1 : i0;
+        const int i1 = i0 + 1 > m - 1 ? m - 1 : i0 + 1;
+        const float w = src - (float)i0;
+        v = raw[(size_t)sh[i0] * PP_COLS + col] * (1.f - w) + raw[(size_t)sh[i1] * PP_COLS + col] * w;
+    }
+    v = (v - mean[c]) / stdv[c];
+    return (v != v) ? 0.f : v;                             // NaN -> 0 (c3:114)
+}
+
 // grid = PP_BLOCKS workgroups: every workgroup builds the (cheap) frame list again and writes its slice of the output — as ONE workgroup
 // with a serial compaction by thread 0 the kernel took 83 us of a 1.3 ms clip (configs[4]).
 #define PP_BLOCKS 24
@@ -51,28 +75,90 @@ __global__ __launch_bounds__(1024) void preprocess_kernel(const float* __restric
     const float ratio = m > 0 ? (float)m / (float)Tn : 1.f;
     for (int i = blockIdx.x * blockDim.x + tid; i < Tn * PP_COLS; i += gridDim.x * blockDim.x) {
         const int t = i / PP_COLS, c = i - t * PP_COLS;
-        const int lm = c / 3, axis = c - lm * 3;
-        int part = 0;
-#pragma unroll
-        for (int p = 1; p < 5; ++p) if (lm >= pp_out0[p]) part = p;
-        const int col = axis * PP_LM + pp_src0[part] + (lm - pp_out0[part]);
-        float v;
-        if (n == 0) v = t == 0 ? 0.f : __builtin_nanf("");     // empty clip -> ONE all-zero frame, NaN padded (c13:11, c3:3-4)
-        else if (m < Tn) v = t < m ? raw[(size_t)sh[t] * PP_COLS + col] : __builtin_nanf("");       // NaN pad (c3:3-4)
-        else {                                                 // tf.image.resize bilinear, half-pixel centres (c3:6)
-            float src = ((float)t + 0.5f) * ratio - 0.5f;
-            src = src < 0.f ? 0.f : src;
-            int i0 = (int)floorf(src); i0 = i0 > m - 1 ? m - 1 : i0;
-            const int i1 = i0 + 1 > m - 1 ? m - 1 : i0 + 1;
-            const float w = src - (float)i0;
-            v = raw[(size_t)sh[i0] * PP_COLS + col] * (1.f - w) + raw[(size_t)sh[i1] * PP_COLS + col] * w;
-        }
-        v = (v - mean[c]) / stdv[c];
-        out[i] = (v != v) ? 0.f : v;                           // NaN -> 0 (c3:114)
+        out[i] = pp_value(raw, sh, n, m, Tn, ratio, t, c, mean, stdv);
     }
 }
 
 int launch_preprocess(const float* raw, const int* n_frames, int max_frames, const float* mean, const float* stdv, float* out, int T, hipStream_t s) {
     hipLaunchKernelGGL(preprocess_kernel, dim3(PP_BLOCKS), dim3(1024), (size_t)max_frames * sizeof(int), s, raw, n_frames, max_frames, mean, stdv, out, T);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---- batched ragged form: B clips packed back to back in raw [N_total,276] (16-byte aligned), clip b = rows [offsets[b], offsets[b+1])
+// of a device-resident int64 table (graph-capturable), out [B,T,276] (16-byte aligned).  Grid (k, B): the k workgroups of a clip each
+// rebuild its kept-frame list in LDS (only the odd frames are tested: even frames are always kept) and write every k-th float4 of its
+// T*276 outputs through pp_value, so every element is bit-identical to preprocess_kernel's for the same clip.
+#define PPB_THREADS 256
+
+// hand-present test of one frame (c3:89-93): the sum in preprocess_kernel's order (axis, then landmark), read as float4 / float2
+// (a frame row is 1104 bytes and an axis block starts 368 bytes into it: both multiples of 16)
+__device__ __forceinline__ bool pp_hand_present(const float* __restrict__ row) {
+    float sacc = 0.f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float4* p = reinterpret_cast<const float4*>(row + a * PP_LM);
+#pragma unroll
+        for (int q = 0; q < 10; ++q) {
+            const float4 v = p[q];
+            sacc += (v.x != v.x) ? 0.f : v.x; sacc += (v.y != v.y) ? 0.f : v.y;
+            sacc += (v.z != v.z) ? 0.f : v.z; sacc += (v.w != v.w) ? 0.f : v.w;
+        }
+        const float2 v = *reinterpret_cast<const float2*>(row + a * PP_LM + 40);
+        sacc += (v.x != v.x) ? 0.f : v.x; sacc += (v.y != v.y) ? 0.f : v.y;
+    }
+    return sacc != 0.f;
+}
+
+__global__ __launch_bounds__(PPB_THREADS) void preprocess_batch_kernel(const float* __restrict__ raw, int64_t n_total, const int64_t* __restrict__ offsets,
+                                                                       int max_frames, const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                       float* __restrict__ out, int Tn) {
+    extern __shared__ int sh[];            // compacted source index list [max_frames]
+    __shared__ int s_wcnt[PPB_THREADS / WAVE], s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, b = blockIdx.y;
+    // clip rows, clamped to the packed buffer: a bad table cannot make the kernel read outside raw
+    int64_t lo = offsets[b], hi = offsets[b + 1];
+    lo = lo < 0 ? 0 : (lo > n_total ? n_total : lo);
+    hi = hi < lo ? lo : (hi > n_total ? n_total : hi);
+    const int n = hi - lo > max_frames ? max_frames : (int)(hi - lo);
+    const float* clip = raw + (size_t)lo * PP_COLS;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int f0 = 0; f0 < n; f0 += PPB_THREADS) {
+        const int f = f0 + tid;
+        const int keep = f < n && ((f & 1) == 0 || pp_hand_present(clip + (size_t)f * PP_COLS)) ? 1 : 0;
+        const unsigned long long bal = __ballot(keep);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wcnt[wid] = __popcll(bal);
+        __syncthreads();
+        int off = s_base;
+        for (int w = 0; w < wid; ++w) off += s_wcnt[w];
+        if (keep) sh[off + before] = f;
+        __syncthreads();
+        if (tid == 0) { int t = 0; for (int w = 0; w < PPB_THREADS / WAVE; ++w) t += s_wcnt[w]; s_base += t; }
+        __syncthreads();
+    }
+    const int m = s_base;
+    const float ratio = m > 0 ? (float)m / (float)Tn : 1.f;
+    float* o = out + (size_t)b * Tn * PP_COLS;
+    const int nq = Tn * (PP_COLS / 4);
+    for (int q = blockIdx.x * PPB_THREADS + tid; q < nq; q += gridDim.x * PPB_THREADS) {
+        const int t = q / (PP_COLS / 4), c = (q - t * (PP_COLS / 4)) * 4;
+        float4 v;
+        v.x = pp_value(clip, sh, n, m, Tn, ratio, t, c + 0, mean, stdv);
+        v.y = pp_value(clip, sh, n, m, Tn, ratio, t, c + 1, mean, stdv);
+        v.z = pp_value(clip, sh, n, m, Tn, ratio, t, c + 2, mean, stdv);
+        v.w = pp_value(clip, sh, n, m, Tn, ratio, t, c + 3, mean, stdv);
+        *reinterpret_cast<float4*>(o + (size_t)t * PP_COLS + c) = v;
+    }
+}
+
+int launch_preprocess_batch(const float* raw, int64_t n_total, const int64_t* offsets, int B, int max_frames, const float* mean, const float* stdv,
+                            float* out, int T, hipStream_t s) {
+    if (B == 0) return 0;
+    // about 1024 workgroups in all (4 per CU) once B >= 64; at most 16 per clip (T = 384: 26 float4 stores per thread at k = 4)
+    int k = 1024 / B;
+    k = k < 1 ? 1 : (k > 16 ? 16 : k);
+    hipLaunchKernelGGL(preprocess_batch_kernel, dim3(k, B), dim3(PPB_THREADS), (size_t)max_frames * sizeof(int), s, raw, n_total, offsets, max_frames,
+                       mean, stdv, out, T);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

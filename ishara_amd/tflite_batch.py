@@ -1,0 +1,314 @@
+"""Batched counterpart of `TFLiteModel`: many ragged raw clips per call, and the test-set score of conv-hybrid-model.ipynb c18:1-15
+computed on the device.
+
+`TFLiteModel` runs the reference's `serving_default` signature one clip at a time (B = 1).  The reference's accuracy figure comes from a
+loop over the test set (c18) that calls it per clip, maps the one-hot output back to characters and averages
+(len(target) - Levenshtein(pred, target)) / len(target) on the host.  `BatchedTFLiteModel` runs `batch_size` clips per hipGraph replay:
+
+  packed raw clips [N, 276] + offsets [B+1] --ishara_preprocess_batch--> x [B, T, 276] --ishara_forward(training=0)--> logits
+  --ishara_greedy_decode--> indices, lengths [--ishara_edit_distance (len < 3 fallback, pad-59 targets)--> dist, tlen]
+
+Per batch the host packs the clips into one pinned staging buffer (offsets | targets | raw frames), copies it with one non-blocking
+H2D copy on a copy stream, replays the graph on the current stream and copies the results (indices | lengths | dist | tlen) back with one
+D2H copy.  Two staging slots: batch i+1 is packed and copied while batch i replays; the host waits once per batch.  A last partial batch
+fills its unused slots with empty clips (equal offsets), whose outputs are dropped.  Each clip's result equals `TFLiteModel(...)(clip)`:
+the preprocessing is bit-identical per clip, and an inference-mode forward pass has no cross-sample statistics.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .model import Model, _stream
+from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS
+
+PAD_TOKEN_IDX = 59           # c1:5: the targets' padding; never a decoded index (the blank is C - 1 = 59)
+MAX_SCORE_LABEL_LEN = 64     # one wavefront lane per target symbol (ishara_edit_distance)
+_ROW_BYTES = N_COLS * 4
+
+
+def _align(n: int, a: int) -> int:
+    return (n + a - 1) // a * a
+
+
+# ---------------------------------------------------------------------------------------------------- host helpers (no device)
+def check_clip(x, max_frames: int) -> np.ndarray:
+    """One raw clip as float32 [n, 276], n <= max_frames (the checks of TFLiteModel.predict_indices)."""
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] != N_COLS:
+        raise ValueError(f"inputs must be [n_frames, {N_COLS}], got {x.shape}")
+    if x.shape[0] > max_frames:
+        raise ValueError(f"clip of {x.shape[0]} frames exceeds max_frames={max_frames}")
+    return x
+
+
+def batch_offsets(lengths: Sequence[int], batch_size: int) -> np.ndarray:
+    """int64 [batch_size + 1] row offsets of clips packed back to back; slots past len(lengths) are empty clips (equal offsets)."""
+    if len(lengths) > batch_size:
+        raise ValueError(f"{len(lengths)} clips in a batch of {batch_size}")
+    off = np.zeros(batch_size + 1, dtype=np.int64)
+    off[1:len(lengths) + 1] = np.cumsum(np.asarray(lengths, dtype=np.int64))
+    off[len(lengths) + 1:] = off[len(lengths)]
+    return off
+
+
+def pack_clips(clips: Sequence[np.ndarray], raw: np.ndarray, offsets: np.ndarray) -> int:
+    """Copy checked clips back to back into raw [capacity, 276]; fill offsets [batch_size + 1] (padding slots empty).  Returns the rows used."""
+    off = batch_offsets([c.shape[0] for c in clips], offsets.shape[0] - 1)
+    rows = int(off[-1])
+    if rows > raw.shape[0]:
+        raise ValueError(f"{rows} frames exceed the staging capacity of {raw.shape[0]}")
+    for c, o in zip(clips, off[:-1]):
+        raw[o:o + c.shape[0]] = c
+    offsets[:] = off
+    return rows
+
+
+def check_packed(frames, offsets, max_frames: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Pre-packed input (frames [N, 276] float32, offsets [B + 1] int64, non-decreasing, inside [0, N], clips of at most max_frames)."""
+    frames = np.asarray(frames, dtype=np.float32)
+    offsets = np.asarray(offsets)
+    if frames.ndim != 2 or frames.shape[1] != N_COLS:
+        raise ValueError(f"packed frames must be [N, {N_COLS}], got {frames.shape}")
+    if offsets.ndim != 1 or offsets.shape[0] < 1 or not np.issubdtype(offsets.dtype, np.integer):
+        raise ValueError("offsets must be a 1-D integer array [B + 1]")
+    offsets = offsets.astype(np.int64)
+    n = np.diff(offsets)
+    if offsets[0] < 0 or offsets[-1] > frames.shape[0] or (n < 0).any():
+        raise ValueError(f"offsets must be non-decreasing inside [0, {frames.shape[0]}]")
+    if n.size and n.max() > max_frames:
+        raise ValueError(f"clip of {int(n.max())} frames exceeds max_frames={max_frames}")
+    return frames, offsets
+
+
+def encode_phrase(target, char_to_num: Optional[Dict[str, int]], max_len: int) -> np.ndarray:
+    """A target phrase as int32 [max_len] padded with 59: a string through char_to_num (c1:3-9), or an index sequence."""
+    if isinstance(target, str):
+        if char_to_num is None:
+            raise ValueError("string targets need char_to_num")
+        unknown = sorted({ch for ch in target if ch not in char_to_num})
+        if unknown:
+            raise ValueError(f"target {target!r}: characters {unknown} are not in char_to_num")
+        idx = np.array([char_to_num[ch] for ch in target], dtype=np.int64)
+    else:
+        idx = np.asarray(target)
+        if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+            raise ValueError("an index target must be a 1-D integer sequence")
+        idx = idx.astype(np.int64)
+    if idx.size == 0:
+        raise ValueError("empty target: the score divides by its length (c18:9)")
+    if idx.size > max_len:
+        raise ValueError(f"target of {idx.size} symbols exceeds max_label_len={max_len}")
+    if (idx < 0).any() or (idx >= PAD_TOKEN_IDX).any():
+        raise ValueError(f"target indices must lie in [0, {PAD_TOKEN_IDX})")
+    out = np.full(max_len, PAD_TOKEN_IDX, dtype=np.int32)
+    out[:idx.size] = idx
+    return out
+
+
+def apply_fallback(idx: np.ndarray) -> np.ndarray:
+    """The wrapper's rule (c13:22-23): a decode shorter than 3 symbols becomes the constant phrase."""
+    return FALLBACK_PHRASE if idx.shape[0] < 3 else idx
+
+
+def one_hot(idx: np.ndarray) -> np.ndarray:
+    """tf.one_hot(x, 59) (c13:24): index 59 -> zero row."""
+    out = np.zeros((idx.shape[0], 59), dtype=np.float32)
+    ok = idx < 59
+    out[np.arange(idx.shape[0])[ok], idx[ok]] = 1.0
+    return out
+
+
+def normalized_scores(dist: np.ndarray, tlen: np.ndarray) -> Tuple[float, np.ndarray]:
+    """(len(target) - distance) / len(target) per clip and np.sum(scores) / len(scores) (c18:9-15), in float64 as the host scorer does."""
+    scores = [(int(t) - int(d)) / int(t) for d, t in zip(dist, tlen)]
+    mean = float(np.sum(scores) / len(scores)) if scores else 0.0
+    return mean, np.asarray(scores, dtype=np.float64)
+
+
+# ---------------------------------------------------------------------------------------------------- device runner
+class BatchedTFLiteModel:
+    def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, batch_size: int = 64, max_frames: int = 1024,
+                 use_graph: bool = True):
+        if model.F != N_COLS:
+            raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
+        if batch_size < 1 or batch_size > model.max_batch:
+            raise ValueError(f"batch_size {batch_size} outside 1..max_batch={model.max_batch}")
+        if max_frames < 1 or max_frames > 8192:
+            raise ValueError(f"max_frames {max_frames} outside 1..8192")
+        L = int(model._cfg.max_label_len)
+        if L < 1 or L > MAX_SCORE_LABEL_LEN:
+            raise ValueError(f"max_label_len {L} outside 1..{MAX_SCORE_LABEL_LEN} (device scoring: one wavefront lane per target symbol)")
+        if model.device is None:
+            raise ValueError("the model has no device: build it with device='cuda:N'")
+        self.model, self.batch_size, self.max_frames, self.T, self.L = model, batch_size, max_frames, model.T, L
+        dev, bs, T = model.device, batch_size, model.T
+        mean = np.concatenate([(stats[n][0] if stats else np.zeros((c, 3), np.float32)).reshape(-1) for n, c in PARTS])
+        std = np.concatenate([(stats[n][1] if stats else np.ones((c, 3), np.float32)).reshape(-1) for n, c in PARTS])
+        self._mean = torch.from_numpy(mean.astype(np.float32)).to(dev)
+        self._std = torch.from_numpy(std.astype(np.float32)).to(dev)
+        # staging layout (bytes), the same on the host (pinned) and on the device: offsets int64 [bs+1] | targets int32 [bs, L] | raw f32 [cap, 276]
+        self._cap = bs * max_frames
+        self._tgt_at = _align((bs + 1) * 8, 256)
+        self._raw_at = _align(self._tgt_at + bs * L * 4, 256)
+        nbytes = self._raw_at + self._cap * _ROW_BYTES
+        self._h_in = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._d_in = [torch.zeros(nbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        for d in self._d_in:                     # every slot starts as bs empty clips with all-pad targets
+            self._off(d).zero_()
+            self._tgt(d).fill_(PAD_TOKEN_IDX)
+        # results: indices int32 [bs, T] | lengths [bs] | dist [bs] | tlen [bs], one D2H copy per batch
+        self._d_res = torch.zeros(bs * T + 3 * bs, dtype=torch.int32, device=dev)
+        self._h_res = [torch.empty(bs * T + 3 * bs, dtype=torch.int32, pin_memory=True) for _ in range(2)]
+        self._idx = self._d_res[:bs * T].view(bs, T)
+        self._len, self._dist, self._tlen = (self._d_res[bs * T + k * bs: bs * T + (k + 1) * bs] for k in range(3))
+        self._x = torch.zeros((bs, T, N_COLS), dtype=torch.float32, device=dev)
+        self._logits = torch.zeros((bs, T, model.C), dtype=torch.float32, device=dev)
+        self._copy_stream = torch.cuda.Stream(device=dev)
+        self._copied = [torch.cuda.Event() for _ in range(2)]
+        self._consumed = [None, None]            # event after the replay that last read a device slot
+        self._done = [torch.cuda.Event() for _ in range(2)]
+        self.use_graph = use_graph
+        self._graphs: Dict[Tuple[int, bool], torch.cuda.CUDAGraph] = {}
+
+    # ---- views of a staging buffer (host or device)
+    def _off(self, buf):
+        return buf[:(self.batch_size + 1) * 8].view(torch.int64)
+
+    def _tgt(self, buf):
+        return buf[self._tgt_at:self._tgt_at + self.batch_size * self.L * 4].view(torch.int32).view(self.batch_size, self.L)
+
+    def _raw(self, buf):
+        return buf[self._raw_at:].view(torch.float32).view(self._cap, N_COLS)
+
+    # ---- device work of one batch
+    def _launch(self, slot: int, scoring: bool):
+        lib, m, d, bs = self.model._lib, self.model, self._d_in[slot], self.batch_size
+        st = _stream()
+        _lib.check(lib.ishara_preprocess_batch(_lib.ptr(self._raw(d)), self._cap, _lib.ptr(self._off(d)), bs, self.max_frames,
+                                               _lib.ptr(self._mean), _lib.ptr(self._std), _lib.ptr(self._x), self.T, st), "ishara_preprocess_batch")
+        _lib.check(lib.ishara_forward(m._h, _lib.ptr(self._x), bs, _lib.ptr(self._logits), 0, C.c_uint32(0), st), "ishara_forward")
+        _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), bs, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), st),
+                   "ishara_greedy_decode")
+        if scoring:
+            _lib.check(lib.ishara_edit_distance(_lib.ptr(self._idx), _lib.ptr(self._len), bs, self.T, _lib.ptr(self._tgt(d)), self.L,
+                                                _lib.ptr(self._dist), _lib.ptr(self._tlen), st), "ishara_edit_distance")
+
+    def _graph(self, slot: int, scoring: bool):
+        key = (slot, scoring)
+        if key not in self._graphs:              # as TFLiteModel._capture: warm-up outside the capture, then capture once
+            side = torch.cuda.Stream(device=self.model.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._launch(slot, scoring)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._launch(slot, scoring)
+            self._graphs[key] = g
+        return self._graphs[key]
+
+    def _run(self, slot: int, scoring: bool):
+        """The device sequence on the current stream, on the inputs already in device slot `slot`."""
+        if self.use_graph:
+            self._graph(slot, scoring).replay()
+        else:
+            self._launch(slot, scoring)
+
+    # ---- host pipeline
+    def _batches(self, clips):
+        """Yield (fill(raw, offsets) -> rows, clip count) per batch for a list of clips or pre-packed (frames, offsets)."""
+        bs = self.batch_size
+        if isinstance(clips, tuple) and len(clips) == 2 and np.ndim(clips[1]) == 1:
+            frames, offsets = check_packed(clips[0], clips[1], self.max_frames)
+            n = offsets.shape[0] - 1
+            for b0 in range(0, n, bs):
+                off = offsets[b0:min(b0 + bs, n) + 1]
+
+                def fill(raw, out_off, off=off):
+                    rows = int(off[-1] - off[0])
+                    if rows:
+                        raw[:rows] = frames[off[0]:off[-1]]
+                    out_off[:off.shape[0]] = off - off[0]
+                    out_off[off.shape[0]:] = rows
+                    return rows
+                yield fill, off.shape[0] - 1
+        else:
+            clips = [check_clip(c, self.max_frames) for c in clips]
+            for b0 in range(0, len(clips), bs):
+                part = clips[b0:b0 + bs]
+                yield (lambda raw, out_off, part=part: pack_clips(part, raw, out_off)), len(part)
+
+    def _process(self, clips, targets=None):
+        """Run every batch; returns the host results per batch: (indices [n, T], lengths, dist, tlen)."""
+        scoring = targets is not None
+        bs = self.batch_size
+        cur = torch.cuda.current_stream()
+        out, pending = [], None
+        for i, (fill, n) in enumerate(self._batches(clips)):
+            s = i & 1
+            h, d = self._h_in[s], self._d_in[s]
+            # the pinned slot is free: the batch that used it two steps ago was collected (its `done` waited on its copy)
+            rows = fill(self._raw(h).numpy(), self._off(h).numpy())
+            if scoring:
+                t = self._tgt(h).numpy()
+                t[:n] = targets[i * bs:i * bs + n]
+                t[n:] = PAD_TOKEN_IDX
+            nbytes = self._raw_at + rows * _ROW_BYTES
+            with torch.cuda.stream(self._copy_stream):
+                if self._consumed[s] is not None:    # the replay that last read this device slot
+                    self._copy_stream.wait_event(self._consumed[s])
+                d[:nbytes].copy_(h[:nbytes], non_blocking=True)
+                self._copied[s].record(self._copy_stream)
+            cur.wait_event(self._copied[s])
+            self._run(s, scoring)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            self._consumed[s] = ev
+            self._h_res[s].copy_(self._d_res, non_blocking=True)
+            self._done[s].record(cur)
+            if pending is not None:
+                out.append(self._collect(*pending))
+            pending = (s, n)
+        if pending is not None:
+            out.append(self._collect(*pending))
+        return out
+
+    def _collect(self, s: int, n: int):
+        self._done[s].synchronize()                  # the one host wait of a batch
+        r = self._h_res[s].numpy()
+        bs, T = self.batch_size, self.T
+        idx = r[:bs * T].reshape(bs, T)[:n].copy()
+        ln, dist, tlen = (r[bs * T + k * bs: bs * T + k * bs + n].copy() for k in range(3))
+        return idx, ln, dist, tlen
+
+    # ---- public surface
+    def predict_indices(self, clips) -> List[np.ndarray]:
+        """Greedy decode per clip (before the len < 3 fallback): equal to `TFLiteModel.predict_indices` clip by clip."""
+        res = []
+        for idx, ln, _, _ in self._process(clips):
+            res.extend(idx[b, :ln[b]].astype(np.int64) for b in range(idx.shape[0]))
+        return res
+
+    def __call__(self, clips) -> List[Dict[str, np.ndarray]]:
+        """`TFLiteModel.__call__` per clip: {'outputs': one-hot [n_chars, 59]} after the fallback (c13:22-24), on the host as there."""
+        return [{"outputs": one_hot(apply_fallback(idx))} for idx in self.predict_indices(clips)]
+
+    def score(self, clips, targets, char_to_num: Optional[Dict[str, int]] = None) -> Dict[str, object]:
+        """The test-set loop of c18:1-15 as one call: mean of (len(target) - Levenshtein(pred, target)) / len(target) over the clips, pred
+        the wrapper's output (fallback applied).  targets: strings (encoded through char_to_num) or index sequences, one per clip.  The
+        distances are computed on the device; the scores in float64 on the host from the integer distances and target lengths."""
+        enc = np.stack([encode_phrase(t, char_to_num, self.L) for t in targets]) if len(targets) else np.zeros((0, self.L), np.int32)
+        n_clips = (np.asarray(clips[1]).shape[0] - 1) if (isinstance(clips, tuple) and len(clips) == 2 and np.ndim(clips[1]) == 1) else len(clips)
+        if enc.shape[0] != n_clips:
+            raise ValueError(f"{enc.shape[0]} targets for {n_clips} clips")
+        parts = self._process(clips, enc)
+        dist = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, np.int32)
+        tlen = np.concatenate([p[3] for p in parts]) if parts else np.zeros(0, np.int32)
+        mean, scores = normalized_scores(dist, tlen)
+        return dict(mean_score=mean, scores=scores, distances=dist.astype(np.int64))

@@ -156,6 +156,19 @@ int ishara_preprocess_batch(const float* raw, int64_t n_total, const int64_t* of
 int ishara_edit_distance(const int32_t* out_idx, const int32_t* out_len, int32_t B, int32_t T, const int32_t* targets, int32_t L,
                          int32_t* dist, int32_t* tlen, ishara_stream s);
 
+/* CTC prefix beam search (Hannun et al. 2014) with optional character-bigram shallow fusion; the semantics of ishara_amd/ctc_beam.py.
+ * logits [B,T,C] fp32 (log_softmax taken on the device), blank index, beam width W, nbest <= W; lm [C,C] natural-log probabilities
+ * (row = previous class, row blank = start of phrase; column = next class, column blank = end of phrase) or NULL; ranking key
+ * (pb (+) pnb) + alpha * sum(lm) + beta * len.  2 <= C <= 64, 1 <= W <= 32, 1 <= nbest <= W, 1 <= T <= 4096.
+ * -> out_idx [B,nbest,T] int32 padded with -1, out_len [B,nbest], out_score [B,nbest]; an n-best slot without a hypothesis has len -1
+ * and score -inf.  With nbest = 1 out_idx / out_len have the layout of ishara_greedy_decode (ishara_edit_distance reads them).  Unlike
+ * the greedy decoder it uses the last frame too.  workspace: ishara_ctc_beam_workspace_bytes(B, T, C, W), 4-byte aligned, no
+ * initialisation needed.  One kernel, graph-capturable, bit-identical from run to run; B = 0 is a no-op. */
+int64_t ishara_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t C, int32_t beam_width);
+int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
+                           const float* lm, float alpha, float beta, void* workspace,
+                           int32_t* out_idx, int32_t* out_len, float* out_score, ishara_stream s);
+
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */
 typedef struct ishara_clip_aug {

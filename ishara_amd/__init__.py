@@ -7,3 +7,4 @@ from ._lib import IsharaError  # noqa: F401
 from .conformer import ConformerEncoder  # noqa: F401  (torch family: conformer/conformer.py)
 from .squeezeformer import Squeezeformer, SqueezeformerEncoder  # noqa: F401  (torch family: squeezeformer/encoder.py, model.py)
 from .tflite_batch import BatchedTFLiteModel  # noqa: F401  (batched raw-clip inference + device test-set scoring)
+from .ctc_beam import CharBigramLM, prefix_beam_search  # noqa: F401  (CTC prefix beam search: host reference, bigram LM)

@@ -239,6 +239,10 @@ int launch_preprocess_batch(const float* raw, int64_t n_total, const int64_t* of
 // ---- test-set scoring (score.hip): edit distance of greedy decodes (len < 3 -> fallback phrase) to pad-59 targets [B,L], L <= 64
 #define SCORE_MAX_L 64
 int launch_edit_distance(const int* out_idx, const int* out_len, int B, int T, const int* targets, int L, int* dist, int* tlen, hipStream_t s);
+// ---- CTC prefix beam search (ctc_beam.hip): logits [B,T,C] f32 -> n-best prefixes; ws = B * ctc_beam_workspace_words(T, W) int32 (trie)
+__host__ __device__ size_t ctc_beam_workspace_words(int T, int W);
+int launch_ctc_beam(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm, float alpha, float beta,
+                    void* ws, int* out_idx, int* out_len, float* out_score, hipStream_t s);
 // ---- training input batch (input_batch.hip): device store of raw clips + per-clip augmentation table -> x [B,T,F]
 #define CLIP_MAX_T 4096
 int launch_clip_batch(const float* raw, const ishara_clip_aug* clips, int B, int T, int layout, float* x, hipStream_t s);

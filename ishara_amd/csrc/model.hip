@@ -1085,6 +1085,24 @@ extern "C" int ishara_edit_distance(const int32_t* out_idx, const int32_t* out_l
     if (B > 0 && (!out_idx || !out_len || !targets || !dist || !tlen)) { ishara_set_error("ishara_edit_distance: null argument"); return -1; }
     return launch_edit_distance(out_idx, out_len, B, T, targets, L, dist, tlen, (hipStream_t)s);
 }
+extern "C" int64_t ishara_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t C, int32_t beam_width) {
+    (void)C;
+    if (B < 0 || T < 1 || T > 4096 || beam_width < 1 || beam_width > 32) return -1;
+    return (int64_t)B * (int64_t)ctc_beam_workspace_words(T, beam_width) * 4;
+}
+extern "C" int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
+                                      const float* lm, float alpha, float beta, void* workspace,
+                                      int32_t* out_idx, int32_t* out_len, float* out_score, ishara_stream s) {
+    if (C < 2 || C > 64) { ishara_set_error("ishara_ctc_beam_decode: C=%d unsupported (2..64: one lane per class)", C); return -1; }
+    if (blank < 0 || blank >= C) { ishara_set_error("ishara_ctc_beam_decode: blank %d outside 0..%d", blank, C - 1); return -1; }
+    if (beam_width < 1 || beam_width > 32) { ishara_set_error("ishara_ctc_beam_decode: beam_width %d unsupported (1..32)", beam_width); return -1; }
+    if (nbest < 1 || nbest > beam_width) { ishara_set_error("ishara_ctc_beam_decode: nbest %d outside 1..beam_width=%d", nbest, beam_width); return -1; }
+    if (B < 0 || B > 2147483647 / 2 || T < 1 || T > 4096) { ishara_set_error("ishara_ctc_beam_decode: B=%d T=%d unsupported (B >= 0, 1 <= T <= 4096)", B, T); return -1; }
+    if (!(alpha == alpha && beta == beta) || alpha - alpha != 0.0f || beta - beta != 0.0f) { ishara_set_error("ishara_ctc_beam_decode: alpha and beta must be finite"); return -1; }
+    if (B > 0 && (!logits || !workspace || !out_idx || !out_len || !out_score)) { ishara_set_error("ishara_ctc_beam_decode: null argument"); return -1; }
+    if ((uintptr_t)workspace % 4) { ishara_set_error("ishara_ctc_beam_decode: workspace must be 4-byte aligned"); return -1; }
+    return launch_ctc_beam(logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len, out_score, (hipStream_t)s);
+}
 extern "C" int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
                                  float* x, ishara_stream s) {
     if (B < 0 || T < 1 || T > CLIP_MAX_T) { ishara_set_error("ishara_clip_batch: B=%d T=%d unsupported (B >= 0, 1 <= T <= %d)", B, T, CLIP_MAX_T); return -1; }

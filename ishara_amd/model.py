@@ -426,6 +426,30 @@ class Model:
         return [idx[b, :ln[b]].astype(np.int64) for b in range(B)]
 
 
+    def beam_decode(self, logits, beam_width: int = 16, nbest: int = 1, lm=None, alpha: float = 0.0, beta: float = 0.0
+                    ) -> List[List[Tuple[np.ndarray, float]]]:
+        """CTC prefix beam search (ishara_amd/ctc_beam.py semantics, blank = C - 1) of logits [B, T, C] on the device -> per clip a list
+        of (indices int64, score), best first, at most nbest entries.  lm: a [C, C] log-probability table (e.g. CharBigramLM) or None.
+        Unlike decode_batch it uses the last frame too.  The workspace of the latest shape is kept for the next call; the call waits for
+        its results, so successive calls never overlap, but calls from several threads at once on one Model would share it (not supported)."""
+        from . import ctc_beam
+        logits = torch.as_tensor(logits).to(self.device, torch.float32).contiguous()
+        if logits.ndim != 3:
+            raise ValueError(f"logits must be [B, T, C], got {tuple(logits.shape)}")
+        B, T, Cc = logits.shape
+        ctc_beam.check_device_args(Cc, T, beam_width, nbest)
+        lm_dev = ctc_beam.lm_to_device(lm, Cc, self.device)
+        nbytes = max(ctc_beam.workspace_bytes(self._lib, B, T, Cc, beam_width), 4)
+        ws = getattr(self, "_beam_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._beam_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        idx = torch.empty((B, nbest, T), dtype=torch.int32, device=self.device)
+        ln = torch.empty((B, nbest), dtype=torch.int32, device=self.device)
+        sc = torch.empty((B, nbest), dtype=torch.float32, device=self.device)
+        ctc_beam.launch(self._lib, logits, B, T, Cc, beam_width, nbest, lm_dev, alpha, beta, ws, idx, ln, sc, _stream())
+        idx, ln, sc = idx.cpu().numpy(), ln.cpu().numpy(), sc.cpu().numpy()
+        return [[(idx[b, n, :ln[b, n]].astype(np.int64), float(sc[b, n])) for n in range(nbest) if ln[b, n] >= 0] for b in range(B)]
+
 def make_config(dim=256, num_conv_squeeze_blocks=2, num_conv_conform_blocks=2, kernel_sizes=(11, 5, 3),
                 num_conv_per_block=3, dropout_rate=0.2, num_heads=8, expansion_factor=2, transformer_kernel_size=15,
                 input_shape=(176, 276), num_classes=60, top_dim=0, squeeze_expansion=0, conformer_expansion=0,

@@ -6,7 +6,7 @@ loop over the test set (c18) that calls it per clip, maps the one-hot output bac
 (len(target) - Levenshtein(pred, target)) / len(target) on the host.  `BatchedTFLiteModel` runs `batch_size` clips per hipGraph replay:
 
   packed raw clips [N, 276] + offsets [B+1] --ishara_preprocess_batch--> x [B, T, 276] --ishara_forward(training=0)--> logits
-  --ishara_greedy_decode--> indices, lengths [--ishara_edit_distance (len < 3 fallback, pad-59 targets)--> dist, tlen]
+  --ishara_greedy_decode (ishara_ctc_beam_decode top-1 with beam_width > 0)--> indices, lengths [--ishara_edit_distance (len < 3 fallback, pad-59 targets)--> dist, tlen]
 
 Per batch the host packs the clips into one pinned staging buffer (offsets | targets | raw frames), copies it with one non-blocking
 H2D copy on a copy stream, replays the graph on the current stream and copies the results (indices | lengths | dist | tlen) back with one
@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .model import Model, _stream
-from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS
+from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS, _beam_launch, _beam_setup
 
 PAD_TOKEN_IDX = 59           # c1:5: the targets' padding; never a decoded index (the blank is C - 1 = 59)
 MAX_SCORE_LABEL_LEN = 64     # one wavefront lane per target symbol (ishara_edit_distance)
@@ -133,7 +133,9 @@ def normalized_scores(dist: np.ndarray, tlen: np.ndarray) -> Tuple[float, np.nda
 # ---------------------------------------------------------------------------------------------------- device runner
 class BatchedTFLiteModel:
     def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, batch_size: int = 64, max_frames: int = 1024,
-                 use_graph: bool = True):
+                 use_graph: bool = True, beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0):
+        """beam_width / lm / lm_alpha / lm_beta as for TFLiteModel: 0 keeps the greedy decode; > 0 captures the beam decoder (top-1) in
+        its place, and predict_indices / __call__ / score() work on the beam's top-1."""
         if model.F != N_COLS:
             raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
         if batch_size < 1 or batch_size > model.max_batch:
@@ -168,6 +170,7 @@ class BatchedTFLiteModel:
         self._len, self._dist, self._tlen = (self._d_res[bs * T + k * bs: bs * T + (k + 1) * bs] for k in range(3))
         self._x = torch.zeros((bs, T, N_COLS), dtype=torch.float32, device=dev)
         self._logits = torch.zeros((bs, T, model.C), dtype=torch.float32, device=dev)
+        self._beam = _beam_setup(model, bs, beam_width, lm, lm_alpha, lm_beta)
         self._copy_stream = torch.cuda.Stream(device=dev)
         self._copied = [torch.cuda.Event() for _ in range(2)]
         self._consumed = [None, None]            # event after the replay that last read a device slot
@@ -192,8 +195,11 @@ class BatchedTFLiteModel:
         _lib.check(lib.ishara_preprocess_batch(_lib.ptr(self._raw(d)), self._cap, _lib.ptr(self._off(d)), bs, self.max_frames,
                                                _lib.ptr(self._mean), _lib.ptr(self._std), _lib.ptr(self._x), self.T, st), "ishara_preprocess_batch")
         _lib.check(lib.ishara_forward(m._h, _lib.ptr(self._x), bs, _lib.ptr(self._logits), 0, C.c_uint32(0), st), "ishara_forward")
-        _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), bs, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), st),
-                   "ishara_greedy_decode")
+        if self._beam is None:
+            _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), bs, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), st),
+                       "ishara_greedy_decode")
+        else:
+            _beam_launch(m, self._beam, self._logits, bs, self._idx, self._len, st)
         if scoring:
             _lib.check(lib.ishara_edit_distance(_lib.ptr(self._idx), _lib.ptr(self._len), bs, self.T, _lib.ptr(self._tgt(d)), self.L,
                                                 _lib.ptr(self._dist), _lib.ptr(self._tlen), st), "ishara_edit_distance")
@@ -289,7 +295,7 @@ class BatchedTFLiteModel:
 
     # ---- public surface
     def predict_indices(self, clips) -> List[np.ndarray]:
-        """Greedy decode per clip (before the len < 3 fallback): equal to `TFLiteModel.predict_indices` clip by clip."""
+        """The decode per clip (greedy, or the beam's top-1; before the len < 3 fallback): equal to `TFLiteModel.predict_indices` clip by clip."""
         res = []
         for idx, ln, _, _ in self._process(clips):
             res.extend(idx[b, :ln[b]].astype(np.int64) for b in range(idx.shape[0]))

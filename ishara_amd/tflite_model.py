@@ -47,8 +47,38 @@ def write_inference_args(path: str = "inference_args.json") -> str:
     return path
 
 
+class _BeamConfig:
+    """Device state of a wrapper's beam decoder, allocated once at construction (graph replays reuse it)."""
+    def __init__(self, width, lm_dev, alpha, beta, ws, score):
+        self.width, self.lm, self.alpha, self.beta, self.ws, self.score = width, lm_dev, alpha, beta, ws, score
+
+
+def _beam_setup(model: Model, batch: int, beam_width: int, lm, alpha: float, beta: float) -> Optional[_BeamConfig]:
+    """None for beam_width == 0 (greedy); else the LM table, the workspace and the top-1 score buffer on the model's device."""
+    from . import ctc_beam
+    if beam_width == 0:
+        if lm is not None:
+            raise ValueError("an lm needs beam_width > 0")
+        return None
+    ctc_beam.check_device_args(model.C, model.T, beam_width, 1)
+    dev = model.device
+    lm_dev = ctc_beam.lm_to_device(lm, model.C, dev)
+    ws = torch.empty(max(ctc_beam.workspace_bytes(model._lib, batch, model.T, model.C, beam_width), 4), dtype=torch.uint8, device=dev)
+    score = torch.zeros(batch, dtype=torch.float32, device=dev)
+    return _BeamConfig(int(beam_width), lm_dev, float(alpha), float(beta), ws, score)
+
+
+def _beam_launch(model: Model, cfg: _BeamConfig, logits, batch: int, idx, ln, stream) -> None:
+    """ishara_ctc_beam_decode with nbest = 1: idx [batch, T] / ln [batch] in the layout ishara_greedy_decode writes."""
+    from . import ctc_beam
+    ctc_beam.launch(model._lib, logits, batch, model.T, model.C, cfg.width, 1, cfg.lm, cfg.alpha, cfg.beta, cfg.ws, idx, ln, cfg.score, stream)
+
+
 class TFLiteModel:
-    def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, max_frames: int = 1024, use_graph: bool = True):
+    def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, max_frames: int = 1024, use_graph: bool = True,
+                 beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0):
+        """beam_width = 0: the reference's greedy decode (c8:4-12).  beam_width > 0: the CTC prefix beam search of ishara_amd/ctc_beam.py
+        (top-1, optional LM table lm [C, C] weighted by lm_alpha, lm_beta per character) replaces it inside the same graph."""
         if model.F != N_COLS:
             raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
         self.model, self.max_frames, self.T = model, max_frames, model.T
@@ -63,6 +93,7 @@ class TFLiteModel:
         self._logits = torch.zeros((1, self.T, model.C), dtype=torch.float32, device=dev)
         self._idx = torch.zeros((1, self.T), dtype=torch.int32, device=dev)
         self._len = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._beam = _beam_setup(model, 1, beam_width, lm, lm_alpha, lm_beta)
         self._graph = None
         if use_graph:
             self._capture()
@@ -72,8 +103,11 @@ class TFLiteModel:
         _lib.check(lib.ishara_preprocess(_lib.ptr(self._raw), _lib.ptr(self._n), self.max_frames, _lib.ptr(self._mean), _lib.ptr(self._std),
                                          _lib.ptr(self._x), self.T, _stream()), "ishara_preprocess")
         _lib.check(lib.ishara_forward(m._h, _lib.ptr(self._x), 1, _lib.ptr(self._logits), 0, C.c_uint32(0), _stream()), "ishara_forward")
-        _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), 1, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), _stream()),
-                   "ishara_greedy_decode")
+        if self._beam is None:
+            _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), 1, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), _stream()),
+                       "ishara_greedy_decode")
+        else:
+            _beam_launch(m, self._beam, self._logits, 1, self._idx, self._len, _stream())
 
     def _capture(self):
         side = torch.cuda.Stream(device=self.model.device)

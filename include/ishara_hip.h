@@ -208,6 +208,8 @@ int ishara_debug_set_nt_big(int32_t on);
 int ishara_debug_force_regstage(int32_t on);
 
 /* ---- single-operator entry points (parity tests of the individual kernels) ------------ */
+/* dt: ISHARA_F32 / ISHARA_BF16 / ISHARA_F16; the backward operators refuse ISHARA_F16 (inference only), every operator refuses an unknown
+ * dtype, both before anything is launched. */
 /* y = act(x @ W + b): x [M,K] (dtype dt), W [K,N] f32, y [M,N] (dt); scratch >= ishara_op_scratch_bytes */
 int64_t ishara_op_scratch_bytes(int32_t M, int32_t K, int32_t N);
 int ishara_op_dense_fwd(int32_t dt, const void* x, const float* W, const float* bias, void* y,
@@ -218,6 +220,20 @@ int ishara_op_dense_fwd_ex(int32_t dt, const void* x, const float* W, const floa
 /* dx = dy @ W^T ; dW += x^T dy ; db += colsum(dy) */
 int ishara_op_dense_bwd(int32_t dt, const void* x, const float* W, const void* dy, void* dx,
                         float* dW, float* db, int32_t M, int32_t K, int32_t N, void* scratch, ishara_stream s);
+/* QKV projection of the attention module at inference: LayerNorm of x [B*T, H*dh] (gamma, beta f32; gamma NULL: none; H*dh <= 512 with it),
+ * x @ W + b (W [H*dh, 3*H*dh] f32, bias [3*H*dh] or NULL) scattered to q, k [B,H,T,dh] and vt [B,H,dh,T] (dt) — head_major 1: W's columns
+ * are [q|k|v] per head, 0: [q of all heads | k | v].  T, dh multiples of 8.  The LayerNorm runs inside the GEMM or as a kernel of its own
+ * exactly as in ishara_forward.  scratch >= ishara_op_qkv_scratch_bytes, 16-byte aligned. */
+int64_t ishara_op_qkv_scratch_bytes(int32_t B, int32_t T, int32_t H, int32_t dh);
+int ishara_op_qkv_fwd(int32_t dt, const void* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias,
+                      void* q, void* k, void* vt, int32_t B, int32_t T, int32_t H, int32_t dh, int32_t head_major, void* scratch, ishara_stream s);
+/* the head's classifier: logits [M, C] f32 = x [M, K] (dt) @ W [K, C] f32 + bias.  route 1: the A-stationary kernel over the zero-padded
+ * 64-row weight shadow, storing the C real columns (16-bit dt, C <= 64, C % 4 == 0, K 256 / 512); 2: dense_narrow (16-bit dt, C <= 64,
+ * K % 32 == 0); 3: the NT GEMM with fp32 output; 0: the route ishara_forward takes — 1 when it applies and M <= 1536, else 2 when it applies
+ * and M <= 4096, else 3.  A route that does not take the shape returns an error and launches nothing.  scratch >=
+ * ishara_op_scratch_bytes(M, K, C), 16-byte aligned. */
+int ishara_op_classifier_fwd(int32_t dt, const void* x, const float* W, const float* bias, float* logits, int32_t M, int32_t K, int32_t C,
+                             int32_t route, void* scratch, ishara_stream s);
 /* y[m,:C] = x[m,:C] - logsumexp(x[m,:C]) over C fp32 logits in rows of stride ld >= C floats (columns C..ld-1 of the outputs are zeroed: a class
  * count padded to the GEMMs' 16-byte row alignment); dx = dy - exp(y) * rowsum(dy).  Replaces F.log_softmax(self.fc(...), dim=-1) of the
  * reference's torch Squeezeformer (squeezeformer/model.py:448-449). */
@@ -243,7 +259,7 @@ int64_t ishara_op_dwconv_scratch_bytes(int32_t C, int32_t k);
 int ishara_op_dwconv_bwd(int32_t dt, int32_t inop, const void* dy, const void* x, const float* w, void* dx,
                          float* dw, float* dbias, void* scratch, int32_t B, int32_t T, int32_t C, int32_t k,
                          int32_t padl, ishara_stream s);
-/* attention on packed qkv [B*T, 3*H*dh] (head-major packing): o [B*T, H*dh]; scratch holds q,k,vt,lse,delta */
+/* attention on packed qkv [B*T, 3*H*dh] (head-major packing): o [B*T, H*dh]; scratch holds q,k,vt,lse,delta.  ISHARA_F16: rate 0 only */
 int64_t ishara_op_attn_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh);
 int ishara_op_attn_fwd(int32_t dt, const void* qkv, void* o, int32_t B, int32_t H, int32_t T, int32_t dh,
                        float scale, uint32_t seed, uint32_t site, float rate, int32_t impl,

@@ -534,20 +534,26 @@ static uint32_t* attn_maskw(ishara_model* m, const Buf& off) {
 }
 int wgrad_flush(ishara_model* m) { return launch_gemm_tn_flush(&m->tn_defer, m->s); }
 
+// Whether the GEMM [M,K] x [K,N] (weight shadow row stride ldt) applies the LayerNorm in front of it as an operand prologue of the
+// A-stationary kernel; if so the prologue fields of ea are set (side outputs mean / rstd / xn: training only, nullptr at inference).
+// false: the caller runs layernorm_fwd first.  ishara_forward (ln_prologue) and ishara_op_qkv_fwd both decide here.
+static bool ln_as_prologue(int dt, int M, int N, int K, int ldt, const float* gamma, const float* beta, float eps, float* mean, float* rstd, void* xn, EpiArgs& ea) {
+    EpiArgs probe = ea;
+    probe.ln_gamma = gamma; probe.ln_beta = beta; probe.ln_mean = mean; probe.pro_out = xn;
+    if (!gemm_nt_as_prologue_ok(dt, dt, dt, M, N, K, ldt, probe)) return false;
+    ea.ln_gamma = gamma; ea.ln_beta = beta; ea.ln_eps = eps;
+    ea.ln_mean = mean; ea.ln_rstd = rstd; ea.pro_out = xn;
+    return true;
+}
+
 // LayerNorm as a prologue of the GEMM that consumes it (gemm_as.hip): the wave holds whole rows of K, so the statistics cost two
 // cross-lane adds; the normalised rows go to `xn` (training: the weight-gradient GEMM reads them) and the statistics to mean / rstd.
 // Shapes the A-stationary kernel does not take run the separate LayerNorm kernel.  Returns the GEMM's A operand.
 static const void* ln_prologue(ishara_model* m, const DenseW& w, const Run& r, const void* x, const Norm& ln, float eps, Buf xn, Buf mean, Buf rstd, EpiArgs& ea, int* rc) {
     *rc = 0;
-    EpiArgs probe = ea;
-    probe.ln_gamma = m->P(ln.gamma); probe.ln_beta = m->P(ln.beta);
-    probe.ln_mean = r.training ? m->Wf(mean) : nullptr; probe.pro_out = r.training ? m->W(xn) : nullptr;     // inference: no side outputs
-    if (gemm_nt_as_prologue_ok(m->dt, m->dt, m->dt, r.M, w.N, w.K, w.ldt, probe)) {
-        ea.ln_gamma = m->P(ln.gamma); ea.ln_beta = m->P(ln.beta); ea.ln_eps = eps;
-        ea.ln_mean = probe.ln_mean; ea.ln_rstd = r.training ? m->Wf(rstd) : nullptr;
-        ea.pro_out = probe.pro_out;
+    if (ln_as_prologue(m->dt, r.M, w.N, w.K, w.ldt, m->P(ln.gamma), m->P(ln.beta), eps, r.training ? m->Wf(mean) : nullptr, r.training ? m->Wf(rstd) : nullptr,
+                       r.training ? m->W(xn) : nullptr, ea))      // inference: no side outputs
         return x;
-    }
     *rc = [&]() -> int {
         CKP(m, "layernorm_fwd", 2.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_layernorm_fwd(m->dt, x, m->P(ln.gamma), m->P(ln.beta), eps, m->W(xn), m->Wf(mean), m->Wf(rstd), r.M, m->d, m->s));
         return 0;
@@ -691,6 +697,38 @@ int confconv_fwd(ishara_model* m, ConfConv& c, const Run& r, const void* x) {
     return 0;
 }
 
+// ---- the classifier Dense of the head: fp32 logits [M, C] from A [M, K] (dt) and the weight shadow Wt (rows of ldt elements, at least
+// 64 rows, zero-filled beyond C).  ishara_forward and ishara_op_classifier_fwd both run it here.
+//   CLS_AS      the A-stationary MFMA kernel over N = 64 shadow rows, storing the C real columns only (ldc = n_valid = C)
+//   CLS_NARROW  dense_narrow (one lane per class)
+//   CLS_GEMM    the NT GEMM with fp32 output (launch_gemm_nt picks the kernel)
+//   CLS_AUTO    what the model takes for (dt, M, K, C): CLS_AS for 16-bit dt, M <= 1536, C <= 64, C % 4 == 0, K 256 / 512; else CLS_NARROW
+//               for 16-bit dt, M <= 4096, C <= 64, K % 32 == 0; else CLS_GEMM.  ISHARA_NO_INFER_FUSION or a forced tile kernel
+//               (ishara_debug_force_regstage) rule out CLS_AS, the former CLS_NARROW too.
+enum { CLS_AUTO = 0, CLS_AS = 1, CLS_NARROW = 2, CLS_GEMM = 3 };
+static int cls_route_auto(int dt, int M, int K, int C) {
+    const bool fusion = getenv("ISHARA_NO_INFER_FUSION") == nullptr;
+    if (dt_is16(dt) && M <= 1536 && C <= 64 && C % 4 == 0 && (K == 256 || K == 512) && !g_force_regstage && fusion) return CLS_AS;      // a clip's worth of rows
+    if (dt_is16(dt) && M <= 4096 && C <= 64 && K % 32 == 0 && fusion) return CLS_NARROW;      // few rows: the latency of a clip
+    return CLS_GEMM;
+}
+// m: the model whose profiler records the launch (nullptr: none)
+#define CKP_OPT(m, key, by, fl, expr) do { if (m) CKP(m, key, by, fl, expr); else CK(expr); } while (0)
+static int classifier_fwd(ishara_model* m, int route, int dt, const void* A, const void* Wt, int ldt, const float* bias, float* logits, int M, int K, int C, hipStream_t s) {
+    if (route == CLS_AUTO) route = cls_route_auto(dt, M, K, C);
+    OpArgs no; EpiArgs ec; ec.bias = bias;
+    if (route == CLS_AS) {
+        ec.ldc = C; ec.n_valid = C;
+        CKP_OPT(m, "classifier(as)", 0, 2.0 * M * C * K, launch_gemm_nt(dt, dt, DT_F32, OP_NONE, A, Wt, logits, M, 64, K, ldt, no, ec, s));
+    } else if (route == CLS_NARROW) {
+        CKP_OPT(m, "dense_narrow", 0, 2.0 * M * C * K, launch_dense_narrow(dt, A, Wt, ldt, bias, logits, M, C, K, s));
+    } else {
+        const double by = (double)M * K * dt_size(dt) + (double)M * C * 4 + (double)K * C * dt_size(dt);
+        CKP_OPT(m, gemm_nt_kernel_name(dt, dt, DT_F32, OP_NONE, A, M, C, K, ldt, ec), by, 2.0 * M * C * K, launch_gemm_nt(dt, dt, DT_F32, OP_NONE, A, Wt, logits, M, C, K, ldt, no, ec, s));
+    }
+    return 0;
+}
+
 extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float* logits, int32_t training, uint32_t seed, ishara_stream st) {
     if (!m->ws) { ishara_set_error("ishara_forward: model is not bound"); return -1; }
     if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("ishara_forward: this handle is an encoder-only family; use ishara_encoder_forward"); return -1; }
@@ -736,15 +774,7 @@ extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float*
     // ---- head: Dense(relu) -> Dropout(0.4) -> Dense  (c7:61-63)
     EpiArgs et; et.act = ACT_RELU; et.drop = dspec(r, m->head_site, m->cfg.head_dropout);
     CK(gemm_fwd(m, m->topW, h, dt, m->W(m->head_hh), dt, r.M, OP_NONE, no, et));
-    EpiArgs ec;
-    if (dt_is16(dt) && r.M <= 1536 && m->C <= 64 && m->C % 4 == 0 && (m->clsW.K == 256 || m->clsW.K == 512) && !g_force_regstage && getenv("ISHARA_NO_INFER_FUSION") == nullptr) {
-        // a clip's worth of rows: the A-stationary MFMA kernel over the zero-padded weight shadow (N = 64), storing the real columns only
-        ec.bias = m->clsW.b >= 0 ? m->P(m->clsW.b) : nullptr; ec.ldc = m->C; ec.n_valid = m->C;
-        CKP(m, "classifier(as)", 0, 2.0 * r.M * m->C * m->clsW.K, launch_gemm_nt(dt, dt, DT_F32, OP_NONE, m->W(m->head_hh), m->ws + m->clsW.wt, logits, r.M, 64, m->clsW.K, m->clsW.ldt, no, ec, m->s));
-    } else if (dt_is16(dt) && r.M <= 4096 && m->C <= 64 && m->clsW.K % 32 == 0 && getenv("ISHARA_NO_INFER_FUSION") == nullptr)       // few rows: the narrow-output kernel (latency of a clip)
-        CKP(m, "dense_narrow", 0, 2.0 * r.M * m->C * m->clsW.K, launch_dense_narrow(dt, m->W(m->head_hh), m->ws + m->clsW.wt, m->clsW.ldt, m->clsW.b >= 0 ? m->P(m->clsW.b) : nullptr, logits, r.M, m->C, m->clsW.K, m->s));
-    else
-    CK(gemm_fwd(m, m->clsW, m->W(m->head_hh), dt, logits, DT_F32, r.M, OP_NONE, no, ec));
+    CK(classifier_fwd(m, CLS_AUTO, dt, m->W(m->head_hh), m->ws + m->clsW.wt, m->clsW.ldt, m->clsW.b >= 0 ? m->P(m->clsW.b) : nullptr, logits, r.M, m->clsW.K, m->C, m->s));
     m->lastB = B; m->last_training = training; m->last_seed = seed; m->last_x = x;
     return 0;
 }
@@ -1113,8 +1143,16 @@ extern "C" int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips,
 }
 
 // ---- operator tests: dense
+// every operator entry point checks its dtype first: ISHARA_F32 / BF16 / F16 known, F16 only where an fp16 kernel exists (forward /
+// inference: the backward operators refuse it); nothing is launched for a refused call
+static bool op_dt_ok(const char* op, int dt, bool f16_ok) {
+    if (dt != DT_F32 && dt != DT_BF16 && dt != DT_F16) { ishara_set_error("%s: unknown dtype %d (ISHARA_F32 = 0, ISHARA_BF16 = 1, ISHARA_F16 = 2)", op, dt); return false; }
+    if (dt == DT_F16 && !f16_ok) { ishara_set_error("%s: ISHARA_F16 is inference-only (no fp16 backward kernels)", op); return false; }
+    return true;
+}
+#define OP_DT(op, dt, f16_ok) do { if (!op_dt_ok(op, dt, f16_ok)) return -1; } while (0)
 static void op_shadow_layout(int dt, int K, int N, size_t& wt, int& ldt, size_t& wn, int& ldn, size_t& slab, size_t& total, int M) {
-    const int bk = dt == DT_BF16 ? 64 : 32;
+    const int bk = dt_is16(dt) ? 64 : 32;      // the K tile the model's shadows use (plan_shadow): 64 for both 16-bit types
     const size_t es = dt_size(dt);
     ldt = (int)rup(K, bk); ldn = (int)rup(N, bk);
     wt = 0;
@@ -1124,10 +1162,11 @@ static void op_shadow_layout(int dt, int K, int N, size_t& wt, int& ldt, size_t&
 }
 extern "C" int64_t ishara_op_scratch_bytes(int32_t M, int32_t K, int32_t N) {
     size_t wt, wn, slab, total; int ldt, ldn;
-    op_shadow_layout(DT_F32, K, N, wt, ldt, wn, ldn, slab, total, M);
+    op_shadow_layout(DT_F32, K, N, wt, ldt, wn, ldn, slab, total, M);      // (the f32 layout is the largest: 4-byte elements, K tile >= half the 16-bit one)
     return (int64_t)total;
 }
 extern "C" int ishara_op_dense_fwd(int32_t dt, const void* x, const float* Wm, const float* bias, void* y, int32_t M, int32_t K, int32_t N, int32_t act, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_dense_fwd", dt, true);
     hipStream_t s = (hipStream_t)st;
     size_t wt, wn, slab, total; int ldt, ldn;
     op_shadow_layout(dt, K, N, wt, ldt, wn, ldn, slab, total, M);
@@ -1140,6 +1179,7 @@ extern "C" int ishara_op_dense_fwd(int32_t dt, const void* x, const float* Wm, c
 // y = act(x @ W + b) + resid
 extern "C" int ishara_op_dense_fwd_ex(int32_t dt, const void* x, const float* Wm, const float* bias, const void* resid, void* y,
                                       int32_t M, int32_t K, int32_t N, int32_t act, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_dense_fwd_ex", dt, true);
     hipStream_t s = (hipStream_t)st;
     size_t wt, wn, slab, total; int ldt, ldn;
     op_shadow_layout(dt, K, N, wt, ldt, wn, ldn, slab, total, M);
@@ -1151,6 +1191,7 @@ extern "C" int ishara_op_dense_fwd_ex(int32_t dt, const void* x, const float* Wm
 }
 extern "C" int ishara_op_dense_bwd(int32_t dt, const void* x, const float* Wm, const void* dy, void* dx, float* dW, float* db,
                                    int32_t M, int32_t K, int32_t N, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_dense_bwd", dt, false);
     hipStream_t s = (hipStream_t)st;
     size_t wt, wn, slab, total; int ldt, ldn;
     op_shadow_layout(dt, K, N, wt, ldt, wn, ldn, slab, total, M);
@@ -1161,17 +1202,88 @@ extern "C" int ishara_op_dense_bwd(int32_t dt, const void* x, const float* Wm, c
     if (dx) CK(launch_gemm_nt(dt, dt, dt, OP_NONE, dy, sc + wn, dx, M, K, N, ldn, no, ea, s));
     return launch_gemm_tn(dt, dt, dt, OP_NONE, OP_NONE, x, dy, dW, db, (float*)(sc + slab), M, K, N, no, no, s);
 }
+// QKV projection of the attention module at inference (mhsa_fwd): LayerNorm (gamma NULL: none), x @ W + b, and the EPI_QKV scatter into
+// q, k [B,H,T,dh] and vt [B,H,dh,T].  scratch: the weight shadow, then the LayerNorm output and its row statistics where the LayerNorm
+// runs as a kernel of its own
+static void qkv_scratch_layout(int B, int T, int H, int dh, size_t& xn, size_t& mean, size_t& rstd, size_t& total) {
+    const int M = B * T, d = H * dh;
+    size_t wt, wn, slab, base; int ldt, ldn;
+    op_shadow_layout(DT_F32, d, 3 * d, wt, ldt, wn, ldn, slab, base, M);
+    xn = rup(base, 256);
+    mean = xn + rup((size_t)M * d * 4, 256);
+    rstd = mean + rup((size_t)M * 4, 256);
+    total = rstd + rup((size_t)M * 4, 256);
+}
+extern "C" int64_t ishara_op_qkv_scratch_bytes(int32_t B, int32_t T, int32_t H, int32_t dh) {
+    if (B < 1 || T < 1 || H < 1 || dh < 1) return -1;
+    size_t xn, mean, rstd, total;
+    qkv_scratch_layout(B, T, H, dh, xn, mean, rstd, total);
+    return (int64_t)total;
+}
+extern "C" int ishara_op_qkv_fwd(int32_t dt, const void* x, const float* gamma, const float* beta, float eps, const float* Wm, const float* bias,
+                                 void* q, void* k, void* vt, int32_t B, int32_t T, int32_t H, int32_t dh, int32_t head_major, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_qkv_fwd", dt, true);
+    if (B < 1 || T < 1 || H < 1 || dh < 1 || T % 8 != 0 || dh % 8 != 0 || (head_major != 0 && head_major != 1)) {
+        ishara_set_error("ishara_op_qkv_fwd: B=%d T=%d H=%d dh=%d head_major=%d unsupported (T, dh multiples of 8; head_major 0 / 1)", B, T, H, dh, head_major); return -1;
+    }
+    const int d = H * dh, M = B * T;
+    if ((gamma != nullptr) != (beta != nullptr) || (gamma && d > 512)) { ishara_set_error("ishara_op_qkv_fwd: LayerNorm needs both gamma and beta and H*dh <= 512 (H*dh=%d)", d); return -1; }
+    if (!x || !Wm || !q || !k || !vt || !scratch || ((uintptr_t)x | (uintptr_t)scratch) % 16 != 0) { ishara_set_error("ishara_op_qkv_fwd: null or misaligned buffer (x, scratch: 16-byte aligned)"); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    size_t wt, wn, slab, total; int ldt, ldn;
+    op_shadow_layout(dt, d, 3 * d, wt, ldt, wn, ldn, slab, total, M);
+    char* sc = (char*)scratch;
+    HIP_CHECK_RET(hipMemsetAsync(sc, 0, slab, s));
+    CK(launch_make_shadow(dt, Wm, d, 3 * d, sc + wt, ldt, sc + wn, ldn, s));
+    OpArgs no;
+    EpiArgs eq; eq.mode = EPI_QKV; eq.q = q; eq.k = k; eq.vt = vt; eq.H = H; eq.dh = dh; eq.T = T; eq.head_major = head_major;
+    const void* A = x;
+    if (gamma && !ln_as_prologue(dt, M, 3 * d, d, ldt, gamma, beta, eps, nullptr, nullptr, nullptr, eq)) {      // the model's decision (ln_prologue)
+        size_t xn, mean, rstd, tot;
+        qkv_scratch_layout(B, T, H, dh, xn, mean, rstd, tot);
+        CK(launch_layernorm_fwd(dt, x, gamma, beta, eps, sc + xn, (float*)(sc + mean), (float*)(sc + rstd), M, d, s));
+        A = sc + xn;
+    }
+    eq.bias = bias;
+    return launch_gemm_nt(dt, dt, dt, OP_NONE, A, sc + wt, nullptr, M, 3 * d, d, ldt, no, eq, s);
+}
+// the head's classifier: fp32 logits [M, C] = x [M, K] @ W [K, C] + b through `route` (classifier_fwd; 0 = the model's choice)
+extern "C" int ishara_op_classifier_fwd(int32_t dt, const void* x, const float* Wm, const float* bias, float* logits, int32_t M, int32_t K, int32_t C,
+                                        int32_t route, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_classifier_fwd", dt, true);
+    if (route < CLS_AUTO || route > CLS_GEMM) { ishara_set_error("ishara_op_classifier_fwd: unknown route %d (0 auto, 1 A-stationary, 2 dense_narrow, 3 GEMM)", route); return -1; }
+    if (M < 1 || K < 1 || C < 1) { ishara_set_error("ishara_op_classifier_fwd: bad shape M=%d K=%d C=%d", M, K, C); return -1; }
+    const int r = route == CLS_AUTO ? cls_route_auto(dt, M, K, C) : route;
+    const char* why = nullptr;
+    if (r != CLS_GEMM && !dt_is16(dt)) why = "16-bit operands only";
+    else if (r == CLS_AS && (C > 64 || C % 4 != 0 || (K != 256 && K != 512))) why = "C <= 64, C % 4 == 0 and K 256 / 512 only";
+    else if (r == CLS_AS && g_force_regstage) why = "the A-stationary kernel is switched off (ishara_debug_force_regstage)";
+    else if (r == CLS_NARROW && (C > 64 || K % 32 != 0)) why = "C <= 64 and K % 32 == 0 only";
+    else if (r == CLS_GEMM && K % (dt_is16(dt) ? 8 : 4) != 0) why = "16-byte operand rows only";
+    if (why) { ishara_set_error("ishara_op_classifier_fwd: route %d does not take dt=%d M=%d K=%d C=%d: %s", r, dt, M, K, C, why); return -1; }
+    if (!x || !Wm || !logits || !scratch || ((uintptr_t)x | (uintptr_t)scratch) % 16 != 0) { ishara_set_error("ishara_op_classifier_fwd: null or misaligned buffer (x, scratch: 16-byte aligned)"); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    size_t wt, wn, slab, total; int ldt, ldn;
+    op_shadow_layout(dt, K, C, wt, ldt, wn, ldn, slab, total, M);      // rup(C, 128) >= 64 zero-filled shadow rows: the N = 64 A-stationary route reads them
+    char* sc = (char*)scratch;
+    HIP_CHECK_RET(hipMemsetAsync(sc, 0, slab, s));
+    CK(launch_make_shadow(dt, Wm, K, C, sc + wt, ldt, sc + wn, ldn, s));
+    return classifier_fwd(nullptr, r, dt, x, sc + wt, ldt, bias, logits, M, K, C, s);
+}
 // row log-softmax over fp32 logits and its backward: the output layer of the torch Squeezeformer (squeezeformer/model.py:448-449)
 extern "C" int ishara_op_log_softmax_fwd(const float* x, float* y, int32_t M, int32_t C, int32_t ld, ishara_stream s) { return launch_log_softmax_fwd(x, y, M, C, ld, (hipStream_t)s); }
 extern "C" int ishara_op_log_softmax_bwd(const float* dy, const float* y, float* dx, int32_t M, int32_t C, int32_t ld, ishara_stream s) { return launch_log_softmax_bwd(dy, y, dx, M, C, ld, (hipStream_t)s); }
 extern "C" int ishara_op_layernorm_fwd(int32_t dt, const void* x, const float* gamma, const float* beta, float eps, void* y, float* mean, float* rstd, int32_t M, int32_t C, ishara_stream s) {
+    OP_DT("ishara_op_layernorm_fwd", dt, true);
     return launch_layernorm_fwd(dt, x, gamma, beta, eps, y, mean, rstd, M, C, (hipStream_t)s);
 }
 extern "C" int ishara_op_layernorm_bwd(int32_t dt, const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, void* dx, float* dgamma, float* dbeta, int32_t M, int32_t C, ishara_stream s) {
+    OP_DT("ishara_op_layernorm_bwd", dt, false);
     return launch_layernorm_bwd(dt, dy, x, mean, rstd, gamma, nullptr, dx, dgamma, dbeta, nullptr, M, C, (hipStream_t)s);
 }
 extern "C" int ishara_op_dwconv_fwd(int32_t dt, int32_t inop, const void* x, const float* w, const float* bias, void* y, float* ssum, float* ssq,
                                     int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, ishara_stream s) {
+    OP_DT("ishara_op_dwconv_fwd", dt, true);
     return launch_dwconv_fwd(dt, inop, x, w, bias, y, ssum, ssq, nullptr, B, T, C, k, padl, (hipStream_t)s);
 }
 // the same with caller scratch for the deterministic statistics (partial rows summed in a fixed order): the path the model takes, and the
@@ -1179,11 +1291,13 @@ extern "C" int ishara_op_dwconv_fwd(int32_t dt, int32_t inop, const void* x, con
 extern "C" int64_t ishara_op_dwconv_fwd_scratch_bytes(int32_t B, int32_t T, int32_t C) { return (int64_t)(dwconv_fwd_scratch_floats(B, T, C) * sizeof(float)); }
 extern "C" int ishara_op_dwconv_fwd_ex(int32_t dt, int32_t inop, const void* x, const float* w, const float* bias, void* y, float* ssum, float* ssq,
                                        void* scratch, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, ishara_stream s) {
+    OP_DT("ishara_op_dwconv_fwd_ex", dt, true);
     return launch_dwconv_fwd(dt, inop, x, w, bias, y, ssum, ssq, (float*)scratch, B, T, C, k, padl, (hipStream_t)s);
 }
 extern "C" int64_t ishara_op_dwconv_scratch_bytes(int32_t C, int32_t k) { return (int64_t)(dwconv_bwd_scratch_floats(C, k) * sizeof(float)); }
 extern "C" int ishara_op_dwconv_bwd(int32_t dt, int32_t inop, const void* dy, const void* x, const float* w, void* dx, float* dw, float* dbias,
                                     void* scratch, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, ishara_stream s) {
+    OP_DT("ishara_op_dwconv_bwd", dt, false);
     return launch_dwconv_bwd(dt, inop, dy, x, w, dx, dw, dbias, (float*)scratch, B, T, C, k, padl, (hipStream_t)s);
 }
 // scratch layout: q | k | vt | lse | delta
@@ -1202,15 +1316,19 @@ static void attn_scratch(char* sc, int dt, int B, int H, int T, int dh, void*& q
 }
 extern "C" int ishara_op_attn_fwd(int32_t dt, const void* qkv, void* o, int32_t B, int32_t H, int32_t T, int32_t dh, float scale,
                                   uint32_t seed, uint32_t site, float rate, int32_t impl, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_attn_fwd", dt, true);
+    if (dt == DT_F16 && rate > 0.f) { ishara_set_error("ishara_op_attn_fwd: ISHARA_F16 is inference-only: no attention dropout (rate %g)", rate); return -1; }
     hipStream_t s = (hipStream_t)st;
     void *q, *k, *vt; float *lse, *delta; uint32_t* maskw;
     attn_scratch((char*)scratch, dt, B, H, T, dh, q, k, vt, lse, delta, maskw);
     if (dt == DT_BF16) hipLaunchKernelGGL(qkv_split_kernel<bf16>, dim3(1024), dim3(256), 0, s, (const bf16*)qkv, (bf16*)q, (bf16*)k, (bf16*)vt, B, H, T, dh);
+    else if (dt == DT_F16) hipLaunchKernelGGL(qkv_split_kernel<f16>, dim3(1024), dim3(256), 0, s, (const f16*)qkv, (f16*)q, (f16*)k, (f16*)vt, B, H, T, dh);
     else hipLaunchKernelGGL(qkv_split_kernel<float>, dim3(1024), dim3(256), 0, s, (const float*)qkv, (float*)q, (float*)k, (float*)vt, B, H, T, dh);
     return launch_attn_fwd(dt, q, k, vt, o, lse, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), impl, maskw, s);
 }
 extern "C" int ishara_op_attn_bwd(int32_t dt, const void* o, const void* dout, void* dqkv, int32_t B, int32_t H, int32_t T, int32_t dh, float scale,
                                   uint32_t seed, uint32_t site, float rate, int32_t impl, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_attn_bwd", dt, false);
     hipStream_t s = (hipStream_t)st;
     void *q, *k, *vt; float *lse, *delta; uint32_t* maskw;
     attn_scratch((char*)scratch, dt, B, H, T, dh, q, k, vt, lse, delta, maskw);

@@ -135,3 +135,16 @@ def check(rc: int, what: str = ""):
 def ptr(t):
     """Device/host pointer of a torch tensor (or None)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream():
+    """The current torch stream of the current device, as the library's ishara_stream."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def aligned(nbytes: int, device):
+    """`nbytes` of device memory at a 256-byte aligned address: (the tensor that owns it, the aligned pointer)."""
+    import torch
+    t = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
+    return t, C.c_void_p(t.data_ptr() + (-t.data_ptr()) % 256)

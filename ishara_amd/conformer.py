@@ -21,11 +21,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IsharaError
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._handle import Handle
+from ._lib import IsharaError, stream as _stream
 
 
 def head_major_perm(dim: int, heads: int) -> np.ndarray:
@@ -103,28 +100,16 @@ class _EncoderFn(torch.autograd.Function):
         return dx, enc.grads[:enc.n_train].clone(), None
 
 
-class _TorchFamilyEncoder:
+class _TorchFamilyEncoder(Handle):
     """Shared host side of the two torch encoder families: one library handle, flat parameter / gradient buffers, state_dict in
     the reference's keys and layouts, torch.autograd integration.  Subclasses fill an `_lib.Config` and a layout map."""
 
     def _create(self, cfg, layout_map, in_features, seq_len, max_batch, device, seed):
-        self._lib = _lib.load()
-        self._cfg = cfg
-        self.T, self.F_in, self.max_batch = seq_len, in_features, max_batch
+        self._create_handle(cfg)
+        self.T, self.F_in = seq_len, in_features
         self._map = layout_map
-        self._h = C.c_void_p()
-        _lib.check(self._lib.ishara_create(C.byref(cfg), C.byref(self._h)), "ishara_create")
-        self.n_total = int(self._lib.ishara_param_total(self._h))
-        self.n_train = int(self._lib.ishara_param_trainable(self._h))
-        self.entries = []
-        for i in range(self._lib.ishara_param_entries(self._h)):
-            name, nd, sh, off, tr = C.c_char_p(), C.c_int32(), (C.c_int64 * 2)(), C.c_int64(), C.c_int32()
-            _lib.check(self._lib.ishara_param_info(self._h, i, C.byref(name), C.byref(nd), C.byref(sh), C.byref(off), C.byref(tr)))
-            shape = (int(sh[0]),) if nd.value == 1 else (int(sh[0]), int(sh[1]))
-            self.entries.append((name.value.decode(), shape, int(off.value), bool(tr.value)))
         self.T_out = int(self._lib.ishara_encoder_output_frames(self._h))
         self.training = True
-        self.device = None
         self._seed, self._steps = seed * 7919 + 17, 0
         self._gen = 0                     # forward passes so far (autograd graphs check it: the library saves ONE pass)
         self._synced_version = -1         # `flat._version` at the last ishara_sync_weights
@@ -133,31 +118,10 @@ class _TorchFamilyEncoder:
 
     # ------------------------------------------------------------------ device state
     def _to_device(self, device, seed):
-        if not torch.cuda.is_available():
-            raise IsharaError("ishara_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path")
-        self.device = dev = torch.device(device)
-        torch.cuda.set_device(dev)
-        self.params = torch.zeros(self.n_total, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros(self.n_total, dtype=torch.float32, device=dev)
-        self.opt_m = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
-        self.opt_v = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
-        self.opt_slow = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
-        wsb = int(self._lib.ishara_workspace_bytes(self._h))
-        self.workspace = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
-        ws_ptr = self.workspace.data_ptr() + (-self.workspace.data_ptr()) % 256
-        _lib.check(self._lib.ishara_bind(self._h, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.opt_m), _lib.ptr(self.opt_v),
-                                         _lib.ptr(self.opt_slow), C.c_void_p(ws_ptr), wsb), "ishara_bind")
+        self._bind_device(device)
         # the flat trainable vector as a leaf torch optimisers can step; it aliases the library's parameter buffer
         self.flat = torch.nn.Parameter(self.params[:self.n_train], requires_grad=True)
         self.load_state_dict(self._default_state(seed))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ishara_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ nn.Module surface
     def train(self, mode: bool = True):

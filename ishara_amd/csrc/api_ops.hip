@@ -1,0 +1,283 @@
+// Entry points of libishara_hip.so that need no model handle: decoding, CTC, preprocessing, clip batches, scoring, the debug switches
+// and the ishara_op_* operator entry points the tests drive single kernels through (with the two kernels only they use).
+#include "model_types.h"
+
+__global__ void dropout_mask_kernel(float* out, int rows, int cols, DropSpec d) {
+    const size_t n = (size_t)rows * cols;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / cols), c = (uint32_t)(i % cols);
+        out[i] = (d.thr == 0u || rng_keep(rng_row_key(d.key, r), c, d.thr)) ? d.scale : 0.f;
+    }
+}
+// packed qkv [M,3d] (head-major) -> q,k [B,H,T,dh], vt [B,H,dh,T]   (operator tests only)
+template <typename T>
+__global__ void qkv_split_kernel(const T* qkv, T* q, T* k, T* vt, int B, int H, int Tn, int dh) {
+    const int d = H * dh;
+    const size_t n = (size_t)B * Tn * 3 * d;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t m = i / (3 * d);
+        const int col = (int)(i - m * 3 * d);
+        const int h = col / (3 * dh), w = col - h * 3 * dh, part = w / dh, e = w - part * dh;
+        const int b = (int)(m / Tn), t = (int)(m - (size_t)b * Tn);
+        const T v = qkv[i];
+        if (part == 0) q[((size_t)(b * H + h) * Tn + t) * dh + e] = v;
+        else if (part == 1) k[((size_t)(b * H + h) * Tn + t) * dh + e] = v;
+        else vt[((size_t)(b * H + h) * dh + e) * Tn + t] = v;
+    }
+}
+
+// ------------------------------------------------------------------ stand-alone entry points
+extern "C" int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t* out_idx, int32_t* out_len, ishara_stream s) {
+    if (T > 4096) { ishara_set_error("greedy_decode: T too large"); return -1; }
+    return launch_greedy_decode(logits, B, T, C, blank, out_idx, out_len, (hipStream_t)s);
+}
+extern "C" int64_t ishara_ctc_workspace_bytes(int32_t B, int32_t T, int32_t L) { return (int64_t)(ctc_workspace_floats(B, T, L) * sizeof(float)); }
+extern "C" int ishara_ctc_loss(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                               float* nll, float* dlogits, float grad_scale, void* ws, ishara_stream s) {
+    return launch_ctc(logits, labels, B, T, C, L, blank, nll, dlogits, grad_scale, (float*)ws, (hipStream_t)s);
+}
+extern "C" int ishara_dropout_mask(uint32_t seed, uint32_t site, int32_t rows, int32_t cols, float rate, float* out, ishara_stream s) {
+    const DropSpec d = make_drop(seed, site, rate, true);
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(1024), dim3(256), 0, (hipStream_t)s, out, rows, cols, d);
+    return launch_rc();
+}
+
+static int g_dbg_epi = 0;
+// bit 0: 1 register-staged NT kernel / 0 LDS-DMA NT kernel; bit 1: 1 register-transposing TN kernel; bit 2: 1 LDS-tiled dwconv; bit 3: 1 LDS-DMA 64x128 NT kernel; bits 4-7: NT ablation; bits 8-12: TN ablation; bit 13: 1 tile NT kernel instead of the A-stationary one; bits 14-15: wgrad workgroups auto / 256 / 512 / 768; bit 16: 1 two-kernel attention backward instead of the one-pass kernel
+// A-stationary GEMM switches (gemm_as.hip as_default_flags: 1 paired half-line stores, 2 non-temporal side outputs, 16 chunked K = 256 form); -1: library default
+extern "C" int ishara_debug_set_as_flags(int32_t flags) { g_as_flags_override = flags; return 0; }
+extern "C" int ishara_debug_set_nt_big(int32_t on) { g_nt_big = on; return 0; }
+extern "C" int ishara_debug_force_regstage(int32_t on) { g_force_regstage = (on & 1) ? 1 : ((on >> 3) & 1 ? 2 : ((on >> 13) & 1 ? 3 : 0)); g_dbg_epi = (on >> 4) & 15; g_dbg_tn = (on >> 8) & 31; g_force_tn_regstage = (on >> 1) & 1; g_force_dw_lds = (on >> 2) & 1; { const int tb = (on >> 14) & 3; g_tn_blocks = tb == 1 ? 256 : (tb == 2 ? 512 : (tb == 3 ? 768 : 0)); } g_attn_bwd_two_pass = (on >> 16) & 1; return 0; }
+
+extern "C" int ishara_preprocess(const float* raw, const int32_t* n_frames, int32_t max_frames, const float* mean, const float* stdv,
+                                 float* out, int32_t T, ishara_stream s) {
+    if (max_frames <= 0 || max_frames > 8192) { ishara_set_error("ishara_preprocess: max_frames %d unsupported (1..8192)", max_frames); return -1; }
+    return launch_preprocess(raw, n_frames, max_frames, mean, stdv, out, T, (hipStream_t)s);
+}
+extern "C" int ishara_preprocess_batch(const float* raw, int64_t n_total, const int64_t* offsets, int32_t B, int32_t max_frames,
+                                       const float* mean, const float* stdv, float* out, int32_t T, ishara_stream s) {
+    if (max_frames <= 0 || max_frames > 8192) { ishara_set_error("ishara_preprocess_batch: max_frames %d unsupported (1..8192)", max_frames); return -1; }
+    if (B < 0 || B > 65535 || T < 1 || T > 4096) { ishara_set_error("ishara_preprocess_batch: B=%d T=%d unsupported (0 <= B <= 65535, 1 <= T <= 4096)", B, T); return -1; }
+    if (n_total < 0) { ishara_set_error("ishara_preprocess_batch: n_total %lld < 0", (long long)n_total); return -1; }
+    if (B > 0 && (!offsets || !mean || !stdv || !out || (n_total > 0 && !raw))) { ishara_set_error("ishara_preprocess_batch: null raw / offsets / mean / stdv / out"); return -1; }
+    if (((uintptr_t)raw | (uintptr_t)out) % 16) { ishara_set_error("ishara_preprocess_batch: raw and out must be 16-byte aligned"); return -1; }
+    return launch_preprocess_batch(raw, n_total, offsets, B, max_frames, mean, stdv, out, T, (hipStream_t)s);
+}
+extern "C" int ishara_edit_distance(const int32_t* out_idx, const int32_t* out_len, int32_t B, int32_t T, const int32_t* targets, int32_t L,
+                                    int32_t* dist, int32_t* tlen, ishara_stream s) {
+    if (L < 1 || L > SCORE_MAX_L) { ishara_set_error("ishara_edit_distance: target length L=%d unsupported (1..%d: one wavefront lane per target symbol)", L, SCORE_MAX_L); return -1; }
+    if (B < 0 || T < 1 || T > 4096) { ishara_set_error("ishara_edit_distance: B=%d T=%d unsupported (B >= 0, 1 <= T <= 4096)", B, T); return -1; }
+    if (B > 0 && (!out_idx || !out_len || !targets || !dist || !tlen)) { ishara_set_error("ishara_edit_distance: null argument"); return -1; }
+    return launch_edit_distance(out_idx, out_len, B, T, targets, L, dist, tlen, (hipStream_t)s);
+}
+extern "C" int64_t ishara_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t C, int32_t beam_width) {
+    (void)C;
+    if (B < 0 || T < 1 || T > 4096 || beam_width < 1 || beam_width > 32) return -1;
+    return (int64_t)B * (int64_t)ctc_beam_workspace_words(T, beam_width) * 4;
+}
+extern "C" int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
+                                      const float* lm, float alpha, float beta, void* workspace,
+                                      int32_t* out_idx, int32_t* out_len, float* out_score, ishara_stream s) {
+    if (C < 2 || C > 64) { ishara_set_error("ishara_ctc_beam_decode: C=%d unsupported (2..64: one lane per class)", C); return -1; }
+    if (blank < 0 || blank >= C) { ishara_set_error("ishara_ctc_beam_decode: blank %d outside 0..%d", blank, C - 1); return -1; }
+    if (beam_width < 1 || beam_width > 32) { ishara_set_error("ishara_ctc_beam_decode: beam_width %d unsupported (1..32)", beam_width); return -1; }
+    if (nbest < 1 || nbest > beam_width) { ishara_set_error("ishara_ctc_beam_decode: nbest %d outside 1..beam_width=%d", nbest, beam_width); return -1; }
+    if (B < 0 || B > 2147483647 / 2 || T < 1 || T > 4096) { ishara_set_error("ishara_ctc_beam_decode: B=%d T=%d unsupported (B >= 0, 1 <= T <= 4096)", B, T); return -1; }
+    if (!(alpha == alpha && beta == beta) || alpha - alpha != 0.0f || beta - beta != 0.0f) { ishara_set_error("ishara_ctc_beam_decode: alpha and beta must be finite"); return -1; }
+    if (B > 0 && (!logits || !workspace || !out_idx || !out_len || !out_score)) { ishara_set_error("ishara_ctc_beam_decode: null argument"); return -1; }
+    if ((uintptr_t)workspace % 4) { ishara_set_error("ishara_ctc_beam_decode: workspace must be 4-byte aligned"); return -1; }
+    return launch_ctc_beam(logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len, out_score, (hipStream_t)s);
+}
+extern "C" int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
+                                 float* x, ishara_stream s) {
+    if (B < 0 || T < 1 || T > CLIP_MAX_T) { ishara_set_error("ishara_clip_batch: B=%d T=%d unsupported (B >= 0, 1 <= T <= %d)", B, T, CLIP_MAX_T); return -1; }
+    if (layout != ISHARA_LAYOUT_FLAT && layout != ISHARA_LAYOUT_HANDS_LIPS_XY) { ishara_set_error("ishara_clip_batch: unknown layout %d", layout); return -1; }
+    if (B > 0 && (!clips || !x)) { ishara_set_error("ishara_clip_batch: null clips / x"); return -1; }
+    if (((uintptr_t)raw | (uintptr_t)x) % 16) { ishara_set_error("ishara_clip_batch: raw and x must be 16-byte aligned"); return -1; }
+    return launch_clip_batch(raw, clips, B, T, layout, x, (hipStream_t)s);
+}
+
+// ---- operator tests: dense
+// every operator entry point checks its dtype first: ISHARA_F32 / BF16 / F16 known, F16 only where an fp16 kernel exists (forward /
+// inference: the backward operators refuse it); nothing is launched for a refused call
+static bool op_dt_ok(const char* op, int dt, bool f16_ok) {
+    if (dt != DT_F32 && dt != DT_BF16 && dt != DT_F16) { ishara_set_error("%s: unknown dtype %d (ISHARA_F32 = 0, ISHARA_BF16 = 1, ISHARA_F16 = 2)", op, dt); return false; }
+    if (dt == DT_F16 && !f16_ok) { ishara_set_error("%s: ISHARA_F16 is inference-only (no fp16 backward kernels)", op); return false; }
+    return true;
+}
+#define OP_DT(op, dt, f16_ok) do { if (!op_dt_ok(op, dt, f16_ok)) return -1; } while (0)
+// the weight shadows of one Dense [K, N] at the head of an operator's scratch: Wt | Wn | wgrad slab (byte offsets wt, wn, slab; total bytes)
+struct OpShadow {
+    size_t wt, wn, slab, total; int ldt, ldn;
+    OpShadow(int dt, int K, int N, int M) {
+        const int bk = dt_is16(dt) ? 64 : 32;      // the K tile the model's shadows use (plan_shadow): 64 for both 16-bit types
+        const size_t es = dt_size(dt);
+        ldt = (int)rup(K, bk); ldn = (int)rup(N, bk);
+        wt = 0;
+        wn = rup(rup(N, 128) * (size_t)ldt * es, 256);
+        slab = wn + rup(rup(K, 128) * (size_t)ldn * es, 256);
+        total = slab + gemm_tn_slab_floats(M, K, N, dt) * sizeof(float);
+    }
+    // zero-fills both shadows (their padding) and writes W into them
+    int build(int dt, const float* Wm, int K, int N, char* sc, hipStream_t s) const {
+        HIP_CHECK_RET(hipMemsetAsync(sc, 0, slab, s));
+        return launch_make_shadow(dt, Wm, K, N, sc + wt, ldt, sc + wn, ldn, s);
+    }
+};
+extern "C" int64_t ishara_op_scratch_bytes(int32_t M, int32_t K, int32_t N) {
+    return (int64_t)OpShadow(DT_F32, K, N, M).total;      // (the f32 layout is the largest: 4-byte elements, K tile >= half the 16-bit one)
+}
+extern "C" int ishara_op_dense_fwd(int32_t dt, const void* x, const float* Wm, const float* bias, void* y, int32_t M, int32_t K, int32_t N, int32_t act, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_dense_fwd", dt, true);
+    hipStream_t s = (hipStream_t)st;
+    const OpShadow sh(dt, K, N, M);
+    char* sc = (char*)scratch;
+    CK(sh.build(dt, Wm, K, N, sc, s));
+    OpArgs no; EpiArgs ea; ea.bias = bias; ea.act = act; ea.dbg = g_dbg_epi;
+    return launch_gemm_nt(dt, dt, dt, OP_NONE, x, sc + sh.wt, y, M, N, K, sh.ldt, no, ea, s);
+}
+// y = act(x @ W + b) + resid
+extern "C" int ishara_op_dense_fwd_ex(int32_t dt, const void* x, const float* Wm, const float* bias, const void* resid, void* y,
+                                      int32_t M, int32_t K, int32_t N, int32_t act, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_dense_fwd_ex", dt, true);
+    hipStream_t s = (hipStream_t)st;
+    const OpShadow sh(dt, K, N, M);
+    char* sc = (char*)scratch;
+    CK(sh.build(dt, Wm, K, N, sc, s));
+    OpArgs no; EpiArgs ea; ea.bias = bias; ea.act = act; ea.resid = resid; ea.dbg = g_dbg_epi;
+    return launch_gemm_nt(dt, dt, dt, OP_NONE, x, sc + sh.wt, y, M, N, K, sh.ldt, no, ea, s);
+}
+extern "C" int ishara_op_dense_bwd(int32_t dt, const void* x, const float* Wm, const void* dy, void* dx, float* dW, float* db,
+                                   int32_t M, int32_t K, int32_t N, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_dense_bwd", dt, false);
+    hipStream_t s = (hipStream_t)st;
+    const OpShadow sh(dt, K, N, M);
+    char* sc = (char*)scratch;
+    CK(sh.build(dt, Wm, K, N, sc, s));
+    OpArgs no; EpiArgs ea;
+    if (dx) CK(launch_gemm_nt(dt, dt, dt, OP_NONE, dy, sc + sh.wn, dx, M, K, N, sh.ldn, no, ea, s));
+    return launch_gemm_tn(dt, dt, dt, OP_NONE, OP_NONE, x, dy, dW, db, (float*)(sc + sh.slab), M, K, N, no, no, s);
+}
+// QKV projection of the attention module at inference (mhsa_fwd): LayerNorm (gamma NULL: none), x @ W + b, and the EPI_QKV scatter into
+// q, k [B,H,T,dh] and vt [B,H,dh,T].  scratch: the weight shadow, then the LayerNorm output and its row statistics where the LayerNorm
+// runs as a kernel of its own
+static void qkv_scratch_layout(int B, int T, int H, int dh, size_t& xn, size_t& mean, size_t& rstd, size_t& total) {
+    const int M = B * T, d = H * dh;
+    xn = rup(OpShadow(DT_F32, d, 3 * d, M).total, 256);
+    mean = xn + rup((size_t)M * d * 4, 256);
+    rstd = mean + rup((size_t)M * 4, 256);
+    total = rstd + rup((size_t)M * 4, 256);
+}
+extern "C" int64_t ishara_op_qkv_scratch_bytes(int32_t B, int32_t T, int32_t H, int32_t dh) {
+    if (B < 1 || T < 1 || H < 1 || dh < 1) return -1;
+    size_t xn, mean, rstd, total;
+    qkv_scratch_layout(B, T, H, dh, xn, mean, rstd, total);
+    return (int64_t)total;
+}
+extern "C" int ishara_op_qkv_fwd(int32_t dt, const void* x, const float* gamma, const float* beta, float eps, const float* Wm, const float* bias,
+                                 void* q, void* k, void* vt, int32_t B, int32_t T, int32_t H, int32_t dh, int32_t head_major, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_qkv_fwd", dt, true);
+    if (B < 1 || T < 1 || H < 1 || dh < 1 || T % 8 != 0 || dh % 8 != 0 || (head_major != 0 && head_major != 1)) {
+        ishara_set_error("ishara_op_qkv_fwd: B=%d T=%d H=%d dh=%d head_major=%d unsupported (T, dh multiples of 8; head_major 0 / 1)", B, T, H, dh, head_major); return -1;
+    }
+    const int d = H * dh, M = B * T;
+    if ((gamma != nullptr) != (beta != nullptr) || (gamma && d > 512)) { ishara_set_error("ishara_op_qkv_fwd: LayerNorm needs both gamma and beta and H*dh <= 512 (H*dh=%d)", d); return -1; }
+    if (!x || !Wm || !q || !k || !vt || !scratch || ((uintptr_t)x | (uintptr_t)scratch) % 16 != 0) { ishara_set_error("ishara_op_qkv_fwd: null or misaligned buffer (x, scratch: 16-byte aligned)"); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    const OpShadow sh(dt, d, 3 * d, M);
+    char* sc = (char*)scratch;
+    CK(sh.build(dt, Wm, d, 3 * d, sc, s));
+    OpArgs no;
+    EpiArgs eq; eq.mode = EPI_QKV; eq.q = q; eq.k = k; eq.vt = vt; eq.H = H; eq.dh = dh; eq.T = T; eq.head_major = head_major;
+    const void* A = x;
+    if (gamma && !ln_as_prologue(dt, M, 3 * d, d, sh.ldt, gamma, beta, eps, nullptr, nullptr, nullptr, eq)) {      // the model's decision (ln_prologue)
+        size_t xn, mean, rstd, tot;
+        qkv_scratch_layout(B, T, H, dh, xn, mean, rstd, tot);
+        CK(launch_layernorm_fwd(dt, x, gamma, beta, eps, sc + xn, (float*)(sc + mean), (float*)(sc + rstd), M, d, s));
+        A = sc + xn;
+    }
+    eq.bias = bias;
+    return launch_gemm_nt(dt, dt, dt, OP_NONE, A, sc + sh.wt, nullptr, M, 3 * d, d, sh.ldt, no, eq, s);
+}
+// the head's classifier: fp32 logits [M, C] = x [M, K] @ W [K, C] + b through `route` (classifier_fwd; 0 = the model's choice)
+extern "C" int ishara_op_classifier_fwd(int32_t dt, const void* x, const float* Wm, const float* bias, float* logits, int32_t M, int32_t K, int32_t C,
+                                        int32_t route, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_classifier_fwd", dt, true);
+    if (route < CLS_AUTO || route > CLS_GEMM) { ishara_set_error("ishara_op_classifier_fwd: unknown route %d (0 auto, 1 A-stationary, 2 dense_narrow, 3 GEMM)", route); return -1; }
+    if (M < 1 || K < 1 || C < 1) { ishara_set_error("ishara_op_classifier_fwd: bad shape M=%d K=%d C=%d", M, K, C); return -1; }
+    const int r = route == CLS_AUTO ? cls_route_auto(dt, M, K, C) : route;
+    const char* why = nullptr;
+    if (r != CLS_GEMM && !dt_is16(dt)) why = "16-bit operands only";
+    else if (r == CLS_AS && (C > 64 || C % 4 != 0 || (K != 256 && K != 512))) why = "C <= 64, C % 4 == 0 and K 256 / 512 only";
+    else if (r == CLS_AS && g_force_regstage) why = "the A-stationary kernel is switched off (ishara_debug_force_regstage)";
+    else if (r == CLS_NARROW && (C > 64 || K % 32 != 0)) why = "C <= 64 and K % 32 == 0 only";
+    else if (r == CLS_GEMM && K % (dt_is16(dt) ? 8 : 4) != 0) why = "16-byte operand rows only";
+    if (why) { ishara_set_error("ishara_op_classifier_fwd: route %d does not take dt=%d M=%d K=%d C=%d: %s", r, dt, M, K, C, why); return -1; }
+    if (!x || !Wm || !logits || !scratch || ((uintptr_t)x | (uintptr_t)scratch) % 16 != 0) { ishara_set_error("ishara_op_classifier_fwd: null or misaligned buffer (x, scratch: 16-byte aligned)"); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    const OpShadow sh(dt, K, C, M);      // rup(C, 128) >= 64 zero-filled shadow rows: the N = 64 A-stationary route reads them
+    char* sc = (char*)scratch;
+    CK(sh.build(dt, Wm, K, C, sc, s));
+    return classifier_fwd(nullptr, r, dt, x, sc + sh.wt, sh.ldt, bias, logits, M, K, C, s);
+}
+// row log-softmax over fp32 logits and its backward: the output layer of the torch Squeezeformer (squeezeformer/model.py:448-449)
+extern "C" int ishara_op_log_softmax_fwd(const float* x, float* y, int32_t M, int32_t C, int32_t ld, ishara_stream s) { return launch_log_softmax_fwd(x, y, M, C, ld, (hipStream_t)s); }
+extern "C" int ishara_op_log_softmax_bwd(const float* dy, const float* y, float* dx, int32_t M, int32_t C, int32_t ld, ishara_stream s) { return launch_log_softmax_bwd(dy, y, dx, M, C, ld, (hipStream_t)s); }
+extern "C" int ishara_op_layernorm_fwd(int32_t dt, const void* x, const float* gamma, const float* beta, float eps, void* y, float* mean, float* rstd, int32_t M, int32_t C, ishara_stream s) {
+    OP_DT("ishara_op_layernorm_fwd", dt, true);
+    return launch_layernorm_fwd(dt, x, gamma, beta, eps, y, mean, rstd, M, C, (hipStream_t)s);
+}
+extern "C" int ishara_op_layernorm_bwd(int32_t dt, const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, void* dx, float* dgamma, float* dbeta, int32_t M, int32_t C, ishara_stream s) {
+    OP_DT("ishara_op_layernorm_bwd", dt, false);
+    return launch_layernorm_bwd(dt, dy, x, mean, rstd, gamma, nullptr, dx, dgamma, dbeta, nullptr, M, C, (hipStream_t)s);
+}
+extern "C" int ishara_op_dwconv_fwd(int32_t dt, int32_t inop, const void* x, const float* w, const float* bias, void* y, float* ssum, float* ssq,
+                                    int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, ishara_stream s) {
+    OP_DT("ishara_op_dwconv_fwd", dt, true);
+    return launch_dwconv_fwd(dt, inop, x, w, bias, y, ssum, ssq, nullptr, B, T, C, k, padl, (hipStream_t)s);
+}
+// the same with caller scratch for the deterministic statistics (partial rows summed in a fixed order): the path the model takes, and the
+// only one that reaches the streaming K = 11 / 15 kernel at B > 8
+extern "C" int64_t ishara_op_dwconv_fwd_scratch_bytes(int32_t B, int32_t T, int32_t C) { return (int64_t)(dwconv_fwd_scratch_floats(B, T, C) * sizeof(float)); }
+extern "C" int ishara_op_dwconv_fwd_ex(int32_t dt, int32_t inop, const void* x, const float* w, const float* bias, void* y, float* ssum, float* ssq,
+                                       void* scratch, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, ishara_stream s) {
+    OP_DT("ishara_op_dwconv_fwd_ex", dt, true);
+    return launch_dwconv_fwd(dt, inop, x, w, bias, y, ssum, ssq, (float*)scratch, B, T, C, k, padl, (hipStream_t)s);
+}
+extern "C" int64_t ishara_op_dwconv_scratch_bytes(int32_t C, int32_t k) { return (int64_t)(dwconv_bwd_scratch_floats(C, k) * sizeof(float)); }
+extern "C" int ishara_op_dwconv_bwd(int32_t dt, int32_t inop, const void* dy, const void* x, const float* w, void* dx, float* dw, float* dbias,
+                                    void* scratch, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, ishara_stream s) {
+    OP_DT("ishara_op_dwconv_bwd", dt, false);
+    return launch_dwconv_bwd(dt, inop, dy, x, w, dx, dw, dbias, (float*)scratch, B, T, C, k, padl, (hipStream_t)s);
+}
+// scratch layout: q | k | vt | lse | delta | maskw (q, k, vt sized for 4-byte elements whatever the dtype)
+struct AttnScratch {
+    void *q, *k, *vt; float *lse, *delta; uint32_t* maskw; size_t total;
+    AttnScratch(char* sc, int B, int H, int T, int dh) {
+        const size_t seg = rup((size_t)B * H * T * dh * 4, 256), row = rup((size_t)B * H * T * 4, 256);
+        q = sc; k = sc + seg; vt = sc + 2 * seg;
+        lse = (float*)(sc + 3 * seg);
+        delta = (float*)(sc + 3 * seg + row);
+        maskw = (uint32_t*)(sc + 3 * seg + 2 * row);
+        total = 3 * seg + 2 * row + rup(attn_mask_words(B, H, T) * 4, 256);
+    }
+};
+extern "C" int64_t ishara_op_attn_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh) { return (int64_t)AttnScratch(nullptr, B, H, T, dh).total; }
+extern "C" int ishara_op_attn_fwd(int32_t dt, const void* qkv, void* o, int32_t B, int32_t H, int32_t T, int32_t dh, float scale,
+                                  uint32_t seed, uint32_t site, float rate, int32_t impl, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_attn_fwd", dt, true);
+    if (dt == DT_F16 && rate > 0.f) { ishara_set_error("ishara_op_attn_fwd: ISHARA_F16 is inference-only: no attention dropout (rate %g)", rate); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    const AttnScratch a((char*)scratch, B, H, T, dh);
+    if (dt == DT_BF16) hipLaunchKernelGGL(qkv_split_kernel<bf16>, dim3(1024), dim3(256), 0, s, (const bf16*)qkv, (bf16*)a.q, (bf16*)a.k, (bf16*)a.vt, B, H, T, dh);
+    else if (dt == DT_F16) hipLaunchKernelGGL(qkv_split_kernel<f16>, dim3(1024), dim3(256), 0, s, (const f16*)qkv, (f16*)a.q, (f16*)a.k, (f16*)a.vt, B, H, T, dh);
+    else hipLaunchKernelGGL(qkv_split_kernel<float>, dim3(1024), dim3(256), 0, s, (const float*)qkv, (float*)a.q, (float*)a.k, (float*)a.vt, B, H, T, dh);
+    return launch_attn_fwd(dt, a.q, a.k, a.vt, o, a.lse, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), impl, a.maskw, s);
+}
+extern "C" int ishara_op_attn_bwd(int32_t dt, const void* o, const void* dout, void* dqkv, int32_t B, int32_t H, int32_t T, int32_t dh, float scale,
+                                  uint32_t seed, uint32_t site, float rate, int32_t impl, void* scratch, ishara_stream st) {
+    OP_DT("ishara_op_attn_bwd", dt, false);
+    hipStream_t s = (hipStream_t)st;
+    const AttnScratch a((char*)scratch, B, H, T, dh);
+    return launch_attn_bwd(dt, a.q, a.k, a.vt, o, dout, a.lse, a.delta, dqkv, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), 1, impl, a.maskw, s);
+}

@@ -32,12 +32,12 @@ static int grid_for(size_t n8) { const size_t g = (n8 + 255) / 256; return (int)
 int r5_from_f32(int dt, const float* x, void* y, size_t n, hipStream_t s) {
     if (dt == DT_BF16) hipLaunchKernelGGL(r5_from_f32_kernel<bf16>, dim3(grid_for(n / 8)), dim3(256), 0, s, x, (bf16*)y, n / 8);
     else hipLaunchKernelGGL(r5_from_f32_kernel<float>, dim3(grid_for(n / 8)), dim3(256), 0, s, x, (float*)y, n / 8);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 int r5_to_f32(int dt, const void* x, float* y, size_t n, hipStream_t s) {
     if (dt == DT_BF16) hipLaunchKernelGGL(r5_to_f32_kernel<bf16>, dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16*)x, y, n / 8);
     else hipLaunchKernelGGL(r5_to_f32_kernel<float>, dim3(grid_for(n / 8)), dim3(256), 0, s, (const float*)x, y, n / 8);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 
 static const float R5_EPS = 1e-5f;      // nn.LayerNorm / nn.BatchNorm1d default eps
@@ -49,22 +49,12 @@ int r5_validate(const ishara_config& c) {
     return 0;
 }
 
-static DenseW dense_named(ishara_model* m, const std::string& wname, const std::string& bname, int K, int N) {
-    DenseW w; w.K = K; w.N = N;
-    w.w = m->addp(wname, K, N, true);
-    w.b = m->addp(bname, N, 0, true);
-    return w;
-}
-static Norm norm_named(ishara_model* m, const std::string& p, int c) {
-    Norm n; n.gamma = m->addp(p + ".weight", c, 0, true); n.beta = m->addp(p + ".bias", c, 0, true);
-    return n;
-}
 static R5FFN r5_build_ffn(ishara_model* m, const std::string& p) {
     R5FFN f;
     const int d = m->d, e = m->cfg.expansion_factor;
-    f.W1 = dense_named(m, p + ".linear1.weight", p + ".linear1.bias", d, d * e);
-    f.W2 = dense_named(m, p + ".linear2.weight", p + ".linear2.bias", d * e, d);
-    f.ln = norm_named(m, p + ".layer_norm", d);
+    f.W1 = m->dense_named(p + ".linear1.weight", p + ".linear1.bias", d, d * e);
+    f.W2 = m->dense_named(p + ".linear2.weight", p + ".linear2.bias", d * e, d);
+    f.ln = m->norm_named(p + ".layer_norm", d);
     f.site_in = m->nsites++; f.site_out = m->nsites++;
     return f;
 }
@@ -75,31 +65,27 @@ void r5_build_graph(ishara_model* m) {
         const std::string p = "layers." + std::to_string(i);
         R5Block b;
         b.ffn1 = r5_build_ffn(m, p + ".ffn1");
-        b.mha.Wqkv = dense_named(m, p + ".attention.attention.in_proj_weight", p + ".attention.attention.in_proj_bias", d, 3 * d);
-        b.mha.Wp = dense_named(m, p + ".attention.attention.out_proj.weight", p + ".attention.attention.out_proj.bias", d, d);
-        b.mha.ln = norm_named(m, p + ".attention.layer_norm", d);
+        b.mha.Wqkv = m->dense_named(p + ".attention.attention.in_proj_weight", p + ".attention.attention.in_proj_bias", d, 3 * d);
+        b.mha.Wp = m->dense_named(p + ".attention.attention.out_proj.weight", p + ".attention.attention.out_proj.bias", d, d);
+        b.mha.ln = m->norm_named(p + ".attention.layer_norm", d);
         b.mha.site_attn = m->nsites++;
         ConfConv& c = b.conv;
         c.k = k; c.bn_eps = R5_EPS; c.ln_eps = R5_EPS; c.bn_keep = 0.9f; c.bn_unbiased = 1;      // nn.BatchNorm1d(momentum=0.1): new = 0.9 old + 0.1 batch
-        c.Wp1 = dense_named(m, p + ".conv.pointwise_conv1.weight", p + ".conv.pointwise_conv1.bias", d, 2 * d);
+        c.Wp1 = m->dense_named(p + ".conv.pointwise_conv1.weight", p + ".conv.pointwise_conv1.bias", d, 2 * d);
         c.dw = m->addp(p + ".conv.depthwise_conv.weight", k, d, true);
         c.dwb = m->addp(p + ".conv.depthwise_conv.bias", d, 0, true);
         c.bn.gamma = m->addp(p + ".conv.batch_norm.weight", d, 0, true);
         c.bn.beta = m->addp(p + ".conv.batch_norm.bias", d, 0, true);
         c.bn.mm = m->addp(p + ".conv.batch_norm.running_mean", d, 0, false);
         c.bn.mv = m->addp(p + ".conv.batch_norm.running_var", d, 0, false);
-        c.Wp2 = dense_named(m, p + ".conv.pointwise_conv2.weight", p + ".conv.pointwise_conv2.bias", d, d);
-        c.ln = norm_named(m, p + ".conv.layer_norm", d);
+        c.Wp2 = m->dense_named(p + ".conv.pointwise_conv2.weight", p + ".conv.pointwise_conv2.bias", d, d);
+        c.ln = m->norm_named(p + ".conv.layer_norm", d);
         b.ffn2 = r5_build_ffn(m, p + ".ffn2");
-        b.ln = norm_named(m, p + ".layer_norm", d);
+        b.ln = m->norm_named(p + ".layer_norm", d);
         m->r5.push_back(b);
         m->layer_entry_end.push_back(m->entries.size());
     }
-    int64_t off = 0;
-    for (auto& e : m->entries) if (e.trainable) { e.offset = off; off += e.shape[0] * (e.ndim == 2 ? e.shape[1] : 1); }
-    m->n_train = off;
-    for (auto& e : m->entries) if (!e.trainable) { e.offset = off; off += e.shape[0] * (e.ndim == 2 ? e.shape[1] : 1); }
-    m->n_total = off;
+    finish_param_layout(m);
     m->bucket_lo.push_back(0); m->bucket_hi.push_back(m->n_train);      // one gradient range, final when the backward pass ends
     m->bucket_after_layer.assign(m->r5.size(), -1);
 }
@@ -114,21 +100,14 @@ void r5_plan_workspace(ishara_model* m) {
     m->shadow_end = m->cur;
     m->shadow_tab_off = m->alloc(m->denses.size() * sizeof(ShadowDesc)).off;
     m->r5_x = m->act(d);
-    auto plan_ffn = [&](R5FFN& f) {
-        f.za = m->act(de); f.u = m->act(de); f.r = m->act(d); f.mean = m->f32(Mx); f.rstd = m->f32(Mx); f.out = m->act(d);
-    };
     for (auto& b : m->r5) {
-        plan_ffn(b.ffn1);
+        plan_post_ln_ffn(m, b.ffn1, Mx, d, de);
         R5MHSA& a = b.mha;
         a.q = m->act(d); a.k = m->act(d); a.vt = m->act(d); a.o = m->act(d);
         a.lse = m->f32((size_t)B * m->H * T); a.maskw = m->f32(attn_mask_words(B, m->H, T));
         a.r = m->act(d); a.mean = m->f32(Mx); a.rstd = m->f32(Mx); a.out = m->act(d);
-        ConfConv& c = b.conv;
-        c.g = m->act(2 * d); c.v = m->act(d); c.bnv = m->act(d);
-        c.ssum = m->f32((size_t)B * d); c.ssq = m->f32((size_t)B * d);
-        c.mean = m->f32(d); c.rstd = m->f32(d); c.a = m->f32(d); c.bsh = m->f32(d);
-        c.r = m->act(d); c.lnmean = m->f32(Mx); c.lnrstd = m->f32(Mx); c.out = m->act(d);
-        plan_ffn(b.ffn2);
+        plan_confconv(m, b.conv, Mx, B, d);
+        plan_post_ln_ffn(m, b.ffn2, Mx, d, de);
         b.mean = m->f32(Mx); b.rstd = m->f32(Mx); b.out = m->act(d);
     }
     const int maxw = de > 3 * d ? de : 3 * d;
@@ -136,12 +115,7 @@ void r5_plan_workspace(ishara_model* m) {
     m->t1 = m->act(maxw); m->t2 = m->act(maxw); m->t3 = m->act(maxw);
     m->S1 = m->f32((size_t)B * maxw); m->S2 = m->f32((size_t)B * maxw); m->E = m->f32((size_t)B * maxw);
     m->Fc = m->f32(maxw); m->Ecol = m->f32(maxw);
-    size_t slabf = 0;
-    for (DenseW* w : m->denses) { const size_t f = gemm_tn_slab_floats((int)Mx, w->K, w->N, m->dt); if (f > slabf) slabf = f; }
-    if (layernorm_bwd_scratch_floats(d) > slabf) slabf = layernorm_bwd_scratch_floats(d);
-    if (dwconv_bwd_scratch_floats(2 * maxw, 31) > slabf) slabf = dwconv_bwd_scratch_floats(2 * maxw, 31);
-    if (dwconv_fwd_scratch_floats(B, T, 2 * maxw) > slabf) slabf = dwconv_fwd_scratch_floats(B, T, 2 * maxw);
-    m->slab = m->f32(slabf);
+    m->slab = m->f32(slab_floats(m, Mx, B, T, maxw));
     m->delta = m->f32((size_t)B * m->H * T);
     m->ws_need = m->cur;
 }
@@ -209,12 +183,9 @@ int r5_ffn_bwd(ishara_model* m, R5FFN& f, const Run& r, const void* x, const voi
     OpArgs no;
     void* dr = m->W(m->t4);                                         // gradient of r = x + drop(linear2(...)): also the residual branch
     CK(r5_ln_bwd(m, r, g, m->W(f.r), f.ln, f.mean, f.rstd, dr));
-    const void* gs = dr;
-    const DropSpec od = dspec(r, f.site_out, m->cfg.dropout_rate);
-    if (od.thr) {
-        CKP(m, "map_rows", 2.0 * r.M * m->d * (double)dt_size(dt), 0, launch_map_rows(dt, MAP_DROPMASK, dr, m->W(m->t3), nullptr, od, r.M, m->T, m->d, m->s));
-        gs = m->W(m->t3);
-    }
+    int rc = 0;
+    const void* gs = grad_through_dropout(m, r, f.site_out, m->cfg.dropout_rate, dr, m->W(m->t3), m->T, m->d, &rc);
+    CK(rc);
     if (f.factor != 1.f) {                                        // gradient of the branch = factor * dr
         CKP(m, "map_rows", 2.0 * r.M * m->d * (double)dt_size(dt), 0, launch_map_rows(dt, MAP_ROWSCALE, gs, m->W(m->t3), m->Wf(m->fac), DropSpec{0, 0, 1.f}, r.M, m->T, m->d, m->s));
         gs = m->W(m->t3);

@@ -113,6 +113,8 @@ bool gemm_nt_as_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs&
 bool gemm_nt_as_prologue_ok(int dtA, int dtM, int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);   // gemm_as.hip: the A-stationary kernel takes this shape
 const char* gemm_nt_kernel_name(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);
 extern int g_force_tn_regstage;   // tests: 1 forces the register-transposing TN kernel
+// the other switches of ishara_debug_force_regstage / _set_as_flags / _set_nt_big (api_ops.hip sets them; defined beside the kernels they steer)
+extern int g_force_regstage, g_dbg_tn, g_force_dw_lds, g_tn_blocks, g_attn_bwd_two_pass, g_as_flags_override, g_nt_big;
 extern int g_tn_phase;   // 0 GEMM + slab sums, 1 GEMM kernel only, 2 slab sums only
 const char* gemm_tn_kernel_name(int dtA, int dtB, int dtM, int opA, int opB, int M, int Ka, int Nb, bool brs = false);
 

@@ -1,6 +1,6 @@
 // Shared host-side types of libishara_hip.so: the model handle, its parameter / workspace bookkeeping, the profiled-launch
-// macros and the GEMM wrappers.  Included by model.hip (the Keras get_model family) and conformer_r5.hip (the torch
-// ConformerEncoder family).
+// macros and what the host units share.  Included by model.hip (handle life cycle and shared plumbing), keras_hybrid.hip (the Keras
+// get_model family), conformer_r5.hip / squeezeformer_r4.hip (the torch encoder families) and api_ops.hip (stand-alone entry points).
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -28,6 +28,7 @@
     } while (0)
 
 static inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline int launch_rc() { return hipGetLastError() == hipSuccess ? 0 : -2; }      // after hipLaunchKernelGGL: 0, or -2 when the launch failed
 
 // ------------------------------------------------------------------ model description
 struct ParamEntry { std::string name; int ndim; int64_t shape[2]; int64_t offset; bool trainable; };
@@ -162,13 +163,15 @@ struct ishara_model {
     }
     Buf act(int cols) { return alloc((size_t)Bmax * T * cols * dt_size(dt)); }
     Buf f32(size_t n) { return alloc(n * sizeof(float)); }
-    DenseW dense(const std::string& name, int K, int N, bool bias) {
+    DenseW dense_named(const std::string& wname, const std::string& bname, int K, int N) {      // empty bname: no bias
         DenseW w; w.K = K; w.N = N;
-        w.w = addp(name + "/kernel", K, N, true);
-        if (bias) w.b = addp(name + "/bias", N, 0, true);
+        w.w = addp(wname, K, N, true);
+        if (!bname.empty()) w.b = addp(bname, N, 0, true);
         return w;
     }
+    DenseW dense(const std::string& name, int K, int N, bool bias) { return dense_named(name + "/kernel", bias ? name + "/bias" : "", K, N); }      // Keras names
     Norm norm(const std::string& name, int c) { Norm n; n.gamma = addp(name + "/gamma", c, 0, true); n.beta = addp(name + "/beta", c, 0, true); return n; }
+    Norm norm_named(const std::string& prefix, int c) { Norm n; n.gamma = addp(prefix + ".weight", c, 0, true); n.beta = addp(prefix + ".bias", c, 0, true); return n; }      // torch state_dict names
     BNp bnp(const std::string& name, int c) {
         BNp b; b.gamma = addp(name + "/gamma", c, 0, true); b.beta = addp(name + "/beta", c, 0, true);
         b.mm = addp(name + "/moving_mean", c, 0, false); b.mv = addp(name + "/moving_variance", c, 0, false);
@@ -181,17 +184,33 @@ struct ishara_model {
 };
 
 
-// ------------------------------------------------------------------ shared helpers (model.hip)
+// ------------------------------------------------------------------ shared helpers (model.hip unless noted)
 struct Run { int B, M, training; uint32_t seed; };
 static inline DropSpec dspec(const Run& r, uint32_t site, float rate) { return make_drop(r.seed, site, rate, r.training != 0); }
 static inline DropSpec dspec_attn(const Run& r, uint32_t site, float rate) { return make_drop_attn(r.seed, site, rate, r.training != 0); }   // attention probabilities: common.h rng_quad
+void finish_param_layout(ishara_model* m);      // after the last addp: offsets, n_train, n_total
 void plan_shadow(ishara_model* m, DenseW& w, int min_ldt = 0, int min_ldn = 0);
+void plan_confconv(ishara_model* m, ConfConv& c, size_t rows, int B, int d);
+void plan_post_ln_ffn(ishara_model* m, R5FFN& f, size_t rows, int d, int de);
+size_t wgrad_slab_floats(const ishara_model* m, size_t M, int min_K = 0);
+size_t slab_floats(const ishara_model* m, size_t M, int B, int T, int maxw, int min_K = 0);
 // profiled GEMM launches over a planned Dense weight: forward C = epi(A W), dgrad dX = epi(dY W^T), wgrad dW += A^T dY (+ bias grad)
 int gemm_fwd(ishara_model* m, const DenseW& w, const void* A, int dtA, void* Cc, int dtC, int M, int aop, const OpArgs& oa, EpiArgs ea);
 int gemm_dgrad(ishara_model* m, const DenseW& w, const void* dY, int dtA, void* dX, int M, int aop, const OpArgs& oa, const EpiArgs& ea);
 int gemm_wgrad(ishara_model* m, const DenseW& w, const void* A, int dtA, int aop, const OpArgs& oa, const void* dY, int dtB, int bop, const OpArgs& ob, int M, int ka_valid = 0, int nb_valid = 0,
                const float* bias_rowscale = nullptr, int bias_T = 0, const TnPsa* psa = nullptr);
 int wgrad_flush(ishara_model* m);
+int red_flush(ishara_model* m);
+int layernorm_bwd_deferred(ishara_model* m, const Run& r, const void* dy, const void* x, Buf mean, Buf rstd, const Norm& ln, const void* resid, void* dx);
+int dwconv_bwd_deferred(ishara_model* m, const Run& r, double by_factor, int inop, const void* dy, const DwBnArgs* bn, const void* x, int dw, int dwb, void* dx, int C, int k, int padl);
+const void* grad_through_dropout(ishara_model* m, const Run& r, uint32_t site, float rate, const void* g, void* tmp, int T, int cols, int* rc);
+// Keras get_model hybrid family (keras_hybrid.hip); confconv_* also serve the torch families, ln_as_prologue / classifier_fwd the operator entry points
+void keras_build_graph(ishara_model* m);
+void keras_plan_workspace(ishara_model* m);
+bool ln_as_prologue(int dt, int M, int N, int K, int ldt, const float* gamma, const float* beta, float eps, float* mean, float* rstd, void* xn, EpiArgs& ea);
+enum { CLS_AUTO = 0, CLS_AS = 1, CLS_NARROW = 2, CLS_GEMM = 3 };      // routes of classifier_fwd
+int cls_route_auto(int dt, int M, int K, int C);
+int classifier_fwd(ishara_model* m, int route, int dt, const void* A, const void* Wt, int ldt, const float* bias, float* logits, int M, int K, int C, hipStream_t s);
 int confconv_fwd(ishara_model* m, ConfConv& c, const Run& r, const void* x);
 int confconv_bwd(ishara_model* m, ConfConv& c, const Run& r, const void* x, const void* g, void* gn);
 int r5_ffn_fwd(ishara_model* m, R5FFN& f, const Run& r, const void* x);

@@ -4,7 +4,7 @@
 //       reads row T-1-i+j of the [2T-1, d] table.  Flash-style kernels below (no [T, T] matrix in memory), forward and three backward
 //       passes (dq + du/dv, dk/dv, dpos) that recompute the probabilities from the saved log-sum-exp.
 //   R2  RelPositionalEncoding (modules.py:59-108): table built on the host at create time (fp32 sin / cos, positions T-1 .. -(T-1)).
-//   R3  ConvModule (convolution.py:199-238): the ConfConv composition of model.hip with Swish after the BatchNorm, no depthwise bias.
+//   R3  ConvModule (convolution.py:199-238): the ConfConv composition of keras_hybrid.hip with Swish after the BatchNorm, no depthwise bias.
 //   R4  post-LN SqueezeformerBlock (encoder.py:208-247) with the half-step FFN residual, DepthwiseConv2dSubsampling
 //       (convolution.py:39-73), TimeReductionLayer (:241-269), recover_resolution (modules.py:137-142) and the encoder loop
 //       (encoder.py:135-166) with its ResidualConnectionModule around the reduced-rate blocks (:88-103).
@@ -249,13 +249,12 @@ __global__ void r4_fill_f32(float* p, size_t n, float v) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 static int g1d(size_t n) { const size_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-#define R4_OK() (hipGetLastError() == hipSuccess ? 0 : -2)
 template <int MODE>
 static int r4_rows_launch(int dt, const void* src, const void* a, void* dst, int B, int Tdst, int Tsrc, int d, hipStream_t s) {
     const int grid = g1d((size_t)B * Tdst * d);
     if (dt == DT_BF16) hipLaunchKernelGGL((r4_rows<bf16, MODE>), dim3(grid), dim3(256), 0, s, (const bf16*)src, (const bf16*)a, (bf16*)dst, B, Tdst, Tsrc, d);
     else hipLaunchKernelGGL((r4_rows<float, MODE>), dim3(grid), dim3(256), 0, s, (const float*)src, (const float*)a, (float*)dst, B, Tdst, Tsrc, d);
-    return R4_OK();
+    return launch_rc();
 }
 
 // ------------------------------------------------------------------ R1: relative-position attention
@@ -509,7 +508,7 @@ static int launch_relattn_fwd(int dt, const void* q, const void* k, const void* 
     const dim3 grid((T + RA_QB - 1) / RA_QB, B * H);
     if (dt == DT_BF16) { RA_DISPATCH(relattn_fwd_kernel, bf16, grid, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (bf16*)o, lse, H, T, scale, drop) }
     else { RA_DISPATCH(relattn_fwd_kernel, float, grid, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (float*)o, lse, H, T, scale, drop) }
-    return R4_OK();
+    return launch_rc();
 }
 static int launch_relattn_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
                               const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
@@ -524,26 +523,16 @@ static int launch_relattn_bwd(int dt, const void* q, const void* k, const void* 
         RA_DISPATCH(relattn_bwd_dkv_kernel, float, gq, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)dO, lse, (const float*)delta, (float*)dk, (float*)dv, H, T, scale, drop)
         RA_DISPATCH(relattn_bwd_dpos_kernel, float, gp, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)dO, lse, (const float*)delta, dposp, H, T, scale, drop)
     }
-    return R4_OK();
+    return launch_rc();
 }
 
 // ------------------------------------------------------------------ construction
-static DenseW r4_dense(ishara_model* m, const std::string& wname, const std::string& bname, int K, int N) {
-    DenseW w; w.K = K; w.N = N;
-    w.w = m->addp(wname, K, N, true);
-    if (!bname.empty()) w.b = m->addp(bname, N, 0, true);
-    return w;
-}
-static Norm r4_norm(ishara_model* m, const std::string& p, int c) {
-    Norm n; n.gamma = m->addp(p + ".weight", c, 0, true); n.beta = m->addp(p + ".bias", c, 0, true);
-    return n;
-}
 static R5FFN r4_build_ffn(ishara_model* m, const std::string& mod, const std::string& ln, float factor) {
     R5FFN f;
     const int d = m->d, e = m->cfg.expansion_factor;
-    f.W1 = r4_dense(m, mod + ".sequential.0.weight", mod + ".sequential.0.bias", d, d * e);
-    f.W2 = r4_dense(m, mod + ".sequential.3.weight", mod + ".sequential.3.bias", d * e, d);
-    f.ln = r4_norm(m, ln, d);
+    f.W1 = m->dense_named(mod + ".sequential.0.weight", mod + ".sequential.0.bias", d, d * e);
+    f.W2 = m->dense_named(mod + ".sequential.3.weight", mod + ".sequential.3.bias", d * e, d);
+    f.ln = m->norm_named(ln, d);
     f.site_in = m->nsites++; f.site_out = m->nsites++;
     f.factor = factor;
     return f;
@@ -575,11 +564,11 @@ void r4_build_graph(ishara_model* m) {
     S->T3 = (S->T2 - 3) / 2 + 1; S->Fr = (d - 1) / 2; S->Kp = (int)rup(S->Fr, 8); S->Trec = 2 * S->T3;
     S->w1 = m->addp("conv_subsample.sequential.0.weight", d, 9, true); S->b1 = m->addp("conv_subsample.sequential.0.bias", d, 0, true);
     S->w2 = m->addp("conv_subsample.sequential.2.conv.weight", d, 9, true); S->b2 = m->addp("conv_subsample.sequential.2.conv.bias", d, 0, true);
-    S->Win = r4_dense(m, "input_proj.0.weight", "input_proj.0.bias", d * S->F2, d);
+    S->Win = m->dense_named("input_proj.0.weight", "input_proj.0.bias", d * S->F2, d);
     S->site_in = m->nsites++;
     S->trw = m->addp("time_reduction_layer.sequential.0.conv.weight", 9, 0, true); S->trb = m->addp("time_reduction_layer.sequential.0.conv.bias", 1, 0, true);
-    S->Wred = r4_dense(m, "time_reduction_proj.weight", "time_reduction_proj.bias", S->Fr, d);
-    S->Wrec = r4_dense(m, "time_recover_layer.weight", "time_recover_layer.bias", d, d);
+    S->Wred = m->dense_named("time_reduction_proj.weight", "time_reduction_proj.bias", S->Fr, d);
+    S->Wrec = m->dense_named("time_recover_layer.weight", "time_recover_layer.bias", d, d);
     const float factor = c.half_step_residual ? 0.5f : 1.0f;
     int Tl = S->T2;
     for (int idx = 0; idx < L; ++idx) {
@@ -592,25 +581,25 @@ void r4_build_graph(ishara_model* m) {
         const std::string a = s + ".0.module.attention";
         RelMHSA& A = Ly.mha;
         A.u = m->addp(a + ".u_bias", d, 0, true); A.v = m->addp(a + ".v_bias", d, 0, true);
-        A.Wq = r4_dense(m, a + ".query_proj.weight", a + ".query_proj.bias", d, d);
-        A.Wk = r4_dense(m, a + ".key_proj.weight", a + ".key_proj.bias", d, d);
-        A.Wv = r4_dense(m, a + ".value_proj.weight", a + ".value_proj.bias", d, d);
-        A.Wpos = r4_dense(m, a + ".pos_proj.weight", "", d, d);
-        A.Wo = r4_dense(m, a + ".out_proj.weight", a + ".out_proj.bias", d, d);
-        A.ln = r4_norm(m, s + ".1", d);
+        A.Wq = m->dense_named(a + ".query_proj.weight", a + ".query_proj.bias", d, d);
+        A.Wk = m->dense_named(a + ".key_proj.weight", a + ".key_proj.bias", d, d);
+        A.Wv = m->dense_named(a + ".value_proj.weight", a + ".value_proj.bias", d, d);
+        A.Wpos = m->dense_named(a + ".pos_proj.weight", "", d, d);
+        A.Wo = m->dense_named(a + ".out_proj.weight", a + ".out_proj.bias", d, d);
+        A.ln = m->norm_named(s + ".1", d);
         A.site_attn = m->nsites++; A.site_out = m->nsites++;
         Ly.ffn1 = r4_build_ffn(m, s + ".2.module", s + ".3", factor);
         ConfConv& cv = Ly.conv;
         const std::string cs = s + ".4.module.sequential";
         cv.k = k; cv.bn_eps = R4_EPS; cv.ln_eps = R4_EPS; cv.bn_keep = 0.9f; cv.bn_unbiased = 1; cv.swish_after_bn = 1; cv.has_out_drop = 1;
-        cv.Wp1 = r4_dense(m, cs + ".1.conv.weight", cs + ".1.conv.bias", d, 2 * d);
+        cv.Wp1 = m->dense_named(cs + ".1.conv.weight", cs + ".1.conv.bias", d, 2 * d);
         cv.dw = m->addp(cs + ".3.conv.weight", k, d, true);
         cv.dwb = -1;
         cv.bn.gamma = m->addp(cs + ".4.weight", d, 0, true); cv.bn.beta = m->addp(cs + ".4.bias", d, 0, true);
         cv.bn.mm = m->addp(cs + ".4.running_mean", d, 0, false); cv.bn.mv = m->addp(cs + ".4.running_var", d, 0, false);
-        cv.Wp2 = r4_dense(m, cs + ".6.conv.weight", cs + ".6.conv.bias", d, d);
+        cv.Wp2 = m->dense_named(cs + ".6.conv.weight", cs + ".6.conv.bias", d, d);
         cv.site_out = m->nsites++;
-        cv.ln = r4_norm(m, s + ".5", d);
+        cv.ln = m->norm_named(s + ".5", d);
         Ly.ffn2 = r4_build_ffn(m, s + ".6.module", s + ".7", factor);
         // the table this layer's length needs
         int pe = -1;
@@ -621,11 +610,7 @@ void r4_build_graph(ishara_model* m) {
         m->layer_entry_end.push_back(m->entries.size());
     }
     S->Tout = Tl;
-    int64_t off = 0;
-    for (auto& e : m->entries) if (e.trainable) { e.offset = off; off += e.shape[0] * (e.ndim == 2 ? e.shape[1] : 1); }
-    m->n_train = off;
-    for (auto& e : m->entries) if (!e.trainable) { e.offset = off; off += e.shape[0] * (e.ndim == 2 ? e.shape[1] : 1); }
-    m->n_total = off;
+    finish_param_layout(m);
     m->bucket_lo.push_back(0); m->bucket_hi.push_back(m->n_train);
     m->bucket_after_layer.assign(S->layers.size(), -1);
     // R2: RelPositionalEncoding rows for T frames (modules.py:73-108): row r = relative position T-1-r, even columns sin, odd cos
@@ -674,12 +659,8 @@ void r4_plan_workspace(ishara_model* m) {
         RelMHSA& a = L.mha;
         a.q = A(d); a.k = A(d); a.vv = A(d); a.o = A(d); a.lse = m->f32((size_t)B * m->H * L.T); a.posp = m->f32((size_t)(2 * L.T - 1) * d);
         a.r = A(d); a.mean = m->f32(Mx); a.rstd = m->f32(Mx); a.out = A(d);
-        for (R5FFN* f : {&L.ffn1, &L.ffn2}) { f->za = A(de); f->u = A(de); f->r = A(d); f->mean = m->f32(Mx); f->rstd = m->f32(Mx); f->out = A(d); }
-        ConfConv& c = L.conv;
-        c.g = A(2 * d); c.v = A(d); c.bnv = A(d); c.sw = A(d);
-        c.ssum = m->f32((size_t)B * d); c.ssq = m->f32((size_t)B * d);
-        c.mean = m->f32(d); c.rstd = m->f32(d); c.a = m->f32(d); c.bsh = m->f32(d);
-        c.r = A(d); c.lnmean = m->f32(Mx); c.lnrstd = m->f32(Mx); c.out = A(d);
+        plan_post_ln_ffn(m, L.ffn1, Mx, d, de); plan_post_ln_ffn(m, L.ffn2, Mx, d, de);
+        plan_confconv(m, L.conv, Mx, B, d);      // with sw (swish_after_bn)
         if (L.wrapped) L.wrap_out = A(d);
     }
     const size_t Mmax = (size_t)B * Tmax;
@@ -688,12 +669,7 @@ void r4_plan_workspace(ishara_model* m) {
     m->t1 = m->alloc(Mmax * maxw * es); m->t2 = m->alloc(Mmax * maxw * es); m->t3 = m->alloc(Mmax * maxw * es);
     m->S1 = m->f32((size_t)B * maxw); m->S2 = m->f32((size_t)B * maxw); m->E = m->f32((size_t)B * maxw);
     m->Fc = m->f32(maxw); m->Ecol = m->f32(maxw); m->fac = m->f32(B);
-    size_t slabf = 0;
-    for (DenseW* w : m->denses) { const size_t f = gemm_tn_slab_floats((int)Mmax, w->K > S->Kp ? w->K : S->Kp, w->N, m->dt); if (f > slabf) slabf = f; }
-    if (layernorm_bwd_scratch_floats(d) > slabf) slabf = layernorm_bwd_scratch_floats(d);
-    if (dwconv_bwd_scratch_floats(2 * maxw, 31) > slabf) slabf = dwconv_bwd_scratch_floats(2 * maxw, 31);
-    if (dwconv_fwd_scratch_floats(B, Tmax, 2 * maxw) > slabf) slabf = dwconv_fwd_scratch_floats(B, Tmax, 2 * maxw);
-    m->slab = m->f32(slabf);
+    m->slab = m->f32(slab_floats(m, Mmax, B, Tmax, maxw, S->Kp));      // K at least Kp: the padded time_reduction_proj wgrad (r4_backward)
     m->delta = m->f32((size_t)B * m->H * Tmax);
     m->ws_need = m->cur;
 }
@@ -710,6 +686,7 @@ void r4_destroy(ishara_model* m) { delete m->r4; m->r4 = nullptr; }
 int r4_output_frames(const ishara_model* m) { return m->r4->Tout; }
 
 // ------------------------------------------------------------------ forward
+static const void* r4_layer_out(ishara_model* m, const R4Layer& L) { return L.wrapped ? m->W(L.wrap_out) : m->W(L.ffn2.out); }
 static int r4_mhsa_fwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, const void* x) {
     RelMHSA& a = L.mha;
     const int dt = m->dt, d = m->d, T = L.T;
@@ -743,7 +720,7 @@ int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t tra
     // ---- DepthwiseConv2dSubsampling + input_proj (encoder.py:148-149)
     hipLaunchKernelGGL(r4_sub1_fwd, dim3(g1d((size_t)B * d * S->T1 * S->F1)), dim3(256), 0, m->s, x, m->P(S->w1), m->P(S->b1), m->Wf(S->y1), B, S->T0, S->F, d, S->T1, S->F1);
     R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_fwd<TT>), dim3(g1d((size_t)B * S->T2 * d * S->F2)), dim3(256), 0, m->s, m->Wf(S->y1), m->P(S->w2), m->P(S->b2), m->W<TT>(S->sub), B, d, S->T1, S->F1, S->T2, S->F2));
-    if (R4_OK()) return -2;
+    CK(launch_rc());
     EpiArgs ein; ein.drop = dspec(r, S->site_in, m->cfg.dropout_rate);
     CK(gemm_fwd(m, S->Win, m->W(S->sub), dt, m->W(S->h0), dt, r.M, OP_NONE, no, ein));
     const void* h = m->W(S->h0);
@@ -790,12 +767,9 @@ static int r4_mhsa_bwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, co
     OpArgs no; EpiArgs e0;
     void* dr = m->W(m->t4);
     CK(r5_ln_bwd(m, r, g, m->W(a.r), a.ln, a.mean, a.rstd, dr));
-    const void* gs = dr;
-    const DropSpec od = dspec(r, a.site_out, m->cfg.dropout_rate);
-    if (od.thr) {
-        CKP(m, "map_rows", 2.0 * r.M * d * (double)dt_size(dt), 0, launch_map_rows(dt, MAP_DROPMASK, dr, m->W(m->t3), nullptr, od, r.M, T, d, m->s));
-        gs = m->W(m->t3);
-    }
+    int rc = 0;
+    const void* gs = grad_through_dropout(m, r, a.site_out, m->cfg.dropout_rate, dr, m->W(m->t3), T, d, &rc);
+    CK(rc);
     CK(gemm_dgrad(m, a.Wo, gs, dt, m->W(m->t1), r.M, OP_NONE, no, e0));                          // d context
     CK(gemm_wgrad(m, a.Wo, m->W(a.o), dt, OP_NONE, no, gs, dt, OP_NONE, no, r.M));
     hipLaunchKernelGGL(r4_fill_f32, dim3(g1d((size_t)(2 * T - 1) * d)), dim3(256), 0, m->s, m->Wf(S->dposp), (size_t)(2 * T - 1) * d, 0.f);
@@ -839,7 +813,7 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
             if (idx == S->reduce) h = m->W(S->red);
             if (idx == S->recover) h = m->W(S->rec);
             lin[idx] = h;
-            h = S->layers[idx].wrapped ? m->W(S->layers[idx].wrap_out) : m->W(S->layers[idx].ffn2.out);
+            h = r4_layer_out(m, S->layers[idx]);
         }
     }
 #define SWAP() do { void* _t = g; g = gn; gn = _t; } while (0)
@@ -869,7 +843,7 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
             hipLaunchKernelGGL(r4_fill_f32, dim3(g1d((size_t)S->Kp * d)), dim3(256), 0, m->s, m->Wf(S->dwred), (size_t)S->Kp * d, 0.f);
             CKP(m, "wgrad(time_reduction_proj)", 0, 0, launch_gemm_tn(dt, dt, dt, OP_NONE, OP_NONE, m->W(S->trout), g, m->Wf(S->dwred), m->G(S->Wred.b), m->Wf(m->slab), B * S->T3, S->Kp, d, no, no, m->s));
             hipLaunchKernelGGL(r4_axpy_f32, dim3(g1d((size_t)S->Fr * d)), dim3(256), 0, m->s, m->Wf(S->dwred), m->G(S->Wred.w), (size_t)S->Fr * d);
-            const void* hprev = idx > 0 ? (S->layers[idx - 1].wrapped ? m->W(S->layers[idx - 1].wrap_out) : m->W(S->layers[idx - 1].ffn2.out)) : m->W(S->h0);
+            const void* hprev = idx > 0 ? r4_layer_out(m, S->layers[idx - 1]) : m->W(S->h0);
             R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_bwd_w<TT>), dim3(64), dim3(256), 0, m->s, (const TT*)m->W(m->t1), m->Wf(S->trpre), (const TT*)hprev, m->G(S->trw), m->G(S->trb), B, S->T2, d, S->T3, S->Fr, S->Kp));
             R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_bwd_x<TT>), dim3(g1d((size_t)B * S->T2 * d)), dim3(256), 0, m->s, (const TT*)m->W(m->t1), m->Wf(S->trpre), m->P(S->trw),
                                             have_skip ? (const TT*)m->W(S->gskip) : (const TT*)nullptr, (TT*)gn, B, S->T2, d, S->T3, S->Fr, S->Kp));
@@ -880,12 +854,9 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
     m->T = keepT;
     // ---- input_proj and the convolution subsampling
     Run r0{B, B * S->T2, 1, m->last_seed};
-    const void* gs = g;
-    const DropSpec din = dspec(r0, S->site_in, m->cfg.dropout_rate);
-    if (din.thr) {
-        CKP(m, "map_rows", 2.0 * r0.M * d * (double)dt_size(dt), 0, launch_map_rows(dt, MAP_DROPMASK, g, gn, nullptr, din, r0.M, S->T2, d, m->s));
-        gs = gn;
-    }
+    int rc = 0;
+    const void* gs = grad_through_dropout(m, r0, S->site_in, m->cfg.dropout_rate, g, gn, S->T2, d, &rc);
+    CK(rc);
     CK(gemm_wgrad(m, S->Win, m->W(S->sub), dt, OP_NONE, no, gs, dt, OP_NONE, no, r0.M));
     CK(gemm_dgrad(m, S->Win, gs, dt, m->W(S->dsub), r0.M, OP_NONE, no, e0));
     float* dz1 = m->Wf(S->dz1);
@@ -893,7 +864,7 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
     R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_bwd_x<TT>), dim3(g1d((size_t)B * d * S->T1 * S->F1)), dim3(256), 0, m->s, (const TT*)m->W(S->dsub), (const TT*)m->W(S->sub), m->P(S->w2), m->Wf(S->y1), dz1, B, d, S->T1, S->F1, S->T2, S->F2));
     hipLaunchKernelGGL(r4_sub1_bwd_w, dim3(d), dim3(256), 0, m->s, dz1, m->last_x, m->G(S->w1), m->G(S->b1), B, S->T0, S->F, d, S->T1, S->F1);
     if (dx) hipLaunchKernelGGL(r4_sub1_bwd_x, dim3(g1d((size_t)B * S->T0 * S->F)), dim3(256), 0, m->s, dz1, m->P(S->w1), dx, B, S->T0, S->F, d, S->T1, S->F1);
-    if (R4_OK()) return -2;
+    CK(launch_rc());
     if (!m->bucket_ev.empty()) HIP_CHECK_RET(hipEventRecord(m->bucket_ev.back(), m->s));
     return 0;
 }

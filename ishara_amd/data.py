@@ -342,7 +342,6 @@ class DeviceBatchAdapter:
 
     def batch(self, idx) -> Tuple["torch.Tensor", "torch.Tensor"]:
         """One device batch of the store's clips `idx` (draws for all of them, emits this rank's slice)."""
-        import ctypes
         import torch
         from . import _lib
         idx = np.asarray(idx, np.int64)
@@ -361,7 +360,6 @@ class DeviceBatchAdapter:
         ev.record()
         x = torch.empty((b, self.T, _LAYOUT_F[self.layout]), dtype=torch.float32, device=self.store.device)
         _lib.check(self._lib.ishara_clip_batch(_lib.ptr(self.store.raw), _lib.ptr(dev), b, self.T, _LAYOUT_IDS[self.layout],
-                                               _lib.ptr(x), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                   "ishara_clip_batch")
+                                               _lib.ptr(x), _lib.stream()), "ishara_clip_batch")
         y = self.store.phrases.index_select(0, dev[b * C_CLIP_AUG_BYTES:used].view(torch.int64))
         return x, y

@@ -20,13 +20,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IsharaError
+from ._handle import Handle
+from ._lib import stream as _stream
 
 PAD_TOKEN_IDX = 59  # c1:5
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class _Scalar:
@@ -123,26 +120,13 @@ def _keras_init(name: str, shape, g: np.random.Generator) -> np.ndarray:
     return g.uniform(-lim, lim, size=shape).astype(np.float32)
 
 
-class Model:
+class Model(Handle):
     def __init__(self, cfg: _lib.Config, device: Optional[str] = "cuda:0", seed: int = 0):
-        self._lib = _lib.load()
-        self._cfg = cfg
-        self._h = C.c_void_p()
-        _lib.check(self._lib.ishara_create(C.byref(cfg), C.byref(self._h)), "ishara_create")
+        self._create_handle(cfg)
         self.T, self.F, self.C = cfg.frames, cfg.features, cfg.num_classes
-        self.max_batch = cfg.max_batch
-        self.n_total = int(self._lib.ishara_param_total(self._h))
-        self.n_train = int(self._lib.ishara_param_trainable(self._h))
-        self.entries = []
-        for i in range(self._lib.ishara_param_entries(self._h)):
-            name, nd, sh, off, tr = C.c_char_p(), C.c_int32(), (C.c_int64 * 2)(), C.c_int64(), C.c_int32()
-            _lib.check(self._lib.ishara_param_info(self._h, i, C.byref(name), C.byref(nd), C.byref(sh), C.byref(off), C.byref(tr)))
-            shape = (int(sh[0]),) if nd.value == 1 else (int(sh[0]), int(sh[1]))
-            self.entries.append((name.value.decode(), shape, int(off.value), bool(tr.value)))
         self.optimizer = Optimizer()
         self.loss = "ctc"
         self.stop_training = False
-        self.device = None
         self._step_seed = seed * 7919 + 17
         self._steps = 0
         if device is not None:
@@ -150,34 +134,11 @@ class Model:
 
     # ------------------------------------------------------------------ device state
     def _to_device(self, device, seed):
-        if not torch.cuda.is_available():
-            raise IsharaError("ishara_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path")
-        self.device = torch.device(device)
-        torch.cuda.set_device(self.device)
-        dev = self.device
-        self.params = torch.zeros(self.n_total, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros(self.n_total, dtype=torch.float32, device=dev)
-        self.opt_m = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
-        self.opt_v = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
-        self.opt_slow = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
-        wsb = int(self._lib.ishara_workspace_bytes(self._h))
-        self.workspace = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
-        off = (-self.workspace.data_ptr()) % 256
-        self._ws_ptr = self.workspace.data_ptr() + off
-        _lib.check(self._lib.ishara_bind(self._h, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.opt_m),
-                                         _lib.ptr(self.opt_v), _lib.ptr(self.opt_slow), C.c_void_p(self._ws_ptr), wsb), "ishara_bind")
-        self._loss_buf = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._nll_buf = torch.zeros(self.max_batch, dtype=torch.float32, device=dev)
+        self._bind_device(device)
+        self._loss_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._nll_buf = torch.zeros(self.max_batch, dtype=torch.float32, device=self.device)
         g = np.random.default_rng(seed)
         self.set_weights({name: _keras_init(name, shape, g) for name, shape, _, _ in self.entries})
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ishara_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ weights
     def get_weights(self) -> Dict[str, np.ndarray]:

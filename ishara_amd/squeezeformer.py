@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import stream as _stream
 from .conformer import _TorchFamilyEncoder
 
 
@@ -114,8 +115,6 @@ class _FcLogSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, lib):
-        import ctypes as C
-        from .model import _stream
         B, T, d = x.shape
         M, N = B * T, weight.shape[0]
         Np = (N + 7) // 8 * 8                                      # class count padded to the GEMMs' 16-byte row alignment (zero weight columns)
@@ -124,8 +123,7 @@ class _FcLogSoftmaxFn(torch.autograd.Function):
         Wk[:, :N] = weight.detach().t()                            # nn.Linear [C, d] -> the library's [K, N]
         z = torch.empty(M, Np, dtype=torch.float32, device=x.device)
         y = torch.empty_like(z)
-        sc = torch.empty(int(lib.ishara_op_scratch_bytes(M, d, Np)) + 256, dtype=torch.uint8, device=x.device)
-        scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
+        sc, scp = _lib.aligned(lib.ishara_op_scratch_bytes(M, d, Np), x.device)
         _lib.check(lib.ishara_op_dense_fwd_ex(_lib.F32, _lib.ptr(x2), _lib.ptr(Wk), None, None, _lib.ptr(z), M, d, Np, 0, scp, _stream()), "fc")
         _lib.check(lib.ishara_op_log_softmax_fwd(_lib.ptr(z), _lib.ptr(y), M, N, Np, _stream()), "log_softmax")
         ctx.save_for_backward(x2, Wk, y)
@@ -134,7 +132,6 @@ class _FcLogSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .model import _stream
         x2, Wk, y = ctx.saved_tensors
         lib, (sc, scp), (B, T, d, N, Np) = ctx.lib, ctx.scratch, ctx.shape
         M = B * T

@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import Model, _stream
+from ._lib import stream as _stream
+from .model import Model
 from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS, _beam_launch, _beam_setup
 
 PAD_TOKEN_IDX = 59           # c1:5: the targets' padding; never a decoded index (the blank is C - 1 = 59)

@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import Model, _stream
+from ._lib import stream as _stream
+from .model import Model
 
 N_COLS = 276
 # concat order of pre_process1 (c3:111) with landmark counts

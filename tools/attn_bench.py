@@ -4,7 +4,7 @@ import ctypes as C, sys, torch
 sys.path.insert(0, ".")
 from ishara_amd import _lib
 lib = _lib.load()
-st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream
 B, H, T, dh = 256, 8, 384, 32
 def timeit(fn, n=5):
     for _ in range(2): fn()
@@ -17,8 +17,7 @@ qkv = (torch.randn(B * T, 3 * H * dh, device="cuda") * 0.5).bfloat16()
 o = torch.empty(B * T, H * dh, device="cuda", dtype=torch.bfloat16)
 do = torch.randn(B * T, H * dh, device="cuda").bfloat16()
 dqkv = torch.empty_like(qkv)
-sc = torch.empty(int(lib.ishara_op_attn_scratch_bytes(B, H, T, dh)) + 256, dtype=torch.uint8, device="cuda")
-scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
+sc, scp = _lib.aligned(lib.ishara_op_attn_scratch_bytes(B, H, T, dh), "cuda")
 scale = dh ** -0.5
 for rate in (0.0, 0.1):
     f = timeit(lambda: lib.ishara_op_attn_fwd(1, _lib.ptr(qkv), _lib.ptr(o), B, H, T, dh, C.c_float(scale), 7, 3, C.c_float(rate), 1, scp, st()))

@@ -6,7 +6,7 @@ import ctypes as C, sys, torch
 sys.path.insert(0, ".")
 from ishara_amd import _lib
 lib = _lib.load()
-st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream
 SHAPES = [(32768, 512, 512, 0, False), (32768, 1024, 512, 1, True), (32768 + 256, 512, 1024, 2, True), (34816, 640, 768, 0, True)]
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 for rnd in range(rounds):
@@ -16,8 +16,7 @@ for rnd in range(rounds):
         r = torch.randn(M, N, generator=g).bfloat16() if with_resid else None
         xd, Wd, bd = x.cuda(), W.cuda(), b.cuda()
         rd = r.cuda() if with_resid else None
-        sc = torch.empty(int(lib.ishara_op_scratch_bytes(M, K, N)) + 256, dtype=torch.uint8, device="cuda")
-        scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
+        sc, scp = _lib.aligned(lib.ishara_op_scratch_bytes(M, K, N), "cuda")
         outs = {}
         for on in (0, 1, 1):
             lib.ishara_debug_set_nt_big(on)

@@ -5,7 +5,7 @@ import ctypes as C, sys, numpy as np, torch
 sys.path.insert(0, ".")
 from ishara_amd import _lib
 lib = _lib.load()
-st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream
 B, T, Cc, L = 256, 384, 60, 64
 g = np.random.default_rng(0)
 logits = torch.from_numpy((g.standard_normal((B, T, Cc)) * 2).astype(np.float32)).cuda()

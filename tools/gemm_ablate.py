@@ -9,15 +9,14 @@ sys.path.insert(0, ".")
 from ishara_amd import _lib
 
 lib = _lib.load()
-st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream
 shapes = [(98304, 256, 512), (98304, 512, 256), (98304, 256, 768), (98304, 256, 256)]
 for (M, K, N) in shapes:
     x = torch.randn(M, K, device="cuda").bfloat16()
     W = torch.randn(K, N, device="cuda") / K ** 0.5
     b = torch.randn(N, device="cuda")
     y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-    sc = torch.empty(int(lib.ishara_op_scratch_bytes(M, K, N)) + 256, dtype=torch.uint8, device="cuda")
-    scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
+    sc, scp = _lib.aligned(lib.ishara_op_scratch_bytes(M, K, N), "cuda")
     r = torch.randn(M, N, device="cuda").bfloat16()
     res = {}
     variants = {"as": 0, "as-noepi": 1 << 4, "as-nomfma": 2 << 4, "as-nolds": 4 << 4, "as-nolds-nomfma": 6 << 4, "as-onlyepi": 14 << 4, "as-onlyloadA": 15 << 4,
@@ -45,8 +44,7 @@ for (M, K, N) in [(98304, 256, 512), (98304, 512, 256), (98304, 256, 768)]:
     dy = torch.randn(M, N, device="cuda").bfloat16()
     W = torch.randn(K, N, device="cuda") / K ** 0.5
     dW = torch.zeros(K, N, device="cuda"); db = torch.zeros(N, device="cuda")
-    sc = torch.empty(int(lib.ishara_op_scratch_bytes(M, K, N)) + 256, dtype=torch.uint8, device="cuda")
-    scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
+    sc, scp = _lib.aligned(lib.ishara_op_scratch_bytes(M, K, N), "cuda")
     res = {}
     for rnd in range(3):
         for name, flag in {"tr": 0, "tr-nomma": (1 << 8), "tr-nofrag": (2 << 8), "tr-noload": (4 << 8), "tr-nothing": (7 << 8), "regstage-tn": 2}.items():

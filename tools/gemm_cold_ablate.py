@@ -6,7 +6,7 @@ import ctypes as C, sys, torch
 sys.path.insert(0, ".")
 from ishara_amd import _lib
 lib = _lib.load()
-st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream
 NB = 12
 def timeit(fn, n=24):
     for i in range(NB): fn(i)
@@ -21,8 +21,7 @@ for (M, K, N) in [(98304, 256, 512), (98304, 512, 256)]:
     ys = [torch.empty(M, N, device="cuda", dtype=torch.bfloat16) for _ in range(NB)]
     W = torch.randn(K, N, device="cuda") / K ** 0.5
     b = torch.randn(N, device="cuda")
-    sc = torch.empty(int(lib.ishara_op_scratch_bytes(M, K, N)) + 256, dtype=torch.uint8, device="cuda")
-    scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
+    sc, scp = _lib.aligned(lib.ishara_op_scratch_bytes(M, K, N), "cuda")
     # the op's own fixed part (slab memset + weight shadows), to subtract: a GEMM on 256 rows
     f0 = lambda i: lib.ishara_op_dense_fwd_ex(1, _lib.ptr(xs[0]), _lib.ptr(W), _lib.ptr(b), None, _lib.ptr(ys[0]), 256, K, N, 0, scp, st())
     base = min(timeit(f0) for _ in range(3))

@@ -4,7 +4,7 @@ import ctypes as C, sys, torch
 sys.path.insert(0, ".")
 from ishara_amd import _lib
 lib = _lib.load()
-st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream
 M, Cc = 98304, 256
 def timeit(fn, n=10):
     for _ in range(3): fn()

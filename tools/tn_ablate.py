@@ -4,14 +4,13 @@ import ctypes as C, sys, torch
 sys.path.insert(0, ".")
 from ishara_amd import _lib
 lib = _lib.load()
-st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream
 SHAPES = [(98304, 256, 512), (98304, 512, 256), (98304, 256, 768), (98304, 256, 256)] if len(sys.argv) < 2 else [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]]
 for (M, K, N) in SHAPES:
     x = torch.randn(M, K, device="cuda").bfloat16(); dy = torch.randn(M, N, device="cuda").bfloat16()
     W = torch.randn(K, N, device="cuda") / K ** 0.5
     dW = torch.zeros(K, N, device="cuda"); db = torch.zeros(N, device="cuda")
-    sc = torch.empty(int(lib.ishara_op_scratch_bytes(M, K, N)) + 256, dtype=torch.uint8, device="cuda")
-    scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
+    sc, scp = _lib.aligned(lib.ishara_op_scratch_bytes(M, K, N), "cuda")
     res = {}
     V = {"tr": 0, "tr256": 1 << 6, "tr512": 2 << 6, "tr768": 3 << 6, "nomma": 1, "nofrag": 2, "nomma-nofrag": 3, "noload": 4, "noepi": 8, "noloop": 16, "nothing": 7 | 8}
     for rnd in range(3):

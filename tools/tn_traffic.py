@@ -18,7 +18,7 @@ import ctypes as C, torch
 sys.path.insert(0, ".")
 from ishara_amd import _lib
 lib = _lib.load()
-st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream
 SHAPES = [(262144, 512, 512), (262144, 512, 1024), (98304, 256, 256), (98304, 256, 512), (98304, 256, 768)]
 V = {"tile128": 0, "tile256": 1}          # ishara_debug_set_nt_big: the 128 x 128 tile kernel / the 256 x 256 tile kernel where it applies
 plan = open("gpurun_out/tn_traffic_plan.txt", "w")
@@ -26,8 +26,7 @@ for (M, K, N) in SHAPES:
     x = torch.randn(M, K, device="cuda").bfloat16(); dy = torch.randn(M, N, device="cuda").bfloat16()
     W = torch.randn(K, N, device="cuda") / K ** 0.5
     dW = torch.zeros(K, N, device="cuda"); db = torch.zeros(N, device="cuda")
-    sc = torch.empty(int(lib.ishara_op_scratch_bytes(M, K, N)) + 256, dtype=torch.uint8, device="cuda")
-    scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
+    sc, scp = _lib.aligned(lib.ishara_op_scratch_bytes(M, K, N), "cuda")
     for name, bits in V.items():
         lib.ishara_debug_set_nt_big(bits)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -206,6 +206,23 @@ int ishara_debug_set_as_flags(int32_t flags);
 /* 0: never use the 256 x 256 two-operand tile GEMM (gemm_big.hip) — A/B runs against the A-stationary kernel inside one process; 1: library default */
 int ishara_debug_set_nt_big(int32_t on);
 int ishara_debug_force_regstage(int32_t on);
+/* Module probe (ISHARA_FAMILY_KERAS_HYBRID, bound handle): one module of the sequential graph run alone through the model's own
+ * orchestration, so that it lands on the kernels ishara_forward / ishara_loss_backward take for it at (dtype, B).  Modules in forward
+ * order: "stem", every Conv1DBlock by its parameter prefix, "squeezeformer_k/{ffn1,mha,conv,ffn2}", "conformer_k/{ffn1,mha,conv,ffn2}",
+ * "head"; first_site / n_sites: the dropout site ids the module draws from.  The name is valid until the thread's next module_info call.
+ * forward: x f32 [B,T,in_cols] ([B,T,F] for the stem; it must stay alive until the stem's backward) is converted to the handle's dtype
+ * where the model holds the module's input, y f32 [B,T,out_cols] (the head: logits).  It invalidates the state of the last ishara_forward.
+ * backward: zero-fills grads[0,trainable), then the module's backward on what its last forward(training=1) with the same B left, then the
+ * deferred gradient sums; dy f32 [B,T,out_cols], dx f32 [B,T,in_cols] or NULL (the stem: NULL).  The head's backward starts at the CTC
+ * kernel (dlogits and their padded 16-bit copy): ishara_debug_head_loss_backward, arguments of ishara_loss_backward plus dx [B,T,dim].
+ * Refused with a message before anything is launched: an unbound handle, another family, i out of range, B outside 1..max_batch,
+ * ISHARA_F16 with training=1, a backward without the matching training forward. */
+int32_t ishara_debug_module_count(ishara_model* m);
+int ishara_debug_module_info(ishara_model* m, int32_t i, const char** name, int32_t* in_cols, int32_t* out_cols, int32_t* first_site, int32_t* n_sites);
+int ishara_debug_module_forward(ishara_model* m, int32_t i, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, ishara_stream s);
+int ishara_debug_module_backward(ishara_model* m, int32_t i, const float* dy, int32_t B, float* dx, ishara_stream s);
+int ishara_debug_head_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll,
+                                    float loss_scale, float* dx, ishara_stream s);
 
 /* ---- single-operator entry points (parity tests of the individual kernels) ------------ */
 /* dt: ISHARA_F32 / ISHARA_BF16 / ISHARA_F16; the backward operators refuse ISHARA_F16 (inference only), every operator refuses an unknown

@@ -85,6 +85,11 @@ SIGNATURES = {
     "ishara_debug_set_as_flags": (C.c_int, [_I32]),
     "ishara_debug_set_nt_big": (C.c_int, [_I32]),
     "ishara_debug_force_regstage": (C.c_int, [_I32]),
+    "ishara_debug_module_count": (_I32, [_P]),
+    "ishara_debug_module_info": (C.c_int, [_P, _I32, C.POINTER(C.c_char_p), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "ishara_debug_module_forward": (C.c_int, [_P, _I32, _P, _I32, _P, _I32, _U32, _P]),
+    "ishara_debug_module_backward": (C.c_int, [_P, _I32, _P, _I32, _P, _P]),
+    "ishara_debug_head_loss_backward": (C.c_int, [_P, _P, _P, _I32, _P, _P, _F, _P, _P]),
     "ishara_op_scratch_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_op_dense_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "ishara_op_dense_fwd_ex": (C.c_int, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),

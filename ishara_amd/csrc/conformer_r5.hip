@@ -31,11 +31,13 @@ __global__ void r5_to_f32_kernel(const T* __restrict__ x, float* __restrict__ y,
 static int grid_for(size_t n8) { const size_t g = (n8 + 255) / 256; return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g)); }
 int r5_from_f32(int dt, const float* x, void* y, size_t n, hipStream_t s) {
     if (dt == DT_BF16) hipLaunchKernelGGL(r5_from_f32_kernel<bf16>, dim3(grid_for(n / 8)), dim3(256), 0, s, x, (bf16*)y, n / 8);
+    else if (dt == DT_F16) hipLaunchKernelGGL(r5_from_f32_kernel<f16>, dim3(grid_for(n / 8)), dim3(256), 0, s, x, (f16*)y, n / 8);      // (the module probe of an fp16 handle)
     else hipLaunchKernelGGL(r5_from_f32_kernel<float>, dim3(grid_for(n / 8)), dim3(256), 0, s, x, (float*)y, n / 8);
     return launch_rc();
 }
 int r5_to_f32(int dt, const void* x, float* y, size_t n, hipStream_t s) {
     if (dt == DT_BF16) hipLaunchKernelGGL(r5_to_f32_kernel<bf16>, dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16*)x, y, n / 8);
+    else if (dt == DT_F16) hipLaunchKernelGGL(r5_to_f32_kernel<f16>, dim3(grid_for(n / 8)), dim3(256), 0, s, (const f16*)x, y, n / 8);
     else hipLaunchKernelGGL(r5_to_f32_kernel<float>, dim3(grid_for(n / 8)), dim3(256), 0, s, (const float*)x, y, n / 8);
     return launch_rc();
 }

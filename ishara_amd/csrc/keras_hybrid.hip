@@ -431,17 +431,9 @@ int classifier_fwd(ishara_model* m, int route, int dt, const void* A, const void
     return 0;
 }
 
-extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float* logits, int32_t training, uint32_t seed, ishara_stream st) {
-    if (!m->ws) { ishara_set_error("ishara_forward: model is not bound"); return -1; }
-    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("ishara_forward: this handle is an encoder-only family; use ishara_encoder_forward"); return -1; }
-    if (B <= 0 || B > m->Bmax) { ishara_set_error("ishara_forward: batch %d outside 1..%d", B, m->Bmax); return -1; }
-    if (m->dt == DT_F16 && training) {
-        ishara_set_error("ishara_forward: ISHARA_F16 is an inference-only storage type (the reference's fp16 is the TFLite export, c14:1-5; it reports NaNs when TRAINING in fp16)");
-        return -1;
-    }
-    m->s = (hipStream_t)st;
-    Run r{B, B * m->T, training, seed};
-    const int dt = m->dt, d = m->d, T = m->T;
+// stem and head of the sequential graph: ishara_forward / ishara_loss_backward and the module probe (ishara_debug_module_*) both run them here
+static int stem_fwd(ishara_model* m, const Run& r, const float* x) {
+    const int dt = m->dt, d = m->d, T = m->T, B = r.B, training = r.training;
     OpArgs no;
     // ---- stem: Dense(no bias) + PE, BatchNorm(momentum .95)  (c7:13-17)
     EpiArgs es; es.addtab = m->Wf(m->pe); es.tab_period = T;
@@ -456,6 +448,29 @@ extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float*
     CKP(m, "bn_finalize", 0, 0, launch_bn_finalize(m->Wf(m->stem_ssum), m->Wf(m->stem_ssq), B, (float)B * T, m->P(m->stem_bn.gamma), m->P(m->stem_bn.beta), 1e-3f, 0.95f,
                           m->P(m->stem_bn.mm), m->P(m->stem_bn.mv), training, m->Wf(m->stem_mean), m->Wf(m->stem_rstd), m->Wf(m->stem_a), m->Wf(m->stem_bsh), d, m->s));
     CKP(m, "col_affine", 2.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_col_affine(dt, m->W(m->stem_h0), m->Wf(m->stem_a), m->Wf(m->stem_bsh), m->W(m->stem_out), r.M, d, m->s));
+    return 0;
+}
+static int head_fwd(ishara_model* m, const Run& r, const void* h, float* logits) {
+    const int dt = m->dt;
+    OpArgs no;
+    // ---- head: Dense(relu) -> Dropout(0.4) -> Dense  (c7:61-63)
+    EpiArgs et; et.act = ACT_RELU; et.drop = dspec(r, m->head_site, m->cfg.head_dropout);
+    CK(gemm_fwd(m, m->topW, h, dt, m->W(m->head_hh), dt, r.M, OP_NONE, no, et));
+    CK(classifier_fwd(m, CLS_AUTO, dt, m->W(m->head_hh), m->ws + m->clsW.wt, m->clsW.ldt, m->clsW.b >= 0 ? m->P(m->clsW.b) : nullptr, logits, r.M, m->clsW.K, m->C, m->s));
+    return 0;
+}
+
+extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float* logits, int32_t training, uint32_t seed, ishara_stream st) {
+    if (!m->ws) { ishara_set_error("ishara_forward: model is not bound"); return -1; }
+    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("ishara_forward: this handle is an encoder-only family; use ishara_encoder_forward"); return -1; }
+    if (B <= 0 || B > m->Bmax) { ishara_set_error("ishara_forward: batch %d outside 1..%d", B, m->Bmax); return -1; }
+    if (m->dt == DT_F16 && training) {
+        ishara_set_error("ishara_forward: ISHARA_F16 is an inference-only storage type (the reference's fp16 is the TFLite export, c14:1-5; it reports NaNs when TRAINING in fp16)");
+        return -1;
+    }
+    m->s = (hipStream_t)st;
+    Run r{B, B * m->T, training, seed};
+    CK(stem_fwd(m, r, x));
     const void* h = m->W(m->stem_out);
     for (const Layer& L : m->layers) {
         if (L.kind == Layer::CONV) { ConvBlock& cb = m->convs[L.idx]; CK(conv_fwd(m, cb, r, h)); h = m->W(cb.out); }
@@ -473,11 +488,8 @@ extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float*
             CK(ffn_fwd(m, cb.ffn2, r, h)); h = m->W(cb.ffn2.out);
         }
     }
-    // ---- head: Dense(relu) -> Dropout(0.4) -> Dense  (c7:61-63)
-    EpiArgs et; et.act = ACT_RELU; et.drop = dspec(r, m->head_site, m->cfg.head_dropout);
-    CK(gemm_fwd(m, m->topW, h, dt, m->W(m->head_hh), dt, r.M, OP_NONE, no, et));
-    CK(classifier_fwd(m, CLS_AUTO, dt, m->W(m->head_hh), m->ws + m->clsW.wt, m->clsW.ldt, m->clsW.b >= 0 ? m->P(m->clsW.b) : nullptr, logits, r.M, m->clsW.K, m->C, m->s));
-    m->lastB = B; m->last_training = training; m->last_seed = seed; m->last_x = x;
+    CK(head_fwd(m, r, h, logits));
+    m->lastB = B; m->last_training = training; m->last_seed = seed; m->last_x = x; m->probe_mod = -1;
     return 0;
 }
 
@@ -604,23 +616,10 @@ int confconv_bwd(ishara_model* m, ConfConv& c, const Run& r, const void* x, cons
     return 0;
 }
 
-extern "C" int ishara_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, ishara_stream st) {
-    if (!m->ws || !m->grads) { ishara_set_error("ishara_loss_backward: model is not bound (grads required)"); return -1; }
-    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("ishara_loss_backward: this handle is an encoder-only family; use ishara_encoder_backward"); return -1; }
-    if (B != m->lastB || !m->last_training) { ishara_set_error("ishara_loss_backward: call ishara_forward(training=1) with the same batch first"); return -1; }
-    m->s = (hipStream_t)st;
-    m->red.njobs = 0; m->red.nblocks = 0; m->red_off = 0; g_red_sink = nullptr;       // ... nor recorded column sums
-    m->tn_defer.pending = false;        // a previous backward pass that returned early (error path) must not leave slab sums behind for this one to add
-    Run r{B, B * m->T, 1, m->last_seed};
-    const int dt = m->dt, d = m->d, T = m->T;
+// head backward: g = gradient with respect to the head's input hin, from dlogits / dlb (the CTC kernel wrote them)
+static int head_bwd(ishara_model* m, const Run& r, const void* hin, void* g) {
+    const int dt = m->dt;
     OpArgs no; EpiArgs e0;
-    float* nl = nll ? nll : m->Wf(m->nllb);
-    CK(launch_fill_u32(m->grads, (size_t)m->n_train, 0u, m->s));      // a kernel, not a memset node: the whole step stays capturable (DESIGN §4, hipGraph note)
-    CKP(m, "ctc", 2.0 * r.M * m->C * 4, 0, launch_ctc(logits, labels, B, T, m->C, m->L, m->C - 1, nl, m->Wf(m->dlogits), loss_scale / (float)B, m->Wf(m->ctcws), m->s, m->cls_pad ? m->W(m->dlb) : nullptr));
-    if (loss) CKP(m, "mean", 0, 0, launch_mean(nl, loss, B, 1.f / (float)B, m->s));
-    // ---- head
-    // input of the head = output of the last layer
-    const void* hin = m->layers.empty() ? m->W(m->stem_out) : layer_out(m, m->layers.back());
     EpiArgs eh; eh.drop = dspec(r, m->head_site, m->cfg.head_dropout); eh.dact = DACT_POS; eh.aux = m->W(m->head_hh);
     if (m->cls_pad && r.M % 64 == 0 && r.M >= 256 && m->clsW.K % 128 == 0 && !g_force_tn_regstage) {
         DenseW wp = m->clsW; wp.N = m->cls_pad;          // reduction / output width of the padded operand; the real classes are the first m->C
@@ -630,9 +629,43 @@ extern "C" int ishara_loss_backward(ishara_model* m, const float* logits, const 
         CK(gemm_dgrad(m, m->clsW, m->Wf(m->dlogits), DT_F32, m->W(m->t1), r.M, OP_NONE, no, eh));
         CK(gemm_wgrad(m, m->clsW, m->W(m->head_hh), dt, OP_NONE, no, m->Wf(m->dlogits), DT_F32, OP_NONE, no, r.M));
     }
-    void* g = m->W(m->gA); void* gn = m->W(m->gB);
     CK(gemm_dgrad(m, m->topW, m->W(m->t1), dt, g, r.M, OP_NONE, no, e0));
     CK(gemm_wgrad(m, m->topW, hin, dt, OP_NONE, no, m->W(m->t1), dt, OP_NONE, no, r.M));
+    return 0;
+}
+// stem backward: parameter gradients from g, the gradient with respect to the stem's output
+static int stem_bwd(ishara_model* m, const Run& r, const void* g) {
+    const int dt = m->dt, d = m->d, T = m->T, B = r.B;
+    OpArgs no;
+    CKP(m, "sample_reduce", 2.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_sample_reduce(dt, g, m->W(m->stem_h0), m->Wf(m->stem_mean), m->Wf(m->stem_rstd), m->Wf(m->S1), m->Wf(m->S2), B, T, d, m->s));
+    CKP(m, "bn_bwd_finalize", 0, 0, launch_bn_bwd_finalize(m->Wf(m->S1), m->Wf(m->S2), m->G(m->stem_bn.gamma), m->G(m->stem_bn.beta), m->Wf(m->Ecol), m->Wf(m->Fc), B, T, d, m->s));
+    CKP(m, "bn_bwd_apply", 6.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_bn_bwd_apply(dt, g, m->W(m->stem_h0), m->Wf(m->stem_mean), m->Wf(m->stem_rstd), m->Wf(m->stem_a), nullptr, m->Wf(m->Ecol), 0, m->Wf(m->Fc), m->W(m->t1), B, T, d, m->s));
+    if (m->stem_kp && r.M % 64 == 0 && r.M >= 256 && d % 128 == 0 && !g_force_tn_regstage) {
+        DenseW wp = m->stemW; wp.K = m->stem_kp;           // packed rows of the forward pass; only the first F rows of dW exist
+        CK(gemm_wgrad(m, wp, m->W(m->stem_xb), dt, OP_NONE, no, m->W(m->t1), dt, OP_NONE, no, r.M, m->F));
+    } else
+        CK(gemm_wgrad(m, m->stemW, m->last_x, DT_F32, OP_NONE, no, m->W(m->t1), dt, OP_NONE, no, r.M));
+    return 0;
+}
+
+extern "C" int ishara_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, ishara_stream st) {
+    if (!m->ws || !m->grads) { ishara_set_error("ishara_loss_backward: model is not bound (grads required)"); return -1; }
+    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("ishara_loss_backward: this handle is an encoder-only family; use ishara_encoder_backward"); return -1; }
+    if (B != m->lastB || !m->last_training) { ishara_set_error("ishara_loss_backward: call ishara_forward(training=1) with the same batch first"); return -1; }
+    m->s = (hipStream_t)st;
+    m->red.njobs = 0; m->red.nblocks = 0; m->red_off = 0; g_red_sink = nullptr;       // ... nor recorded column sums
+    m->tn_defer.pending = false;        // a previous backward pass that returned early (error path) must not leave slab sums behind for this one to add
+    Run r{B, B * m->T, 1, m->last_seed};
+    const int T = m->T;
+    float* nl = nll ? nll : m->Wf(m->nllb);
+    CK(launch_fill_u32(m->grads, (size_t)m->n_train, 0u, m->s));      // a kernel, not a memset node: the whole step stays capturable (DESIGN §4, hipGraph note)
+    CKP(m, "ctc", 2.0 * r.M * m->C * 4, 0, launch_ctc(logits, labels, B, T, m->C, m->L, m->C - 1, nl, m->Wf(m->dlogits), loss_scale / (float)B, m->Wf(m->ctcws), m->s, m->cls_pad ? m->W(m->dlb) : nullptr));
+    if (loss) CKP(m, "mean", 0, 0, launch_mean(nl, loss, B, 1.f / (float)B, m->s));
+    // ---- head
+    // input of the head = output of the last layer
+    const void* hin = m->layers.empty() ? m->W(m->stem_out) : layer_out(m, m->layers.back());
+    void* g = m->W(m->gA); void* gn = m->W(m->gB);
+    CK(head_bwd(m, r, hin, g));
     // ---- layers in reverse; `in_of` = input activation of each module
     for (int li = (int)m->layers.size() - 1; li >= 0; --li) {
         const Layer& L = m->layers[li];
@@ -656,16 +689,165 @@ extern "C" int ishara_loss_backward(ishara_model* m, const float* logits, const 
         if (!m->bucket_ev.empty() && m->bucket_after_layer[li] >= 0) { CK(wgrad_flush(m)); CK(red_flush(m)); HIP_CHECK_RET(hipEventRecord(m->bucket_ev[m->bucket_after_layer[li]], m->s)); }
     }
     // ---- stem
-    CKP(m, "sample_reduce", 2.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_sample_reduce(dt, g, m->W(m->stem_h0), m->Wf(m->stem_mean), m->Wf(m->stem_rstd), m->Wf(m->S1), m->Wf(m->S2), B, T, d, m->s));
-    CKP(m, "bn_bwd_finalize", 0, 0, launch_bn_bwd_finalize(m->Wf(m->S1), m->Wf(m->S2), m->G(m->stem_bn.gamma), m->G(m->stem_bn.beta), m->Wf(m->Ecol), m->Wf(m->Fc), B, T, d, m->s));
-    CKP(m, "bn_bwd_apply", 6.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_bn_bwd_apply(dt, g, m->W(m->stem_h0), m->Wf(m->stem_mean), m->Wf(m->stem_rstd), m->Wf(m->stem_a), nullptr, m->Wf(m->Ecol), 0, m->Wf(m->Fc), m->W(m->t1), B, T, d, m->s));
-    if (m->stem_kp && r.M % 64 == 0 && r.M >= 256 && d % 128 == 0 && !g_force_tn_regstage) {
-        DenseW wp = m->stemW; wp.K = m->stem_kp;           // packed rows of the forward pass; only the first F rows of dW exist
-        CK(gemm_wgrad(m, wp, m->W(m->stem_xb), dt, OP_NONE, no, m->W(m->t1), dt, OP_NONE, no, r.M, m->F));
-    } else
-        CK(gemm_wgrad(m, m->stemW, m->last_x, DT_F32, OP_NONE, no, m->W(m->t1), dt, OP_NONE, no, r.M));
+    CK(stem_bwd(m, r, g));
     CK(wgrad_flush(m));
     CK(red_flush(m));
     if (!m->bucket_ev.empty()) HIP_CHECK_RET(hipEventRecord(m->bucket_ev.back(), m->s));
+    return 0;
+}
+
+// ------------------------------------------------------------------ module probe (debug aid; tests/test_modules_gpu.py)
+// One module of the sequential graph run alone through the functions above, with the model's own Run, site ids and switches: its input
+// sits where the model has it (the output buffer of the module in front), gradients travel through gA / gB.  No buffer of its own.
+struct ProbeMod {
+    enum Kind { STEM, CONV, FFN_, MHSA_, SQZCONV, CONFCONV, HEAD } kind;
+    std::string name; int in_cols, out_cols; uint32_t first_site, n_sites;
+    void* ptr;            // ConvBlock / FFN / MHSA / SqzConv / ConfConv
+    Buf in, out;          // module input / output activation (STEM: no input buffer; HEAD: no output buffer)
+};
+static std::vector<ProbeMod> probe_modules(ishara_model* m) {
+    std::vector<ProbeMod> v;
+    uint32_t site = 0;
+    Buf prev = m->stem_out;
+    auto add = [&](ProbeMod::Kind k, const std::string& name, int in_cols, int out_cols, uint32_t n_sites, void* ptr, Buf out) {
+        v.push_back(ProbeMod{k, name, in_cols, out_cols, site, n_sites, ptr, prev, out});
+        site += n_sites; prev = out;
+    };
+    const int d = m->d;
+    add(ProbeMod::STEM, "stem", m->F, d, 0, nullptr, m->stem_out);
+    for (const Layer& L : m->layers) {
+        if (L.kind == Layer::CONV) {
+            ConvBlock& cb = m->convs[L.idx];
+            const std::string& n = m->entries[cb.W1.w].name;                 // "<prefix>_expand_conv/kernel"
+            add(ProbeMod::CONV, n.substr(0, n.size() - strlen("_expand_conv/kernel")), d, d, 1, &cb, cb.out);
+        } else if (L.kind == Layer::SQZ) {
+            SqzBlock& sb = m->sqz[L.idx];
+            const std::string n = "squeezeformer_" + std::to_string(L.idx);
+            add(ProbeMod::FFN_, n + "/ffn1", d, d, 1 + (sb.ffn1.has_out_drop ? 1 : 0), &sb.ffn1, sb.ffn1.out);
+            add(ProbeMod::MHSA_, n + "/mha", d, d, 1 + (sb.mha.has_out_drop ? 1 : 0), &sb.mha, sb.mha.out);
+            add(ProbeMod::SQZCONV, n + "/conv", d, d, 0, &sb.conv, sb.conv.out);
+            add(ProbeMod::FFN_, n + "/ffn2", d, d, 1 + (sb.ffn2.has_out_drop ? 1 : 0), &sb.ffn2, sb.ffn2.out);
+        } else {
+            ConfBlock& cb = m->conf[L.idx];
+            const std::string n = "conformer_" + std::to_string(L.idx);
+            add(ProbeMod::FFN_, n + "/ffn1", d, d, 1 + (cb.ffn1.has_out_drop ? 1 : 0), &cb.ffn1, cb.ffn1.out);
+            add(ProbeMod::MHSA_, n + "/mha", d, d, 1 + (cb.mha.has_out_drop ? 1 : 0), &cb.mha, cb.mha.out);
+            add(ProbeMod::CONFCONV, n + "/conv", d, d, cb.conv.has_out_drop ? 1 : 0, &cb.conv, cb.conv.out);
+            add(ProbeMod::FFN_, n + "/ffn2", d, d, 1 + (cb.ffn2.has_out_drop ? 1 : 0), &cb.ffn2, cb.ffn2.out);
+        }
+    }
+    add(ProbeMod::HEAD, "head", d, m->C, 1, nullptr, Buf{});
+    return v;
+}
+static bool probe_family_ok(const ishara_model* m, const char* fn) {
+    if (!m) { ishara_set_error("%s: null handle", fn); return false; }
+    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("%s: the module probe exists for ISHARA_FAMILY_KERAS_HYBRID only (family %d)", fn, m->family); return false; }
+    return true;
+}
+extern "C" int32_t ishara_debug_module_count(ishara_model* m) {
+    if (!probe_family_ok(m, "ishara_debug_module_count")) return -1;
+    return (int32_t)probe_modules(m).size();
+}
+extern "C" int ishara_debug_module_info(ishara_model* m, int32_t i, const char** name, int32_t* in_cols, int32_t* out_cols, int32_t* first_site, int32_t* n_sites) {
+    if (!probe_family_ok(m, "ishara_debug_module_info")) return -1;
+    const std::vector<ProbeMod> v = probe_modules(m);
+    if (i < 0 || i >= (int)v.size()) { ishara_set_error("ishara_debug_module_info: module index %d outside 0..%d", i, (int)v.size() - 1); return -1; }
+    static thread_local std::string name_buf;      // valid until this thread's next call
+    name_buf = v[i].name;
+    if (name) *name = name_buf.c_str();
+    if (in_cols) *in_cols = v[i].in_cols;
+    if (out_cols) *out_cols = v[i].out_cols;
+    if (first_site) *first_site = (int32_t)v[i].first_site;
+    if (n_sites) *n_sites = (int32_t)v[i].n_sites;
+    return 0;
+}
+// shared refusals of the probe's launching entry points: nothing is launched for a refused call
+static bool probe_ok(ishara_model* m, const char* fn, int i, int B, const std::vector<ProbeMod>& v, int training, bool need_grads) {
+    if (i < 0 || i >= (int)v.size()) { ishara_set_error("%s: module index %d outside 0..%d", fn, i, (int)v.size() - 1); return false; }
+    if (B <= 0 || B > m->Bmax) { ishara_set_error("%s: batch %d outside 1..%d", fn, B, m->Bmax); return false; }
+    if (m->dt == DT_F16 && training) { ishara_set_error("%s: ISHARA_F16 is an inference-only storage type: training=1 refused", fn); return false; }
+    if (!m->ws || (need_grads && !m->grads)) { ishara_set_error("%s: model is not bound%s", fn, need_grads ? " (grads required)" : ""); return false; }
+    return true;
+}
+extern "C" int ishara_debug_module_forward(ishara_model* m, int32_t i, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, ishara_stream st) {
+    const char* fn = "ishara_debug_module_forward";
+    if (!probe_family_ok(m, fn)) return -1;
+    const std::vector<ProbeMod> v = probe_modules(m);
+    if (!probe_ok(m, fn, i, B, v, training, false)) return -1;
+    if (!x || !y) { ishara_set_error("%s: null x / y", fn); return -1; }
+    m->s = (hipStream_t)st;
+    m->probe_mod = -1; m->last_training = 0;      // the workspace no longer holds a whole forward pass: ishara_loss_backward refuses until the next ishara_forward
+    const ProbeMod& p = v[i];
+    Run r{B, B * m->T, training, seed};
+    const void* in = nullptr;
+    if (p.kind != ProbeMod::STEM) { CK(r5_from_f32(m->dt, x, m->W(p.in), (size_t)r.M * p.in_cols, m->s)); in = m->W(p.in); }
+    switch (p.kind) {
+    case ProbeMod::STEM: CK(stem_fwd(m, r, x)); m->last_x = x; break;
+    case ProbeMod::CONV: CK(conv_fwd(m, *(ConvBlock*)p.ptr, r, in)); break;
+    case ProbeMod::FFN_: CK(ffn_fwd(m, *(FFN*)p.ptr, r, in)); break;
+    case ProbeMod::MHSA_: CK(mhsa_fwd(m, *(MHSA*)p.ptr, r, in)); break;
+    case ProbeMod::SQZCONV: CK(sqzconv_fwd(m, *(SqzConv*)p.ptr, r, in)); break;
+    case ProbeMod::CONFCONV: CK(confconv_fwd(m, *(ConfConv*)p.ptr, r, in)); break;
+    case ProbeMod::HEAD: CK(head_fwd(m, r, in, y)); break;
+    }
+    if (p.kind != ProbeMod::HEAD) CK(r5_to_f32(m->dt, m->W(p.out), y, (size_t)r.M * p.out_cols, m->s));
+    if (training) { m->probe_mod = i; m->probe_B = B; m->probe_seed = seed; }
+    return 0;
+}
+// zero gradients and empty deferred sums, as at the top of ishara_loss_backward
+static int probe_backward_begin(ishara_model* m) {
+    m->red.njobs = 0; m->red.nblocks = 0; m->red_off = 0; g_red_sink = nullptr;
+    m->tn_defer.pending = false;
+    return launch_fill_u32(m->grads, (size_t)m->n_train, 0u, m->s);
+}
+extern "C" int ishara_debug_module_backward(ishara_model* m, int32_t i, const float* dy, int32_t B, float* dx, ishara_stream st) {
+    const char* fn = "ishara_debug_module_backward";
+    if (!probe_family_ok(m, fn)) return -1;
+    const std::vector<ProbeMod> v = probe_modules(m);
+    if (!probe_ok(m, fn, i, B, v, 1, true)) return -1;
+    if (m->probe_mod != i || m->probe_B != B) { ishara_set_error("%s: call ishara_debug_module_forward(training=1) of module %d with batch %d first", fn, i, B); return -1; }
+    const ProbeMod& p = v[i];
+    if (p.kind == ProbeMod::HEAD) { ishara_set_error("%s: the head's backward starts at the CTC kernel: use ishara_debug_head_loss_backward", fn); return -1; }
+    if (!dy) { ishara_set_error("%s: null dy", fn); return -1; }
+    if (p.kind == ProbeMod::STEM && dx) { ishara_set_error("%s: the stem has no input gradient: dx must be NULL", fn); return -1; }
+    m->s = (hipStream_t)st;
+    Run r{B, B * m->T, 1, m->probe_seed};
+    CK(probe_backward_begin(m));
+    void* g = m->W(m->gA); void* gn = m->W(m->gB);
+    CK(r5_from_f32(m->dt, dy, g, (size_t)r.M * p.out_cols, m->s));
+    const void* in = p.kind == ProbeMod::STEM ? nullptr : m->W(p.in);
+    switch (p.kind) {
+    case ProbeMod::STEM: CK(stem_bwd(m, r, g)); break;
+    case ProbeMod::CONV: CK(conv_bwd(m, *(ConvBlock*)p.ptr, r, in, g, gn)); break;
+    case ProbeMod::FFN_: CK(ffn_bwd(m, *(FFN*)p.ptr, r, in, g, gn)); break;
+    case ProbeMod::MHSA_: CK(mhsa_bwd(m, *(MHSA*)p.ptr, r, in, g, gn)); break;
+    case ProbeMod::SQZCONV: CK(sqzconv_bwd(m, *(SqzConv*)p.ptr, r, in, g, gn)); break;
+    case ProbeMod::CONFCONV: CK(confconv_bwd(m, *(ConfConv*)p.ptr, r, in, g, gn)); break;
+    case ProbeMod::HEAD: break;
+    }
+    CK(wgrad_flush(m));
+    CK(red_flush(m));
+    if (dx) CK(r5_to_f32(m->dt, gn, dx, (size_t)r.M * p.in_cols, m->s));
+    return 0;
+}
+extern "C" int ishara_debug_head_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, float* dx, ishara_stream st) {
+    const char* fn = "ishara_debug_head_loss_backward";
+    if (!probe_family_ok(m, fn)) return -1;
+    const std::vector<ProbeMod> v = probe_modules(m);
+    const int i = (int)v.size() - 1;
+    if (!probe_ok(m, fn, i, B, v, 1, true)) return -1;
+    if (m->probe_mod != i || m->probe_B != B) { ishara_set_error("%s: call ishara_debug_module_forward(training=1) of the head (module %d) with batch %d first", fn, i, B); return -1; }
+    if (!logits || !labels) { ishara_set_error("%s: null logits / labels", fn); return -1; }
+    m->s = (hipStream_t)st;
+    Run r{B, B * m->T, 1, m->probe_seed};
+    float* nl = nll ? nll : m->Wf(m->nllb);
+    CK(probe_backward_begin(m));
+    CKP(m, "ctc", 2.0 * r.M * m->C * 4, 0, launch_ctc(logits, labels, B, m->T, m->C, m->L, m->C - 1, nl, m->Wf(m->dlogits), loss_scale / (float)B, m->Wf(m->ctcws), m->s, m->cls_pad ? m->W(m->dlb) : nullptr));
+    if (loss) CKP(m, "mean", 0, 0, launch_mean(nl, loss, B, 1.f / (float)B, m->s));
+    void* g = m->W(m->gA);
+    CK(head_bwd(m, r, m->W(v[i].in), g));
+    CK(wgrad_flush(m));
+    CK(red_flush(m));
+    if (dx) CK(r5_to_f32(m->dt, g, dx, (size_t)r.M * m->d, m->s));
     return 0;
 }

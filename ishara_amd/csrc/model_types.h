@@ -142,6 +142,7 @@ struct ishara_model {
     // run state
     int lastB = 0; int last_training = 0; uint32_t last_seed = 0; const float* last_x = nullptr;
     int opt_iter = 0;
+    int probe_mod = -1, probe_B = 0; uint32_t probe_seed = 0;      // module probe (ishara_debug_module_*): the last training forward of a single module
     hipStream_t s = nullptr;
 
     // ---- build helpers

@@ -354,6 +354,54 @@ class Model(Handle):
             out[k] = dict(launches=int(cnt), ms=float(ms), bytes=float(by), flops=float(fl))
         return out
 
+    # ------------------------------------------------------------------ module probe (debug aid: tests/test_modules_gpu.py)
+    def _module_info(self, i: int):
+        """(name, in_cols, out_cols, first dropout site, number of sites) of module i."""
+        name, a, b, s0, ns = C.c_char_p(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(self._lib.ishara_debug_module_info(self._h, i, C.byref(name), C.byref(a), C.byref(b), C.byref(s0), C.byref(ns)),
+                   "ishara_debug_module_info")
+        return name.value.decode(), a.value, b.value, s0.value, ns.value
+
+    def module_names(self) -> List[str]:
+        """The modules of the sequential graph in forward order: stem, Conv1DBlocks, block sub-modules, head."""
+        n = int(self._lib.ishara_debug_module_count(self._h))
+        if n < 0:
+            _lib.check(n, "ishara_debug_module_count")
+        return [self._module_info(i)[0] for i in range(n)]
+
+    def module_forward(self, i: int, x, training: bool = False, seed: int = 0) -> torch.Tensor:
+        """Module i alone on x [B,T,in_cols] through the model's own orchestration -> f32 [B,T,out_cols] (the head: logits)."""
+        _, cin, cout, _, _ = self._module_info(i)
+        x = torch.as_tensor(x).to(self.device, torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[1:] != (self.T, cin):
+            raise ValueError(f"module {i}: expected input [B,{self.T},{cin}], got {tuple(x.shape)}")
+        y = torch.empty((x.shape[0], self.T, cout), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.ishara_debug_module_forward(self._h, i, _lib.ptr(x), x.shape[0], _lib.ptr(y), 1 if training else 0,
+                                                         C.c_uint32(seed), _stream()), "ishara_debug_module_forward")
+        self._last_x = x          # the stem's weight gradient re-reads it
+        return y
+
+    def module_backward(self, i: int, dy, labels=None, loss_scale: float = 1.0) -> Optional[torch.Tensor]:
+        """Backward of module i after module_forward(i, ..., training=True): dy [B,T,out_cols] -> the gradient with respect to the module's
+        input (None for the stem); the parameter gradients are in `grads`.  The head takes its logits as dy and `labels` [B,L]: CTC + head
+        backward, the loss in `_loss_buf`."""
+        _, cin, cout, _, _ = self._module_info(i)
+        dy = torch.as_tensor(dy).to(self.device, torch.float32).contiguous()
+        if dy.dim() != 3 or dy.shape[1:] != (self.T, cout):
+            raise ValueError(f"module {i}: expected dy [B,{self.T},{cout}], got {tuple(dy.shape)}")
+        B = dy.shape[0]
+        if labels is not None:
+            yl = torch.as_tensor(np.asarray(labels) if not isinstance(labels, torch.Tensor) else labels).to(self.device, torch.int64).contiguous()
+            if yl.shape != (B, self._cfg.max_label_len):
+                raise ValueError(f"labels must be [B,{self._cfg.max_label_len}] padded with {self.C - 1}")
+            dx = torch.empty((B, self.T, cin), dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.ishara_debug_head_loss_backward(self._h, _lib.ptr(dy), _lib.ptr(yl), B, _lib.ptr(self._loss_buf), _lib.ptr(self._nll_buf),
+                                                                 C.c_float(loss_scale), _lib.ptr(dx), _stream()), "ishara_debug_head_loss_backward")
+            return dx
+        dx = None if i == 0 else torch.empty((B, self.T, cin), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.ishara_debug_module_backward(self._h, i, _lib.ptr(dy), B, _lib.ptr(dx), _stream()), "ishara_debug_module_backward")
+        return dx
+
     def ctc_loss(self, y, logits) -> torch.Tensor:
         """CTCLoss(labels, logits) (c6:1-13) on the GPU; returns per-sample nll [B]."""
         logits = logits.to(self.device, torch.float32).contiguous()

@@ -193,8 +193,8 @@ def init_params(cfg: Config, seed: int = 0) -> Dict[str, np.ndarray]:
 # Dropout sites (deterministic order shared with ishara_amd/csrc/model.cpp)
 # ----------------------------------------------------------------------------
 class _Sites:
-    def __init__(self, seed, training):
-        self.seed, self.training, self.n = seed, training, 0
+    def __init__(self, seed, training, first=0):
+        self.seed, self.training, self.n = seed, training, first      # first: the id of the first site drawn (a module evaluated alone)
 
     def mask(self, rows, cols, rate, ref: torch.Tensor, attn: bool = False):
         """Returns multiplicative mask tensor [rows, cols] or None; always
@@ -310,12 +310,18 @@ def ffn(x, P, n1, n2, rate, sites):
     return dense(h, P, n2)
 
 
-def squeezeformer_block(x, P, name, cfg, training, sites):
-    """c5:155-207 (+ConvModule c5:135-153, SqueezeExcite c5:120-133)."""
+def sqz_ffn1(x, P, name, cfg, sites):
     r = cfg.dropout_rate
-    x = x + _drop(ffn(layer_norm(x, P, f"{name}/norm1", 1e-6), P, f"{name}/ffn1_dense1", f"{name}/ffn1_dense2", r, sites), r, sites)
-    x = x + _drop(mhsa(layer_norm(x, P, f"{name}/norm2", 1e-6), P, f"{name}/mha", cfg, r, sites), r, sites)
-    # ConvModule
+    return x + _drop(ffn(layer_norm(x, P, f"{name}/norm1", 1e-6), P, f"{name}/ffn1_dense1", f"{name}/ffn1_dense2", r, sites), r, sites)
+
+
+def sqz_mha(x, P, name, cfg, sites):
+    r = cfg.dropout_rate
+    return x + _drop(mhsa(layer_norm(x, P, f"{name}/norm2", 1e-6), P, f"{name}/mha", cfg, r, sites), r, sites)
+
+
+def sqz_conv(x, P, name, cfg, sites):
+    """ConvModule c5:135-153 + SqueezeExcite c5:120-133 (no dropout site)."""
     u = layer_norm(x, P, f"{name}/conv/norm", 1e-6)
     u = swish(dense(u, P, f"{name}/conv/conv1"))
     u = swish(causal_dwconv(u, P[f"{name}/conv/conv2/depthwise_kernel"]))
@@ -323,16 +329,32 @@ def squeezeformer_block(x, P, name, cfg, training, sites):
     z = u.mean(dim=1)
     z = swish(dense(z, P, f"{name}/conv/se/fc1"))
     z = torch.sigmoid(dense(z, P, f"{name}/conv/se/fc2"))
-    x = u * z[:, None, :] + x
-    x = x + _drop(ffn(layer_norm(x, P, f"{name}/norm3", 1e-6), P, f"{name}/ffn2_dense1", f"{name}/ffn2_dense2", r, sites), r, sites)
-    return x
+    return u * z[:, None, :] + x
 
 
-def conformer_block(x, P, name, cfg, training, sites, new_stats):
-    """c5:311-343 (+FeedForwardModule c5:237-247, ConvolutionModule c5:249-309)."""
+def sqz_ffn2(x, P, name, cfg, sites):
     r = cfg.dropout_rate
-    x = x + ffn(layer_norm(x, P, f"{name}/layer_norm1", 1e-6), P, f"{name}/ffn1/dense1", f"{name}/ffn1/dense2", r, sites)
-    x = x + mhsa(layer_norm(x, P, f"{name}/layer_norm1", 1e-6), P, f"{name}/mha", cfg, cfg.conformer_attn_dropout, sites)
+    return x + _drop(ffn(layer_norm(x, P, f"{name}/norm3", 1e-6), P, f"{name}/ffn2_dense1", f"{name}/ffn2_dense2", r, sites), r, sites)
+
+
+def squeezeformer_block(x, P, name, cfg, training, sites):
+    """c5:155-207 (+ConvModule c5:135-153, SqueezeExcite c5:120-133): the four sub-modules above in order."""
+    x = sqz_ffn1(x, P, name, cfg, sites)
+    x = sqz_mha(x, P, name, cfg, sites)
+    x = sqz_conv(x, P, name, cfg, sites)
+    return sqz_ffn2(x, P, name, cfg, sites)
+
+
+def conf_ffn1(x, P, name, cfg, sites):
+    return x + ffn(layer_norm(x, P, f"{name}/layer_norm1", 1e-6), P, f"{name}/ffn1/dense1", f"{name}/ffn1/dense2", cfg.dropout_rate, sites)
+
+
+def conf_mha(x, P, name, cfg, sites):
+    return x + mhsa(layer_norm(x, P, f"{name}/layer_norm1", 1e-6), P, f"{name}/mha", cfg, cfg.conformer_attn_dropout, sites)
+
+
+def conf_conv(x, P, name, cfg, training, new_stats):
+    """ConvolutionModule c5:249-309 and the LayerNorm behind it (no dropout site)."""
     res = x
     u = dense(x, P, f"{name}/conv/pointwise_conv1")
     d = x.shape[-1]
@@ -340,9 +362,33 @@ def conformer_block(x, P, name, cfg, training, sites, new_stats):
     u = same_dwconv(u, P[f"{name}/conv/depthwise_conv/kernel"], P[f"{name}/conv/depthwise_conv/bias"])
     u = batch_norm(u, P, f"{name}/conv/batch_norm", training, 0.99, new_stats)
     u = dense(u, P, f"{name}/conv/pointwise_conv2")
-    x = layer_norm(u + res, P, f"{name}/conv/layer_norm", 1e-3)
-    x = x + ffn(layer_norm(x, P, f"{name}/layer_norm2", 1e-6), P, f"{name}/ffn2/dense1", f"{name}/ffn2/dense2", r, sites)
-    return x
+    return layer_norm(u + res, P, f"{name}/conv/layer_norm", 1e-3)
+
+
+def conf_ffn2(x, P, name, cfg, sites):
+    return x + ffn(layer_norm(x, P, f"{name}/layer_norm2", 1e-6), P, f"{name}/ffn2/dense1", f"{name}/ffn2/dense2", cfg.dropout_rate, sites)
+
+
+def conformer_block(x, P, name, cfg, training, sites, new_stats):
+    """c5:311-343 (+FeedForwardModule c5:237-247, ConvolutionModule c5:249-309): the four sub-modules above in order."""
+    x = conf_ffn1(x, P, name, cfg, sites)
+    x = conf_mha(x, P, name, cfg, sites)
+    x = conf_conv(x, P, name, cfg, training, new_stats)
+    return conf_ffn2(x, P, name, cfg, sites)
+
+
+def stem(x, P, cfg, training, new_stats):
+    """c7:13-17: Dense(no bias) + positional encoding, BatchNorm."""
+    h = x @ P["stem_conv/kernel"]
+    h = h + positional_encoding(x.shape[1], cfg.dim, h.dtype)
+    return batch_norm(h, P, "stem_bn", training, 0.95, new_stats)
+
+
+def head(h, P, cfg, sites):
+    """c7:61-63: Dense(relu) -> Dropout -> Dense."""
+    h = torch.relu(dense(h, P, "top_conv"))
+    h = _drop(h, cfg.head_dropout, sites)
+    return dense(h, P, "classifier")
 
 
 def forward(P: Dict[str, torch.Tensor], x: torch.Tensor, cfg: Config, training: bool = False,
@@ -354,10 +400,7 @@ def forward(P: Dict[str, torch.Tensor], x: torch.Tensor, cfg: Config, training: 
     the `x + pe` TFOpLambda."""
     sites = _Sites(seed, training)
     new_stats: Dict[str, torch.Tensor] = {}
-    B, T, Fdim = x.shape
-    h = x @ P["stem_conv/kernel"]
-    h = h + positional_encoding(T, cfg.dim, h.dtype)
-    h = batch_norm(h, P, "stem_bn", training, 0.95, new_stats)
+    h = stem(x, P, cfg, training, new_stats)
     if taps is not None: taps["stem"] = h
 
     def conv_blocks(h, tag):
@@ -374,9 +417,7 @@ def forward(P: Dict[str, torch.Tensor], x: torch.Tensor, cfg: Config, training: 
         h = conv_blocks(h, f"conform_{i}")
         h = conformer_block(h, P, f"conformer_{i}", cfg, training, sites, new_stats)
         if taps is not None: taps[f"conformer_{i}"] = h
-    h = torch.relu(dense(h, P, "top_conv"))
-    h = _drop(h, cfg.head_dropout, sites)
-    return dense(h, P, "classifier"), new_stats
+    return head(h, P, cfg, sites), new_stats
 
 
 # ----------------------------------------------------------------------------

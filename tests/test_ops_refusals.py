@@ -104,3 +104,63 @@ def test_qkv_refuses_null_buffers_before_launching(lib):
     rc = lib.ishara_op_qkv_fwd(F16, N, N, N, C.c_float(1e-6), N, N, N, N, N, 1, 64, 4, 32, 1, N, N)
     _refused(lib, rc, "ishara_op_qkv_fwd", "null")
     assert lib.ishara_op_qkv_scratch_bytes(1, 64, 4, 32) > 0 and lib.ishara_op_qkv_scratch_bytes(0, 64, 4, 32) < 0
+
+
+# ---- the module probe (ishara_debug_module_*): refusals that need no device
+def _handle(**kw):
+    from ishara_amd import make_config
+    from ishara_amd.model import Model
+    return Model(make_config(dim=64, num_conv_squeeze_blocks=1, num_conv_conform_blocks=1, max_batch=4, **kw), device=None)
+
+
+def _probe_calls(lib, h, i, B, training=0):
+    f = C.c_float
+    return {
+        "ishara_debug_module_forward": lambda: lib.ishara_debug_module_forward(h, i, N, B, N, training, 1, N),
+        "ishara_debug_module_backward": lambda: lib.ishara_debug_module_backward(h, i, N, B, N, N),
+        "ishara_debug_head_loss_backward": lambda: lib.ishara_debug_head_loss_backward(h, N, N, B, N, N, f(1.0), N, N),
+    }
+
+
+@pytest.mark.parametrize("name", ["ishara_debug_module_forward", "ishara_debug_module_backward", "ishara_debug_head_loss_backward"])
+def test_probe_refuses_an_unbound_handle(lib, name):
+    m = _handle()
+    _refused(lib, _probe_calls(lib, m._h, 1, 2)[name](), name, "not bound")
+
+
+@pytest.mark.parametrize("name", ["ishara_debug_module_forward", "ishara_debug_module_backward"])
+@pytest.mark.parametrize("i", [-1, 16, 100])
+def test_probe_refuses_a_module_index_out_of_range(lib, name, i):
+    m = _handle()
+    assert lib.ishara_debug_module_count(m._h) == 16      # stem, 2 x (3 Conv1DBlocks, 4 sub-modules), head
+    _refused(lib, _probe_calls(lib, m._h, i, 2)[name](), name, "module index", str(i))
+
+
+@pytest.mark.parametrize("name", ["ishara_debug_module_forward", "ishara_debug_module_backward", "ishara_debug_head_loss_backward"])
+@pytest.mark.parametrize("B", [0, -3, 5])
+def test_probe_refuses_a_batch_outside_the_plan(lib, name, B):
+    m = _handle()
+    _refused(lib, _probe_calls(lib, m._h, 1, B)[name](), name, "batch", "1..4")
+
+
+def test_probe_refuses_fp16_training_and_lists_fp16_modules(lib):
+    m = _handle(dtype="f16")
+    _refused(lib, _probe_calls(lib, m._h, 1, 2, training=1)["ishara_debug_module_forward"](), "ishara_debug_module_forward", "ISHARA_F16", "training=1")
+    _refused(lib, _probe_calls(lib, m._h, 1, 2)["ishara_debug_module_backward"](), "ishara_debug_module_backward", "ISHARA_F16")
+    _refused(lib, _probe_calls(lib, m._h, 1, 2, training=0)["ishara_debug_module_forward"](), "ishara_debug_module_forward", "not bound")      # inference is not refused for the dtype
+
+
+def test_probe_refuses_the_encoder_families(lib):
+    from ishara_amd import make_config
+    cfg = make_config(dim=64, num_conv_squeeze_blocks=0, num_conv_conform_blocks=1, num_heads=4, input_shape=(64, 64), max_batch=2, dtype="f32")
+    cfg.family = _lib.FAMILY_TORCH_CONFORMER
+    h = C.c_void_p()
+    assert lib.ishara_create(C.byref(cfg), C.byref(h)) == 0, lib.ishara_last_error()
+    try:
+        assert lib.ishara_debug_module_count(h) < 0
+        _refused(lib, -1, "ishara_debug_module_count", "ISHARA_FAMILY_KERAS_HYBRID")
+        for name, call in _probe_calls(lib, h, 0, 1).items():
+            _refused(lib, call(), name, "ISHARA_FAMILY_KERAS_HYBRID")
+        _refused(lib, lib.ishara_debug_module_info(h, 0, N, N, N, N, N), "ishara_debug_module_info", "ISHARA_FAMILY_KERAS_HYBRID")
+    finally:
+        lib.ishara_destroy(h)

@@ -285,6 +285,45 @@ int ishara_op_attn_bwd(int32_t dt, const void* o, const void* dout, void* dqkv, 
                        int32_t T, int32_t dh, float scale, uint32_t seed, uint32_t site, float rate,
                        int32_t impl, void* scratch, ishara_stream s);
 
+/* ---- the torch Squeezeformer family's own kernels, through the launch code ishara_encoder_forward / _backward use.  dt: ISHARA_F32 /
+ * ISHARA_BF16 (the family has no fp16 kernels: ISHARA_F16 is refused).  Every buffer 16-byte aligned; shapes, null and alignment are checked
+ * before anything is launched; every output, the parameter gradients included, is overwritten. */
+/* Relative-position attention.  q, k, v, o, dO, dq, dk, dv [B*T, H*dh] (dt, head h in columns h*dh ..); pe [2T-1, H*dh] f32 the positional
+ * table; Wpos [H*dh, H*dh] f32 in [in, out] layout; u, vb, du, dvb [H*dh] f32; dh 8 / 16 / 32 / 64; rate in [0, 1).  The forward converts the
+ * table to dt, builds the weight shadow, runs pos_proj (dt operands, f32 output, M = 2T-1) and the attention with scale 1/sqrt(dh) and the
+ * dropout of (seed, site, rate); lse [B*H*T] f32 is optional.  The table copy, posp and lse stay in scratch (ishara_op_relattn_scratch_bytes)
+ * for the backward call, which takes the forward's q, k, v, u, vb, o again and returns dWpos [H*dh, H*dh] and, optionally, dposp [2T-1, H*dh]. */
+int64_t ishara_op_relattn_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh);
+int ishara_op_relattn_fwd(int32_t dt, const void* q, const void* k, const void* v, const float* pe, const float* Wpos, const float* u, const float* vb,
+                          void* o, float* lse, int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
+                          void* scratch, ishara_stream s);
+int ishara_op_relattn_bwd(int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
+                          void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
+                          int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate, void* scratch, ishara_stream s);
+/* DepthwiseConv2dSubsampling: x [B,T0,F] f32, w1, w2 [d,9], b1, b2 [d] f32 -> sub [B*T2, d*F2] (dt), T1 = (T0-3)/2+1, T2 = (T1-3)/2+1, same
+ * for F; T0, F >= 7.  The first convolution's output stays in scratch for the backward call: dsub (dt) -> dw1, db1, dw2, db2 and dx [B,T0,F]
+ * f32 (NULL: not computed). */
+int64_t ishara_op_r4_subsample_scratch_bytes(int32_t B, int32_t T0, int32_t F, int32_t d);
+int ishara_op_r4_subsample_fwd(int32_t dt, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, void* sub,
+                               int32_t B, int32_t T0, int32_t F, int32_t d, void* scratch, ishara_stream s);
+int ishara_op_r4_subsample_bwd(int32_t dt, const float* x, const float* w1, const float* w2, const void* sub, const void* dsub,
+                               float* dw1, float* db1, float* dw2, float* db2, float* dx, int32_t B, int32_t T0, int32_t F, int32_t d,
+                               void* scratch, ishara_stream s);
+/* TimeReductionLayer and time_reduction_proj: h [B,Tin,d] (dt), conv_w [9], conv_b [1], Wred [Fr,d] ([in, out]), bred [d] f32 -> red [B*Tr, d]
+ * (dt); Tr = (Tin-3)/2+1, Fr = (d-1)/2, the Linear runs over K = Kp = Fr rounded up to 8; Tin, d >= 3, d % 8 == 0.  conv_out [B*Tr, Kp] (dt,
+ * optional): the convolution's output with its zero pad columns.  Backward: dred (dt) and extra [B,Tin,d] (dt, NULL: none; added to dh) ->
+ * dh [B,Tin,d] (dt), dconv_w [9], dconv_b [1], dWred [Fr,d], dbred [d]. */
+int64_t ishara_op_r4_time_reduce_scratch_bytes(int32_t B, int32_t Tin, int32_t d);
+int ishara_op_r4_time_reduce_fwd(int32_t dt, const void* h, const float* conv_w, const float* conv_b, const float* Wred, const float* bred,
+                                 void* red, void* conv_out, int32_t B, int32_t Tin, int32_t d, void* scratch, ishara_stream s);
+int ishara_op_r4_time_reduce_bwd(int32_t dt, const void* h, const float* conv_w, const void* dred, const void* extra, void* dh,
+                                 float* dconv_w, float* dconv_b, float* dWred, float* dbred, int32_t B, int32_t Tin, int32_t d,
+                                 void* scratch, ishara_stream s);
+/* row maps over dst [B,Tdst,d] from src [B,Tsrc,d] (dt).  mode 0: dst[t] = src[t/2]; 1: dst[t] = src[t]; 2: dst[t] = src[2t] + src[2t+1];
+ * 3: dst[t] = t < Tsrc ? src[t] : 0; 4: dst = a + src (Tdst == Tsrc; a is read by this mode only) */
+int ishara_op_r4_rows(int32_t dt, int32_t mode, const void* src, const void* a, void* dst, int32_t B, int32_t Tdst, int32_t Tsrc, int32_t d,
+                      ishara_stream s);
+
 #ifdef __cplusplus
 }
 #endif

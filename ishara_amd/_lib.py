@@ -109,6 +109,16 @@ SIGNATURES = {
     "ishara_op_attn_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_op_attn_fwd": (C.c_int, [_I32, _P, _P, _I32, _I32, _I32, _I32, _F, _U32, _U32, _F, _I32, _P, _P]),
     "ishara_op_attn_bwd": (C.c_int, [_I32, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _U32, _U32, _F, _I32, _P, _P]),
+    "ishara_op_relattn_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "ishara_op_relattn_fwd": (C.c_int, [_I32] + [_P] * 9 + [_I32, _I32, _I32, _I32, _U32, _U32, _F, _P, _P]),
+    "ishara_op_relattn_bwd": (C.c_int, [_I32] + [_P] * 14 + [_I32, _I32, _I32, _I32, _U32, _U32, _F, _P, _P]),
+    "ishara_op_r4_subsample_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "ishara_op_r4_subsample_fwd": (C.c_int, [_I32] + [_P] * 6 + [_I32, _I32, _I32, _I32, _P, _P]),
+    "ishara_op_r4_subsample_bwd": (C.c_int, [_I32] + [_P] * 10 + [_I32, _I32, _I32, _I32, _P, _P]),
+    "ishara_op_r4_time_reduce_scratch_bytes": (_I64, [_I32, _I32, _I32]),
+    "ishara_op_r4_time_reduce_fwd": (C.c_int, [_I32] + [_P] * 7 + [_I32, _I32, _I32, _P, _P]),
+    "ishara_op_r4_time_reduce_bwd": (C.c_int, [_I32] + [_P] * 9 + [_I32, _I32, _I32, _P, _P]),
+    "ishara_op_r4_rows": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
 }
 
 _lib = None

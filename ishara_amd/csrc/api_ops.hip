@@ -281,3 +281,204 @@ extern "C" int ishara_op_attn_bwd(int32_t dt, const void* o, const void* dout, v
     const AttnScratch a((char*)scratch, B, H, T, dh);
     return launch_attn_bwd(dt, a.q, a.k, a.vt, o, dout, a.lse, a.delta, dqkv, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), 1, impl, a.maskw, s);
 }
+
+// ---- operator tests: the torch Squeezeformer family's own kernels (squeezeformer_r4.hip), through the launch code the encoder uses.
+// The family has no fp16 kernels: every entry point refuses ISHARA_F16.  Shapes, null and alignment are checked before any HIP call;
+// every output, the parameter gradients included, is overwritten.
+static bool op_r4_dt_ok(const char* op, int dt) {
+    if (dt != DT_F32 && dt != DT_BF16 && dt != DT_F16) { ishara_set_error("%s: unknown dtype %d (ISHARA_F32 = 0, ISHARA_BF16 = 1, ISHARA_F16 = 2)", op, dt); return false; }
+    if (dt == DT_F16) { ishara_set_error("%s: ISHARA_F16 is not supported (the torch Squeezeformer family has no fp16 kernels)", op); return false; }
+    return true;
+}
+#define OP_R4_DT(op, dt) do { if (!op_r4_dt_ok(op, dt)) return -1; } while (0)
+static bool op_misaligned(std::initializer_list<const void*> ps) { uintptr_t a = 0; for (const void* p : ps) a |= (uintptr_t)p; return a % 16 != 0; }
+static bool op_any_null(std::initializer_list<const void*> ps) { for (const void* p : ps) if (!p) return true; return false; }
+static size_t op_shadow_bytes(int K, int N, int M) { const size_t a = OpShadow(DT_F32, K, N, M).total, b = OpShadow(DT_BF16, K, N, M).total; return rup(a > b ? a : b, 256); }
+
+// scratch of the relative attention: pos_proj shadows and wgrad slab | table in the storage dtype | posp | dposp | lse | delta
+struct RelAttnScratch {
+    size_t pedt, posp, dposp, lse, delta, total;
+    RelAttnScratch(int B, int H, int T, int dh) {
+        const size_t d = (size_t)H * dh, R = 2 * (size_t)T - 1, tab = rup(R * d * 4, 256), row = rup((size_t)B * H * T * 4, 256);
+        pedt = op_shadow_bytes((int)d, (int)d, (int)R);
+        posp = pedt + tab; dposp = posp + tab; lse = dposp + tab; delta = lse + row; total = delta + row;
+    }
+};
+static const char* relattn_shape_error(int B, int H, int T, int dh, float rate) {
+    if (dh != 8 && dh != 16 && dh != 32 && dh != 64) return "head dim unsupported (8, 16, 32, 64)";
+    if (B < 1 || H < 1 || T < 1) return "B, H and T must be >= 1";
+    if ((int64_t)B * H > 65535 || (int64_t)B * H * T * dh > 2147483647LL || (2 * (int64_t)T - 1) * H * dh > 2147483647LL) return "shape too large (B*H <= 65535, B*H*T*dh < 2^31)";
+    if (!(rate >= 0.f && rate < 1.f)) return "rate outside [0, 1)";
+    return nullptr;
+}
+extern "C" int64_t ishara_op_relattn_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh) {
+    if (relattn_shape_error(B, H, T, dh, 0.f)) return -1;
+    return (int64_t)RelAttnScratch(B, H, T, dh).total;
+}
+extern "C" int ishara_op_relattn_fwd(int32_t dt, const void* q, const void* k, const void* v, const float* pe, const float* Wpos, const float* u, const float* vb,
+                                     void* o, float* lse, int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate, void* scratch, ishara_stream st) {
+    const char* me = "ishara_op_relattn_fwd";
+    OP_R4_DT(me, dt);
+    if (const char* why = relattn_shape_error(B, H, T, dh, rate)) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d rate=%g: %s", me, B, H, T, dh, rate, why); return -1; }
+    if (op_any_null({q, k, v, pe, Wpos, u, vb, o, scratch}) || op_misaligned({q, k, v, pe, Wpos, u, vb, o, lse, scratch})) {
+        ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only lse may be NULL)", me); return -1;
+    }
+    hipStream_t s = (hipStream_t)st;
+    const int d = H * dh, R = 2 * T - 1;
+    const OpShadow sh(dt, d, d, R);
+    const RelAttnScratch a(B, H, T, dh);
+    char* sc = (char*)scratch;
+    CK(sh.build(dt, Wpos, d, d, sc, s));
+    // the table in the storage type (A operand of the pos_proj GEMM), as r4_forward converts it
+    if (dt != DT_F32) CK(r5_from_f32(dt, pe, sc + a.pedt, (size_t)R * d, s));
+    else HIP_CHECK_RET(hipMemcpyAsync(sc + a.pedt, pe, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    OpArgs no; EpiArgs e0;
+    CK(launch_gemm_nt(dt, dt, DT_F32, OP_NONE, sc + a.pedt, sc + sh.wt, sc + a.posp, R, d, d, sh.ldt, no, e0, s));      // r4_mhsa_fwd's pos_proj
+    CK(launch_relattn_fwd(dt, q, k, v, (const float*)(sc + a.posp), u, vb, o, (float*)(sc + a.lse), B, H, T, dh, 1.0f / sqrtf((float)dh), make_drop_attn(seed, site, rate, true), s));
+    if (lse) HIP_CHECK_RET(hipMemcpyAsync(lse, sc + a.lse, (size_t)B * H * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+extern "C" int ishara_op_relattn_bwd(int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
+                                     void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
+                                     int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate, void* scratch, ishara_stream st) {
+    const char* me = "ishara_op_relattn_bwd";
+    OP_R4_DT(me, dt);
+    if (const char* why = relattn_shape_error(B, H, T, dh, rate)) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d rate=%g: %s", me, B, H, T, dh, rate, why); return -1; }
+    if (op_any_null({q, k, v, u, vb, o, dO, dq, dk, dv, du, dvb, dWpos, scratch}) || op_misaligned({q, k, v, u, vb, o, dO, dq, dk, dv, du, dvb, dWpos, dposp, scratch})) {
+        ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only dposp may be NULL)", me); return -1;
+    }
+    hipStream_t s = (hipStream_t)st;
+    const int d = H * dh, R = 2 * T - 1;
+    const OpShadow sh(dt, d, d, R);
+    const RelAttnScratch a(B, H, T, dh);
+    char* sc = (char*)scratch;
+    float* dp = (float*)(sc + a.dposp);
+    CK(r4_fill_f32_launch(dp, (size_t)R * d, 0.f, s));
+    CK(r4_fill_f32_launch(du, (size_t)d, 0.f, s));
+    CK(r4_fill_f32_launch(dvb, (size_t)d, 0.f, s));
+    CK(r4_fill_f32_launch(dWpos, (size_t)d * d, 0.f, s));
+    CK(launch_relattn_bwd(dt, q, k, v, (const float*)(sc + a.posp), u, vb, o, dO, (const float*)(sc + a.lse), (float*)(sc + a.delta), dq, dk, dv, du, dvb, dp,
+                          B, H, T, dh, 1.0f / sqrtf((float)dh), make_drop_attn(seed, site, rate, true), s));
+    OpArgs no;
+    CK(launch_gemm_tn(dt, DT_F32, dt, OP_NONE, OP_NONE, sc + a.pedt, dp, dWpos, nullptr, (float*)(sc + sh.slab), R, d, d, no, no, s));      // r4_mhsa_bwd's pos_proj weight gradient
+    if (dposp) HIP_CHECK_RET(hipMemcpyAsync(dposp, dp, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// DepthwiseConv2dSubsampling.  scratch: y1 | dz1, both [B, d, T1, F1] f32
+static const char* subsample_shape_error(int B, int T0, int F, int d) {
+    if (B < 1 || d < 1) return "B and d must be >= 1";
+    if (T0 < 7 || F < 7) return "T0 and F must be >= 7 (two 3x3 stride-2 convolutions)";
+    const R4Dims D = r4_dims(T0, F, d);
+    if ((int64_t)B * d * D.T1 * D.F1 > 2147483647LL || (int64_t)B * T0 * F > 2147483647LL) return "shape too large (B*d*T1*F1 < 2^31)";
+    return nullptr;
+}
+extern "C" int64_t ishara_op_r4_subsample_scratch_bytes(int32_t B, int32_t T0, int32_t F, int32_t d) {
+    if (subsample_shape_error(B, T0, F, d)) return -1;
+    const R4Dims D = r4_dims(T0, F, d);
+    return (int64_t)(2 * rup((size_t)B * d * D.T1 * D.F1 * 4, 256));
+}
+extern "C" int ishara_op_r4_subsample_fwd(int32_t dt, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, void* sub,
+                                          int32_t B, int32_t T0, int32_t F, int32_t d, void* scratch, ishara_stream st) {
+    const char* me = "ishara_op_r4_subsample_fwd";
+    OP_R4_DT(me, dt);
+    if (const char* why = subsample_shape_error(B, T0, F, d)) { ishara_set_error("%s: B=%d T0=%d F=%d d=%d: %s", me, B, T0, F, d, why); return -1; }
+    if (op_any_null({x, w1, b1, w2, b2, sub, scratch}) || op_misaligned({x, w1, b1, w2, b2, sub, scratch})) { ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned)", me); return -1; }
+    const R4Dims D = r4_dims(T0, F, d);
+    return r4_subsample_fwd_launch(dt, x, w1, b1, w2, b2, (float*)scratch, sub, B, T0, F, d, D.T1, D.F1, D.T2, D.F2, (hipStream_t)st);
+}
+extern "C" int ishara_op_r4_subsample_bwd(int32_t dt, const float* x, const float* w1, const float* w2, const void* sub, const void* dsub,
+                                          float* dw1, float* db1, float* dw2, float* db2, float* dx, int32_t B, int32_t T0, int32_t F, int32_t d, void* scratch, ishara_stream st) {
+    const char* me = "ishara_op_r4_subsample_bwd";
+    OP_R4_DT(me, dt);
+    if (const char* why = subsample_shape_error(B, T0, F, d)) { ishara_set_error("%s: B=%d T0=%d F=%d d=%d: %s", me, B, T0, F, d, why); return -1; }
+    if (op_any_null({x, w1, w2, sub, dsub, dw1, db1, dw2, db2, scratch}) || op_misaligned({x, w1, w2, sub, dsub, dw1, db1, dw2, db2, dx, scratch})) {
+        ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only dx may be NULL)", me); return -1;
+    }
+    hipStream_t s = (hipStream_t)st;
+    const R4Dims D = r4_dims(T0, F, d);
+    float* y1 = (float*)scratch;
+    float* dz1 = (float*)((char*)scratch + rup((size_t)B * d * D.T1 * D.F1 * 4, 256));
+    CK(r4_fill_f32_launch(dw1, (size_t)d * 9, 0.f, s)); CK(r4_fill_f32_launch(db1, (size_t)d, 0.f, s));
+    CK(r4_fill_f32_launch(dw2, (size_t)d * 9, 0.f, s)); CK(r4_fill_f32_launch(db2, (size_t)d, 0.f, s));
+    return r4_subsample_bwd_launch(dt, dsub, sub, y1, x, w1, w2, dz1, dw1, db1, dw2, db2, dx, B, T0, F, d, D.T1, D.F1, D.T2, D.F2, s);
+}
+
+// TimeReductionLayer + time_reduction_proj.  scratch: the Linear's shadows ([Fr, d], K zero-padded to Kp) | wgrad slab | pre | conv output
+// [B*Tr, Kp] | its gradient | the [Kp, d] weight-gradient scratch
+struct TredScratch {
+    int Tr, Fr, Kp, M; size_t slab, pre, trout, dtrout, dwred, total;
+    TredScratch(int B, int Tin, int d) {
+        Tr = (Tin - 3) / 2 + 1; Fr = (d - 1) / 2; Kp = (int)rup(Fr, 8); M = B * Tr;
+        const OpShadow f(DT_F32, Fr, d, M), h(DT_BF16, Fr, d, M);
+        slab = rup(f.slab > h.slab ? f.slab : h.slab, 256);
+        const size_t sf = gemm_tn_slab_floats(M, Kp, d, DT_F32), sh = gemm_tn_slab_floats(M, Kp, d, DT_BF16);
+        pre = slab + rup((sf > sh ? sf : sh) * 4, 256);
+        trout = pre + rup((size_t)M * Fr * 4, 256);
+        dtrout = trout + rup((size_t)M * Kp * 4, 256);
+        dwred = dtrout + rup((size_t)M * Kp * 4, 256);
+        total = dwred + rup((size_t)Kp * d * 4, 256);
+    }
+};
+static const char* tred_shape_error(int B, int Tin, int d) {
+    if (B < 1) return "B must be >= 1";
+    if (Tin < 3 || d < 3) return "Tin and d must be >= 3 (one 3x3 stride-2 convolution)";
+    if (d % 8 != 0) return "d must be a multiple of 8 (16-byte rows of the Linear)";
+    if ((int64_t)B * Tin * d > 2147483647LL) return "shape too large (B*Tin*d < 2^31)";
+    return nullptr;
+}
+extern "C" int64_t ishara_op_r4_time_reduce_scratch_bytes(int32_t B, int32_t Tin, int32_t d) {
+    if (tred_shape_error(B, Tin, d)) return -1;
+    return (int64_t)TredScratch(B, Tin, d).total;
+}
+extern "C" int ishara_op_r4_time_reduce_fwd(int32_t dt, const void* h, const float* conv_w, const float* conv_b, const float* Wred, const float* bred, void* red, void* conv_out,
+                                            int32_t B, int32_t Tin, int32_t d, void* scratch, ishara_stream st) {
+    const char* me = "ishara_op_r4_time_reduce_fwd";
+    OP_R4_DT(me, dt);
+    if (const char* why = tred_shape_error(B, Tin, d)) { ishara_set_error("%s: B=%d Tin=%d d=%d: %s", me, B, Tin, d, why); return -1; }
+    if (op_any_null({h, conv_w, conv_b, Wred, bred, red, scratch}) || op_misaligned({h, conv_w, conv_b, Wred, bred, red, conv_out, scratch})) {
+        ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only conv_out may be NULL)", me); return -1;
+    }
+    hipStream_t s = (hipStream_t)st;
+    const TredScratch a(B, Tin, d);
+    const OpShadow sh(dt, a.Fr, d, a.M);
+    char* sc = (char*)scratch;
+    CK(sh.build(dt, Wred, a.Fr, d, sc, s));
+    CK(r4_tred_fwd_launch(dt, h, conv_w, conv_b, (float*)(sc + a.pre), sc + a.trout, B, Tin, d, a.Tr, a.Fr, a.Kp, s));
+    OpArgs no; EpiArgs ea; ea.bias = bred;
+    CK(launch_gemm_nt(dt, dt, dt, OP_NONE, sc + a.trout, sc + sh.wt, red, a.M, d, a.Kp, sh.ldt, no, ea, s));      // r4_forward's Linear over K = Kp
+    if (conv_out) HIP_CHECK_RET(hipMemcpyAsync(conv_out, sc + a.trout, (size_t)a.M * a.Kp * dt_size(dt), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+extern "C" int ishara_op_r4_time_reduce_bwd(int32_t dt, const void* h, const float* conv_w, const void* dred, const void* extra, void* dh,
+                                            float* dconv_w, float* dconv_b, float* dWred, float* dbred, int32_t B, int32_t Tin, int32_t d, void* scratch, ishara_stream st) {
+    const char* me = "ishara_op_r4_time_reduce_bwd";
+    OP_R4_DT(me, dt);
+    if (const char* why = tred_shape_error(B, Tin, d)) { ishara_set_error("%s: B=%d Tin=%d d=%d: %s", me, B, Tin, d, why); return -1; }
+    if (op_any_null({h, conv_w, dred, dh, dconv_w, dconv_b, dWred, dbred, scratch}) || op_misaligned({h, conv_w, dred, extra, dh, dconv_w, dconv_b, dWred, dbred, scratch})) {
+        ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only extra may be NULL)", me); return -1;
+    }
+    hipStream_t s = (hipStream_t)st;
+    const TredScratch a(B, Tin, d);
+    const OpShadow sh(dt, a.Fr, d, a.M);
+    char* sc = (char*)scratch;
+    OpArgs no; EpiArgs e0;
+    CK(launch_gemm_nt(dt, dt, dt, OP_NONE, dred, sc + sh.wn, sc + a.dtrout, a.M, a.Kp, d, sh.ldn, no, e0, s));      // r4_backward's dgrad: d conv output [B*Tr, Kp]
+    CK(r4_fill_f32_launch(dWred, (size_t)a.Fr * d, 0.f, s)); CK(r4_fill_f32_launch(dbred, (size_t)d, 0.f, s));
+    CK(r4_fill_f32_launch(dconv_w, 9, 0.f, s)); CK(r4_fill_f32_launch(dconv_b, 1, 0.f, s));
+    CK(r4_tred_wgrad_launch(dt, sc + a.trout, dred, (float*)(sc + a.dwred), dWred, dbred, (float*)(sc + a.slab), a.M, a.Fr, a.Kp, d, s));
+    return r4_tred_bwd_launch(dt, sc + a.dtrout, (const float*)(sc + a.pre), h, conv_w, extra, dconv_w, dconv_b, dh, B, Tin, d, a.Tr, a.Fr, a.Kp, s);
+}
+
+// the row maps r4_rows<MODE> over [B, Tdst, d]: 0 dst[t] = src[t/2]; 1 dst[t] = src[t] (crop); 2 dst[t] = src[2t] + src[2t+1]; 3 dst[t] = t < Tsrc ? src[t] : 0; 4 dst = a + src
+extern "C" int ishara_op_r4_rows(int32_t dt, int32_t mode, const void* src, const void* a, void* dst, int32_t B, int32_t Tdst, int32_t Tsrc, int32_t d, ishara_stream st) {
+    const char* me = "ishara_op_r4_rows";
+    OP_R4_DT(me, dt);
+    if (mode < 0 || mode > 4) { ishara_set_error("%s: unknown mode %d (0..4)", me, mode); return -1; }
+    if (B < 1 || Tdst < 1 || Tsrc < 1 || d < 1 || (int64_t)B * (Tdst > Tsrc ? Tdst : Tsrc) * d > 2147483647LL) { ishara_set_error("%s: bad shape B=%d Tdst=%d Tsrc=%d d=%d", me, B, Tdst, Tsrc, d); return -1; }
+    if ((mode == 0 && Tdst > 2 * Tsrc) || (mode == 1 && Tdst > Tsrc) || (mode == 2 && 2 * Tdst > Tsrc) || (mode == 4 && Tdst != Tsrc)) {
+        ishara_set_error("%s: mode %d reads past the source rows (Tdst=%d Tsrc=%d)", me, mode, Tdst, Tsrc); return -1;
+    }
+    if (!src || !dst || (mode == 4 && !a) || op_misaligned({src, a, dst})) { ishara_set_error("%s: null or misaligned buffer (16-byte aligned; a is read by mode 4 only)", me); return -1; }
+    return r4_rows_mode_launch(dt, mode, src, a, dst, B, Tdst, Tsrc, d, (hipStream_t)st);
+}

@@ -233,3 +233,21 @@ void r4_destroy(ishara_model* m);
 int r4_output_frames(const ishara_model* m);
 int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, hipStream_t st);
 int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStream_t st);
+// its launch code, shared with the operator entry points (api_ops.hip ishara_op_relattn_* / ishara_op_r4_*)
+struct R4Dims { int T1, F1, T2, F2, T3, Fr, Kp; };      // frames / features after each 3x3 stride-2 convolution, the time-reduction conv's width and its padded K
+R4Dims r4_dims(int T0, int F, int d);
+int launch_relattn_fwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
+                       int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
+int launch_relattn_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
+                       const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
+                       int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
+int r4_subsample_fwd_launch(int dt, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y1, void* sub,
+                            int B, int T0, int F, int d, int T1, int F1, int T2, int F2, hipStream_t s);
+int r4_subsample_bwd_launch(int dt, const void* dsub, const void* sub, const float* y1, const float* x, const float* w1, const float* w2, float* dz1,
+                            float* dw1, float* db1, float* dw2, float* db2, float* dx, int B, int T0, int F, int d, int T1, int F1, int T2, int F2, hipStream_t s);
+int r4_tred_fwd_launch(int dt, const void* h, const float* w, const float* b, float* pre, void* out, int B, int Tin, int d, int Tr, int Fr, int Kp, hipStream_t s);
+int r4_tred_wgrad_launch(int dt, const void* trout, const void* g, float* dwred, float* dW, float* db, float* slab, int M, int Fr, int Kp, int d, hipStream_t s);
+int r4_tred_bwd_launch(int dt, const void* dout, const float* pre, const void* h, const float* w, const void* extra, float* dw, float* db, void* dh,
+                       int B, int Tin, int d, int Tr, int Fr, int Kp, hipStream_t s);
+int r4_rows_mode_launch(int dt, int mode, const void* src, const void* a, void* dst, int B, int Tdst, int Tsrc, int d, hipStream_t s);
+int r4_fill_f32_launch(float* p, size_t n, float v, hipStream_t s);

@@ -256,6 +256,70 @@ static int r4_rows_launch(int dt, const void* src, const void* a, void* dst, int
     else hipLaunchKernelGGL((r4_rows<float, MODE>), dim3(grid), dim3(256), 0, s, (const float*)src, (const float*)a, (float*)dst, B, Tdst, Tsrc, d);
     return launch_rc();
 }
+int r4_rows_mode_launch(int dt, int mode, const void* src, const void* a, void* dst, int B, int Tdst, int Tsrc, int d, hipStream_t s) {
+    switch (mode) {
+        case 0: return r4_rows_launch<0>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
+        case 1: return r4_rows_launch<1>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
+        case 2: return r4_rows_launch<2>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
+        case 3: return r4_rows_launch<3>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
+        case 4: return r4_rows_launch<4>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
+        default: ishara_set_error("r4_rows: unknown mode %d (0..4)", mode); return -1;
+    }
+}
+
+// typed launches of the small kernels
+#define R4_TYPED(dt, CALL) do { if ((dt) == DT_BF16) { typedef bf16 TT; CALL; } else { typedef float TT; CALL; } } while (0)
+
+// ---- the launches of the subsampling and time-reduction kernels, shared by the encoder (r4_forward / r4_backward) and the operator entry
+// points (api_ops.hip ishara_op_r4_*): grids included
+R4Dims r4_dims(int T0, int F, int d) {
+    R4Dims D;
+    D.T1 = (T0 - 3) / 2 + 1; D.F1 = (F - 3) / 2 + 1;
+    D.T2 = (D.T1 - 3) / 2 + 1; D.F2 = (D.F1 - 3) / 2 + 1;
+    D.T3 = (D.T2 - 3) / 2 + 1; D.Fr = (d - 1) / 2; D.Kp = (int)rup(D.Fr, 8);
+    return D;
+}
+// x [B,T0,F] f32 -> y1 [B,d,T1,F1] f32 -> sub [B*T2, d*F2] (dt)
+int r4_subsample_fwd_launch(int dt, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y1, void* sub,
+                            int B, int T0, int F, int d, int T1, int F1, int T2, int F2, hipStream_t s) {
+    hipLaunchKernelGGL(r4_sub1_fwd, dim3(g1d((size_t)B * d * T1 * F1)), dim3(256), 0, s, x, w1, b1, y1, B, T0, F, d, T1, F1);
+    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_fwd<TT>), dim3(g1d((size_t)B * T2 * d * F2)), dim3(256), 0, s, y1, w2, b2, (TT*)sub, B, d, T1, F1, T2, F2));
+    return launch_rc();
+}
+// dsub -> dw2, db2, dz1 (scratch [B,d,T1,F1] f32), dw1, db1 (all four accumulated) and dx (NULL: skipped)
+int r4_subsample_bwd_launch(int dt, const void* dsub, const void* sub, const float* y1, const float* x, const float* w1, const float* w2, float* dz1,
+                            float* dw1, float* db1, float* dw2, float* db2, float* dx, int B, int T0, int F, int d, int T1, int F1, int T2, int F2, hipStream_t s) {
+    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_bwd_w<TT>), dim3(d), dim3(256), 0, s, (const TT*)dsub, (const TT*)sub, y1, dw2, db2, B, d, T1, F1, T2, F2));
+    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_bwd_x<TT>), dim3(g1d((size_t)B * d * T1 * F1)), dim3(256), 0, s, (const TT*)dsub, (const TT*)sub, w2, y1, dz1, B, d, T1, F1, T2, F2));
+    hipLaunchKernelGGL(r4_sub1_bwd_w, dim3(d), dim3(256), 0, s, dz1, x, dw1, db1, B, T0, F, d, T1, F1);
+    if (dx) hipLaunchKernelGGL(r4_sub1_bwd_x, dim3(g1d((size_t)B * T0 * F)), dim3(256), 0, s, dz1, w1, dx, B, T0, F, d, T1, F1);
+    return launch_rc();
+}
+// h [B,Tin,d] (dt) -> pre [B,Tr,Fr] f32, out [B*Tr, Kp] (dt, pad columns zero)
+int r4_tred_fwd_launch(int dt, const void* h, const float* w, const float* b, float* pre, void* out, int B, int Tin, int d, int Tr, int Fr, int Kp, hipStream_t s) {
+    R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_fwd<TT>), dim3(g1d((size_t)B * Tr * Kp)), dim3(256), 0, s, (const TT*)h, w, b, pre, (TT*)out, B, Tin, d, Tr, Fr, Kp));
+    return launch_rc();
+}
+// weight gradient of time_reduction_proj over the padded K (the pad columns of trout are zero, so are the rows >= Fr of the product): into the
+// [Kp, d] scratch dwred, then the Fr real rows are added to dW; the bias gradient is added to db
+int r4_tred_wgrad_launch(int dt, const void* trout, const void* g, float* dwred, float* dW, float* db, float* slab, int M, int Fr, int Kp, int d, hipStream_t s) {
+    OpArgs no;
+    hipLaunchKernelGGL(r4_fill_f32, dim3(g1d((size_t)Kp * d)), dim3(256), 0, s, dwred, (size_t)Kp * d, 0.f);
+    CK(launch_gemm_tn(dt, dt, dt, OP_NONE, OP_NONE, trout, g, dwred, db, slab, M, Kp, d, no, no, s));
+    hipLaunchKernelGGL(r4_axpy_f32, dim3(g1d((size_t)Fr * d)), dim3(256), 0, s, dwred, dW, (size_t)Fr * d);
+    return launch_rc();
+}
+// dout [B*Tr, Kp] (dt: gradient of the conv output) -> dw[9], db[1] (accumulated), dh [B,Tin,d] = extra (NULL: 0) + the input gradient
+int r4_tred_bwd_launch(int dt, const void* dout, const float* pre, const void* h, const float* w, const void* extra, float* dw, float* db, void* dh,
+                       int B, int Tin, int d, int Tr, int Fr, int Kp, hipStream_t s) {
+    R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_bwd_w<TT>), dim3(64), dim3(256), 0, s, (const TT*)dout, pre, (const TT*)h, dw, db, B, Tin, d, Tr, Fr, Kp));
+    R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_bwd_x<TT>), dim3(g1d((size_t)B * Tin * d)), dim3(256), 0, s, (const TT*)dout, pre, w, (const TT*)extra, (TT*)dh, B, Tin, d, Tr, Fr, Kp));
+    return launch_rc();
+}
+int r4_fill_f32_launch(float* p, size_t n, float v, hipStream_t s) {
+    hipLaunchKernelGGL(r4_fill_f32, dim3(g1d(n)), dim3(256), 0, s, p, n, v);
+    return launch_rc();
+}
 
 // ------------------------------------------------------------------ R1: relative-position attention
 // q, k, v [B*T, d] (head h in columns h*DH ..), posp [2T-1, d] f32 (pos_proj of the table), u, vb [d] f32.  One thread per query
@@ -503,14 +567,14 @@ __global__ __launch_bounds__(RA_QB) void relattn_bwd_dpos_kernel(const T* __rest
         default: ishara_set_error("relative attention: head dim %d unsupported (8, 16, 32, 64)", dh); return -1;         \
     }
 
-static int launch_relattn_fwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
+int launch_relattn_fwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
                               int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s) {
     const dim3 grid((T + RA_QB - 1) / RA_QB, B * H);
     if (dt == DT_BF16) { RA_DISPATCH(relattn_fwd_kernel, bf16, grid, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (bf16*)o, lse, H, T, scale, drop) }
     else { RA_DISPATCH(relattn_fwd_kernel, float, grid, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (float*)o, lse, H, T, scale, drop) }
     return launch_rc();
 }
-static int launch_relattn_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
+int launch_relattn_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
                               const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
                               int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s) {
     const dim3 gq((T + RA_QB - 1) / RA_QB, B * H), gp((2 * T - 1 + RA_QB - 1) / RA_QB, B * H);
@@ -705,9 +769,6 @@ static int r4_mhsa_fwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, co
     return r5_ln_fwd(m, r, m->W(a.r), a.ln, m->W(a.out), a.mean, a.rstd);
 }
 
-// typed launches of the small kernels
-#define R4_TYPED(dt, CALL) do { if ((dt) == DT_BF16) { typedef bf16 TT; CALL; } else { typedef float TT; CALL; } } while (0)
-
 int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, hipStream_t st) {
     R4State* S = m->r4;
     m->s = st;
@@ -718,9 +779,7 @@ int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t tra
     if (dt != DT_F32)
         for (size_t t = 0; t < S->pe_T.size(); ++t) CK(r5_from_f32(dt, m->Wf(S->pe32[t]), m->W(S->pedt[t]), (size_t)(2 * S->pe_T[t] - 1) * d, m->s));
     // ---- DepthwiseConv2dSubsampling + input_proj (encoder.py:148-149)
-    hipLaunchKernelGGL(r4_sub1_fwd, dim3(g1d((size_t)B * d * S->T1 * S->F1)), dim3(256), 0, m->s, x, m->P(S->w1), m->P(S->b1), m->Wf(S->y1), B, S->T0, S->F, d, S->T1, S->F1);
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_fwd<TT>), dim3(g1d((size_t)B * S->T2 * d * S->F2)), dim3(256), 0, m->s, m->Wf(S->y1), m->P(S->w2), m->P(S->b2), m->W<TT>(S->sub), B, d, S->T1, S->F1, S->T2, S->F2));
-    CK(launch_rc());
+    CK(r4_subsample_fwd_launch(dt, x, m->P(S->w1), m->P(S->b1), m->P(S->w2), m->P(S->b2), m->Wf(S->y1), m->W(S->sub), B, S->T0, S->F, d, S->T1, S->F1, S->T2, S->F2, m->s));
     EpiArgs ein; ein.drop = dspec(r, S->site_in, m->cfg.dropout_rate);
     CK(gemm_fwd(m, S->Win, m->W(S->sub), dt, m->W(S->h0), dt, r.M, OP_NONE, no, ein));
     const void* h = m->W(S->h0);
@@ -731,7 +790,7 @@ int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t tra
         R4Layer& L = S->layers[idx];
         if (idx == S->reduce) {            // time reduction (encoder.py:152-155)
             recover_src = h;
-            R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_fwd<TT>), dim3(g1d((size_t)B * S->T3 * S->Kp)), dim3(256), 0, m->s, (const TT*)h, m->P(S->trw), m->P(S->trb), m->Wf(S->trpre), m->W<TT>(S->trout), B, Tl, d, S->T3, S->Fr, S->Kp));
+            CK(r4_tred_fwd_launch(dt, h, m->P(S->trw), m->P(S->trb), m->Wf(S->trpre), m->W(S->trout), B, Tl, d, S->T3, S->Fr, S->Kp, m->s));
             DenseW wp = S->Wred; wp.K = S->Kp;
             EpiArgs e0;
             CK(gemm_fwd(m, wp, m->W(S->trout), dt, m->W(S->red), dt, B * S->T3, OP_NONE, no, e0));
@@ -772,7 +831,7 @@ static int r4_mhsa_bwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, co
     CK(rc);
     CK(gemm_dgrad(m, a.Wo, gs, dt, m->W(m->t1), r.M, OP_NONE, no, e0));                          // d context
     CK(gemm_wgrad(m, a.Wo, m->W(a.o), dt, OP_NONE, no, gs, dt, OP_NONE, no, r.M));
-    hipLaunchKernelGGL(r4_fill_f32, dim3(g1d((size_t)(2 * T - 1) * d)), dim3(256), 0, m->s, m->Wf(S->dposp), (size_t)(2 * T - 1) * d, 0.f);
+    CK(r4_fill_f32_launch(m->Wf(S->dposp), (size_t)(2 * T - 1) * d, 0.f, m->s));
     const float scale = 1.0f / sqrtf((float)m->dh);
     CKP(m, "relattn_bwd", 12.0 * r.M * d * (double)dt_size(dt), 24.0 * r.B * m->H * (double)T * T * m->dh,
         launch_relattn_bwd(dt, m->W(a.q), m->W(a.k), m->W(a.vv), m->Wf(a.posp), m->P(a.u), m->P(a.v), m->W(a.o), m->W(m->t1), m->Wf(a.lse), m->Wf(m->delta),
@@ -838,15 +897,9 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
         if (idx == S->reduce) {            // g = gradient of red = Linear(swish(conv3x3(h)))
             DenseW wp = S->Wred; wp.K = S->Kp;
             CK(gemm_dgrad(m, wp, g, dt, m->W(m->t1), B * S->T3, OP_NONE, no, e0));                    // d trout [B*T3, Kp]
-            // weight gradient over the padded K (the pad columns of trout are zero, so are the rows >= Fr of the product): into a [Kp, d]
-            // scratch, then the Fr real rows are added to the parameter's gradient
-            hipLaunchKernelGGL(r4_fill_f32, dim3(g1d((size_t)S->Kp * d)), dim3(256), 0, m->s, m->Wf(S->dwred), (size_t)S->Kp * d, 0.f);
-            CKP(m, "wgrad(time_reduction_proj)", 0, 0, launch_gemm_tn(dt, dt, dt, OP_NONE, OP_NONE, m->W(S->trout), g, m->Wf(S->dwred), m->G(S->Wred.b), m->Wf(m->slab), B * S->T3, S->Kp, d, no, no, m->s));
-            hipLaunchKernelGGL(r4_axpy_f32, dim3(g1d((size_t)S->Fr * d)), dim3(256), 0, m->s, m->Wf(S->dwred), m->G(S->Wred.w), (size_t)S->Fr * d);
+            CKP(m, "wgrad(time_reduction_proj)", 0, 0, r4_tred_wgrad_launch(dt, m->W(S->trout), g, m->Wf(S->dwred), m->G(S->Wred.w), m->G(S->Wred.b), m->Wf(m->slab), B * S->T3, S->Fr, S->Kp, d, m->s));
             const void* hprev = idx > 0 ? r4_layer_out(m, S->layers[idx - 1]) : m->W(S->h0);
-            R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_bwd_w<TT>), dim3(64), dim3(256), 0, m->s, (const TT*)m->W(m->t1), m->Wf(S->trpre), (const TT*)hprev, m->G(S->trw), m->G(S->trb), B, S->T2, d, S->T3, S->Fr, S->Kp));
-            R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_bwd_x<TT>), dim3(g1d((size_t)B * S->T2 * d)), dim3(256), 0, m->s, (const TT*)m->W(m->t1), m->Wf(S->trpre), m->P(S->trw),
-                                            have_skip ? (const TT*)m->W(S->gskip) : (const TT*)nullptr, (TT*)gn, B, S->T2, d, S->T3, S->Fr, S->Kp));
+            CK(r4_tred_bwd_launch(dt, m->W(m->t1), m->Wf(S->trpre), hprev, m->P(S->trw), have_skip ? m->W(S->gskip) : nullptr, m->G(S->trw), m->G(S->trb), gn, B, S->T2, d, S->T3, S->Fr, S->Kp, m->s));
             SWAP();
         }
     }
@@ -859,12 +912,8 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
     CK(rc);
     CK(gemm_wgrad(m, S->Win, m->W(S->sub), dt, OP_NONE, no, gs, dt, OP_NONE, no, r0.M));
     CK(gemm_dgrad(m, S->Win, gs, dt, m->W(S->dsub), r0.M, OP_NONE, no, e0));
-    float* dz1 = m->Wf(S->dz1);
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_bwd_w<TT>), dim3(d), dim3(256), 0, m->s, (const TT*)m->W(S->dsub), (const TT*)m->W(S->sub), m->Wf(S->y1), m->G(S->w2), m->G(S->b2), B, d, S->T1, S->F1, S->T2, S->F2));
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_bwd_x<TT>), dim3(g1d((size_t)B * d * S->T1 * S->F1)), dim3(256), 0, m->s, (const TT*)m->W(S->dsub), (const TT*)m->W(S->sub), m->P(S->w2), m->Wf(S->y1), dz1, B, d, S->T1, S->F1, S->T2, S->F2));
-    hipLaunchKernelGGL(r4_sub1_bwd_w, dim3(d), dim3(256), 0, m->s, dz1, m->last_x, m->G(S->w1), m->G(S->b1), B, S->T0, S->F, d, S->T1, S->F1);
-    if (dx) hipLaunchKernelGGL(r4_sub1_bwd_x, dim3(g1d((size_t)B * S->T0 * S->F)), dim3(256), 0, m->s, dz1, m->P(S->w1), dx, B, S->T0, S->F, d, S->T1, S->F1);
-    CK(launch_rc());
+    CK(r4_subsample_bwd_launch(dt, m->W(S->dsub), m->W(S->sub), m->Wf(S->y1), m->last_x, m->P(S->w1), m->P(S->w2), m->Wf(S->dz1), m->G(S->w1), m->G(S->b1), m->G(S->w2), m->G(S->b2), dx,
+                               B, S->T0, S->F, d, S->T1, S->F1, S->T2, S->F2, m->s));
     if (!m->bucket_ev.empty()) HIP_CHECK_RET(hipEventRecord(m->bucket_ev.back(), m->s));
     return 0;
 }

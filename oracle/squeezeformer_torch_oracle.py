@@ -61,23 +61,44 @@ def relative_shift_closed_form(pos_score: torch.Tensor) -> torch.Tensor:
     return pos_score[:, :, i, T - 1 - i + j]
 
 
-def rel_mhsa(x, P, p, heads, drop=None):
-    """MultiHeadedSelfAttentionModule.forward (attention.py:130-139) around RelativeMultiHeadAttention.forward (:69-100).
-    `drop(attn, site)` applies a dropout mask when given (sites: 0 attention probabilities, 1 module output)."""
-    B, T, d = x.shape
+def rel_attention_scores(q, k, posp, u, vb, heads):
+    """The scaled scores of RelativeMultiHeadAttention.forward (attention.py:84-92): ((q + u) k^T + relative_shift((q + v) pos^T)) / sqrt(dh),
+    [B, H, T, T].  q, k [B, T, d]; posp the projected table [2T-1, d] (or [B, 2T-1, d]); u, vb [H, dh] (or [d])."""
+    B, T, d = q.shape
     dh = d // heads
+    if posp.dim() == 2:
+        posp = posp.unsqueeze(0).expand(B, -1, -1)
+    q = q.view(B, T, heads, dh)
+    k = k.view(B, T, heads, dh).permute(0, 2, 1, 3)
+    pos = posp.reshape(B, -1, heads, dh)
+    content = torch.matmul((q + u.view(heads, dh)).transpose(1, 2), k.transpose(2, 3))
+    pos_score = relative_shift(torch.matmul((q + vb.view(heads, dh)).transpose(1, 2), pos.permute(0, 2, 3, 1)))
+    return (content + pos_score) / math.sqrt(dh)
+
+
+def rel_attention(q, k, v, posp, u, vb, heads, mask=None):
+    """The core of RelativeMultiHeadAttention.forward (attention.py:84-98) on projected operands: softmax of rel_attention_scores, dropout
+    on the probabilities, context [B, T, d].  mask: a multiplicative [B, H, T, T] tensor (oracle/rng.py scaled_mask_attn(seed, site,
+    B*H*T, T, rate) reshaped: mask row (b*H + h)*T + i is the kernels' row key), or a callable applied to the probabilities."""
+    B, T, d = q.shape
+    attn = torch.softmax(rel_attention_scores(q, k, posp, u, vb, heads), -1)
+    if mask is not None:
+        attn = mask(attn) if callable(mask) else attn * mask
+    v = v.view(B, T, heads, d // heads).permute(0, 2, 1, 3)
+    return torch.matmul(attn, v).transpose(1, 2).contiguous().view(B, T, d)
+
+
+def rel_mhsa(x, P, p, heads, drop=None):
+    """MultiHeadedSelfAttentionModule.forward (attention.py:130-139) around RelativeMultiHeadAttention.forward (:69-100): the projections
+    around rel_attention.  `drop(attn, site)` applies a dropout mask when given (sites: 0 attention probabilities, 1 module output)."""
+    B, T, d = x.shape
     a = p + ".attention"
     pe = rel_positional_encoding(T, d, x.dtype).repeat(B, 1, 1)
-    q = (x @ P[a + ".query_proj.weight"].t() + P[a + ".query_proj.bias"]).view(B, T, heads, dh)
-    k = (x @ P[a + ".key_proj.weight"].t() + P[a + ".key_proj.bias"]).view(B, T, heads, dh).permute(0, 2, 1, 3)
-    v = (x @ P[a + ".value_proj.weight"].t() + P[a + ".value_proj.bias"]).view(B, T, heads, dh).permute(0, 2, 1, 3)
-    pos = (pe @ P[a + ".pos_proj.weight"].t()).view(B, -1, heads, dh)
-    content = torch.matmul((q + P[a + ".u_bias"]).transpose(1, 2), k.transpose(2, 3))
-    pos_score = relative_shift(torch.matmul((q + P[a + ".v_bias"]).transpose(1, 2), pos.permute(0, 2, 3, 1)))
-    attn = torch.softmax((content + pos_score) / math.sqrt(dh), -1)
-    if drop is not None:
-        attn = drop(attn, 0)
-    ctx = torch.matmul(attn, v).transpose(1, 2).contiguous().view(B, T, d)
+    q = x @ P[a + ".query_proj.weight"].t() + P[a + ".query_proj.bias"]
+    k = x @ P[a + ".key_proj.weight"].t() + P[a + ".key_proj.bias"]
+    v = x @ P[a + ".value_proj.weight"].t() + P[a + ".value_proj.bias"]
+    posp = pe @ P[a + ".pos_proj.weight"].t()
+    ctx = rel_attention(q, k, v, posp, P[a + ".u_bias"], P[a + ".v_bias"], heads, None if drop is None else (lambda attn: drop(attn, 0)))
     out = ctx @ P[a + ".out_proj.weight"].t() + P[a + ".out_proj.bias"]
     return drop(out, 1) if drop is not None else out
 

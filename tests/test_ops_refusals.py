@@ -1,5 +1,6 @@
 """CPU: every single-operator entry point refuses what it has no kernel for — unknown dtypes, ISHARA_F16 for the backward operators (fp16
-is inference-only), fp16 attention with dropout, classifier routes that do not take the shape — with an error and an ishara_last_error()
+is inference-only) and for every operator of the torch Squeezeformer family, fp16 attention with dropout, classifier routes that do not take
+the shape, shapes outside a kernel's range, null or misaligned buffers — with an error and an ishara_last_error()
 message of its own, before any HIP call (all device pointers and the stream are NULL here: a call that got as far as a launch would fail
 with a HIP error instead, or fault)."""
 import ctypes as C
@@ -29,7 +30,35 @@ def _ops():
         "ishara_op_attn_bwd": lambda L, dt: L.ishara_op_attn_bwd(dt, N, N, N, 1, 4, 64, 32, f(0.1), 1, 2, f(0.0), 1, N, N),
         "ishara_op_qkv_fwd": lambda L, dt: L.ishara_op_qkv_fwd(dt, N, N, N, f(1e-6), N, N, N, N, N, 1, 64, 4, 32, 1, N, N),
         "ishara_op_classifier_fwd": lambda L, dt: L.ishara_op_classifier_fwd(dt, N, N, N, N, 64, 256, 60, 0, N, N),
+        **{n: (lambda L, dt, n=n: _r4_call(L, n, dt=dt)) for n in R4_DEFAULTS},
     }
+
+
+# ---- the torch Squeezeformer family's operators: name -> (pointer arguments, keyword defaults of the rest, in call order)
+R4_DEFAULTS = {
+    "ishara_op_relattn_fwd": (9, dict(B=2, H=2, T=33, dh=16, seed=1, site=2, rate=0.0)),
+    "ishara_op_relattn_bwd": (14, dict(B=2, H=2, T=33, dh=16, seed=1, site=2, rate=0.0)),
+    "ishara_op_r4_subsample_fwd": (6, dict(B=2, T0=30, F=16, d=16)),
+    "ishara_op_r4_subsample_bwd": (10, dict(B=2, T0=30, F=16, d=16)),
+    "ishara_op_r4_time_reduce_fwd": (7, dict(B=2, Tin=8, d=24)),
+    "ishara_op_r4_time_reduce_bwd": (9, dict(B=2, Tin=8, d=24)),
+    "ishara_op_r4_rows": (3, dict(B=2, Tdst=8, Tsrc=8, d=16)),
+}
+R4_OPS = sorted(R4_DEFAULTS)
+
+
+def _r4_call(L, name, dt=F32, ptrs=None, mode=4, **kw):
+    """one call of a torch-Squeezeformer operator: NULL pointers (or `ptrs`), the default shape with `kw` replacing single values; the last
+    two arguments (scratch, stream; ishara_op_r4_rows: stream) stay NULL unless `ptrs` is one longer than the pointer count (the scratch)"""
+    nptr, defaults = R4_DEFAULTS[name]
+    vals = {**defaults, **kw}
+    assert set(vals) == set(defaults), (name, kw)
+    rest = [C.c_float(v) if k == "rate" else v for k, v in vals.items()]
+    ptrs = list(ptrs) if ptrs is not None else [N] * nptr
+    if name == "ishara_op_r4_rows":
+        return L.ishara_op_r4_rows(dt, mode, *ptrs[:nptr], *rest, N)
+    scratch = ptrs[nptr] if len(ptrs) > nptr else N
+    return getattr(L, name)(dt, *ptrs[:nptr], *rest, scratch, N)
 
 
 BACKWARD = ["ishara_op_dense_bwd", "ishara_op_layernorm_bwd", "ishara_op_dwconv_bwd", "ishara_op_attn_bwd"]
@@ -59,6 +88,63 @@ def test_unknown_dtype_is_refused(lib, name, dt):
 @pytest.mark.parametrize("name", BACKWARD)
 def test_backward_operators_refuse_f16(lib, name):
     _refused(lib, _ops()[name](lib, F16), name, "ISHARA_F16", "inference-only")
+
+
+@pytest.mark.parametrize("name", R4_OPS)
+def test_torch_squeezeformer_operators_refuse_f16(lib, name):
+    """the family has no fp16 kernels (its typed launches would read ISHARA_F16 buffers as float): forward and backward alike"""
+    _refused(lib, _r4_call(lib, name, dt=F16), name, "ISHARA_F16", "no fp16 kernels")
+
+
+@pytest.mark.parametrize("name", ["ishara_op_relattn_fwd", "ishara_op_relattn_bwd"])
+@pytest.mark.parametrize("kw,word", [(dict(dh=12), "head dim"), (dict(dh=128), "head dim"), (dict(dh=0), "head dim"), (dict(T=0), ">= 1"), (dict(B=0), ">= 1"),
+                                     (dict(B=-2), ">= 1"), (dict(H=0), ">= 1"), (dict(rate=1.0), "rate"), (dict(rate=-0.1), "rate"), (dict(rate=float("nan")), "rate"),
+                                     (dict(B=40000, H=2), "too large")])
+def test_relattn_refuses_shapes_and_rates(lib, name, kw, word):
+    _refused(lib, _r4_call(lib, name, **kw), name, word)
+    assert lib.ishara_op_relattn_scratch_bytes(2, 2, 33, 12) < 0 and lib.ishara_op_relattn_scratch_bytes(2, 2, 0, 16) < 0
+    assert lib.ishara_op_relattn_scratch_bytes(2, 2, 33, 16) > 0
+
+
+@pytest.mark.parametrize("name", ["ishara_op_r4_subsample_fwd", "ishara_op_r4_subsample_bwd"])
+@pytest.mark.parametrize("kw,word", [(dict(T0=6), ">= 7"), (dict(F=6), ">= 7"), (dict(T0=0), ">= 7"), (dict(B=0), ">= 1"), (dict(d=0), ">= 1")])
+def test_subsample_refuses_shapes(lib, name, kw, word):
+    _refused(lib, _r4_call(lib, name, **kw), name, word)
+    assert lib.ishara_op_r4_subsample_scratch_bytes(2, 6, 16, 16) < 0 and lib.ishara_op_r4_subsample_scratch_bytes(2, 7, 7, 16) > 0
+
+
+@pytest.mark.parametrize("name", ["ishara_op_r4_time_reduce_fwd", "ishara_op_r4_time_reduce_bwd"])
+@pytest.mark.parametrize("kw,word", [(dict(Tin=2), ">= 3"), (dict(d=2), ">= 3"), (dict(d=20), "multiple of 8"), (dict(B=0), ">= 1")])
+def test_time_reduce_refuses_shapes(lib, name, kw, word):
+    _refused(lib, _r4_call(lib, name, **kw), name, word)
+    assert lib.ishara_op_r4_time_reduce_scratch_bytes(2, 2, 24) < 0 and lib.ishara_op_r4_time_reduce_scratch_bytes(2, 3, 24) > 0
+
+
+@pytest.mark.parametrize("mode", [-1, 5, 100])
+def test_rows_refuses_unknown_modes(lib, mode):
+    _refused(lib, _r4_call(lib, "ishara_op_r4_rows", mode=mode), "ishara_op_r4_rows", "unknown mode", str(mode))
+
+
+@pytest.mark.parametrize("mode,kw,word", [(0, dict(Tdst=17, Tsrc=8), "past the source"), (1, dict(Tdst=9, Tsrc=8), "past the source"), (2, dict(Tdst=5, Tsrc=8), "past the source"),
+                                          (4, dict(Tdst=8, Tsrc=9), "past the source"), (3, dict(B=0), "bad shape"), (3, dict(d=0), "bad shape"), (3, dict(Tdst=0), "bad shape")])
+def test_rows_refuses_shapes(lib, mode, kw, word):
+    _refused(lib, _r4_call(lib, "ishara_op_r4_rows", mode=mode, **kw), "ishara_op_r4_rows", word)
+
+
+@pytest.mark.parametrize("name", R4_OPS)
+def test_torch_squeezeformer_operators_refuse_null_and_misaligned_buffers(lib, name):
+    """valid shapes with every pointer NULL, with one required pointer NULL, and with one pointer off a 16-byte boundary (the other addresses
+    are made up: a refused call dereferences nothing)"""
+    nptr = R4_DEFAULTS[name][0]
+    _refused(lib, _r4_call(lib, name), name, "null")
+    good = [C.c_void_p(4096 * (i + 1)) for i in range(nptr + 1)]
+    _refused(lib, _r4_call(lib, name, ptrs=good[:0] + [N] + good[1:]), name, "null")
+    for i in (0, nptr - 1, nptr):
+        if name == "ishara_op_r4_rows" and i == nptr:
+            continue
+        bad = list(good)
+        bad[i] = C.c_void_p(4096 * (i + 1) + 8)
+        _refused(lib, _r4_call(lib, name, ptrs=bad), name, "misaligned")
 
 
 def test_f16_attention_refuses_dropout(lib):

@@ -136,7 +136,8 @@ int ishara_optimizer_set_iterations(ishara_model* m, int32_t it);
 int ishara_profile_enable(ishara_model* m, int32_t on);
 int ishara_profile_report(ishara_model* m, char* buf, int32_t cap);
 
-/* decode_phrase (c8:4-12) for a batch: out_idx [B,T] int32 (-1 padded), out_len [B]. */
+/* decode_phrase (c8:4-12) for a batch: logits [B,T,C] f32 -> out_idx [B,T] int32 (-1 padded), out_len [B].  B >= 0 (0: nothing is launched),
+ * 1 <= T <= 4096, C >= 1, 0 <= blank < C, no null buffer; anything else is refused with a message before any HIP call. */
 int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank,
                          int32_t* out_idx, int32_t* out_len, ishara_stream s);
 /* pre_process1(*pre_process00(x)) of the TFLite wrapper (c3:61-115, c13:9-15): raw [max_frames,276] landmarks with NaNs
@@ -190,7 +191,13 @@ enum { ISHARA_LAYOUT_FLAT = 0, ISHARA_LAYOUT_HANDS_LIPS_XY = 1 };
  * over all T*124 values in fp64.  1 <= T <= 4096.  One kernel, graph-capturable, bit-identical from run to run. */
 int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
                       float* x, ishara_stream s);
-/* tf.nn.ctc_loss alone: nll [B]; dlogits [B,T,C] may be NULL; ws = ishara_ctc_workspace_bytes. */
+/* tf.nn.ctc_loss alone: logits [B,T,C] f32, labels [B,L] int64 padded with blank -> nll [B]; dlogits [B,T,C] = grad_scale * d nll / d logits
+ * may be NULL; ws = ishara_ctc_workspace_bytes(B, T, L) bytes, 8-byte aligned, no initialisation needed.  B >= 0 (0: nothing is launched),
+ * T >= 1 with 4*T + 256*ceil((2L+1)/64) bytes of LDS within what a launch grants (T <= 14844 at L = 255), 1 <= L <= 255, 2 <= C <= 64,
+ * 0 <= blank < C; anything else is refused with a message before any HIP call.
+ * A sample with no alignment (T < len + repeats) or with a label outside [0, C) is infeasible: nll[b] = 1e30 (>= 1e29), dlogits[b] =
+ * grad_scale * softmax(logits[b]) (every posterior zero, all finite); an out-of-range label is read as blank, never used as an index.  The
+ * other samples' outputs are bit-identical to a launch without it. */
 int64_t ishara_ctc_workspace_bytes(int32_t B, int32_t T, int32_t L);
 int ishara_ctc_loss(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C,
                     int32_t L, int32_t blank, float* nll, float* dlogits, float grad_scale,
@@ -251,6 +258,10 @@ int ishara_op_qkv_fwd(int32_t dt, const void* x, const float* gamma, const float
  * ishara_op_scratch_bytes(M, K, C), 16-byte aligned. */
 int ishara_op_classifier_fwd(int32_t dt, const void* x, const float* W, const float* bias, float* logits, int32_t M, int32_t K, int32_t C,
                              int32_t route, void* scratch, ishara_stream s);
+/* ishara_ctc_loss as the head runs it: the same arguments, refusals and contract, plus dlb [B*T, 128] bf16 (4-byte aligned, may be NULL): the
+ * rows of dlogits rounded to bf16 and zero padded to 128 classes, the MFMA operand of the classifier's backward.  Written only with dlogits. */
+int ishara_op_ctc_loss(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                       float* nll, float* dlogits, float grad_scale, void* ws, void* dlb, ishara_stream s);
 /* y[m,:C] = x[m,:C] - logsumexp(x[m,:C]) over C fp32 logits in rows of stride ld >= C floats (columns C..ld-1 of the outputs are zeroed: a class
  * count padded to the GEMMs' 16-byte row alignment); dx = dy - exp(y) * rowsum(dy).  Replaces F.log_softmax(self.fc(...), dim=-1) of the
  * reference's torch Squeezeformer (squeezeformer/model.py:448-449). */

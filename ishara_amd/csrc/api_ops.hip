@@ -27,14 +27,45 @@ __global__ void qkv_split_kernel(const T* qkv, T* q, T* k, T* vt, int B, int H, 
 }
 
 // ------------------------------------------------------------------ stand-alone entry points
+// CTC loss and greedy decode: what a launch would fault or fail on is refused here, before any HIP call, each with a message of its own
 extern "C" int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t* out_idx, int32_t* out_len, ishara_stream s) {
-    if (T > 4096) { ishara_set_error("greedy_decode: T too large"); return -1; }
+    const char* me = "ishara_greedy_decode";
+    if (B < 0) { ishara_set_error("%s: B=%d < 0", me, B); return -1; }
+    if (T < 1) { ishara_set_error("%s: T=%d < 1", me, T); return -1; }
+    if (T > 4096) { ishara_set_error("%s: T=%d too large (max 4096: one LDS word per frame)", me, T); return -1; }
+    if (C < 1) { ishara_set_error("%s: C=%d < 1", me, C); return -1; }
+    if (blank < 0 || blank >= C) { ishara_set_error("%s: blank %d outside 0..%d", me, blank, C - 1); return -1; }
+    if (B == 0) return 0;
+    if (!logits || !out_idx || !out_len) { ishara_set_error("%s: null logits / out_idx / out_len", me); return -1; }
     return launch_greedy_decode(logits, B, T, C, blank, out_idx, out_len, (hipStream_t)s);
 }
 extern "C" int64_t ishara_ctc_workspace_bytes(int32_t B, int32_t T, int32_t L) { return (int64_t)(ctc_workspace_floats(B, T, L) * sizeof(float)); }
+static int ctc_loss_checked(const char* me, const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank,
+                            float* nll, float* dlogits, float grad_scale, void* ws, hipStream_t s, void* dlb) {
+    if (B < 0) { ishara_set_error("%s: B=%d < 0", me, B); return -1; }
+    if (T < 1) { ishara_set_error("%s: T=%d < 1", me, T); return -1; }
+    if (L < 1 || L > 255) { ishara_set_error("%s: L=%d outside 1..255 (2L+1 lattice states in at most 8 registers of a 64-lane wave)", me, L); return -1; }
+    if (C < 2 || C > 64) { ishara_set_error("%s: C=%d outside 2..64 (one lane per class)", me, C); return -1; }
+    if (blank < 0 || blank >= C) { ishara_set_error("%s: blank %d outside 0..%d", me, blank, C - 1); return -1; }
+    if (ctc_lds_bytes(T, L) > ctc_lds_limit()) {
+        ishara_set_error("%s: T=%d too large at L=%d: the kernel needs 4*T + 256*ceil((2L+1)/64) = %zu bytes of dynamic LDS, a launch grants %zu (T <= %zu)",
+                         me, T, L, ctc_lds_bytes(T, L), ctc_lds_limit(), (ctc_lds_limit() - ctc_lds_bytes(0, L)) / 4);
+        return -1;
+    }
+    if (B == 0) return 0;
+    if (!logits || !labels || !nll || !ws) { ishara_set_error("%s: null logits / labels / nll / ws (dlogits may be NULL)", me); return -1; }
+    if ((uintptr_t)ws % 8) { ishara_set_error("%s: ws must be 8-byte aligned (fp64 lattices)", me); return -1; }
+    if ((uintptr_t)dlb % 4) { ishara_set_error("%s: dlb must be 4-byte aligned (packed bf16 pairs)", me); return -1; }
+    return launch_ctc(logits, labels, B, T, C, L, blank, nll, dlogits, grad_scale, (float*)ws, s, dlb);
+}
 extern "C" int ishara_ctc_loss(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
                                float* nll, float* dlogits, float grad_scale, void* ws, ishara_stream s) {
-    return launch_ctc(logits, labels, B, T, C, L, blank, nll, dlogits, grad_scale, (float*)ws, (hipStream_t)s);
+    return ctc_loss_checked("ishara_ctc_loss", logits, labels, B, T, C, L, blank, nll, dlogits, grad_scale, ws, (hipStream_t)s, nullptr);
+}
+// the same with the head's second output: dlb [B*T, 128] bf16, the gradient rows zero padded to 128 classes (written only with dlogits)
+extern "C" int ishara_op_ctc_loss(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                                  float* nll, float* dlogits, float grad_scale, void* ws, void* dlb, ishara_stream s) {
+    return ctc_loss_checked("ishara_op_ctc_loss", logits, labels, B, T, C, L, blank, nll, dlogits, grad_scale, ws, (hipStream_t)s, dlb);
 }
 extern "C" int ishara_dropout_mask(uint32_t seed, uint32_t site, int32_t rows, int32_t cols, float rate, float* out, ishara_stream s) {
     const DropSpec d = make_drop(seed, site, rate, true);

@@ -2,12 +2,23 @@
 // blank = last class, logit_length = T) and the greedy decoder (c8:4-12).
 //
 // One workgroup per sample; the lattice has S = 2*len+1 <= 2L+1 states (see ctc_scaled_kernel).
+//
+// Samples without an alignment.  A sample is INFEASIBLE when T < len + repeats (no path through the lattice) or when its label row holds a
+// value outside [0, C).  For such a sample nll[b] = 1e30 (the sentinel: >= 1e29), every posterior is zero, so dlogits[b] = grad_scale *
+// softmax(logits[b]) (finite) and dlb its bf16 copy; an out-of-range label reads as blank (no read outside the logits row, no LDS add outside
+// the class row).  The other samples of the batch are computed exactly as if that sample were not there (one workgroup per sample, nothing
+// shared): their nll, dlogits and dlb are bit-identical.  The caller decides what an nll of 1e30 means (tf.nn.ctc_loss returns inf there).
 #include <type_traits>
 #include "kernels.h"
 
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -2)
 
 static inline int ctc_ns(int L) { return (2 * L + 1 + 63) / 64; }            // lattice states per lane of the recursion wave
+// LDS of one workgroup: lse[T] and ext[64 NS] are requested at launch; cls (4 KiB), s_logp, s_len and s_bad are static.  The kernel is launched
+// without a raised dynamic-LDS attribute, so static + dynamic stay within the 64 KiB every HIP launch is granted.
+static constexpr size_t CTC_LDS_STATIC = 4 * 4 * 64 * sizeof(float) + 2 * sizeof(double), CTC_LDS_LAUNCH = 65536;
+size_t ctc_lds_bytes(int T, int L) { return (size_t)T * sizeof(float) + (size_t)64 * ctc_ns(L) * sizeof(int); }
+size_t ctc_lds_limit() { return CTC_LDS_LAUNCH - CTC_LDS_STATIC; }
 size_t ctc_workspace_floats(int B, int T, int L) { return 4 * (size_t)B * T * 64 * ctc_ns(L); }   // two fp64 lattices [B][T][64*NS]: alpha, beta sums
 
 #define CTC_NEG (-1e30)
@@ -48,7 +59,7 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
     extern __shared__ float shf[];
     float* lse = shf;                                   // [Tn]
     int* ext = reinterpret_cast<int*>(lse + Tn);        // [SP]
-    __shared__ int s_len;
+    __shared__ int s_len, s_bad;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const float* lg = logits + (size_t)b * Tn * C;
     const int64_t* lab = labels + (size_t)b * L;
@@ -56,7 +67,12 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
     double* Hw = Gw + (size_t)Tn * SP;                  // [Tn][SP] bsum
     __shared__ double s_logp;
 
-    if (tid == 0) { int n = 0; for (int i = 0; i < L; ++i) n += (lab[i] != blank) ? 1 : 0; s_len = n; }
+    // a label outside [0, C) makes the sample infeasible (header comment); it enters ext as blank, so nothing below indexes with it
+    if (tid == 0) {
+        int n = 0, bad = 0;
+        for (int i = 0; i < L; ++i) { const int64_t v = lab[i]; n += (v != blank) ? 1 : 0; bad |= (v < 0 || v >= C) ? 1 : 0; }
+        s_len = n; s_bad = bad;
+    }
     for (int t = tid; t < Tn; t += 256) {
         float m = -1e30f;
         for (int c = 0; c < C; ++c) m = fmaxf(m, lg[(size_t)t * C + c]);
@@ -64,7 +80,10 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
         for (int c = 0; c < C; ++c) a += expf(lg[(size_t)t * C + c] - m);
         lse[t] = m + logf(a);
     }
-    for (int s = tid; s < SP; s += 256) ext[s] = (s < 2 * L + 1 && (s & 1)) ? (int)lab[s >> 1] : blank;
+    for (int s = tid; s < SP; s += 256) {
+        const int64_t v = (s < 2 * L + 1 && (s & 1)) ? lab[s >> 1] : (int64_t)blank;
+        ext[s] = (v < 0 || v >= C) ? blank : (int)v;
+    }
     __syncthreads();
     const int len = s_len, S = 2 * len + 1;
 
@@ -165,7 +184,7 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
             float e = 0.f;
             if (m > -1e29) e = ((cand > -1e29) ? __expf((float)(cand - m)) : 0.f) + ((cand2 > -1e29) ? __expf((float)(cand2 - m)) : 0.f);
             e = wave_sum(e);
-            logp = (m > -1e29) ? m + (double)__logf(e) : CTC_NEG;
+            logp = (m > -1e29 && !s_bad) ? m + (double)__logf(e) : CTC_NEG;
             if (lane == 0) { nll[b] = (float)(-logp); s_logp = logp; }
         }
       } else {
@@ -278,7 +297,7 @@ int launch_ctc(const float* logits, const int64_t* labels, int B, int T, int C, 
                float* nll, float* dlogits, float grad_scale, float* ws, hipStream_t s, void* dlb) {
     if (2 * L + 1 > 512 || C > 64) { ishara_set_error("ctc: L=%d (max 255) or C=%d (max 64) unsupported", L, C); return -1; }
     const int ns = ctc_ns(L);
-    const size_t shmem = (size_t)T * sizeof(float) + (size_t)64 * ns * sizeof(int);
+    const size_t shmem = ctc_lds_bytes(T, L);
 #define CTC_L(NS) hipLaunchKernelGGL(ctc_kernel<NS>, dim3(B), dim3(256), shmem, s, logits, labels, T, C, L, blank, nll, dlogits, grad_scale, reinterpret_cast<double*>(ws), reinterpret_cast<uint32_t*>(dlb))
     switch (ns) { case 1: CTC_L(1); break; case 2: CTC_L(2); break; case 3: CTC_L(3); break; case 4: CTC_L(4); break;
                   case 5: CTC_L(5); break; case 6: CTC_L(6); break; case 7: CTC_L(7); break; default: CTC_L(8); break; }

@@ -226,6 +226,9 @@ int launch_attn_bwd(int dt, const void* q, const void* k, const void* vt, const 
 
 // ---- CTC / decode (ctc.hip) ----------------------------------------------------------
 size_t ctc_workspace_floats(int B, int T, int L);
+// the dynamic LDS one workgroup of the loss kernel asks for (lse[T] + the extended labels) and the most a launch grants it
+size_t ctc_lds_bytes(int T, int L);
+size_t ctc_lds_limit();
 // logits [B,T,C] f32; labels [B,L] int64 (padded with blank); nll [B]; dlogits = grad_scale * d nll_b / d logits
 int launch_ctc(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank,
                float* nll, float* dlogits, float grad_scale, float* ws, hipStream_t s, void* dlb = nullptr);

@@ -61,6 +61,7 @@ def _r4_call(L, name, dt=F32, ptrs=None, mode=4, **kw):
     return getattr(L, name)(dt, *ptrs[:nptr], *rest, scratch, N)
 
 
+CTC_LOSS = ["ishara_ctc_loss", "ishara_op_ctc_loss"]
 BACKWARD = ["ishara_op_dense_bwd", "ishara_op_layernorm_bwd", "ishara_op_dwconv_bwd", "ishara_op_attn_bwd"]
 
 
@@ -73,10 +74,12 @@ def _refused(lib, rc, name, *words):
 
 
 def test_every_dtype_taking_operator_is_listed():
-    """every ishara_op_* with a dtype argument (first argument) is covered below"""
+    """every ishara_op_* with a dtype argument (first argument) is covered below; ishara_op_ctc_loss (fp32 only, no dtype argument) has
+    its refusals with ishara_ctc_loss and ishara_greedy_decode at the end of this file"""
     with_dt = {n for n, (_, args) in _lib.SIGNATURES.items() if n.startswith("ishara_op_") and not n.endswith("_bytes")
-               and not n.startswith("ishara_op_log_softmax")}
+               and not n.startswith("ishara_op_log_softmax") and n not in CTC_LOSS}
     assert with_dt == set(_ops())
+    assert set(CTC_LOSS) <= set(_lib.SIGNATURES)
 
 
 @pytest.mark.parametrize("dt", BAD_DT)
@@ -250,3 +253,77 @@ def test_probe_refuses_the_encoder_families(lib):
         _refused(lib, lib.ishara_debug_module_info(h, 0, N, N, N, N, N), "ishara_debug_module_info", "ISHARA_FAMILY_KERAS_HYBRID")
     finally:
         lib.ishara_destroy(h)
+
+
+# ---- CTC loss (both entry points) and greedy decode: refused before any HIP call, each with its own message
+def _ctc_call(lib_, name, ptrs=None, dlb=N, **kw):
+    """one call with made-up non-null addresses (a refused call dereferences nothing) or `ptrs` = dict of logits, labels, nll, dlogits, ws"""
+    v = dict(B=2, T=16, C=60, L=8, blank=59)
+    assert set(kw) <= set(v), kw
+    v.update(kw)
+    p = dict(logits=C.c_void_p(4096), labels=C.c_void_p(8192), nll=C.c_void_p(12288), dlogits=C.c_void_p(16384), ws=C.c_void_p(20480))
+    p.update(ptrs or {})
+    tail = (dlb, N) if name == "ishara_op_ctc_loss" else (N,)
+    return getattr(lib_, name)(p["logits"], p["labels"], v["B"], v["T"], v["C"], v["L"], v["blank"], p["nll"], p["dlogits"], C.c_float(1.0), p["ws"], *tail)
+
+
+def _decode_call(lib_, ptrs=None, **kw):
+    v = dict(B=2, T=16, C=60, blank=59)
+    assert set(kw) <= set(v), kw
+    v.update(kw)
+    p = dict(logits=C.c_void_p(4096), out_idx=C.c_void_p(8192), out_len=C.c_void_p(12288))
+    p.update(ptrs or {})
+    return lib_.ishara_greedy_decode(p["logits"], v["B"], v["T"], v["C"], v["blank"], p["out_idx"], p["out_len"], N)
+
+
+CTC_SHAPES = [(dict(B=-1), ("B=-1",)), (dict(T=0), ("T=0",)), (dict(T=-5), ("T=-5",)), (dict(L=0), ("L=0", "1..255")), (dict(L=256), ("L=256", "1..255")),
+              (dict(C=1, blank=0), ("C=1", "2..64")), (dict(C=65, blank=64), ("C=65", "2..64")), (dict(blank=-1), ("blank -1", "0..59")),
+              (dict(blank=60), ("blank 60", "0..59")), (dict(C=5, blank=5), ("blank 5", "0..4"))]
+
+
+@pytest.mark.parametrize("name", CTC_LOSS)
+@pytest.mark.parametrize("kw,words", CTC_SHAPES, ids=lambda v: "-".join(f"{k}{x}" for k, x in v.items()) if isinstance(v, dict) else None)
+def test_ctc_loss_refuses_shapes(lib, name, kw, words):
+    _refused(lib, _ctc_call(lib, name, **kw), name, *words)
+
+
+@pytest.mark.parametrize("name", CTC_LOSS)
+def test_ctc_loss_refuses_a_frame_count_its_lds_request_cannot_hold(lib, name):
+    """one workgroup asks for 4 T + 256 ceil((2L+1)/64) bytes of dynamic LDS next to 4112 static ones (the class rows of the gradient phase,
+    log p, the label count and flag) and is launched within the 64 KiB every launch is granted: 4 T + 256 NS <= 61424"""
+    for L_, ns in ((8, 1), (255, 8)):
+        tmax = (65536 - 4112 - 256 * ns) // 4
+        _refused(lib, _ctc_call(lib, name, T=tmax + 1, L=L_), name, f"T={tmax + 1}", "LDS", "61424", f"T <= {tmax}")
+        _refused(lib, _ctc_call(lib, name, T=tmax, L=L_, ptrs=dict(ws=N)), name, "null")      # T = tmax passes the shape checks
+    _refused(lib, _ctc_call(lib, name, T=2 ** 31 - 1), name, "LDS")
+
+
+@pytest.mark.parametrize("name", CTC_LOSS)
+def test_ctc_loss_refuses_null_and_misaligned_buffers(lib, name):
+    for k in ("logits", "labels", "nll", "ws"):
+        _refused(lib, _ctc_call(lib, name, ptrs={k: N}), name, "null")
+    for off in (1, 2, 4):
+        _refused(lib, _ctc_call(lib, name, ptrs=dict(ws=C.c_void_p(20480 + off))), name, "ws", "8-byte")
+    if name == "ishara_op_ctc_loss":
+        for off in (1, 2, 3):
+            _refused(lib, _ctc_call(lib, name, dlb=C.c_void_p(24576 + off)), name, "dlb", "4-byte")
+
+
+@pytest.mark.parametrize("name", CTC_LOSS)
+def test_ctc_loss_of_an_empty_batch_is_a_no_op(lib, name):
+    """B == 0 returns 0 without a launch, whatever the pointers; the shape checks still hold"""
+    assert _ctc_call(lib, name, B=0, ptrs=dict(logits=N, labels=N, nll=N, dlogits=N, ws=N)) == 0
+    _refused(lib, _ctc_call(lib, name, B=0, L=300), name, "L=300")
+
+
+@pytest.mark.parametrize("kw,words", [(dict(B=-1), ("B=-1",)), (dict(T=0), ("T=0",)), (dict(T=4097), ("T=4097", "4096")), (dict(C=0, blank=0), ("C=0",)),
+                                      (dict(blank=-1), ("blank -1", "0..59")), (dict(blank=60), ("blank 60", "0..59")), (dict(C=100, blank=100), ("blank 100", "0..99"))],
+                         ids=lambda v: "-".join(f"{k}{x}" for k, x in v.items()) if isinstance(v, dict) else None)
+def test_greedy_decode_refuses_shapes(lib, kw, words):
+    _refused(lib, _decode_call(lib, **kw), "ishara_greedy_decode", *words)
+
+
+def test_greedy_decode_refuses_null_buffers_and_skips_an_empty_batch(lib):
+    for k in ("logits", "out_idx", "out_len"):
+        _refused(lib, _decode_call(lib, ptrs={k: N}), "ishara_greedy_decode", "null")
+    assert _decode_call(lib, B=0, ptrs=dict(logits=N, out_idx=N, out_len=N)) == 0

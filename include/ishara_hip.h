@@ -287,8 +287,15 @@ int64_t ishara_op_dwconv_scratch_bytes(int32_t C, int32_t k);
 int ishara_op_dwconv_bwd(int32_t dt, int32_t inop, const void* dy, const void* x, const float* w, void* dx,
                          float* dw, float* dbias, void* scratch, int32_t B, int32_t T, int32_t C, int32_t k,
                          int32_t padl, ishara_stream s);
-/* attention on packed qkv [B*T, 3*H*dh] (head-major packing): o [B*T, H*dh]; scratch holds q,k,vt,lse,delta.  ISHARA_F16: rate 0 only */
+/* attention on packed qkv [B*T, 3*H*dh] (head-major packing): o [B*T, H*dh]; scratch (256-byte aligned) holds q,k,vt,lse,delta,maskw.
+ * ISHARA_F16: rate 0 only.  impl: 0 lane-split (f32 / bf16 / f16; head dim 8, 16, 24, 32, 48, 64; any T), 1 MFMA (bf16 and, forward only, f16;
+ * head dim 32 / 64; T % 8 == 0; every other dtype / head dim runs the lane-split kernels) with the dropout keep bits cached in the scratch,
+ * 2 the same MFMA kernels with no keep-bit buffer (the backward kernels hash again; bf16 and head dim 32 / 64 only).  B, H, T >= 1,
+ * B*H <= 65535, rate in [0, 1), qkv / o / dout / dqkv 16-byte aligned: anything else is refused before any GPU work.
+ * ishara_op_attn_scratch_layout_bytes: out[0..5] = byte offset and extent of lse [B*H*T] f32, of delta [B*H*T] f32 and of the keep-bit words inside
+ * the scratch; what lies between an extent's end and the next offset (or the scratch's end) is padding no kernel writes. */
 int64_t ishara_op_attn_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh);
+int ishara_op_attn_scratch_layout_bytes(int32_t B, int32_t H, int32_t T, int32_t dh, int64_t* out);
 int ishara_op_attn_fwd(int32_t dt, const void* qkv, void* o, int32_t B, int32_t H, int32_t T, int32_t dh,
                        float scale, uint32_t seed, uint32_t site, float rate, int32_t impl,
                        void* scratch, ishara_stream s);

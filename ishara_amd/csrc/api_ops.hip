@@ -294,23 +294,59 @@ struct AttnScratch {
     }
 };
 extern "C" int64_t ishara_op_attn_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh) { return (int64_t)AttnScratch(nullptr, B, H, T, dh).total; }
+// where lse, delta and the keep-bit words lie inside that scratch: out[0..5] = byte offset and extent (bytes the kernels may write) of lse, of
+// delta and of maskw.  Each region is rounded up to 256 bytes: what lies between an extent's end and the next offset (or the total) is padding
+// that no kernel touches.  No handle, no HIP call.
+extern "C" int ishara_op_attn_scratch_layout_bytes(int32_t B, int32_t H, int32_t T, int32_t dh, int64_t* out) {
+    const char* me = "ishara_op_attn_scratch_layout_bytes";
+    if (B < 1 || H < 1 || T < 1 || dh < 1) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d: B, H, T and dh must be >= 1", me, B, H, T, dh); return -1; }
+    if (!out) { ishara_set_error("%s: null out", me); return -1; }
+    const AttnScratch a(nullptr, B, H, T, dh);
+    const int64_t row = (int64_t)B * H * T * 4;
+    out[0] = (int64_t)(uintptr_t)a.lse; out[1] = row;
+    out[2] = (int64_t)(uintptr_t)a.delta; out[3] = row;
+    out[4] = (int64_t)(uintptr_t)a.maskw; out[5] = (int64_t)attn_mask_words(B, H, T) * 4;
+    return 0;
+}
+// impl: 0 lane-split, 1 MFMA with the keep bits cached in the scratch (DM 2), 2 MFMA with no keep-bit buffer: the backward kernels hash again
+// (DM 1, the product's ISHARA_NO_ATTN_BITS route).  Everything a launch would fault or fail on is refused here, before any HIP call.
+static bool attn_takes_mfma(int dt, int dh, int impl) { return impl >= 1 && dt == DT_BF16 && (dh == 32 || dh == 64); }
+static int attn_op_refused(const char* me, int dt, int B, int H, int T, int dh, float rate, int impl, std::initializer_list<const void*> operands,
+                           std::initializer_list<const char*> operand_names, const void* scratch) {
+    if (B < 1 || H < 1 || T < 1) { ishara_set_error("%s: B=%d H=%d T=%d: B, H and T must be >= 1", me, B, H, T); return -1; }
+    if (dh != 8 && dh != 16 && dh != 24 && dh != 32 && dh != 48 && dh != 64) { ishara_set_error("%s: head dim %d unsupported (8, 16, 24, 32, 48, 64)", me, dh); return -1; }
+    if (impl < 0 || impl > 2) { ishara_set_error("%s: unknown impl %d (0 lane-split, 1 MFMA with cached keep bits, 2 MFMA hashing again in the backward)", me, impl); return -1; }
+    if (impl == 2 && !attn_takes_mfma(dt, dh, impl)) { ishara_set_error("%s: impl 2 has MFMA kernels only: ISHARA_BF16 and head dim 32 / 64 (dtype %d, head dim %d)", me, dt, dh); return -1; }
+    if (attn_takes_mfma(dt, dh, impl) && T % 8 != 0) { ishara_set_error("%s: T=%d: the MFMA kernels need T %% 8 == 0 (16-byte pieces of the V^T rows)", me, T); return -1; }
+    if (!(rate >= 0.f && rate < 1.f)) { ishara_set_error("%s: rate %g outside [0, 1)", me, rate); return -1; }
+    if ((int64_t)B * H > 65535 || (int64_t)B * H * T * dh * 3 > 2147483647LL) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d: shape too large (B*H <= 65535: one grid row per head; 3*B*H*T*dh < 2^31)", me, B, H, T, dh); return -1; }
+    for (size_t i = 0; i < operands.size(); ++i) if (!operands.begin()[i]) { ishara_set_error("%s: null %s", me, operand_names.begin()[i]); return -1; }
+    if (!scratch) { ishara_set_error("%s: null scratch (ishara_op_attn_scratch_bytes)", me); return -1; }
+    for (size_t i = 0; i < operands.size(); ++i)
+        if ((uintptr_t)operands.begin()[i] % 16) { ishara_set_error("%s: misaligned %s: 16-byte aligned operands (vector loads and stores)", me, operand_names.begin()[i]); return -1; }
+    if ((uintptr_t)scratch % 256) { ishara_set_error("%s: misaligned scratch: 256-byte aligned (the layout rounds every region to 256 bytes)", me); return -1; }
+    return 0;
+}
 extern "C" int ishara_op_attn_fwd(int32_t dt, const void* qkv, void* o, int32_t B, int32_t H, int32_t T, int32_t dh, float scale,
                                   uint32_t seed, uint32_t site, float rate, int32_t impl, void* scratch, ishara_stream st) {
     OP_DT("ishara_op_attn_fwd", dt, true);
     if (dt == DT_F16 && rate > 0.f) { ishara_set_error("ishara_op_attn_fwd: ISHARA_F16 is inference-only: no attention dropout (rate %g)", rate); return -1; }
+    if (attn_op_refused("ishara_op_attn_fwd", dt, B, H, T, dh, rate, impl, {qkv, o}, {"qkv", "o"}, scratch)) return -1;
     hipStream_t s = (hipStream_t)st;
     const AttnScratch a((char*)scratch, B, H, T, dh);
     if (dt == DT_BF16) hipLaunchKernelGGL(qkv_split_kernel<bf16>, dim3(1024), dim3(256), 0, s, (const bf16*)qkv, (bf16*)a.q, (bf16*)a.k, (bf16*)a.vt, B, H, T, dh);
     else if (dt == DT_F16) hipLaunchKernelGGL(qkv_split_kernel<f16>, dim3(1024), dim3(256), 0, s, (const f16*)qkv, (f16*)a.q, (f16*)a.k, (f16*)a.vt, B, H, T, dh);
     else hipLaunchKernelGGL(qkv_split_kernel<float>, dim3(1024), dim3(256), 0, s, (const float*)qkv, (float*)a.q, (float*)a.k, (float*)a.vt, B, H, T, dh);
-    return launch_attn_fwd(dt, a.q, a.k, a.vt, o, a.lse, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), impl, a.maskw, s);
+    return launch_attn_fwd(dt, a.q, a.k, a.vt, o, a.lse, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), impl == 2 ? 1 : impl, impl == 2 ? nullptr : a.maskw, s);
 }
 extern "C" int ishara_op_attn_bwd(int32_t dt, const void* o, const void* dout, void* dqkv, int32_t B, int32_t H, int32_t T, int32_t dh, float scale,
                                   uint32_t seed, uint32_t site, float rate, int32_t impl, void* scratch, ishara_stream st) {
     OP_DT("ishara_op_attn_bwd", dt, false);
+    if (attn_op_refused("ishara_op_attn_bwd", dt, B, H, T, dh, rate, impl, {o, dout, dqkv}, {"o", "dout", "dqkv"}, scratch)) return -1;
     hipStream_t s = (hipStream_t)st;
     const AttnScratch a((char*)scratch, B, H, T, dh);
-    return launch_attn_bwd(dt, a.q, a.k, a.vt, o, dout, a.lse, a.delta, dqkv, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), 1, impl, a.maskw, s);
+    return launch_attn_bwd(dt, a.q, a.k, a.vt, o, dout, a.lse, a.delta, dqkv, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), 1, impl == 2 ? 1 : impl,
+                           impl == 2 ? nullptr : a.maskw, s);
 }
 
 // ---- operator tests: the torch Squeezeformer family's own kernels (squeezeformer_r4.hip), through the launch code the encoder uses.

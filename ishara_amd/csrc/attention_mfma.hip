@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256, DH <= 32 ? 3 : 2) void attn_bwd_dkv_mfma_kerne
                 const int wave_f = (qq % AF_QB) >> 5;
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    const int key = kbase + 16 * t;                       // key tile of this wave
+                    const int key = min(kbase + 16 * t, Tn - 8);          // key tile of this wave (a tile wholly past T re-reads the last chunk: its bits are not used)
                     mw[t] = *reinterpret_cast<const u32x4*>(maskbits + (qbw + key / AF_KC) * 256 + wave_f * 64 + (c >> 2) * 16 + 4 * g);
                 }
             }

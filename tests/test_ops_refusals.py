@@ -155,6 +155,73 @@ def test_f16_attention_refuses_dropout(lib):
     _refused(lib, rc, "ishara_op_attn_fwd", "dropout")
 
 
+# ---- ishara_op_attn_fwd / _bwd: shapes, rates, impl values and buffers are refused before the first launch (the qkv split of the forward)
+ATTN_OPS = {"ishara_op_attn_fwd": 2, "ishara_op_attn_bwd": 3}      # name -> operand pointers (qkv, o / o, dout, dqkv)
+ATTN_OPERANDS = {"ishara_op_attn_fwd": ("qkv", "o"), "ishara_op_attn_bwd": ("o", "dout", "dqkv")}
+
+
+def _attn_call(L, name, dt=BF16, ptrs=None, scratch=C.c_void_p(1 << 20), **kw):
+    """one call with made-up aligned addresses (a refused call dereferences nothing) or `ptrs`; `kw` replaces single values of the default shape"""
+    v = dict(B=1, H=4, T=64, dh=32, rate=0.0, impl=1)
+    assert set(kw) <= set(v), kw
+    v.update(kw)
+    n = ATTN_OPS[name]
+    ptrs = list(ptrs) if ptrs is not None else [C.c_void_p(4096 * (i + 1)) for i in range(n)]
+    return getattr(L, name)(dt, *ptrs, v["B"], v["H"], v["T"], v["dh"], C.c_float(0.1), 1, 2, C.c_float(v["rate"]), v["impl"], scratch, N)
+
+
+ATTN_REFUSALS = [(dict(B=0), ">= 1"), (dict(B=-1), ">= 1"), (dict(H=0), ">= 1"), (dict(T=0), ">= 1"), (dict(T=-8), ">= 1"),
+                 (dict(dh=0), "head dim 0"), (dict(dh=12), "head dim 12"), (dict(dh=40), "head dim 40"), (dict(dh=128), "head dim 128"),
+                 (dict(T=60), "T % 8"), (dict(T=1, dh=64), "T % 8"), (dict(T=60, impl=2), "T % 8"),
+                 (dict(rate=1.0), "rate"), (dict(rate=-0.1), "rate"), (dict(rate=float("nan")), "rate"),
+                 (dict(impl=-1), "unknown impl"), (dict(impl=3), "unknown impl"), (dict(impl=2, dh=16), "impl 2"),
+                 (dict(B=40000, H=2), "too large"), (dict(B=64, H=64, T=4096, dh=64), "too large")]
+
+
+@pytest.mark.parametrize("name", sorted(ATTN_OPS))
+@pytest.mark.parametrize("kw,word", ATTN_REFUSALS, ids=lambda v: "-".join(f"{k}{x}" for k, x in v.items()) if isinstance(v, dict) else None)
+def test_attention_refuses_shapes_rates_and_impls(lib, name, kw, word):
+    _refused(lib, _attn_call(lib, name, **kw), name, word)
+
+
+@pytest.mark.parametrize("name", sorted(ATTN_OPS))
+def test_attention_takes_any_frame_count_on_the_lane_split_route(lib, name):
+    """T % 8 != 0 is refused only where the MFMA kernels would take the call: impl 0, f32 and the head dims without an MFMA kernel pass the shape
+    checks (and are refused for the null scratch instead); impl 2 has no lane-split kernels to fall back to"""
+    for kw, dt in ((dict(T=61, impl=0), BF16), (dict(T=61, impl=1), F32), (dict(T=61, dh=24), BF16), (dict(T=1, dh=48), BF16)):
+        _refused(lib, _attn_call(lib, name, dt=dt, scratch=N, **kw), name, "null scratch")
+    _refused(lib, _attn_call(lib, name, dt=F32, impl=2), name, "impl 2")
+
+
+@pytest.mark.parametrize("name", sorted(ATTN_OPS))
+def test_attention_refuses_null_and_misaligned_buffers(lib, name):
+    n = ATTN_OPS[name]
+    good = [C.c_void_p(4096 * (i + 1)) for i in range(n)]
+    who = ATTN_OPERANDS[name]
+    _refused(lib, _attn_call(lib, name, ptrs=[N] * n, scratch=N), name, "null " + who[0])
+    for i in range(n):      # the message names the operand that is at fault
+        _refused(lib, _attn_call(lib, name, ptrs=good[:i] + [N] + good[i + 1:]), name, "null " + who[i])
+        for off in (2, 4, 8):
+            _refused(lib, _attn_call(lib, name, ptrs=good[:i] + [C.c_void_p(4096 * (i + 1) + off)] + good[i + 1:]), name, "misaligned " + who[i] + ":", "16-byte")
+    _refused(lib, _attn_call(lib, name, scratch=N), name, "null scratch")
+    for off in (16, 64, 128):
+        _refused(lib, _attn_call(lib, name, scratch=C.c_void_p((1 << 20) + off)), name, "misaligned scratch", "256-byte")
+
+
+def test_attention_scratch_layout_is_consistent_and_refuses_bad_shapes(lib):
+    """lse | delta | keep-bit words follow the three operand copies, each region on a 256-byte boundary and inside the scratch"""
+    for B, H, T, dh in ((1, 3, 8, 32), (2, 3, 33, 24), (2, 8, 392, 32), (1, 1, 1, 8)):
+        out = (C.c_int64 * 6)()
+        assert lib.ishara_op_attn_scratch_layout_bytes(B, H, T, dh, out) == 0
+        total = lib.ishara_op_attn_scratch_bytes(B, H, T, dh)
+        (lo, le), (do, de), (mo, me) = ((out[2 * i], out[2 * i + 1]) for i in range(3))
+        assert le == de == 4 * B * H * T and me == 4 * 256 * B * H * ((T + 127) // 128) * ((T + 63) // 64)
+        assert lo >= 3 * 4 * B * H * T * dh and lo + le <= do and do + de <= mo and mo + me <= total
+        assert lo % 256 == do % 256 == mo % 256 == total % 256 == 0 and total - (mo + me) < 256 and do - (lo + le) < 256 and mo - (do + de) < 256
+    _refused(lib, lib.ishara_op_attn_scratch_layout_bytes(1, 3, 0, 32, (C.c_int64 * 6)()), "ishara_op_attn_scratch_layout_bytes", ">= 1")
+    _refused(lib, lib.ishara_op_attn_scratch_layout_bytes(1, 3, 8, 32, None), "ishara_op_attn_scratch_layout_bytes", "null")
+
+
 # (dt, M, K, C, route): shapes / dtypes the named route has no kernel for
 @pytest.mark.parametrize("dt,M,K,C_,route,why", [
     (F32, 64, 256, 60, 1, "16-bit"),            # A-stationary: 16-bit operands only

@@ -170,6 +170,20 @@ int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T, int32_t C,
                            const float* lm, float alpha, float beta, void* workspace,
                            int32_t* out_idx, int32_t* out_len, float* out_score, ishara_stream s);
 
+/* CTC forced alignment (Viterbi) of known labels; the semantics of ishara_amd/ctc_align.py.  logits [B,T,C] fp32, labels [B,L] int64 padded
+ * with blank (the label of a row ends at its first blank).  The path maximises the sum of the raw logits along it, carried in fp64, ties
+ * broken stay > s-1 > s-2: the integer outputs are an exact function of the inputs.
+ * -> frame_pos [B,T] int32 (label index emitted at the frame, -1 on a blank frame); start, end [B,L] int32 (symbol i on frames [start, end),
+ * -1 past the label); conf [B,L] fp32 (mean softmax value of the symbol over its span, 0 past the label); score [B] fp32 (log-probability
+ * of the path).  A sample without an alignment (T < len + repeats, or a label outside [0, C), which is read as blank and never used as an
+ * index) gets score -1e30, frame_pos -1, start = end = -1, conf 0; the other samples' outputs are bit-identical to a launch without it.
+ * B >= 0 (0: nothing is launched), 1 <= T <= 4096, 1 <= L <= 255, 2 <= C <= 64, 0 <= blank < C, no null buffer; anything else is refused with
+ * a message before any HIP call.  ws: the bytes the workspace function returns (128 where the back-pointers fit in LDS and the buffer is
+ * not touched, B*T*128 otherwise), 16-byte aligned, no initialisation needed.  One kernel, graph-capturable, bit-identical from run to run. */
+int64_t ishara_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t L);
+int ishara_ctc_align(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                     void* ws, int32_t* frame_pos, int32_t* start, int32_t* end, float* conf, float* score, ishara_stream s);
+
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */
 typedef struct ishara_clip_aug {

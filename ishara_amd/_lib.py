@@ -78,6 +78,8 @@ SIGNATURES = {
     "ishara_edit_distance": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P]),
     "ishara_ctc_beam_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_ctc_beam_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "ishara_ctc_align_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "ishara_ctc_align": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "ishara_clip_batch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "ishara_ctc_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_ctc_loss": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P]),

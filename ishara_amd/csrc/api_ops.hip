@@ -119,6 +119,26 @@ extern "C" int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T,
     if ((uintptr_t)workspace % 4) { ishara_set_error("ishara_ctc_beam_decode: workspace must be 4-byte aligned"); return -1; }
     return launch_ctc_beam(logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len, out_score, (hipStream_t)s);
 }
+// CTC forced alignment: refused before any HIP call, as the loss is
+extern "C" int64_t ishara_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t L) {
+    if (B < 0 || T < 1 || T > 4096 || L < 1 || L > 255) return -1;
+    return (int64_t)ctc_align_workspace_bytes(B, T, L);
+}
+extern "C" int ishara_ctc_align(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                                void* ws, int32_t* frame_pos, int32_t* start, int32_t* end, float* conf, float* score, ishara_stream s) {
+    const char* me = "ishara_ctc_align";
+    if (B < 0) { ishara_set_error("%s: B=%d < 0", me, B); return -1; }
+    if (T < 1 || T > 4096) { ishara_set_error("%s: T=%d outside 1..4096", me, T); return -1; }
+    if (L < 1 || L > 255) { ishara_set_error("%s: L=%d outside 1..255 (2L+1 lattice states in at most 8 registers of a 64-lane wave)", me, L); return -1; }
+    if (C < 2 || C > 64) { ishara_set_error("%s: C=%d outside 2..64", me, C); return -1; }
+    if (blank < 0 || blank >= C) { ishara_set_error("%s: blank %d outside 0..%d", me, blank, C - 1); return -1; }
+    if (B == 0) return 0;
+    if (!logits || !labels || !ws || !frame_pos || !start || !end || !conf || !score) {
+        ishara_set_error("%s: null logits / labels / ws / frame_pos / start / end / conf / score", me); return -1;
+    }
+    if ((uintptr_t)ws % 16) { ishara_set_error("%s: ws must be 16-byte aligned", me); return -1; }
+    return launch_ctc_align(logits, labels, B, T, C, L, blank, ws, frame_pos, start, end, conf, score, (hipStream_t)s);
+}
 extern "C" int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
                                  float* x, ishara_stream s) {
     if (B < 0 || T < 1 || T > CLIP_MAX_T) { ishara_set_error("ishara_clip_batch: B=%d T=%d unsupported (B >= 0, 1 <= T <= %d)", B, T, CLIP_MAX_T); return -1; }

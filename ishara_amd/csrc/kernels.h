@@ -248,6 +248,11 @@ int launch_edit_distance(const int* out_idx, const int* out_len, int B, int T, c
 __host__ __device__ size_t ctc_beam_workspace_words(int T, int W);
 int launch_ctc_beam(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm, float alpha, float beta,
                     void* ws, int* out_idx, int* out_len, float* out_score, hipStream_t s);
+// ---- CTC forced alignment (ctc_align.hip): the best path of a known label, per-symbol frame spans and confidences (ishara_amd/ctc_align.py)
+bool ctc_align_bp_in_lds(int T, int L);                          // the back-pointers (T * 128 bytes) fit in LDS: the workspace is not used
+size_t ctc_align_workspace_bytes(int B, int T, int L);
+int launch_ctc_align(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws, int* frame_pos, int* start,
+                     int* end, float* conf, float* score, hipStream_t s);
 // ---- training input batch (input_batch.hip): device store of raw clips + per-clip augmentation table -> x [B,T,F]
 #define CLIP_MAX_T 4096
 int launch_clip_batch(const float* raw, const ishara_clip_aug* clips, int B, int T, int layout, float* x, hipStream_t s);

@@ -58,6 +58,16 @@ def num_to_char_fn(y, num_to_char: Dict[int, str]) -> List[str]:
     return [num_to_char.get(int(x), "") for x in y]
 
 
+def alignment_table(alignment, num_to_char: Dict[int, str]) -> str:
+    """A forced alignment (ishara_amd.ctc_align.Alignment) as a small text table: a header, one line per symbol of the label (its character,
+    first and last frame, frame count, confidence) and the log-probability of the path; a label without an alignment says so."""
+    lines = [f"{'#':>3} {'sym':>3} {'first':>5} {'last':>5} {'frames':>6} {'conf':>6}"]
+    for i, (sym, start, end, conf) in enumerate(alignment.spans):
+        lines.append(f"{i:>3} {num_to_char.get(int(sym), '?'):>3} {start:>5} {end - 1:>5} {end - start:>6} {conf:>6.3f}")
+    lines.append("no alignment" if alignment.score <= -1e29 else f"log p(path) = {alignment.score:.3f}")
+    return "\n".join(lines)
+
+
 class CallbackEval:
     """Displays a batch of outputs after every epoch (c9:1-29): saves the weights, decodes every batch of
     `dataset` greedily and prints target / prediction pairs.  `model` is an `ishara_amd.Model`."""

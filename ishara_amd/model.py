@@ -459,6 +459,31 @@ class Model(Handle):
         idx, ln, sc = idx.cpu().numpy(), ln.cpu().numpy(), sc.cpu().numpy()
         return [[(idx[b, n, :ln[b, n]].astype(np.int64), float(sc[b, n])) for n in range(nbest) if ln[b, n] >= 0] for b in range(B)]
 
+    def align(self, logits, y) -> list:
+        """CTC forced alignment (ishara_amd/ctc_align.py semantics, blank = C - 1) of logits [B, T, C] to the labels y [B, L] (padded with
+        C - 1) on the device -> per clip an Alignment: the label index every frame emits, the log-probability of the best path and one
+        (symbol, start, end, conf) span per symbol.  The workspace is kept for the next call, as beam_decode keeps its own."""
+        from . import ctc_align
+        logits = torch.as_tensor(logits).to(self.device, torch.float32).contiguous()
+        y = torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(self.device, torch.int64).contiguous()
+        if logits.ndim != 3 or y.ndim != 2 or y.shape[0] != logits.shape[0]:
+            raise ValueError(f"logits must be [B, T, C] and y [B, L], got {tuple(logits.shape)} and {tuple(y.shape)}")
+        B, T, Cc = logits.shape
+        L = y.shape[1]
+        ctc_align.check_device_args(Cc, T, L, Cc - 1)
+        nbytes = max(ctc_align.workspace_bytes(self._lib, B, T, L), 16)
+        ws = getattr(self, "_align_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._align_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        fp = torch.empty((B, T), dtype=torch.int32, device=self.device)
+        st = torch.empty((B, L), dtype=torch.int32, device=self.device)
+        en = torch.empty((B, L), dtype=torch.int32, device=self.device)
+        cf = torch.empty((B, L), dtype=torch.float32, device=self.device)
+        sc = torch.empty(B, dtype=torch.float32, device=self.device)
+        ctc_align.launch(self._lib, logits, y, B, T, Cc, L, Cc - 1, ws, fp, st, en, cf, sc, _stream())
+        return ctc_align.to_alignments(y.cpu().numpy(), *(t.cpu().numpy() for t in (fp, st, en, cf, sc)))
+
+
 def make_config(dim=256, num_conv_squeeze_blocks=2, num_conv_conform_blocks=2, kernel_sizes=(11, 5, 3),
                 num_conv_per_block=3, dropout_rate=0.2, num_heads=8, expansion_factor=2, transformer_kernel_size=15,
                 input_shape=(176, 276), num_classes=60, top_dim=0, squeeze_expansion=0, conformer_expansion=0,

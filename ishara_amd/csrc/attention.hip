@@ -9,7 +9,6 @@
 // (24 and 48 — e.g. the reference's d384 / 8-head sibling model — have no MFMA kernel and run here in bf16 mode too).
 #include "kernels.h"
 
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -2)
 
 DEVI float quad_sum(float v) {
     v += __shfl_xor(v, 1, 64);
@@ -234,13 +233,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
         }                                                                                                 \
     } while (0)
 
-int launch_attn_bwd_mfma(const void* q, const void* k, const void* vt, const void* o, const void* dout, const float* lse,
-                         float* delta, void* dqkv, int B, int H, int T, int dh, float scale, DropSpec drop, uint32_t* maskbits, hipStream_t s);
-int launch_attn_fwd_mfma(const void* q, const void* k, const void* vt, void* o, float* lse,
-                         int B, int H, int T, int dh, float scale, DropSpec drop, uint32_t* maskbits, hipStream_t s);
-
-int launch_attn_fwd_mfma_f16(const void* q, const void* k, const void* vt, void* o, float* lse, int B, int H, int T, int dh, float scale, hipStream_t s);
-
 int launch_attn_fwd(int dt, const void* q, const void* k, const void* vt, void* o, float* lse,
                     int B, int H, int T, int dh, float scale, DropSpec drop, int impl, uint32_t* maskbits, hipStream_t s) {
     if (impl == 1 && dt == DT_BF16 && (dh == 32 || dh == 64)) return launch_attn_fwd_mfma(q, k, vt, o, lse, B, H, T, dh, scale, drop, maskbits, s);
@@ -248,7 +240,7 @@ int launch_attn_fwd(int dt, const void* q, const void* k, const void* vt, void* 
     if (dt == DT_BF16) { ATT_DISPATCH(attn_fwd_kernel, bf16, (const bf16*)q, (const bf16*)k, (const bf16*)vt, (bf16*)o, lse, B, H, T, scale, drop); }
     else if (dt == DT_F16) { ATT_DISPATCH(attn_fwd_kernel, f16, (const f16*)q, (const f16*)k, (const f16*)vt, (f16*)o, lse, B, H, T, scale, drop); }
     else { ATT_DISPATCH(attn_fwd_kernel, float, (const float*)q, (const float*)k, (const float*)vt, (float*)o, lse, B, H, T, scale, drop); }
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 int launch_attn_bwd(int dt, const void* q, const void* k, const void* vt, const void* o, const void* dout,
@@ -263,5 +255,5 @@ int launch_attn_bwd(int dt, const void* q, const void* k, const void* vt, const 
         ATT_DISPATCH(attn_bwd_dq_kernel, float, (const float*)q, (const float*)k, (const float*)vt, (const float*)o, (const float*)dout, lse, delta, (float*)dqkv, B, H, T, scale, drop, head_major);
         ATT_DISPATCH(attn_bwd_dkv_kernel, float, (const float*)q, (const float*)k, (const float*)vt, (const float*)dout, lse, (const float*)delta, (float*)dqkv, B, H, T, scale, drop, head_major);
     }
-    return LAUNCH_OK();
+    return launch_rc();
 }

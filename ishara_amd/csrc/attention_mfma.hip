@@ -918,7 +918,7 @@ static int launch_fused_bwd_(const void* q, const void* k, const void* vt, const
     }
     hipLaunchKernelGGL((attn_bwd_fused_kernel<NW, NT, DM, FULL>), dim3(B * H), dim3(NW * 64), SM, s, (const bf16*)q, (const bf16*)k, (const bf16*)vt, (const bf16*)o,
                        (const bf16*)dout, lse, (bf16*)dqkv, H, T, scale, drop, maskbits);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 template <int NW, int NT>
 static int launch_fused_bwd(int dm, const void* q, const void* k, const void* vt, const void* o, const void* dout, const float* lse, void* dqkv,
@@ -954,7 +954,7 @@ int launch_attn_bwd_mfma(const void* q, const void* k, const void* vt, const voi
     else { ishara_set_error("attn_bwd_mfma: head dim %d unsupported (32, 64)", dh); return -1; }
 #undef ATT_BWD_DM
 #undef ATT_BWD
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 
 size_t attn_mask_words(int B, int H, int T) { return (size_t)B * H * ((T + AF_QB - 1) / AF_QB) * ((T + AF_KC - 1) / AF_KC) * 256; }
@@ -967,7 +967,7 @@ int launch_attn_fwd_mfma_f16(const void* q, const void* k, const void* vt, void*
     if (dh == 32) hipLaunchKernelGGL((attn_fwd_mfma_kernel<32, 0, f16>), grid, dim3(256), 0, s, (const f16*)q, (const f16*)k, (const f16*)vt, (f16*)o, lse, H, T, scale, nodrop, B * H, (uint32_t*)nullptr);
     else if (dh == 64) hipLaunchKernelGGL((attn_fwd_mfma_kernel<64, 0, f16>), grid, dim3(256), 0, s, (const f16*)q, (const f16*)k, (const f16*)vt, (f16*)o, lse, H, T, scale, nodrop, B * H, (uint32_t*)nullptr);
     else { ishara_set_error("attn_fwd_mfma: head dim %d unsupported (32, 64)", dh); return -1; }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 
 int launch_attn_fwd_mfma(const void* q, const void* k, const void* vt, void* o, float* lse,
@@ -982,5 +982,5 @@ int launch_attn_fwd_mfma(const void* q, const void* k, const void* vt, void* o, 
     else { ishara_set_error("attn_fwd_mfma: head dim %d unsupported (32, 64)", dh); return -1; }
 #undef ATT_FWD_DM
 #undef ATT_FWD
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }

@@ -214,3 +214,4 @@ static inline DropSpec make_drop_attn(uint32_t seed, uint32_t site, float rate, 
     } while (0)
 
 void ishara_set_error(const char* fmt, ...);
+static inline int launch_rc() { return hipGetLastError() == hipSuccess ? 0 : -2; }      // after hipLaunchKernelGGL: 0, or -2 when the launch failed

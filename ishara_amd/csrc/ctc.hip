@@ -11,7 +11,6 @@
 #include <type_traits>
 #include "kernels.h"
 
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -2)
 
 static inline int ctc_ns(int L) { return (2 * L + 1 + 63) / 64; }            // lattice states per lane of the recursion wave
 // LDS of one workgroup: lse[T] and ext[64 NS] are requested at launch; cls (4 KiB), s_logp, s_len and s_bad are static.  The kernel is launched
@@ -302,7 +301,7 @@ int launch_ctc(const float* logits, const int64_t* labels, int B, int T, int C, 
     switch (ns) { case 1: CTC_L(1); break; case 2: CTC_L(2); break; case 3: CTC_L(3); break; case 4: CTC_L(4); break;
                   case 5: CTC_L(5); break; case 6: CTC_L(6); break; case 7: CTC_L(7); break; default: CTC_L(8); break; }
 #undef CTC_L
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 __global__ void mean_kernel(const float* __restrict__ v, float* __restrict__ out, int n, float scale) {
@@ -316,7 +315,7 @@ __global__ void mean_kernel(const float* __restrict__ v, float* __restrict__ out
 }
 int launch_mean(const float* v, float* out, int n, float scale, hipStream_t s) {
     hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, v, out, n, scale);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // greedy decode: argmax per frame (first max on ties), keep x[i] (i <= T-2) where
@@ -365,5 +364,5 @@ __global__ __launch_bounds__(256) void greedy_decode_kernel(const float* __restr
 
 int launch_greedy_decode(const float* logits, int B, int T, int C, int blank, int* out_idx, int* out_len, hipStream_t s) {
     hipLaunchKernelGGL(greedy_decode_kernel, dim3(B), dim3(256), T * sizeof(int), s, logits, T, C, blank, out_idx, out_len);
-    return LAUNCH_OK();
+    return launch_rc();
 }

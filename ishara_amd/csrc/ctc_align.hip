@@ -262,5 +262,5 @@ int launch_ctc_align(const float* logits, const int64_t* labels, int B, int T, i
                   case 5: ALIGN_NS(5); break; case 6: ALIGN_NS(6); break; case 7: ALIGN_NS(7); break; default: ALIGN_NS(8); break; }
 #undef ALIGN_NS
 #undef ALIGN_L
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }

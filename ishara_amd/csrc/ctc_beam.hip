@@ -340,5 +340,5 @@ int launch_ctc_beam(const float* logits, int B, int T, int C, int blank, int W, 
     while (nw < W && nw < BM_MAXNW) nw <<= 1;
     hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm, alpha, beta, (int*)ws, out_idx,
                        out_len, out_score);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }

@@ -5,8 +5,6 @@
 // (8 x f32) chunks per lane; all arithmetic is fp32.
 #include "kernels.h"
 
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -2)
-void launch_reduce_slabs(const float* slab, float* out, int n, int splits, size_t stride, hipStream_t s);
 
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
@@ -88,7 +86,7 @@ int launch_layernorm_fwd(int dt, const void* x, const float* gamma, const float*
 #define LN_FG(TT) switch (G) { case 1: LN_F(TT, 1); break; case 2: LN_F(TT, 2); break; case 4: LN_F(TT, 4); break; case 8: LN_F(TT, 8); break; \
                                case 16: LN_F(TT, 16); break; case 32: LN_F(TT, 32); break; default: LN_F(TT, 64); break; }
     if (dt == DT_BF16) { LN_FG(bf16) } else if (dt == DT_F16) { LN_FG(f16) } else { LN_FG(float) }
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // dx = rstd * (g*dy - mean_c(g*dy) - xhat * mean_c(g*dy*xhat)) (+ resid); dgamma += sum_rows dy*xhat; dbeta += sum_rows dy
@@ -170,12 +168,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
     }
 }
 
-void launch_reduce_slabs(const float* slab, float* out, int n, int splits, size_t stride, hipStream_t s);
-void launch_reduce_slabs2(const float* slab, float* out0, int n0, float* out1, int n1, int splits, size_t stride, hipStream_t s, int nb = 0, int nbv = 0);
-bool dwconv_bwd_fused_ok(int dt, int C, int k, int padl);
-int launch_dwconv_bwd_fused(int dt, int inop, const void* dy, const void* x, const float* w, void* dx, float* part,
-                            int B, int T, int C, int k, int padl, int max_rows, hipStream_t s, const DwBnArgs& bn);
-
 int launch_layernorm_bwd(int dt, const void* dy, const void* x, const float* mean, const float* rstd,
                          const float* gamma, const void* resid, void* dx, float* dgamma, float* dbeta,
                          float* scratch, int M, int C, hipStream_t s) {
@@ -188,7 +180,7 @@ int launch_layernorm_bwd(int dt, const void* dy, const void* x, const float* mea
                                case 16: LN_B(TT, 16); break; case 32: LN_B(TT, 32); break; default: LN_B(TT, 64); break; }
     if (dt == DT_BF16) { LN_BG(bf16) } else { LN_BG(float) }
     if (scratch) launch_reduce_slabs2(scratch, dgamma, C, dbeta, C, grid, (size_t)2 * C, s);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 size_t layernorm_bwd_scratch_floats(int C) { return (size_t)2048 * 2 * C; }
 
@@ -1016,7 +1008,7 @@ int launch_dwconv_fwd(int dt, int inop, const void* x, const float* w, const flo
     }
     if (part && part_rows) *part_rows = P;          // the caller sums the partial rows itself (eca_fwd's inference form)
     else if (part) hipLaunchKernelGGL(stats_reduce_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, part, P, colsum, colsq, B, C);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // dw[j,c] += sum_{b,t} dy[b,t,c] * in(x)[b, t-padl+j, c] ; dbias[c] += sum dy.
@@ -1158,7 +1150,7 @@ int launch_dwconv_bwd(int dt, int inop, const void* dy, const void* x, const flo
         if (rows < 0) return -2;
         launch_reduce_slabs(scratch, dw, k * C, rows, (size_t)(k + 1) * C, s);
         if (dbias) launch_reduce_slabs(scratch + (size_t)k * C, dbias, C, rows, (size_t)(k + 1) * C, s);
-        return LAUNCH_OK();
+        return launch_rc();
     }
     const int outop = inop == DWIN_SWISH ? OUT_DSWISH : (inop == DWIN_GLU ? OUT_DGLU : OUT_NONE);
     const bool reg = dw_reg_ok(C, k) && !g_force_dw_lds;
@@ -1195,7 +1187,7 @@ int launch_dwconv_bwd(int dt, int inop, const void* dy, const void* x, const flo
         if (dt == DT_BF16) hipLaunchKernelGGL(dwconv_wgrad_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)x, dw, dbias, B, T, C, k, padl, inop);
         else hipLaunchKernelGGL(dwconv_wgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, dw, dbias, B, T, C, k, padl, inop);
     }
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // =====================================================================================
@@ -1257,7 +1249,7 @@ int launch_sample_reduce(int dt, const void* dy, const void* other, const float*
     if (dt == DT_BF16) hipLaunchKernelGGL(sample_reduce_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)other, mean, rstd, S1, S2, B, T, C);
     else if (dt == DT_F16) hipLaunchKernelGGL(sample_reduce_kernel<f16>, grid, dim3(256), 0, s, (const f16*)dy, (const f16*)other, mean, rstd, S1, S2, B, T, C);
     else hipLaunchKernelGGL(sample_reduce_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)other, mean, rstd, S1, S2, B, T, C);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // =====================================================================================
@@ -1311,7 +1303,7 @@ int launch_bn_finalize(const float* ssum, const float* ssq, int nb, float count,
                           float* mean, float* rstd, float* a, float* b, int C, hipStream_t s, float var_corr, int stride) {
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + FIN_CL - 1) / FIN_CL), dim3(FIN_CL * FIN_BL), 0, s, ssum, ssq, nb, count, gamma, beta, eps, momentum,
                        moving_mean, moving_var, training, mean, rstd, a, b, C, var_corr, stride ? stride : C);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // =====================================================================================
@@ -1375,14 +1367,14 @@ __global__ __launch_bounds__(1024) void eca_fwd_kernel(const float* __restrict__
 int launch_eca_fwd(const float* gap, const float* a, const float* b, const float* w5, float invT,
                    float* gn, float* sgate, float* P, float* Q, int B, int C, hipStream_t s, float* rs, DropSpec dp, int dp_fold) {
     hipLaunchKernelGGL(eca_fwd_kernel, dim3(B), dim3(256), (C + 4) * sizeof(float), s, gap, a, b, w5, invT, gn, sgate, P, Q, C, rs, dp, dp_fold, EcaInfer{});
-    return LAUNCH_OK();
+    return launch_rc();
 }
 // training form over the depthwise conv's partial statistic rows: sums them per sample (-> gap_out [B, C]) and gates with bn_finalize's constants
 int launch_eca_fwd_part(const float* part, int prows, float* gap_out, const float* a, const float* b, const float* w5, float invT,
                         float* gn, float* sgate, float* P, float* Q, int B, int C, hipStream_t s, float* rs, DropSpec dp, int dp_fold) {
     EcaInfer inf; inf.part = part; inf.prows = prows; inf.gap_out = gap_out;
     hipLaunchKernelGGL(eca_fwd_kernel, dim3(B), dim3(256), (3 * C + 4) * sizeof(float), s, (const float*)nullptr, a, b, w5, invT, gn, sgate, P, Q, C, rs, dp, dp_fold, inf);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 int launch_eca_fwd_infer(const float* part, int prows, const float* mm, const float* mv, const float* gamma, const float* beta, float eps, const float* w5, float invT,
                          float* gn, float* sgate, float* P, float* Q, int B, int C, hipStream_t s) {
@@ -1390,7 +1382,7 @@ int launch_eca_fwd_infer(const float* part, int prows, const float* mm, const fl
     const int threads = B <= 8 ? (C + 4 > 512 ? 1024 : 512) : 256;      // a clip or a few: a thread per channel (one workgroup per sample is all the parallelism there is)
     hipLaunchKernelGGL(eca_fwd_kernel, dim3(B), dim3(threads), (3 * C + 4) * sizeof(float), s, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, w5, invT, gn, sgate, P, Q, C,
                        (float*)nullptr, DropSpec{0, 0, 1.f}, 0, inf);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // =====================================================================================
@@ -1442,7 +1434,7 @@ static int run_affine(int dt, const void* x, const float* P, const float* Q, con
     if (dt == DT_BF16) hipLaunchKernelGGL(affine_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)x, P, Q, (const bf16*)resid, (bf16*)y, T, C, per_sample);
     else if (dt == DT_F16) hipLaunchKernelGGL(affine_kernel<f16>, grid, dim3(256), 0, s, (const f16*)x, P, Q, (const f16*)resid, (f16*)y, T, C, per_sample);
     else hipLaunchKernelGGL(affine_kernel<float>, grid, dim3(256), 0, s, (const float*)x, P, Q, (const float*)resid, (float*)y, T, C, per_sample);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 int launch_sample_affine(int dt, const void* x, const float* P, const float* Q, const void* resid, void* y, int B, int T, int C, hipStream_t s) {
     return run_affine(dt, x, P, Q, resid, y, B, T, C, 1, s);
@@ -1609,7 +1601,7 @@ int launch_eca_bn_bwd_finalize(float* S1, float* S2, const float* gap, const flo
     const size_t shm = (size_t)(2 * (CC + 4) + 2 * (CC + 16) + (p.G ? p.N + 4 * (CC + 16) : 0)) * sizeof(float);
     hipLaunchKernelGGL(eca_bwd_sample_kernel, dim3(B, nchunk), dim3(256), shm, s, S1, S2, gn, sgate, w5, gamma, beta, E, dw5part, C, CC, p);
     hipLaunchKernelGGL(eca_bn_bwd_channel_kernel, dim3((C + FIN_CL - 1) / FIN_CL), dim3(FIN_CL * FIN_BL), 0, s, S1, S2, gap, sgate, mean, rstd, dgamma, dbeta, E, Fc, dw5part, B * nchunk, dw5, B, T, C);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 __global__ __launch_bounds__(1024) void bn_bwd_channel_kernel(const float* __restrict__ S1, const float* __restrict__ S2, float* __restrict__ dgamma,
@@ -1635,7 +1627,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_channel_kernel(const float* __res
 int launch_bn_bwd_finalize(const float* S1, const float* S2, float* dgamma, float* dbeta, float* Ecol, float* Fc,
                            int B, int T, int C, hipStream_t s) {
     hipLaunchKernelGGL(bn_bwd_channel_kernel, dim3((C + FIN_CL - 1) / FIN_CL), dim3(FIN_CL * FIN_BL), 0, s, S1, S2, dgamma, dbeta, Ecol, Fc, B, T, C);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // dx = a[c] * (dy*sg[b,c] + E - xhat*Fc[c]) = dy*k1 + k0 - x*k2 with per-(sample,channel) constants
@@ -1687,7 +1679,7 @@ int launch_bn_bwd_apply(int dt, const void* dy, const void* x, const float* mean
     dim3 grid(gx, B);
     if (dt == DT_BF16) hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)x, mean, rstd, a, sg, E, e_per_sample, Fc, (bf16*)dx, T, C);
     else hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, mean, rstd, a, sg, E, e_per_sample, Fc, (float*)dx, T, C);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // =====================================================================================
@@ -1742,7 +1734,7 @@ __global__ __launch_bounds__(256) void se_fwd_kernel(const float* __restrict__ g
 int launch_se_fwd(const float* gap, float invT, const float* W1, const float* b1, const float* W2, const float* b2,
                   float* hid_pre, float* se, int B, int C, int R, hipStream_t s) {
     hipLaunchKernelGGL(se_fwd_kernel, dim3(B), dim3(256), (C + R + 256) * sizeof(float), s, gap, invT, W1, b1, W2, b2, hid_pre, se, C, R);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // Squeeze-excite backward, step 1 (one workgroup per sample): dz2 = dse*se*(1-se), dhp = (W2 dz2) * swish'(hid_pre), dgapT = W1 dhp / T;
@@ -1834,7 +1826,7 @@ int launch_se_bwd(const float* dse, const float* gap, float invT, const float* W
                   float* dgapT, float* scr, int B, int C, int R, hipStream_t s) {
     hipLaunchKernelGGL(se_bwd_kernel, dim3(B), dim3(256), (C + R + 256) * sizeof(float), s, dse, gap, invT, W1, W2, hid_pre, se, scr, dgapT, C, R);
     hipLaunchKernelGGL(se_wgrad_kernel, dim3((2 * C * R + C + R + 63) / 64), dim3(256), 0, s, scr, gap, invT, dW1, db1, dW2, db2, B, C, R);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // =====================================================================================
@@ -1886,7 +1878,7 @@ int launch_map_rows(int dt, int op, const void* x, void* y, const float* rs, Dro
     if (dt == DT_BF16) hipLaunchKernelGGL(map_rows_kernel<bf16>, dim3(grid), dim3(256), 0, s, (const bf16*)x, (bf16*)y, op, rs, drop, M, T, C);
     else if (dt == DT_F16) hipLaunchKernelGGL(map_rows_kernel<f16>, dim3(grid), dim3(256), 0, s, (const f16*)x, (f16*)y, op, rs, drop, M, T, C);
     else hipLaunchKernelGGL(map_rows_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (float*)y, op, rs, drop, M, T, C);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 
 // ------------------------------------------------------------------ row log-softmax (the torch Squeezeformer's output layer)
@@ -1929,10 +1921,10 @@ __global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const float* __res
 int launch_log_softmax_fwd(const float* x, float* y, int M, int C, int ld, hipStream_t s) {
     if (M < 1 || C < 1 || ld < C) { ishara_set_error("log_softmax: M=%d C=%d ld=%d", M, C, ld); return -1; }
     hipLaunchKernelGGL(log_softmax_fwd_kernel, dim3(max(1, min((M + 3) / 4, 2048))), dim3(256), 0, s, x, y, M, C, ld);
-    return LAUNCH_OK();
+    return launch_rc();
 }
 int launch_log_softmax_bwd(const float* dy, const float* y, float* dx, int M, int C, int ld, hipStream_t s) {
     if (M < 1 || C < 1 || ld < C) { ishara_set_error("log_softmax: M=%d C=%d ld=%d", M, C, ld); return -1; }
     hipLaunchKernelGGL(log_softmax_bwd_kernel, dim3(max(1, min((M + 3) / 4, 2048))), dim3(256), 0, s, dy, y, dx, M, C, ld);
-    return LAUNCH_OK();
+    return launch_rc();
 }

@@ -44,9 +44,6 @@ typedef bf16x8 as_v8;
 #define AS_NAME(x) x
 #endif
 
-extern int g_force_regstage;
-bool gemm_nt_as_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);
-
 #define AS_NS 32            // output columns (staged weight rows) per step
 #define AS_SMALL_M 1536     // K <= 512: at or below this many rows the workgroups take 64 rows instead of 128 / 192, and the columns are split
                             // down to one 32-column step per workgroup (latency of a B = 1 clip: 22.6 -> ~7 us per K = 512 GEMM)
@@ -619,9 +616,7 @@ static int as_inst_mask(bool c_bf16, int mask, int K = 256) {
 #endif
 #define AS_LAUNCH(MASK) AS_LAUNCH2(MASK, 0)
 // library default of EpiArgs.as_flags (bit 0 paired half-line stores, bit 1 non-temporal side outputs); ISHARA_AS_FLAGS overrides (A/B runs)
-#ifdef AS_F16
-extern int g_as_flags_override;
-#else
+#ifndef AS_F16
 int g_as_flags_override = -1;       // tests / A-B runs inside one process (ishara_debug_set_as_flags)
 #endif
 static int as_default_flags() {
@@ -661,7 +656,7 @@ static int run_as(const void* A, const void* Bt, void* C, int M, int N, int ldb,
                 case AS_QKV: AS_PRO(AS_QKV, 1); break;
                 default: ishara_set_error("gemm_nt_as: LayerNorm prologue with epilogue mask %d is not compiled", mask); return -1;
             }
-            return hipGetLastError() == hipSuccess ? 0 : -2;
+            return launch_rc();
         }
         if (ea.pa_P) {               // per-sample affine prologue: the project GEMM of a Conv1DBlock
             switch (mask) {
@@ -669,7 +664,7 @@ static int run_as(const void* A, const void* Bt, void* C, int M, int N, int ldb,
                 case AS_RESID | AS_ROWSCALE: AS_PRO(AS_RESID | AS_ROWSCALE, 2); break;
                 default: ishara_set_error("gemm_nt_as: affine prologue with epilogue mask %d is not compiled", mask); return -1;
             }
-            return hipGetLastError() == hipSuccess ? 0 : -2;
+            return launch_rc();
         }
 #undef AS_PRO
     }
@@ -715,7 +710,7 @@ static int run_as(const void* A, const void* Bt, void* C, int M, int N, int ldb,
     else {
         if (mask == 0) AS_LAUNCH(0); else AS_LAUNCH(AS_ALL);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 #undef AS_LAUNCH
 

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_big_kernel(const bf16* __restr
 // The weight-gradient (TN) form of the same tile: dW[Ka, Nb] (+)= A[M, Ka]^T . B[M, Nb], split over M, one 256 x 256 output tile and one
 // M-split per workgroup, the partial tile written to the caller's fp32 slab (summed by the caller: launch_reduce_slabs2).
 //
-// Why: the 128 x 128 tile kernel (gemm.hip gemm_tn_tr_kernel) has 16 - 32 workgroups per M-split at d = 512 that all request the same operand
+// Why: the 128 x 128 tile kernel (gemm_tn.hip gemm_tn_tr_kernel) has 16 - 32 workgroups per M-split at d = 512 that all request the same operand
 // rows; each keeps its own copy in flight in LDS, so of the 96 KB a CU has in flight only a quarter is distinct bytes, and the kernel runs at
 // 2.9 TB/s of operand bytes whatever the L2 does (tools/tn_traffic.py: pacing the sibling workgroups so that L2 serves every re-read brought the
 // fetched bytes from 1.7x to 1.0x of the operands and left the time unchanged).  With 256 x 256 tiles there are 4 - 16 workgroups per split.
@@ -442,7 +442,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(const bf16* __restr
     }
 }
 
-extern int g_nt_big;
 int g_tn_big = 1;
 // rows per M-split of the big weight-gradient kernel (0: the shape is not one it takes)
 int gemm_tn_big_plan(int M, int Ka, int Nb, int* splits_out) {
@@ -471,10 +470,9 @@ int launch_gemm_tn_big(const void* A, const void* B, float* slab, int want_bias,
     const int tiles = (Ka >> 8) * (Nb >> 8);
     hipLaunchKernelGGL(gemm_tn_big_kernel, dim3(tiles * splits), dim3(512), 2 * BG_BUF, s, (const bf16*)A, (const bf16*)B, slab, want_bias, M, Ka, Nb, rps, tiles, splits, brs, brsT);
     *splits_out = splits;
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 
-extern int g_nt_big;
 static int big_env() { const char* e = getenv("ISHARA_NT_BIG"); return e ? atoi(e) : 1; }
 int g_nt_big = big_env();           // 0: never (A/B runs, ishara_debug_set_nt_big)
 
@@ -493,7 +491,7 @@ static int run_big(const void* A, const void* Bt, void* C, int M, int N, int K, 
     }
     if (!ok) return 1;
     hipLaunchKernelGGL((gemm_nt_big_kernel<TC>), dim3((M >> 8) * (N >> 8)), dim3(512), 2 * BG_BUF, s, (const bf16*)A, (const bf16*)Bt, (TC*)C, M, N, K, ldb, ea, g_nt_big >> 1);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 
 // returns 1 when the shape is not one this kernel takes (the caller goes on to the other kernels)

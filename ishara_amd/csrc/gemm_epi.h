@@ -1,5 +1,5 @@
 // Fused GEMM epilogue on 8-wide row chunks (bias, PE table, saved pre-activation, activation, dropout, drop-path row scale, act', residual,
-// QKV head split) — shared by the tile kernels of gemm.hip and gemm_big.hip.
+// QKV head split) — shared by the tile kernels of gemm_nt.hip and gemm_big.hip.
 #pragma once
 #include "kernels.h"
 

@@ -211,5 +211,5 @@ __global__ __launch_bounds__(CB_THREADS) void clip_batch_kernel(const float* __r
 int launch_clip_batch(const float* raw, const ishara_clip_aug* clips, int B, int T, int layout, float* x, hipStream_t s) {
     if (B == 0) return 0;
     hipLaunchKernelGGL(clip_batch_kernel, dim3(B), dim3(CB_THREADS), 0, s, raw, clips, T, layout, x);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }

@@ -1,5 +1,5 @@
 // The Keras get_model hybrid family: the layer graph get_model(...) builds (conv-hybrid-model.ipynb c7:12-65), its workspace plan and
-// the forward / backward orchestration over the kernels in gemm.hip, elementwise.hip, attention.hip and ctc.hip.  confconv_fwd / _bwd
+// the forward / backward orchestration over the kernels in gemm_nt.hip, gemm_tn.hip, elementwise.hip, attention.hip and ctc.hip.  confconv_fwd / _bwd
 // also serve the torch families, ln_as_prologue and classifier_fwd the operator entry points (api_ops.hip).
 #include "model_types.h"
 #include <stdlib.h>
@@ -311,7 +311,7 @@ static int conv_fwd(ishara_model* m, ConvBlock& cb, const Run& r, const void* x)
         probe.pro_out = r.training ? m->W(cb.h4) : nullptr;
         if (gemm_nt_as_prologue_ok(dt, dt, dt, r.M, cb.W2.N, cb.W2.K, cb.W2.ldt, probe)) {
             // training: h4 is written only when the backward pass needs it in memory — not when the project conv's weight-gradient GEMM applies
-            // P, Q itself (gemm.hip TnPsa: whole samples per M-split; the drop-path scale, if any, must be the folded one)
+            // P, Q itself (gemm_tn.hip TnPsa: whole samples per M-split; the drop-path scale, if any, must be the folded one)
             cb.psa = r.training && m->psa_on && (!ds.thr || cb.folded) && gemm_tn_psa_ok(dt, dt, dt, r.M, cb.W2.K, cb.W2.N, T);
             e2.pa_P = m->Wf(cb.P); e2.pa_Q = m->Wf(cb.Q); e2.T = T; e2.pro_out = (r.training && !cb.psa) ? m->W(cb.h4) : nullptr;
             CK(gemm_fwd(m, cb.W2, m->W(cb.h2), dt, m->W(cb.out), dt, r.M, OP_NONE, no, e2));

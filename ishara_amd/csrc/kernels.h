@@ -64,6 +64,18 @@ struct EpiArgs {
 // a multiple of 128, row stride ldb (elements) a multiple of the K tile (64 bf16 / 32 f32).
 int launch_gemm_nt(int dtA, int dtM, int dtC, int op, const void* A, const void* Bt, void* C,
                    int M, int N, int K, int ldb, const OpArgs& oa, const EpiArgs& ea, hipStream_t s);
+// the kernel launch_gemm_nt runs a call on (gemm_nt.hip: the one place that decides), and its profiler key = the prefix of its rocprof name
+enum NtRoute { NT_REFUSED, NT_AS_F16, NT_BIG, NT_AS, NT_TILE_T, NT_GLDS, NT_REG };
+NtRoute gemm_nt_route(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);
+const char* gemm_nt_kernel_name(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);
+bool gemm_nt_as_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);                    // gemm_as.hip
+// the kernel also takes ea's prologue (ln_* / pa_*): bf16 output, K in {256, 512}, whole 16-row tiles inside one sample for pa_*
+bool gemm_nt_as_prologue_ok(int dtA, int dtM, int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);   // gemm_as.hip: the A-stationary kernel takes this shape
+const char* gemm_nt_as_name(int dtC, int K, const EpiArgs& ea, int M, int N);
+int launch_gemm_nt_as(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);
+int launch_gemm_nt_as_f16(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);   // gemm_as_f16.hip
+bool gemm_nt_big_applicable(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);              // gemm_big.hip
+int launch_gemm_nt_big(int dtA, int dtM, int dtC, int op, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);
 
 // dW[Ka,Nb] += opA(A)[M,Ka]^T . opB(B)[M,Nb]   (fp32 accumulate into `out`, row-major [Ka,Nb]);
 // dbias[Nb] += colsum(opB(B)) when dbias != nullptr.  slab = fp32 scratch of
@@ -77,6 +89,10 @@ size_t gemm_tn_slab_floats(int M, int Ka, int Nb, int dtM);
 struct RedJob { const float* slab; float* out0; float* out1; size_t stride; int n0, n, splits, nb, nbv, first_block; };
 struct RedSink { RedJob job[RED_MAXJOBS]; int njobs = 0; int nblocks = 0; };
 extern RedSink* g_red_sink;
+// out[0..n) += column sums of slab[:, 0..n) (rows `stride` floats apart); _slabs2: out0[0..n0) and out1[0..n1) from slab[:, 0..n0) and [n0..n0+n1) in one launch
+void launch_reduce_slabs(const float* slab, float* out, int n, int splits, size_t stride, hipStream_t s);
+void launch_reduce_slabs2(const float* slab, float* out0, int n0, float* out1, int n1, int splits, size_t stride, hipStream_t s, int nb = 0, int nbv = 0);
+bool reduce_cols_ok(const float* slab, const float* out0, const float* out1, int n0, int n, size_t stride);   // the atomics-free column kernels (and a RedSink) take the job
 bool reduce_sink_full();                                   // no room for another job: flush before the next deferring operator
 int launch_reduce_flush(RedSink* sink, hipStream_t s);
 bool gemm_tn_bias_rowscale_ok(int dtA, int dtB, int dtM, int M, int Ka, int Nb, int T);   // the transposed-read kernel takes the call and T % 32 == 0
@@ -108,15 +124,18 @@ int launch_dense_narrow(int dt, const void* A, const void* Wt, int ldt, const fl
 // xb[M, Kp] (bf16) = x[M, F] (f32), zero padded to Kp columns (F % 4 == 0, Kp % 8 == 0)
 int launch_pack_rows_bf16(const float* x, void* xb, int M, int F, int Kp, hipStream_t s, int dt = DT_BF16);   // dt: DT_BF16 or DT_F16 (the fp16 inference path)
 
-bool gemm_nt_as_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);
-// the kernel also takes ea's prologue (ln_* / pa_*): bf16 output, K in {256, 512}, whole 16-row tiles inside one sample for pa_*
-bool gemm_nt_as_prologue_ok(int dtA, int dtM, int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);   // gemm_as.hip: the A-stationary kernel takes this shape
-const char* gemm_nt_kernel_name(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);
+// the kernel launch_gemm_tn runs a call on (gemm_tn.hip: the one place that decides; arguments as the launcher's, brs / psa: there is a bias row scale / a TnPsa)
+enum TnRoute { TN_REFUSED, TN_BIG, TN_TR, TN_TR_BRS, TN_TR_PSA, TN_REG };
+TnRoute gemm_tn_route(int dtA, int dtB, int dtM, int opA, int opB, int M, int Ka, int Nb, int ka_valid, int nb_valid, bool brs, int brsT, bool psa, int psaT);
+const char* gemm_tn_kernel_name(int dtA, int dtB, int dtM, int opA, int opB, int M, int Ka, int Nb, int ka_valid = 0, int nb_valid = 0,
+                                const float* bias_rowscale = nullptr, int bias_T = 0, const TnPsa* psa = nullptr);
+// the 256 x 256 tile wgrad kernel (gemm_big.hip): rows per M-split (0: not a shape it takes); the launcher answers 1 for such a shape
+int gemm_tn_big_plan(int M, int Ka, int Nb, int* splits_out);
+int launch_gemm_tn_big(const void* A, const void* B, float* slab, int want_bias, int M, int Ka, int Nb, int* splits_out, const float* brs, int brsT, hipStream_t s);
 extern int g_force_tn_regstage;   // tests: 1 forces the register-transposing TN kernel
 // the other switches of ishara_debug_force_regstage / _set_as_flags / _set_nt_big (api_ops.hip sets them; defined beside the kernels they steer)
 extern int g_force_regstage, g_dbg_tn, g_force_dw_lds, g_tn_blocks, g_attn_bwd_two_pass, g_as_flags_override, g_nt_big;
 extern int g_tn_phase;   // 0 GEMM + slab sums, 1 GEMM kernel only, 2 slab sums only
-const char* gemm_tn_kernel_name(int dtA, int dtB, int dtM, int opA, int opB, int M, int Ka, int Nb, bool brs = false);
 
 // weight shadows: Wt[Np][Kp] (transposed) and Wn[Kp2][Np2] (as-is, padded) in dtM
 int launch_make_shadow(int dtM, const float* W, int K, int N, void* Wt, int ldt, void* Wn, int ldn, hipStream_t s);
@@ -158,6 +177,10 @@ int launch_dwconv_bwd_bn(int dt, int inop, const void* dy, const DwBnArgs& bn, c
                          float* dw, float* dbias, float* scratch, int B, int T, int C, int k, int padl, hipStream_t s);
 int launch_dwconv_bwd(int dt, int inop, const void* dy, const void* x, const float* w, void* dx,
                       float* dw, float* dbias, float* scratch, int B, int T, int C, int k, int padl, hipStream_t s);
+// the one-pass kernel behind the two launchers above (dwconv_bwd.hip): partial rows into `part`, summed by the caller
+bool dwconv_bwd_fused_ok(int dt, int C, int k, int padl);
+int launch_dwconv_bwd_fused(int dt, int inop, const void* dy, const void* x, const float* w, void* dx, float* part,
+                            int B, int T, int C, int k, int padl, int max_rows, hipStream_t s, const DwBnArgs& bn);
 
 // BN finalize from per-sample sums ssum/ssq [nb,C] (count = rows they cover): mean, rstd,
 // a = gamma*rstd, b = beta - mean*a ; moving statistics update when training
@@ -223,6 +246,12 @@ int launch_attn_fwd(int dt, const void* q, const void* k, const void* vt, void* 
 int launch_attn_bwd(int dt, const void* q, const void* k, const void* vt, const void* o, const void* dout,
                     const float* lse, float* delta, void* dqkv, int B, int H, int T, int dh, float scale,
                     DropSpec drop, int head_major, int impl, uint32_t* maskbits, hipStream_t s);
+// the MFMA kernels behind impl == 1 (attention_mfma.hip)
+int launch_attn_fwd_mfma(const void* q, const void* k, const void* vt, void* o, float* lse,
+                         int B, int H, int T, int dh, float scale, DropSpec drop, uint32_t* maskbits, hipStream_t s);
+int launch_attn_fwd_mfma_f16(const void* q, const void* k, const void* vt, void* o, float* lse, int B, int H, int T, int dh, float scale, hipStream_t s);
+int launch_attn_bwd_mfma(const void* q, const void* k, const void* vt, const void* o, const void* dout, const float* lse,
+                         float* delta, void* dqkv, int B, int H, int T, int dh, float scale, DropSpec drop, uint32_t* maskbits, hipStream_t s);
 
 // ---- CTC / decode (ctc.hip) ----------------------------------------------------------
 size_t ctc_workspace_floats(int B, int T, int L);

@@ -28,7 +28,6 @@
     } while (0)
 
 static inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
-static inline int launch_rc() { return hipGetLastError() == hipSuccess ? 0 : -2; }      // after hipLaunchKernelGGL: 0, or -2 when the launch failed
 
 // ------------------------------------------------------------------ model description
 struct ParamEntry { std::string name; int ndim; int64_t shape[2]; int64_t offset; bool trainable; };
@@ -48,7 +47,7 @@ struct ConvBlock {
     Buf z1, h2, h4, out, ssum, ssq, mean, rstd, a, bsh, gn, sg, P, Q, rs;
     bool folded = false;      // last training forward folded the drop-path scale into h4 (= rs[b] * (h2 P + Q)): see conv_fwd
     bool psa = false;         // last training forward did not write h4: the project conv's weight gradient applies the per-sample affine itself
-                              // and emits the BatchNorm / ECA backward statistics (gemm.hip, TnPsa)
+                              // and emits the BatchNorm / ECA backward statistics (gemm_tn.hip, TnPsa)
 };
 struct FFN {
     Norm ln; float eps; DenseW Wa, Wb; uint32_t site_in = 0, site_out = 0; bool has_out_drop = false;
@@ -124,7 +123,7 @@ struct ishara_model {
     std::vector<DenseW*> denses;
     // temps
     RedSink red; Buf red_arena; size_t red_cap = 0, red_off = 0; bool red_on = false;      // deferred column sums of LayerNorm / depthwise-conv parameter gradients (model.hip red_scratch)
-    TnDefer tn_defer; Buf slab2[2]; bool tn_defer_on = false;      // deferred wgrad slab sums (gemm.hip): two alternating slab buffers
+    TnDefer tn_defer; Buf slab2[2]; bool tn_defer_on = false;      // deferred wgrad slab sums (gemm_tn.hip): two alternating slab buffers
     Buf gA, gB, t1, t2, t3, S1, S2, E, Fc, Ecol, ecap, dse, dgapT, slab, ctcws, dlogits, nllb, delta;
     Buf psaG, psaR; bool psa_on = false;   // TnPsa outputs: G [B, d], Rpart [B][d / 64][2d]
     size_t shadow_begin = 0, shadow_end = 0;

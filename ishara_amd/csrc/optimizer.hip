@@ -31,7 +31,7 @@ int launch_radam_lookahead(float* theta, const float* grad, float* m, float* v, 
                            RAdamArgs a, hipStream_t s) {
     const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipLaunchKernelGGL(radam_lookahead_kernel, dim3(grid), dim3(256), 0, s, theta, grad, m, v, slow, n, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 
 __global__ void scale_kernel(float* __restrict__ x, int64_t n, float scale) {
@@ -41,5 +41,5 @@ __global__ void scale_kernel(float* __restrict__ x, int64_t n, float scale) {
 int launch_scale(float* x, int64_t n, float scale, hipStream_t s) {
     const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipLaunchKernelGGL(scale_kernel, dim3(grid), dim3(256), 0, s, x, n, scale);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(1024) void preprocess_kernel(const float* __restric
 
 int launch_preprocess(const float* raw, const int* n_frames, int max_frames, const float* mean, const float* stdv, float* out, int T, hipStream_t s) {
     hipLaunchKernelGGL(preprocess_kernel, dim3(PP_BLOCKS), dim3(1024), (size_t)max_frames * sizeof(int), s, raw, n_frames, max_frames, mean, stdv, out, T);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }
 
 // ---- batched ragged form: B clips packed back to back in raw [N_total,276] (16-byte aligned), clip b = rows [offsets[b], offsets[b+1])
@@ -160,5 +160,5 @@ int launch_preprocess_batch(const float* raw, int64_t n_total, const int64_t* of
     k = k < 1 ? 1 : (k > 16 ? 16 : k);
     hipLaunchKernelGGL(preprocess_batch_kernel, dim3(k, B), dim3(PPB_THREADS), (size_t)max_frames * sizeof(int), s, raw, n_total, offsets, max_frames,
                        mean, stdv, out, T);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }

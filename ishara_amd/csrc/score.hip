@@ -57,5 +57,5 @@ __global__ __launch_bounds__(SC_WAVES * WAVE) void edit_distance_kernel(const in
 int launch_edit_distance(const int* out_idx, const int* out_len, int B, int T, const int* targets, int L, int* dist, int* tlen, hipStream_t s) {
     if (B == 0) return 0;
     hipLaunchKernelGGL(edit_distance_kernel, dim3((B + SC_WAVES - 1) / SC_WAVES), dim3(SC_WAVES * WAVE), 0, s, out_idx, out_len, T, targets, L, B, dist, tlen);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_rc();
 }

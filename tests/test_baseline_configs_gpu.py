@@ -31,7 +31,7 @@ def test_config4_train_step_vs_oracle(dtype):
 
 
 def test_config2_b64_train_step_vs_oracle():
-    """configs[1]'s model at B = 64 against the fp64 oracle: the batch at which the project conv's weight-gradient GEMM (gemm.hip TnPsa) folds TWO
+    """configs[1]'s model at B = 64 against the fp64 oracle: the batch at which the project conv's weight-gradient GEMM (gemm_tn.hip TnPsa) folds TWO
     samples per M-split — sample boundaries inside the kernel's step loop, parked accumulators, the per-sample statistics of dh4 — and the
     forward GEMM prologues run with split columns.  (B = 2 above exercises one sample per split; tests/test_full_size_gpu.py compares the two
     HIP routes with each other at this batch.)  bf16, dropout on; ~20 s of oracle time."""

@@ -96,7 +96,7 @@ def test_ctc_loss_is_permutation_equivariant(models):
 def test_project_conv_wgrad_per_sample_affine_matches_materialised_operand(models):
     """Conv1DBlock backward, two routes: (a) the project conv's weight-gradient GEMM reads h2 and applies the per-sample affine
     (BatchNorm . ECA gate . drop-path) to its per-sample accumulators, emitting the BatchNorm / ECA statistics of dh4 on the way
-    (gemm.hip TnPsa: 32 M-splits of 2 samples at B = 64); (b) ISHARA_NO_PSA: h4 is written by the forward pass, the GEMM reads it,
+    (gemm_tn.hip TnPsa: 32 M-splits of 2 samples at B = 64); (b) ISHARA_NO_PSA: h4 is written by the forward pass, the GEMM reads it,
     and a separate pass over dh4 and h2 produces the statistics.  Same weights, batch and dropout seed: the logits are bit-identical
     (the forward pass differs only in what it stores) and the gradients agree to bf16 rounding of dh4 / h4."""
     import os

@@ -129,6 +129,32 @@ int ishara_optimizer_step(ishara_model* m, float lr, float weight_decay, ishara_
 int32_t ishara_optimizer_iterations(const ishara_model* m);
 int ishara_optimizer_set_iterations(ishara_model* m, int32_t it);
 
+/* Global-norm gradient clipping, the non-finite guard and microbatch accumulation: three device-side pieces a training loop composes
+ * without a host synchronise (Keras `global_clipnorm=`; torch clip_grad_norm_ + GradScaler's skipped step, integration.py:433,438,750).
+ *
+ * ishara_gradient_stats writes norm, coef and nonfinite of the 16-byte device record `out` (it never writes `skipped`; zero the record once):
+ *   norm      = grad_scale * sqrt(sum_i (double)g[i]^2): every element squared and summed in fp64, in a fixed order (bit-identical from
+ *               run to run; finite for elements up to the fp32 maximum)
+ *   coef      = grad_scale * min(1, clip_norm / (norm + 1e-6)) when clip_norm > 0 (the clip_grad_norm_ formula), else grad_scale
+ *   nonfinite = number of NaN / +-Inf elements, saturating at INT32_MAX
+ * ishara_gradient_accumulate: acc[i] = first ? g[i] : acc[i] + g[i], one fp32 add per element.
+ * g, acc: [n] f32 at 16-byte aligned addresses, 1 <= n <= 2^31 - 1; ws: ishara_grad_stats_workspace_bytes(n) bytes, 8-byte aligned, needs no
+ * initialisation; grad_scale finite and >= 0; clip_norm not NaN (<= 0: no clipping).  `prof` may be NULL: a handle only lends its
+ * profiler (keys grad_stats, 4 n bytes; grad_accumulate, 12 n bytes).  Anything else is refused with a message before any HIP call.
+ *
+ * ishara_optimizer_step_ex is ishara_optimizer_step with a gradient source (`grad`, 16-byte aligned, NULL: the bound grads), a record
+ * (`st`, NULL: none) and the skip switch (needs `st`).  With st the update uses grad[i] * st->coef.  With skip_nonfinite != 0 and
+ * st->nonfinite > 0 the step writes nothing to params or the three slots and adds 1 to st->skipped.  A skipped step still consumes
+ * its iteration number: the counter and the bias corrections live on the host, which cannot see the record without a synchronise; the
+ * weight shadows are refreshed as after any step.  ishara_optimizer_step_ex(m, lr, wd, NULL, NULL, 0, s) is ishara_optimizer_step. */
+typedef struct ishara_grad_stats { float norm; float coef; int32_t nonfinite; int32_t skipped; } ishara_grad_stats;
+int64_t ishara_grad_stats_workspace_bytes(int64_t n);
+int ishara_gradient_stats(ishara_model* prof, const float* g, int64_t n, float grad_scale, float clip_norm, ishara_grad_stats* out, void* ws,
+                          ishara_stream s);
+int ishara_gradient_accumulate(ishara_model* prof, float* acc, const float* g, int64_t n, int32_t first, ishara_stream s);
+int ishara_optimizer_step_ex(ishara_model* m, float lr, float weight_decay, const float* grad, ishara_grad_stats* st, int32_t skip_nonfinite,
+                             ishara_stream s);
+
 /* HIP-event profiler (no reference counterpart: the reference profiles with %%timeit / Keras
  * progress bars).  When enabled, every kernel launch of forward / loss_backward /
  * optimizer_step is bracketed by events on the launch stream; the report is text, one line per

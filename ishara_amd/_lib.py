@@ -43,6 +43,11 @@ class ClipAug(C.Structure):
 LAYOUT_FLAT, LAYOUT_HANDS_LIPS_XY = 0, 1
 
 
+class GradStats(C.Structure):
+    """ishara_grad_stats: the 16-byte device record of ishara_gradient_stats / ishara_optimizer_step_ex (field order of the header)."""
+    _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("nonfinite", C.c_int32), ("skipped", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/ishara_hip.h declares
 _P, _I32, _I64, _U32, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 SIGNATURES = {
@@ -70,6 +75,10 @@ SIGNATURES = {
     "ishara_optimizer_step": (C.c_int, [_P, _F, _F, _P]),
     "ishara_optimizer_iterations": (_I32, [_P]),
     "ishara_optimizer_set_iterations": (C.c_int, [_P, _I32]),
+    "ishara_grad_stats_workspace_bytes": (_I64, [_I64]),
+    "ishara_gradient_stats": (C.c_int, [_P, _P, _I64, _F, _F, _P, _P, _P]),
+    "ishara_gradient_accumulate": (C.c_int, [_P, _P, _P, _I64, _I32, _P]),
+    "ishara_optimizer_step_ex": (C.c_int, [_P, _F, _F, _P, _P, _I32, _P]),
     "ishara_profile_enable": (C.c_int, [_P, _I32]),
     "ishara_profile_report": (C.c_int, [_P, C.c_char_p, _I32]),
     "ishara_greedy_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),

@@ -1012,11 +1012,12 @@ int launch_dwconv_fwd(int dt, int inop, const void* x, const float* w, const flo
 }
 
 // dw[j,c] += sum_{b,t} dy[b,t,c] * in(x)[b, t-padl+j, c] ; dbias[c] += sum dy.
-// grid = (C/128, splits); each workgroup loops over (sample, time-tile) pairs and issues
-// one atomic per (tap, channel) at the end.  thread -> 4 channels x taps {tl, tl+8, tl+16, tl+24}.
+// grid = (C/128, splits); each workgroup loops over (sample, time-tile) pairs and at the end either writes its sums into row
+// blockIdx.y of `part` ([splits][(k+1)*C], dw then dbias, every element written; summed by reduce_slabs in a fixed order, so the
+// gradient repeats bit for bit) or, without `part`, issues one atomic per (tap, channel).  thread -> 4 channels x taps {tl, tl+8, tl+16, tl+24}.
 template <typename T>
 __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                           float* __restrict__ dw, float* __restrict__ dbias,
+                                                           float* __restrict__ dw, float* __restrict__ dbias, float* __restrict__ part,
                                                            int B, int Tn, int C, int k, int padl, int inop) {
     __shared__ __attribute__((aligned(16))) float xt[(DWG_TT + DW_MAXK - 1) * DW_CT];
     __shared__ __attribute__((aligned(16))) float dt_[DWG_TT * DW_CT];
@@ -1114,7 +1115,15 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const T* __restrict__
         }
     }
     const int ch = c0 + cl * 4;
-    if (ch < C) {
+    if (ch < C && part) {
+        float* row = part + (size_t)blockIdx.y * (k + 1) * C;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = tl + 8 * q;
+            if (j < k) *reinterpret_cast<float4*>(row + (size_t)j * C + ch) = make_float4(acc[q][0], acc[q][1], acc[q][2], acc[q][3]);
+        }
+        if (tl == 0) *reinterpret_cast<float4*>(row + (size_t)k * C + ch) = make_float4(accb[0], accb[1], accb[2], accb[3]);
+    } else if (ch < C) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int j = tl + 8 * q;
@@ -1182,10 +1191,15 @@ int launch_dwconv_bwd(int dt, int inop, const void* dy, const void* x, const flo
     } else {
         const int ntt = (T + DWG_TT - 1) / DWG_TT;
         const int cblocks = (C + DW_CT - 1) / DW_CT;
-        int splits = max(1, min(B * ntt, 1024 / cblocks));
+        float* part = g_force_dw_lds ? nullptr : scratch;      // partial rows when the caller gave room for them (DWG_BLOCKS rows), else atomics
+        int splits = max(1, min(B * ntt, (part ? DWG_BLOCKS : 1024) / cblocks));
         dim3 grid(cblocks, splits);
-        if (dt == DT_BF16) hipLaunchKernelGGL(dwconv_wgrad_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)x, dw, dbias, B, T, C, k, padl, inop);
-        else hipLaunchKernelGGL(dwconv_wgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, dw, dbias, B, T, C, k, padl, inop);
+        if (dt == DT_BF16) hipLaunchKernelGGL(dwconv_wgrad_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)x, dw, dbias, part, B, T, C, k, padl, inop);
+        else hipLaunchKernelGGL(dwconv_wgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, dw, dbias, part, B, T, C, k, padl, inop);
+        if (part) {
+            launch_reduce_slabs(part, dw, k * C, splits, (size_t)(k + 1) * C, s);
+            if (dbias) launch_reduce_slabs(part + (size_t)k * C, dbias, C, splits, (size_t)(k + 1) * C, s);
+        }
     }
     return launch_rc();
 }

@@ -290,4 +290,15 @@ int launch_clip_batch(const float* raw, const ishara_clip_aug* clips, int B, int
 struct RAdamArgs { float lr, wd, beta1, beta2, eps, c1, c2, r_t; int rect; int sync; float slow_step; };
 int launch_radam_lookahead(float* theta, const float* grad, float* m, float* v, float* slow, int64_t n,
                            RAdamArgs a, hipStream_t s);
+// the same update reading the device record of launch_grad_stats: g = grad[i] * st->coef; skip != 0 and st->nonfinite > 0: nothing is
+// written but st->skipped += 1
+int launch_radam_lookahead_ex(float* theta, const float* grad, float* m, float* v, float* slow, int64_t n,
+                              RAdamArgs a, ishara_grad_stats* st, int skip, hipStream_t s);
 int launch_scale(float* x, int64_t n, float scale, hipStream_t s);
+
+// ---- gradient statistics and accumulation (grad_ops.hip) ------------------------------------
+// g, acc [n] f32 at 16-byte aligned addresses, 1 <= n <= 2^31 - 1; ws: grad_stats_workspace_bytes(n) bytes, 8-byte aligned, needs no
+// initialisation (every row read was written by the same call)
+int64_t grad_stats_workspace_bytes(int64_t n);
+int launch_grad_stats(const float* g, int64_t n, float grad_scale, float clip_norm, ishara_grad_stats* out, void* ws, hipStream_t s);
+int launch_grad_accumulate(float* acc, const float* g, int64_t n, int first, hipStream_t s);

@@ -4,6 +4,9 @@
 // squeezeformer_r4.hip; the stand-alone and operator entry points: api_ops.hip.  Everything is launched on the caller's stream.
 #include "model_types.h"
 #include <algorithm>
+#include <cmath>
+#include <initializer_list>
+#include <utility>
 #include <stdlib.h>
 
 // ------------------------------------------------------------------ error string
@@ -349,8 +352,8 @@ extern "C" int ishara_grad_buckets_enable(ishara_model* m) {
 }
 
 // ------------------------------------------------------------------ optimizer
-extern "C" int ishara_optimizer_step(ishara_model* m, float lr, float weight_decay, ishara_stream st) {
-    if (!m->om || !m->ov || !m->oslow || !m->grads) { ishara_set_error("ishara_optimizer_step: optimizer slots are not bound"); return -1; }
+static int optimizer_step(ishara_model* m, const char* who, float lr, float weight_decay, const float* grad, ishara_grad_stats* rec, int skip, ishara_stream st) {
+    if (!m->om || !m->ov || !m->oslow || !m->grads) { ishara_set_error("%s: optimizer slots are not bound", who); return -1; }
     hipStream_t s = (hipStream_t)st;
     m->opt_iter += 1;
     const double t = (double)m->opt_iter, b1 = 0.9, b2 = 0.999;
@@ -365,8 +368,59 @@ extern "C" int ishara_optimizer_step(ishara_model* m, float lr, float weight_dec
     a.sync = (m->opt_iter % 5 == 0) ? 1 : 0;   // Lookahead(sync_period=5, slow_step_size=0.5) (c7:69)
     a.slow_step = 0.5f;
     m->s = s;
-    CKP(m, "radam_lookahead", 28.0 * m->n_train, 0, launch_radam_lookahead(m->params, m->grads, m->om, m->ov, m->oslow, m->n_train, a, s));
-    CKP(m, "weight_shadows", 0, 0, ishara_sync_weights(m, st));
+    if (!grad) grad = m->grads;
+    if (rec) CKP(m, "radam_lookahead", 28.0 * m->n_train, 0, launch_radam_lookahead_ex(m->params, grad, m->om, m->ov, m->oslow, m->n_train, a, rec, skip, s));
+    else CKP(m, "radam_lookahead", 28.0 * m->n_train, 0, launch_radam_lookahead(m->params, grad, m->om, m->ov, m->oslow, m->n_train, a, s));
+    CKP(m, "weight_shadows", 0, 0, ishara_sync_weights(m, st));      // also after a skipped step: the host cannot know it was one
+    return 0;
+}
+extern "C" int ishara_optimizer_step(ishara_model* m, float lr, float weight_decay, ishara_stream st) {
+    return optimizer_step(m, "ishara_optimizer_step", lr, weight_decay, nullptr, nullptr, 0, st);
+}
+extern "C" int ishara_optimizer_step_ex(ishara_model* m, float lr, float weight_decay, const float* grad, ishara_grad_stats* rec, int32_t skip_nonfinite,
+                                        ishara_stream st) {
+    const char* who = "ishara_optimizer_step_ex";
+    if (!m) { ishara_set_error("%s: null handle", who); return -1; }
+    if ((uintptr_t)grad % 16 != 0) { ishara_set_error("%s: misaligned grad: %p is not on a 16-byte boundary", who, (const void*)grad); return -1; }
+    if ((uintptr_t)rec % 4 != 0) { ishara_set_error("%s: misaligned st: %p is not on a 4-byte boundary", who, (void*)rec); return -1; }
+    if (skip_nonfinite && !rec) { ishara_set_error("%s: skip_nonfinite needs the record: null st", who); return -1; }
+    return optimizer_step(m, who, lr, weight_decay, grad, rec, skip_nonfinite != 0, st);
+}
+
+// ------------------------------------------------------------------ gradient statistics / accumulation (grad_ops.hip)
+static bool grad_vec_ok(const char* who, std::initializer_list<std::pair<const char*, const void*>> ps, int64_t n) {
+    for (auto& p : ps) if (!p.second) { ishara_set_error("%s: null %s", who, p.first); return false; }
+    for (auto& p : ps) if ((uintptr_t)p.second % 16 != 0) { ishara_set_error("%s: misaligned %s: %p is not on a 16-byte boundary", who, p.first, p.second); return false; }
+    if (n < 1 || n > 2147483647LL) { ishara_set_error("%s: n=%lld is outside 1..2147483647", who, (long long)n); return false; }
+    return true;
+}
+extern "C" int64_t ishara_grad_stats_workspace_bytes(int64_t n) {
+    if (n < 1 || n > 2147483647LL) { ishara_set_error("ishara_grad_stats_workspace_bytes: n=%lld is outside 1..2147483647", (long long)n); return -1; }
+    return grad_stats_workspace_bytes(n);
+}
+extern "C" int ishara_gradient_stats(ishara_model* prof, const float* g, int64_t n, float grad_scale, float clip_norm, ishara_grad_stats* out, void* ws,
+                                     ishara_stream st) {
+    const char* who = "ishara_gradient_stats";
+    if (!grad_vec_ok(who, {{"g", g}}, n)) return -1;
+    if (!out || !ws) { ishara_set_error("%s: null %s", who, !out ? "out" : "ws"); return -1; }
+    if ((uintptr_t)out % 4 != 0) { ishara_set_error("%s: misaligned out: %p is not on a 4-byte boundary", who, (void*)out); return -1; }
+    if ((uintptr_t)ws % 8 != 0) { ishara_set_error("%s: misaligned ws: %p is not on an 8-byte boundary", who, ws); return -1; }
+    if (!(grad_scale >= 0.f) || std::isinf(grad_scale)) { ishara_set_error("%s: grad_scale %g is not a finite value >= 0", who, (double)grad_scale); return -1; }
+    if (std::isnan(clip_norm)) { ishara_set_error("%s: clip_norm is NaN", who); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    if (!prof) return launch_grad_stats(g, n, grad_scale, clip_norm, out, ws, s);
+    prof->s = s;
+    CKP(prof, "grad_stats", 4.0 * n, 0, launch_grad_stats(g, n, grad_scale, clip_norm, out, ws, s));
+    return 0;
+}
+extern "C" int ishara_gradient_accumulate(ishara_model* prof, float* acc, const float* g, int64_t n, int32_t first, ishara_stream st) {
+    const char* who = "ishara_gradient_accumulate";
+    if (!grad_vec_ok(who, {{"acc", acc}, {"g", g}}, n)) return -1;
+    if (acc == g) { ishara_set_error("%s: acc and g are the same buffer", who); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    if (!prof) return launch_grad_accumulate(acc, g, n, first != 0, s);
+    prof->s = s;
+    CKP(prof, "grad_accumulate", 12.0 * n, 0, launch_grad_accumulate(acc, g, n, first != 0, s));
     return 0;
 }
 extern "C" int32_t ishara_optimizer_iterations(const ishara_model* m) { return m->opt_iter; }

@@ -109,3 +109,26 @@ class CallbackEval:
         self.last_score = mean_score([p for p, _ in pairs], [t for _, t in pairs])
         if logs is not None:
             logs["val_levenshtein"] = self.last_score
+
+
+class TrainStateCheckpoint:
+    """Keras-style callback: `model.save_state(path)` at the end of every `every_epochs`-th epoch, so that a preempted run resumes with
+    `load_state(path)` and `fit(..., initial_epoch=...)`.  `path` may hold `{epoch}` (1-based, as Keras' ModelCheckpoint formats it).  The
+    epoch must end on a whole accumulation cycle (save_state refuses in the middle of one)."""
+
+    def __init__(self, path: str, every_epochs: int = 1):
+        if every_epochs < 1:
+            raise ValueError("every_epochs must be >= 1")
+        self.path, self.every_epochs = path, int(every_epochs)
+        self.model = None
+        self.last_path: Optional[str] = None
+
+    def set_model(self, model): self.model = model
+    def on_train_begin(self, logs=None): pass
+    def on_train_end(self, logs=None): pass
+    def on_epoch_begin(self, epoch, logs=None): pass
+    def on_train_batch_end(self, batch, logs=None): pass
+
+    def on_epoch_end(self, epoch, logs=None):
+        if (epoch + 1) % self.every_epochs == 0:
+            self.last_path = self.model.save_state(self.path.format(epoch=epoch + 1))

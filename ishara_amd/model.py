@@ -40,9 +40,15 @@ class _Scalar:
 
 class Optimizer:
     """Lookahead(RectifiedAdam(sma_threshold=4), sync_period=5) — c7:68-69.  The update itself is
-    one fused HIP kernel over the flat parameter buffer (csrc/optimizer.hip)."""
+    one fused HIP kernel over the flat parameter buffer (csrc/optimizer.hip).
 
-    def __init__(self, learning_rate=1e-3, weight_decay=0.0):
+    `global_clipnorm` (Keras' argument; torch's clip_grad_norm_(params, max_norm)): the gradient of a step is scaled so that its global L2 norm
+    is at most this value.  `skip_nonfinite` (what torch's GradScaler does for an overflowed step): a step whose gradient holds a NaN or Inf
+    leaves parameters and optimizer slots untouched.  `accumulate_steps` = k: `train_on_batch` sums the gradients of k microbatches and
+    applies their mean as one step.  All three act on the device (csrc/grad_ops.hip) without a host synchronise; at their defaults the
+    training step is the code path it was without them."""
+
+    def __init__(self, learning_rate=1e-3, weight_decay=0.0, global_clipnorm=None, skip_nonfinite=False, accumulate_steps=1):
         self._lr = _Scalar(learning_rate)
         # The reference assigns `.weight_decay` on the Lookahead wrapper (c11:64), which is not
         # one of its hyper-parameters, so RectifiedAdam keeps weight_decay=0 (SURVEY §8a row 10).
@@ -50,6 +56,18 @@ class Optimizer:
         self._wd = _Scalar(weight_decay)
         self.apply_weight_decay = False
         self.iterations = 0
+        self.global_clipnorm = global_clipnorm
+        self.skip_nonfinite = skip_nonfinite
+        self.accumulate_steps = accumulate_steps
+
+    def train_options(self):
+        """(accumulate_steps, clip norm or 0.0, skip_nonfinite), checked"""
+        k, clip = self.accumulate_steps, self.global_clipnorm
+        if not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"accumulate_steps must be an integer >= 1, got {k!r}")
+        if clip is not None and not (float(clip) > 0 and math.isfinite(float(clip))):
+            raise ValueError(f"global_clipnorm must be a finite value > 0 or None, got {clip!r}")
+        return int(k), 0.0 if clip is None else float(clip), bool(self.skip_nonfinite)
 
     @property
     def learning_rate(self): return self._lr
@@ -129,6 +147,11 @@ class Model(Handle):
         self.stop_training = False
         self._step_seed = seed * 7919 + 17
         self._steps = 0
+        self._micro = 0            # microbatches already summed into the accumulator of the running cycle
+        self._grad_acc = None      # [n_train] f32, allocated by the first accumulating cycle
+        self._gstats = None        # the 16-byte ishara_grad_stats record (4 x int32 storage) and the workspace of its kernel
+        self._gstats_ws = None
+        self._skipped_seen = 0
         if device is not None:
             self._to_device(device, seed)
 
@@ -253,6 +276,16 @@ class Model(Handle):
         return self._loss_buf, logits
 
     def apply_gradients(self):
+        """The optimizer step on `grads`.  With optimizer.global_clipnorm or .skip_nonfinite set: the statistics of `grads`, then the step
+        that reads them (no all-reduce here: train_on_batch places it in front of the statistics).  Accumulation is train_on_batch's."""
+        k, clip, skip = self.optimizer.train_options()
+        if k > 1 or self._micro:
+            raise ValueError("apply_gradients steps on one gradient; with accumulate_steps > 1 drive the cycle through train_on_batch")
+        if clip > 0.0 or skip:
+            src = self.grads[:self.n_train]
+            self._launch_grad_stats(src, 1.0, clip)
+            self._apply_gradients_ex(src, skip)
+            return
         wd = float(self.optimizer.weight_decay) if self.optimizer.apply_weight_decay else 0.0
         _lib.check(self._lib.ishara_optimizer_step(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _stream()),
                    "ishara_optimizer_step")
@@ -262,8 +295,19 @@ class Model(Handle):
     def train_on_batch(self, x, y, seed: Optional[int] = None, allreduce: bool = True) -> torch.Tensor:
         """One Keras train_step (c12): forward, CTC, backward, [RCCL grad all-reduce], update.
         Returns the device loss tensor (no host sync).  `allreduce=False` skips the gradient exchange (bench.py's diagnostic
-        of the exposed all-reduce time; replicas diverge — never for training)."""
+        of the exposed all-reduce time; replicas diverge — never for training).
+
+        With `optimizer.global_clipnorm`, `.skip_nonfinite` or `.accumulate_steps` > 1 set, a call is one microbatch of a cycle of
+        k = accumulate_steps: forward, CTC, backward (loss_scale 1/world), the gradient added into an accumulator (k > 1); the k-th call then
+        all-reduces the accumulator once, takes the statistics of the summed gradient with grad_scale = 1/k (after the all-reduce, so
+        every rank sees the same norm) and steps the optimizer on gradient * coef.  `_steps` and `optimizer.iterations` advance once per
+        cycle; microbatch j draws its dropout masks from seed index `_steps * k + j`.  The bucketed all-reduce overlap
+        (parallel.overlap_enabled) applies only when accumulate_steps == 1; otherwise the accumulator is reduced in one piece.  Still no
+        host sync: `grad_stats()` reads the record when asked."""
         from . import parallel
+        k, clip, skip = self.optimizer.train_options()
+        if k > 1 or clip > 0.0 or skip or self._micro:
+            return self._train_microbatch(x, y, seed, allreduce, k, clip, skip)
         world = parallel.world_size()
         if not allreduce:
             loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world)
@@ -284,6 +328,100 @@ class Model(Handle):
         self.apply_gradients()
         return loss
 
+    def _train_microbatch(self, x, y, seed, allreduce, k, clip, skip) -> torch.Tensor:
+        """microbatch `_micro` of a cycle of k; the k-th one ends the cycle with all-reduce, statistics and the step"""
+        from . import parallel
+        world = parallel.world_size()
+        if self._micro >= k:
+            raise ValueError(f"accumulate_steps was lowered to {k} in the middle of a cycle ({self._micro} microbatches summed)")
+        overlap = allreduce and k == 1 and world > 1 and parallel.overlap_enabled()
+        if overlap:
+            self.enable_grad_buckets()
+        if seed is None:
+            seed = (self._step_seed + 0x9E3779B1 * (self._steps * k + self._micro)) & 0xFFFFFFFF
+            if world > 1:
+                seed = (seed ^ (parallel.rank() * 0x85EBCA6B)) & 0xFFFFFFFF
+        loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world)
+        src = self.grads[:self.n_train]
+        if k > 1:
+            if self._grad_acc is None:
+                self._grad_acc = torch.empty(self.n_train, dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.ishara_gradient_accumulate(self._h, _lib.ptr(self._grad_acc), _lib.ptr(src), self.n_train,
+                                                            1 if self._micro == 0 else 0, _stream()), "ishara_gradient_accumulate")
+            self._micro += 1
+            if self._micro < k:
+                return loss
+            src = self._grad_acc
+        if overlap:
+            parallel.allreduce_buckets_(self)
+        elif allreduce and world > 1:
+            parallel.allreduce_sum_(src)
+        self._launch_grad_stats(src, 1.0 / k, clip)
+        self._apply_gradients_ex(src, skip)
+        self._micro = 0
+        return loss
+
+    def _launch_grad_stats(self, src: torch.Tensor, grad_scale: float, clip: float):
+        """norm / coef / nonfinite of `src` into the device record (allocated, zeroed, on first use)"""
+        if self._gstats is None:
+            self._gstats = torch.zeros(4, dtype=torch.int32, device=self.device)
+            self._gstats_ws = torch.empty(int(self._lib.ishara_grad_stats_workspace_bytes(self.n_train)), dtype=torch.uint8, device=self.device)
+        _lib.check(self._lib.ishara_gradient_stats(self._h, _lib.ptr(src), src.numel(), C.c_float(grad_scale), C.c_float(clip),
+                                                   _lib.ptr(self._gstats), _lib.ptr(self._gstats_ws), _stream()), "ishara_gradient_stats")
+
+    def _apply_gradients_ex(self, src: torch.Tensor, skip: bool):
+        wd = float(self.optimizer.weight_decay) if self.optimizer.apply_weight_decay else 0.0
+        _lib.check(self._lib.ishara_optimizer_step_ex(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _lib.ptr(src),
+                                                      _lib.ptr(self._gstats), 1 if skip else 0, _stream()), "ishara_optimizer_step_ex")
+        self.optimizer.iterations += 1
+        self._steps += 1
+
+    def grad_stats(self) -> Dict[str, float]:
+        """{norm, coef, nonfinite, skipped} of the last cycle that ran with clipping, skipping or accumulation: the global L2 norm of the
+        (mean) gradient, the factor the step applied to the summed gradient, the count of NaN / Inf elements, and the number of steps
+        skipped so far.  This read is the only host synchronise of the feature."""
+        if self._gstats is None:
+            raise _lib.IsharaError("grad_stats: no training step has run with global_clipnorm, skip_nonfinite or accumulate_steps set")
+        raw = self._gstats.cpu().numpy()
+        f = raw.view(np.float32)
+        return dict(norm=float(f[0]), coef=float(f[1]), nonfinite=int(raw[2]), skipped=int(raw[3]))
+
+    # ------------------------------------------------------------------ resumable state
+    def save_state(self, path: str) -> str:
+        """Everything a preempted run needs to go on as if it had not stopped (train_state.py): parameters with the BatchNorm moving
+        statistics, the optimizer slots m / v / slow, the iteration and dropout-seed counters, learning rate, weight decay and the
+        clipping / skipping / accumulation settings -> `path` (.npz).  Refused in the middle of an accumulation cycle: the accumulator
+        is not part of the state."""
+        from . import train_state as TS
+        if self._micro:
+            raise ValueError(f"save_state: in the middle of an accumulation cycle ({self._micro} of {self.optimizer.accumulate_steps} microbatches); "
+                             "save after the cycle's last train_on_batch")
+        o = self.optimizer
+        skipped = int(self._gstats.cpu()[3]) if self._gstats is not None else 0
+        st = TS.pack_state(self.entries, *(t.detach().cpu().numpy() for t in (self.params, self.opt_m, self.opt_v, self.opt_slow)),
+                           iterations=o.iterations, steps=self._steps, step_seed=self._step_seed, learning_rate=float(o.learning_rate),
+                           weight_decay=float(o.weight_decay), apply_weight_decay=o.apply_weight_decay, global_clipnorm=o.global_clipnorm,
+                           skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped)
+        return TS.save_state_file(path, st)
+
+    def load_state(self, path: str):
+        """Restores what save_state wrote into this model (same architecture: the entry list is checked)."""
+        from . import train_state as TS
+        st = TS.load_state_file(path, self.entries)
+        for t, k in ((self.params, "params"), (self.opt_m, "opt_m"), (self.opt_v, "opt_v"), (self.opt_slow, "opt_slow")):
+            t.copy_(torch.from_numpy(st[k]))
+        o = self.optimizer
+        o.iterations, self._steps, self._step_seed, self._micro = st["iterations"], st["steps"], st["step_seed"], 0
+        o.learning_rate, o.weight_decay, o.apply_weight_decay = st["learning_rate"], st["weight_decay"], st["apply_weight_decay"]
+        o.global_clipnorm, o.skip_nonfinite, o.accumulate_steps = st["global_clipnorm"], st["skip_nonfinite"], st["accumulate_steps"]
+        if self._gstats is None:
+            self._gstats = torch.zeros(4, dtype=torch.int32, device=self.device)
+            self._gstats_ws = torch.empty(int(self._lib.ishara_grad_stats_workspace_bytes(self.n_train)), dtype=torch.uint8, device=self.device)
+        self._gstats[3] = st["skipped"]
+        self._skipped_seen = st["skipped"]
+        _lib.check(self._lib.ishara_optimizer_set_iterations(self._h, st["iterations"]), "ishara_optimizer_set_iterations")
+        _lib.check(self._lib.ishara_sync_weights(self._h, _stream()), "ishara_sync_weights")
+
     # ---- gradient buckets (SURVEY 8e: all-reduce overlapped with the backward pass; opt-in, see parallel.overlap_enabled)
     def grad_buckets(self) -> List[Tuple[int, int]]:
         """(offset, count) ranges of the flat gradient in the order the backward pass completes them."""
@@ -302,16 +440,19 @@ class Model(Handle):
         _lib.check(self._lib.ishara_grad_bucket_wait(self._h, i, C.c_void_p(side_stream.cuda_stream)), "ishara_grad_bucket_wait")
 
     def fit(self, train_dataset: Iterable, validation_data: Optional[Iterable] = None, epochs: int = 1,
-            callbacks: Sequence[Callback] = (), steps_per_epoch: Optional[int] = None, verbose: int = 1) -> History:
+            callbacks: Sequence[Callback] = (), steps_per_epoch: Optional[int] = None, verbose: int = 1, initial_epoch: int = 0) -> History:
         """model.fit(train_dataset, validation_data=, epochs=, callbacks=[...]) — c12:1-10.
-        Datasets are re-iterable objects yielding (x [B,T,F] float32, y [B,64] int64)."""
+        Datasets are re-iterable objects yielding (x [B,T,F] float32, y [B,64] int64).  `initial_epoch` (Keras): the epoch to start
+        from when a run is resumed (after load_state); epochs initial_epoch .. epochs - 1 run.  With optimizer.global_clipnorm or
+        .skip_nonfinite the epoch logs gain `grad_norm` (the last cycle's) and `skipped_steps` (in this epoch): one device read per epoch.
+        With accumulate_steps = k every batch is a microbatch; an epoch whose batch count is no multiple of k leaves its last cycle open."""
         hist = History()
         for cb in callbacks:
             if hasattr(cb, "set_model"): cb.set_model(self)
             elif not getattr(cb, "model", None): cb.model = self
         for cb in callbacks: getattr(cb, "on_train_begin", lambda logs=None: None)()
         self.stop_training = False
-        for epoch in range(epochs):
+        for epoch in range(initial_epoch, epochs):
             logs: Dict[str, float] = {}
             for cb in callbacks: cb.on_epoch_begin(epoch, logs)
             tot = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -324,6 +465,11 @@ class Model(Handle):
                 for cb in callbacks: getattr(cb, "on_train_batch_end", lambda b, logs=None: None)(bi, logs)
             logs["loss"] = float(tot.item()) / max(n, 1)
             logs["lr"] = float(self.optimizer.learning_rate)
+            if (self.optimizer.global_clipnorm is not None or self.optimizer.skip_nonfinite) and self._gstats is not None:
+                gs = self.grad_stats()
+                logs["grad_norm"] = gs["norm"]
+                logs["skipped_steps"] = gs["skipped"] - self._skipped_seen
+                self._skipped_seen = gs["skipped"]
             if validation_data is not None:
                 logs["val_loss"] = self.evaluate(validation_data)
             for cb in callbacks: cb.on_epoch_end(epoch, logs)

@@ -1,0 +1,187 @@
+"""Training-loop state around the flat fp32 gradient: host references of the device kernels in csrc/grad_ops.hip and of the clipped /
+skipped optimizer step (numpy, in the manner of ctc_beam.prefix_beam_search and ctc_align.viterbi_align), and the resumable-state file
+of `Model.save_state` / `load_state` (pack / unpack / validate on numpy arrays: nothing here needs a GPU).
+
+Semantics (include/ishara_hip.h):
+  norm      = grad_scale * sqrt(sum_i g[i]^2), every square and the sum in fp64, stored as fp32
+  coef      = grad_scale * min(1, clip_norm / (norm + 1e-6)) when clip_norm > 0 (torch.nn.utils.clip_grad_norm_), else grad_scale
+  nonfinite = number of NaN / +-Inf elements (saturating at INT32_MAX)
+  the step  = Lookahead(RectifiedAdam) on g * coef; with skip_nonfinite and nonfinite > 0 it writes nothing, counts itself in `skipped`
+              and still consumes its iteration number (the counter lives on the host, which does not read the device record).
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+FORMAT_VERSION = 1
+GRAD_WG_SPAN = 1024       # elements one workgroup covers per grid-stride round (csrc/grad_ops.hip)
+GRAD_GRID_CAP = 2048      # most workgroups of a launch (csrc/grad_ops.hip)
+INT32_MAX = 2 ** 31 - 1
+
+ARRAYS = ("params", "opt_m", "opt_v", "opt_slow")
+SCALARS = ("format_version", "iterations", "steps", "step_seed", "learning_rate", "weight_decay", "apply_weight_decay",
+           "global_clipnorm", "skip_nonfinite", "accumulate_steps", "skipped")
+ENTRY_KEYS = ("entry_names", "entry_shapes", "entry_offsets", "entry_trainable")
+
+
+def grad_stats_workspace_bytes(n: int) -> int:
+    """what ishara_grad_stats_workspace_bytes(n) returns: one 16-byte row per workgroup of the launch"""
+    return 16 * min(GRAD_GRID_CAP, -(-int(n) // GRAD_WG_SPAN))
+
+
+def grad_stats_reference(g: Union[np.ndarray, Sequence[np.ndarray]], grad_scale: float = 1.0, clip_norm: float = 0.0) -> Dict[str, float]:
+    """{norm, coef, nonfinite} of the gradient `g` (one array, or a list of arrays taken as one vector) as ishara_gradient_stats defines them.
+    The sum of squares is taken in fp64; norm and coef are rounded as the kernel rounds them (fp32 store, fp32 coef arithmetic)."""
+    parts = [g] if isinstance(g, np.ndarray) else list(g)
+    ss, bad = 0.0, 0
+    for p in parts:
+        p = np.asarray(p, dtype=np.float32).reshape(-1)
+        d = p.astype(np.float64)
+        with np.errstate(over="ignore", invalid="ignore"):
+            ss += float(np.sum(d * d))
+        bad += int(np.count_nonzero(~np.isfinite(p)))
+    gs = np.float32(grad_scale)
+    with np.errstate(over="ignore", invalid="ignore"):
+        norm = np.float32(float(gs) * math.sqrt(ss)) if not math.isnan(ss) else np.float32(np.nan)
+        coef = gs
+        if clip_norm > 0:
+            coef = gs * min(np.float32(1.0), np.float32(clip_norm) / (norm + np.float32(1e-6)))
+    return dict(norm=float(norm), coef=float(np.float32(coef)), nonfinite=min(bad, INT32_MAX))
+
+
+def radam_coeffs(step: int, beta1: float = 0.9, beta2: float = 0.999, sma_threshold: float = 4.0) -> dict:
+    """the host-side scalars of step `step` (1-based): bias corrections, rectification term and whether it applies"""
+    b1p, b2p = beta1 ** step, beta2 ** step
+    sma_inf = 2.0 / (1.0 - beta2) - 1.0
+    sma_t = sma_inf - 2.0 * step * b2p / (1.0 - b2p)
+    rect = sma_t >= sma_threshold
+    r_t = math.sqrt(max((sma_t - 4.0) / (sma_inf - 4.0) * (sma_t - 2.0) / (sma_inf - 2.0) * sma_inf / sma_t, 0.0)) if rect else 0.0
+    return dict(c1=1.0 / (1.0 - b1p), c2=1.0 / (1.0 - b2p), r_t=r_t, rect=bool(rect))
+
+
+def step_state_init(theta: np.ndarray) -> dict:
+    """{m, v, slow, step, skipped} before the first step: zero moments, the Lookahead slow weights at theta_0"""
+    return dict(m=np.zeros_like(theta), v=np.zeros_like(theta), slow=theta.copy(), step=0, skipped=0)
+
+
+def clipped_step_reference(theta: np.ndarray, grad: np.ndarray, state: dict, lr: float, coef: float = 1.0, nonfinite: int = 0,
+                           skip_nonfinite: bool = False, weight_decay: float = 0.0, beta1: float = 0.9, beta2: float = 0.999,
+                           eps: float = 1e-7, sync_period: int = 5, slow_step: float = 0.5) -> np.ndarray:
+    """One ishara_optimizer_step_ex in numpy fp32: Lookahead(RectifiedAdam(sma_threshold=4), sync_period=5) on grad * coef -> the new theta;
+    `state` (step_state_init) is updated in place.  With skip_nonfinite and nonfinite > 0: theta and the slots stay, state["skipped"] and
+    state["step"] advance."""
+    state["step"] += 1
+    if skip_nonfinite and nonfinite > 0:
+        state["skipped"] += 1
+        return theta
+    c = radam_coeffs(state["step"], beta1, beta2)
+    g = grad * np.float32(coef)
+    state["m"] = beta1 * state["m"] + (1 - beta1) * g
+    state["v"] = beta2 * state["v"] + (1 - beta2) * g * g
+    m_hat = state["m"] * np.float32(c["c1"])
+    if c["rect"]:
+        upd = np.float32(c["r_t"]) * m_hat / (np.sqrt(state["v"] * np.float32(c["c2"])) + np.float32(eps))
+    else:
+        upd = m_hat
+    if weight_decay:
+        upd = upd + np.float32(weight_decay) * theta
+    theta = theta - np.float32(lr) * upd
+    if state["step"] % sync_period == 0:
+        state["slow"] = state["slow"] + np.float32(slow_step) * (theta - state["slow"])
+        theta = state["slow"].copy()
+    return theta
+
+
+# ---------------------------------------------------------------------------------- the state file
+class TrainStateError(ValueError):
+    pass
+
+
+def _entry_arrays(entries: Iterable[Tuple[str, tuple, int, bool]]) -> Dict[str, np.ndarray]:
+    entries = list(entries)
+    shapes = np.full((len(entries), 2), -1, dtype=np.int64)
+    for i, (_, s, _, _) in enumerate(entries):
+        shapes[i, :len(s)] = s
+    return dict(entry_names=np.array([n for n, _, _, _ in entries], dtype=np.str_), entry_shapes=shapes,
+                entry_offsets=np.array([o for _, _, o, _ in entries], dtype=np.int64),
+                entry_trainable=np.array([bool(t) for _, _, _, t in entries], dtype=np.bool_))
+
+
+def pack_state(entries, params: np.ndarray, opt_m: np.ndarray, opt_v: np.ndarray, opt_slow: np.ndarray, *, iterations: int, steps: int,
+               step_seed: int, learning_rate: float, weight_decay: float, apply_weight_decay: bool = False,
+               global_clipnorm: Optional[float] = None, skip_nonfinite: bool = False, accumulate_steps: int = 1, skipped: int = 0
+               ) -> Dict[str, np.ndarray]:
+    """The arrays of one state file (np.savez(path, **pack_state(...))): the flat fp32 `params` (BatchNorm moving statistics included), the
+    three optimizer slots, the counters, the hyper-parameters, the format version and the entry list the buffers were laid out by."""
+    out = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in zip(ARRAYS, (params, opt_m, opt_v, opt_slow))}
+    out.update(_entry_arrays(entries))
+    out.update(format_version=np.int64(FORMAT_VERSION), iterations=np.int64(iterations), steps=np.int64(steps), step_seed=np.int64(step_seed),
+               learning_rate=np.float64(learning_rate), weight_decay=np.float64(weight_decay), apply_weight_decay=np.bool_(apply_weight_decay),
+               global_clipnorm=np.float64(0.0 if global_clipnorm is None else global_clipnorm), skip_nonfinite=np.bool_(skip_nonfinite),
+               accumulate_steps=np.int64(accumulate_steps), skipped=np.int64(skipped))
+    validate_state(out, entries)
+    return out
+
+
+def validate_state(z, entries) -> None:
+    """Refuses, with a message, a state whose version is unknown, that lacks an array, or whose entry list or buffer sizes are not the
+    model's (`entries` = [(name, shape, offset, trainable)]).  `z`: a mapping of name -> array (a dict, or an open .npz)."""
+    keys = set(z.files) if hasattr(z, "files") else set(z)
+    if "format_version" not in keys:
+        raise TrainStateError("train state: missing entry 'format_version' (not a state file of save_state?)")
+    ver = int(z["format_version"])
+    if ver != FORMAT_VERSION:
+        raise TrainStateError(f"train state: unknown format version {ver} (this build reads version {FORMAT_VERSION})")
+    for k in ARRAYS + SCALARS + ENTRY_KEYS:
+        if k not in keys:
+            raise TrainStateError(f"train state: missing entry '{k}'")
+    entries = list(entries)
+    want = _entry_arrays(entries)
+    names, shapes = [str(n) for n in z["entry_names"]], np.asarray(z["entry_shapes"])
+    if len(names) != len(entries):
+        raise TrainStateError(f"train state: {len(names)} parameter entries, the model has {len(entries)}")
+    for i, (n, s, o, t) in enumerate(entries):
+        if names[i] != n:
+            raise TrainStateError(f"train state: entry {i} is '{names[i]}', the model has '{n}' there")
+        got = tuple(int(v) for v in shapes[i] if v >= 0)
+        if got != tuple(s):
+            raise TrainStateError(f"train state: wrong shape of '{n}': {got}, the model has {tuple(s)}")
+    if not np.array_equal(z["entry_offsets"], want["entry_offsets"]) or not np.array_equal(z["entry_trainable"], want["entry_trainable"]):
+        raise TrainStateError("train state: the parameter layout (offsets / trainable flags) is not the model's")
+    n_total = sum(int(np.prod(s)) for _, s, _, _ in entries)
+    n_train = sum(int(np.prod(s)) for _, s, _, t in entries if t)
+    for k, n in zip(ARRAYS, (n_total, n_train, n_train, n_train)):
+        a = z[k]
+        if a.dtype != np.float32 or a.shape != (n,):
+            raise TrainStateError(f"train state: wrong shape of '{k}': {a.dtype}{tuple(a.shape)}, expected float32({n},)")
+    if int(z["accumulate_steps"]) < 1 or int(z["iterations"]) < 0 or int(z["steps"]) < 0:
+        raise TrainStateError("train state: a counter is out of range")
+
+
+def unpack_state(z, entries) -> dict:
+    """validate_state, then plain Python values: the four arrays (float32, flat) and the scalars; global_clipnorm is None when off"""
+    validate_state(z, entries)
+    out = {k: np.array(z[k], dtype=np.float32) for k in ARRAYS}
+    for k in ("iterations", "steps", "step_seed", "accumulate_steps", "skipped"):
+        out[k] = int(z[k])
+    for k in ("learning_rate", "weight_decay"):
+        out[k] = float(z[k])
+    for k in ("apply_weight_decay", "skip_nonfinite"):
+        out[k] = bool(z[k])
+    clip = float(z["global_clipnorm"])
+    out["global_clipnorm"] = clip if clip > 0 else None
+    return out
+
+
+def save_state_file(path: str, state: Dict[str, np.ndarray]) -> str:
+    path = path if path.endswith(".npz") else path + ".npz"
+    np.savez(path, **state)
+    return path
+
+
+def load_state_file(path: str, entries) -> dict:
+    with np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False) as z:
+        return unpack_state(z, entries)

@@ -75,7 +75,8 @@ extern "C" int ishara_dropout_mask(uint32_t seed, uint32_t site, int32_t rows, i
 
 static int g_dbg_epi = 0;
 // bit 0: 1 register-staged NT kernel / 0 LDS-DMA NT kernel; bit 1: 1 register-transposing TN kernel; bit 2: 1 LDS-tiled dwconv; bit 3: 1 LDS-DMA 64x128 NT kernel; bits 4-7: NT ablation; bits 8-12: TN ablation; bit 13: 1 tile NT kernel instead of the A-stationary one; bits 14-15: wgrad workgroups auto / 256 / 512 / 768; bit 16: 1 two-kernel attention backward instead of the one-pass kernel
-// A-stationary GEMM switches (gemm_as.hip as_default_flags: 1 paired half-line stores, 2 non-temporal side outputs, 16 chunked K = 256 form); -1: library default
+// A-stationary GEMM switches (gemm_as.hip as_default_flags: 1 paired half-line stores, 2 non-temporal side outputs, 16 / 32 chunked K = 256 / 512 form; gemm_cs.hip cs_flags: 64 the
+// C-stationary route, 128 at any M); -1: library default
 extern "C" int ishara_debug_set_as_flags(int32_t flags) { g_as_flags_override = flags; return 0; }
 extern "C" int ishara_debug_set_nt_big(int32_t on) { g_nt_big = on; return 0; }
 extern "C" int ishara_debug_force_regstage(int32_t on) { g_force_regstage = (on & 1) ? 1 : ((on >> 3) & 1 ? 2 : ((on >> 13) & 1 ? 3 : 0)); g_dbg_epi = (on >> 4) & 15; g_dbg_tn = (on >> 8) & 31; g_force_tn_regstage = (on >> 1) & 1; g_force_dw_lds = (on >> 2) & 1; { const int tb = (on >> 14) & 3; g_tn_blocks = tb == 1 ? 256 : (tb == 2 ? 512 : (tb == 3 ? 768 : 0)); } g_attn_bwd_two_pass = (on >> 16) & 1; return 0; }
@@ -197,6 +198,15 @@ extern "C" int ishara_op_dense_fwd_ex(int32_t dt, const void* x, const float* Wm
     CK(sh.build(dt, Wm, K, N, sc, s));
     OpArgs no; EpiArgs ea; ea.bias = bias; ea.act = act; ea.resid = resid; ea.dbg = g_dbg_epi;
     return launch_gemm_nt(dt, dt, dt, OP_NONE, x, sc + sh.wt, y, M, N, K, sh.ldt, no, ea, s);
+}
+// the profiler key (= rocprof name prefix) of the kernel ishara_op_dense_fwd_ex runs for these arguments under the current switches: host only,
+// nothing is launched — so a test can tell WHICH kernel a route decision picks when two routes give identical outputs
+extern "C" const char* ishara_debug_dense_kernel_name(int32_t dt, int32_t M, int32_t K, int32_t N, int32_t act, int32_t with_resid) {
+    if (!op_dt_ok("ishara_debug_dense_kernel_name", dt, true) || M < 1 || K < 1 || N < 1) return "";
+    const OpShadow sh(dt, K, N, M);
+    const void* aligned = reinterpret_cast<const void*>(uintptr_t(256));      // stands for 16-byte aligned operands; never dereferenced
+    EpiArgs ea; ea.bias = reinterpret_cast<const float*>(aligned); ea.act = act; ea.resid = with_resid ? aligned : nullptr; ea.dbg = g_dbg_epi;
+    return gemm_nt_kernel_name(dt, dt, dt, OP_NONE, aligned, M, N, K, sh.ldt, ea);
 }
 extern "C" int ishara_op_dense_bwd(int32_t dt, const void* x, const float* Wm, const void* dy, void* dx, float* dW, float* db,
                                    int32_t M, int32_t K, int32_t N, void* scratch, ishara_stream st) {

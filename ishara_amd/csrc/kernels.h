@@ -56,7 +56,8 @@ struct EpiArgs {
     // A-stationary kernel, 16-bit C: bit 0 — a row's two 64-byte halves of a 128-byte line are stored back to back every second column step
     // instead of one step apart (cold HBM takes half lines that arrive a step apart at 3.8 TB/s, whole lines at 4.6+: tools/micro/store_cold.hip);
     // bit 1 — non-temporal hint on the side outputs (saved pre-activations, prologue rows); bits 4 / 5 — the chunked form (one workgroup per CU, 64 KB
-    // weight stages, a wait + barrier per stage instead of per column step) at K = 256 / 512.  -1: the library default (gemm_as.hip, ISHARA_AS_FLAGS)
+    // weight stages, a wait + barrier per stage instead of per column step) at K = 256 / 512; bit 6 — the C-stationary kernel (gemm_cs.hip) for K = 512, N = 256 at
+    // M > 49152, bit 7 — at any M (tests).  -1: the library default (115; ISHARA_AS_FLAGS)
     int as_flags = -1;
 };
 
@@ -65,7 +66,7 @@ struct EpiArgs {
 int launch_gemm_nt(int dtA, int dtM, int dtC, int op, const void* A, const void* Bt, void* C,
                    int M, int N, int K, int ldb, const OpArgs& oa, const EpiArgs& ea, hipStream_t s);
 // the kernel launch_gemm_nt runs a call on (gemm_nt.hip: the one place that decides), and its profiler key = the prefix of its rocprof name
-enum NtRoute { NT_REFUSED, NT_AS_F16, NT_BIG, NT_AS, NT_TILE_T, NT_GLDS, NT_REG };
+enum NtRoute { NT_REFUSED, NT_AS_F16, NT_BIG, NT_CS, NT_AS, NT_TILE_T, NT_GLDS, NT_REG };
 NtRoute gemm_nt_route(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);
 const char* gemm_nt_kernel_name(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);
 bool gemm_nt_as_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);                    // gemm_as.hip
@@ -74,6 +75,10 @@ bool gemm_nt_as_prologue_ok(int dtA, int dtM, int dtC, int M, int N, int K, int 
 const char* gemm_nt_as_name(int dtC, int K, const EpiArgs& ea, int M, int N);
 int launch_gemm_nt_as(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);
 int launch_gemm_nt_as_f16(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);   // gemm_as_f16.hip
+// the C-stationary kernel of the K = 512 -> N = 256 projections at training-size M (gemm_cs.hip; as_flags bit 6 turns the route on, bit 7 drops the row threshold)
+bool gemm_nt_cs_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);
+const char* gemm_nt_cs_name(const EpiArgs& ea);
+int launch_gemm_nt_cs(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);
 bool gemm_nt_big_applicable(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);              // gemm_big.hip
 int launch_gemm_nt_big(int dtA, int dtM, int dtC, int op, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);
 

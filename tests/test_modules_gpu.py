@@ -67,9 +67,14 @@ VARIANT_ENV = {"no_psa": "ISHARA_NO_PSA", "no_deferred_reduce": "ISHARA_NO_DEFER
 _cache = {}
 
 
+def _kw(shape):
+    """the model fields of a shape: a name in SHAPES, or the dict itself (tests/test_modules_ragged_gpu.py)"""
+    return SHAPES[shape] if isinstance(shape, str) else shape
+
+
 def _model(shape, dtype, dropout, B, variant):
     """One model per (shape, dtype, dropout, B, create-time switch), kept until the next key asks (cases are ordered by key)."""
-    key = (shape, dtype, dropout, B, VARIANT_ENV.get(variant, ""))
+    key = (repr(shape), dtype, dropout, B, VARIANT_ENV.get(variant, ""))
     if _cache.get("key") != key:
         _cache.clear()
         torch.cuda.empty_cache()
@@ -78,7 +83,7 @@ def _model(shape, dtype, dropout, B, variant):
         if env:
             os.environ[env] = "1"
         try:
-            model = get_model(**SHAPES[shape], dropout_rate=dropout, head_dropout=0.4 if dropout > 0 else 0.0,
+            model = get_model(**_kw(shape), dropout_rate=dropout, head_dropout=0.4 if dropout > 0 else 0.0,
                               conformer_attn_dropout=0.1 if dropout > 0 else 0.0, dtype=dtype, max_batch=B, seed=3)
         finally:
             os.environ.pop("ISHARA_WS_GUARD", None)
@@ -91,7 +96,7 @@ def _model(shape, dtype, dropout, B, variant):
 
 
 def _ocfg(shape, dropout):
-    kw = dict(SHAPES[shape])
+    kw = dict(_kw(shape))
     kw["kernel_sizes"] = tuple(kw["kernel_sizes"])
     return O.Config(dropout_rate=dropout, head_dropout=0.4 if dropout > 0 else 0.0, conformer_attn_dropout=0.1 if dropout > 0 else 0.0, **kw)
 
@@ -131,9 +136,17 @@ def _check_routes(name, kind, shape, dtype, dropout, B, variant, report):
 @pytest.mark.parametrize("shape,dtype,dropout,B,variant,name", _cases(),
                          ids=lambda v: str(v).replace("/", ".") if not isinstance(v, float) else f"drop{v}")
 def test_module_matches_fp64(shape, dtype, dropout, B, variant, name):
-    model, W, flat = _model(shape, dtype, dropout, B, variant)
+    check_module(shape, dtype, dropout, B, variant, name)
+
+
+def check_module(shape, dtype, dropout, B, variant, name, kw=None, log_test="module", check_routes=_check_routes):
+    """One module at one case against fp64, product route and profiled route.  kw: the model fields where `shape` is only the case's label
+    (tests/test_modules_ragged_gpu.py); check_routes(name, kind, shape, dtype, dropout, B, variant, report): what the profile report must name."""
+    if kw is None:
+        kw = shape
+    model, W, flat = _model(kw, dtype, dropout, B, variant)
     lib = model._lib
-    ocfg = _ocfg(shape, dropout)
+    ocfg = _ocfg(kw, dropout)
     names = model.module_names()
     assert names == MP.expected_modules(ocfg)
     i = names.index(name)
@@ -154,7 +167,7 @@ def test_module_matches_fp64(shape, dtype, dropout, B, variant, name):
         dy = MP.round_to(g.standard_normal((B, T, cout)), dtype)
     ref = MP.reference(name, ocfg, W, x, dy, seed, first, labels=labels)
     assert ref["sites_used"] == nsites
-    bound = MP.bounds(kind, dtype)
+    bound = MP.bounds(kind, dtype, shape)
     mine = np.zeros(model.n_train, bool)
     for n, s, o, t in model.entries:
         if t and MP.owns(name, n):
@@ -191,11 +204,11 @@ def test_module_matches_fp64(shape, dtype, dropout, B, variant, name):
             assert stray == 0, f"{stray} gradient elements outside {name}'s entries are not zero"
             assert np.array_equal(pflat[:model.n_train], flat[:model.n_train].cpu().numpy()), "a module run changed trainable parameters"
             obs, bad = MP.compare(name, dtype, B, T, got, ref, W, bound)
-            _log_observed(dict(test="module", module=name, kind=kind, shape=shape, dtype=dtype, dropout=dropout, B=B, variant=variant, route=route, **obs))
+            _log_observed(dict(test=log_test, module=name, kind=kind, shape=shape, dtype=dtype, dropout=dropout, B=B, variant=variant, route=route, **obs))
             print(f"observed[{route}] {obs}")
             failures += [f"[{route}] {b}" for b in bad]
             if report is not None:
-                _check_routes(name, kind, shape, dtype, dropout, B, variant, report)
+                check_routes(name, kind, shape, dtype, dropout, B, variant, report)
     finally:
         if regstage:
             lib.ishara_debug_force_regstage(0)

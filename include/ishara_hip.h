@@ -254,6 +254,10 @@ int ishara_dropout_mask(uint32_t seed, uint32_t site, int32_t rows, int32_t cols
 int ishara_debug_set_as_flags(int32_t flags);
 /* the kernel (profiler key) ishara_op_dense_fwd_ex would run for these arguments, with a bias, under the current switches; host only, launches nothing */
 const char* ishara_debug_dense_kernel_name(int32_t dt, int32_t M, int32_t K, int32_t N, int32_t act, int32_t with_resid);
+/* the depthwise-conv kernel ishara_op_dwconv_fwd(_ex) (backward != 0: ishara_op_dwconv_bwd, or the model's BatchNorm-folding call) would run
+ * for these arguments under the current switches: the prefix of its profiler name, a two-pass backward as "dgrad+wgrad", "" for a refused
+ * call.  flags: 1 statistics wanted, 2 scratch given, 4 BatchNorm backward folded in.  Host only, launches nothing; valid until the next call */
+const char* ishara_debug_dwconv_kernel_name(int32_t dt, int32_t backward, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, int32_t flags);
 /* 0: never use the 256 x 256 two-operand tile GEMM (gemm_big.hip) — A/B runs against the A-stationary kernel inside one process; 1: library default */
 int ishara_debug_set_nt_big(int32_t on);
 int ishara_debug_force_regstage(int32_t on);

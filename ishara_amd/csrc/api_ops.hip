@@ -208,6 +208,14 @@ extern "C" const char* ishara_debug_dense_kernel_name(int32_t dt, int32_t M, int
     EpiArgs ea; ea.bias = reinterpret_cast<const float*>(aligned); ea.act = act; ea.resid = with_resid ? aligned : nullptr; ea.dbg = g_dbg_epi;
     return gemm_nt_kernel_name(dt, dt, dt, OP_NONE, aligned, M, N, K, sh.ldt, ea);
 }
+// the same for the depthwise conv: the kernel launch_dwconv_fwd (backward != 0: launch_dwconv_bwd_bn / launch_dwconv_bwd) runs for these
+// arguments under the current switches, a two-pass backward as "dgrad+wgrad", "" for a refused call.  flags: 1 statistics wanted, 2 scratch
+// given, 4 BatchNorm backward folded in (launch_dwconv_bwd_bn).  Host only: nothing is launched.  The answer is valid until the next call
+extern "C" const char* ishara_debug_dwconv_kernel_name(int32_t dt, int32_t backward, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, int32_t flags) {
+    if (!op_dt_ok("ishara_debug_dwconv_kernel_name", dt, !backward) || B < 1 || T < 1 || C < 1) return "";
+    if (backward) return dwconv_bwd_kernel_name(dt, C, k, padl, (flags & 2) != 0, (flags & 4) != 0);
+    return dwconv_fwd_kernel_name(dt, B, T, C, k, (flags & 1) != 0, (flags & 2) != 0);
+}
 extern "C" int ishara_op_dense_bwd(int32_t dt, const void* x, const float* Wm, const void* dy, void* dx, float* dW, float* db,
                                    int32_t M, int32_t K, int32_t N, void* scratch, ishara_stream st) {
     OP_DT("ishara_op_dense_bwd", dt, false);

@@ -14,6 +14,10 @@
 // the dw[K][4] accumulators are fp32 registers (float2 pairs -> v_pk_fma_f32).  A workgroup = (256 / (C/4)) item lanes x
 // C/4 channel quads looping over (sample, segment) items; at the end the lanes are combined in LDS and the workgroup writes
 // ONE partial row part[blockIdx.x][(K+1)*C] (dw then dbias), summed by reduce_slabs: no same-address atomics.
+//
+// Below it: the two weight-gradient kernels of the two-pass backward (dwconv_wgrad_win_kernel for K in {3, 5, 11, 15},
+// dwconv_wgrad_kernel for every K), whose data gradient is the forward tile / register-window kernel with flipped taps
+// (dwconv.hip).  Which of all these a call runs on is decided by dwconv_bwd_route (dwconv.hip).
 #include "common.h"
 #include "kernels.h"
 
@@ -44,7 +48,7 @@ template <> struct DwRow<float> {
     DEVI void pack(dwf2 lo, dwf2 hi) { r = make_float4(lo.x, lo.y, hi.x, hi.y); }
 };
 // BatchNorm backward applied to a dy row as it enters the window (BN = true): row <- dy * k1 + k0 - h * k2, the arithmetic of
-// bn_bwd_apply_kernel (elementwise.hip), rounded to the storage type exactly where that kernel's output was
+// bn_bwd_apply_kernel (bn_gate.hip), rounded to the storage type exactly where that kernel's output was
 template <typename T> DEVI void dw_bn_row(DwRow<T>& d, const DwRow<T>& h, const dwf2 (&k0)[2], const dwf2 (&k1)[2], const dwf2 (&k2)[2]) {
     dwf2 dl, dh, hl, hh;
     d.unpack(dl, dh); h.unpack(hl, hh);
@@ -216,11 +220,226 @@ __global__ __launch_bounds__(256, (DwCfg<K, BN>::WPS)) void dwconv_bwd_fused_ker
     for (int q = tid; q < n; q += 256) dst[q] = red[q];
 }
 
-bool dwconv_bwd_fused_ok(int dt, int C, int k, int padl) {
-    if (!(k == 3 || k == 5 || k == 11 || k == 15)) return false;
-    if (dt != DT_BF16 && k > 5) return false;                 // fp32 rows would need K*4 more registers for the window
-    if (C % 4 != 0 || C / 4 > 256 || padl < 0 || padl >= k) return false;
-    return true;
+#define DWG_TT 32   // time tile of the weight-grad kernels (two LDS tiles must fit 64 KB)
+
+// weight gradient, LDS tile + per-thread tap accumulators: thread = 4 channels x all K taps x 4 consecutive time steps
+// of a 32-step tile; the in(x) window slides through registers, so an item costs 2 LDS reads per K*4 FMAs (the older
+// tap-lane mapping below needs 5 reads per 16 FMAs and is LDS-bound).  Accumulators live across the items of the
+// workgroup; lanes are combined with LDS atomics and one partial row per workgroup goes to `part`.
+template <typename T, int K>
+__global__ __launch_bounds__(256) void dwconv_wgrad_win_kernel(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ part,
+                                                               int B, int Tn, int C, int padl, int inop) {
+    __shared__ __attribute__((aligned(16))) float xt[(DWG_TT + K - 1) * DW_CT];
+    __shared__ __attribute__((aligned(16))) float dt_[DWG_TT * DW_CT];
+    __shared__ float red[(K + 1) * DW_CT];
+    const int tid = threadIdx.x;
+    const int c0 = blockIdx.x * DW_CT;
+    const int Cin = (inop == DWIN_GLU) ? 2 * C : C;
+    constexpr int rows = DWG_TT + K - 1;
+    const int ntt = (Tn + DWG_TT - 1) / DWG_TT;
+    const int cl = tid & 31, tl = tid >> 5;          // 32 channel lanes x 8 time lanes (4 steps each)
+    for (int q = tid; q < (K + 1) * DW_CT; q += 256) red[q] = 0.f;
+    float acc[K][4], accb[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0.f;
+    const int ch8 = c0 + (tid & 15) * 8;
+    for (int item = blockIdx.y; item < B * ntt; item += gridDim.y) {
+        const int b = item / ntt, t0 = (item % ntt) * DWG_TT;
+        __syncthreads();
+        for (int r = tid >> 4; r < rows; r += 16) {
+            const int tin = t0 - padl + r;
+            float v[8];
+            if (tin >= 0 && tin < Tn && ch8 < C) {
+                const T* p = x + ((size_t)b * Tn + tin) * Cin + ch8;
+                load8(p, v);
+                if (inop == DWIN_SWISH) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = swishf_(v[e]);
+                } else if (inop == DWIN_GLU) {
+                    float g[8];
+                    load8(p + C, g);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] *= sigmoidf_(g[e]);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = 0.f;
+            }
+            float* dst = xt + r * DW_CT + (tid & 15) * 8;
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+            *reinterpret_cast<float4*>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        }
+        for (int r = tid >> 4; r < DWG_TT; r += 16) {
+            const int t = t0 + r;
+            float v[8];
+            if (t < Tn && ch8 < C) load8(dy + ((size_t)b * Tn + t) * C + ch8, v);
+            else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = 0.f;
+            }
+            float* dst = dt_ + r * DW_CT + (tid & 15) * 8;
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+            *reinterpret_cast<float4*>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        }
+        __syncthreads();
+        float4 win[K];                                   // in(x) rows tl*4 + (0..K-1)
+#pragma unroll
+        for (int j = 0; j < K - 1; ++j) win[j + 1] = *reinterpret_cast<const float4*>(xt + (tl * 4 + j) * DW_CT + cl * 4);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int j = 0; j < K - 1; ++j) win[j] = win[j + 1];
+            win[K - 1] = *reinterpret_cast<const float4*>(xt + (tl * 4 + u + K - 1) * DW_CT + cl * 4);
+            const float4 d = *reinterpret_cast<const float4*>(dt_ + (tl * 4 + u) * DW_CT + cl * 4);
+            accb[0] += d.x; accb[1] += d.y; accb[2] += d.z; accb[3] += d.w;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                acc[j][0] += d.x * win[j].x; acc[j][1] += d.y * win[j].y; acc[j][2] += d.z * win[j].z; acc[j][3] += d.w * win[j].w;
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) atomicAdd(red + j * DW_CT + cl * 4 + e, acc[j][e]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) atomicAdd(red + K * DW_CT + cl * 4 + e, accb[e]);
+    __syncthreads();
+    // part[(blockIdx.y)][K+1][C]
+    float* dst = part + (size_t)blockIdx.y * (K + 1) * C;
+    for (int q = tid; q < (K + 1) * DW_CT; q += 256) {
+        const int j = q / DW_CT, c = c0 + (q % DW_CT);
+        if (c < C) dst[(size_t)j * C + c] = red[q];
+    }
+}
+
+// dw[j,c] += sum_{b,t} dy[b,t,c] * in(x)[b, t-padl+j, c] ; dbias[c] += sum dy.
+// grid = (C/128, splits); each workgroup loops over (sample, time-tile) pairs and at the end either writes its sums into row
+// blockIdx.y of `part` ([splits][(k+1)*C], dw then dbias, every element written; summed by reduce_slabs in a fixed order, so the
+// gradient repeats bit for bit) or, without `part`, issues one atomic per (tap, channel).  thread -> 4 channels x taps {tl, tl+8, tl+16, tl+24}.
+template <typename T>
+__global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                           float* __restrict__ dw, float* __restrict__ dbias, float* __restrict__ part,
+                                                           int B, int Tn, int C, int k, int padl, int inop) {
+    __shared__ __attribute__((aligned(16))) float xt[(DWG_TT + DW_MAXK - 1) * DW_CT];
+    __shared__ __attribute__((aligned(16))) float dt_[DWG_TT * DW_CT];
+    const int tid = threadIdx.x;
+    const int c0 = blockIdx.x * DW_CT;
+    const int Cin = (inop == DWIN_GLU) ? 2 * C : C;
+    const int rows = DWG_TT + k - 1;
+    const int ntt = (Tn + DWG_TT - 1) / DWG_TT;
+    const int cl = tid & 31, tl = tid >> 5;
+    float acc[4][4], accb[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[q][e] = 0.f;
+    // staging registers: x tile rows (tid>>4)+16*it (it < NX), dy tile rows (tid>>4)+16*it (it < 2); the next item's
+    // loads are issued before the current item's compute and written to LDS after it (one LDS image, two barriers/item)
+    constexpr int NX = (DWG_TT + DW_MAXK - 1 + 15) / 16;
+    float xv[NX][8], xg[NX][8], dv[2][8];
+    bool xok[NX], dok[2];
+    const int ch8 = c0 + (tid & 15) * 8;
+    auto gload = [&](int item) {
+        const int b = item / ntt, t0 = (item % ntt) * DWG_TT;
+#pragma unroll
+        for (int it = 0; it < NX; ++it) {
+            const int r = (tid >> 4) + 16 * it;
+            const int tin = t0 - padl + r;
+            xok[it] = r < rows && tin >= 0 && tin < Tn && ch8 < C;
+            if (xok[it]) {
+                const T* p = x + ((size_t)b * Tn + tin) * Cin + ch8;
+                load8(p, xv[it]);
+                if (inop == DWIN_GLU) load8(p + C, xg[it]);
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int t = t0 + (tid >> 4) + 16 * it;
+            dok[it] = t < Tn && ch8 < C;
+            if (dok[it]) load8(dy + ((size_t)b * Tn + t) * C + ch8, dv[it]);
+        }
+    };
+    auto lstore = [&]() {
+#pragma unroll
+        for (int it = 0; it < NX; ++it) {
+            const int r = (tid >> 4) + 16 * it;
+            if (r < rows) {
+                if (xok[it]) {
+                    if (inop == DWIN_SWISH) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) xv[it][e] = swishf_(xv[it][e]);
+                    } else if (inop == DWIN_GLU) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) xv[it][e] *= sigmoidf_(xg[it][e]);
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) xv[it][e] = 0.f;
+                }
+                float* dst = xt + r * DW_CT + (tid & 15) * 8;
+                *reinterpret_cast<float4*>(dst) = make_float4(xv[it][0], xv[it][1], xv[it][2], xv[it][3]);
+                *reinterpret_cast<float4*>(dst + 4) = make_float4(xv[it][4], xv[it][5], xv[it][6], xv[it][7]);
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int r = (tid >> 4) + 16 * it;
+            if (!dok[it]) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) dv[it][e] = 0.f;
+            }
+            float* dst = dt_ + r * DW_CT + (tid & 15) * 8;
+            *reinterpret_cast<float4*>(dst) = make_float4(dv[it][0], dv[it][1], dv[it][2], dv[it][3]);
+            *reinterpret_cast<float4*>(dst + 4) = make_float4(dv[it][4], dv[it][5], dv[it][6], dv[it][7]);
+        }
+    };
+    const int nitems = B * ntt;
+    int item = blockIdx.y;
+    if (item < nitems) gload(item);
+    for (; item < nitems; item += gridDim.y) {
+        __syncthreads();                       // previous item's compute is done with the LDS image
+        lstore();
+        __syncthreads();
+        const int nxt = item + gridDim.y;
+        if (nxt < nitems) gload(nxt);          // in flight during the compute below
+        for (int t = 0; t < DWG_TT; ++t) {
+            const float4 d = *reinterpret_cast<const float4*>(dt_ + t * DW_CT + cl * 4);
+            if (tl == 0) { accb[0] += d.x; accb[1] += d.y; accb[2] += d.z; accb[3] += d.w; }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = tl + 8 * q;
+                if (j < k) {
+                    const float4 xq = *reinterpret_cast<const float4*>(xt + (t + j) * DW_CT + cl * 4);
+                    acc[q][0] += d.x * xq.x; acc[q][1] += d.y * xq.y; acc[q][2] += d.z * xq.z; acc[q][3] += d.w * xq.w;
+                }
+            }
+        }
+    }
+    const int ch = c0 + cl * 4;
+    if (ch < C && part) {
+        float* row = part + (size_t)blockIdx.y * (k + 1) * C;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = tl + 8 * q;
+            if (j < k) *reinterpret_cast<float4*>(row + (size_t)j * C + ch) = make_float4(acc[q][0], acc[q][1], acc[q][2], acc[q][3]);
+        }
+        if (tl == 0) *reinterpret_cast<float4*>(row + (size_t)k * C + ch) = make_float4(accb[0], accb[1], accb[2], accb[3]);
+    } else if (ch < C) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = tl + 8 * q;
+            if (j < k) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) atomicAdd(dw + (size_t)j * C + ch + e, acc[q][e]);
+            }
+        }
+        if (dbias && tl == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) atomicAdd(dbias + ch + e, accb[e]);
+        }
+    }
 }
 
 // partial rows: returns the number of rows written to `part` ((k+1)*C floats each), or -1
@@ -253,4 +472,20 @@ int launch_dwconv_bwd_fused(int dt, int inop, const void* dy, const void* x, con
                             int B, int T, int C, int k, int padl, int max_rows, hipStream_t s, const DwBnArgs& bn) {
     if (dt == DT_BF16) return run_dw_fused<bf16>(inop, (const bf16*)dy, (const bf16*)x, w, (bf16*)dx, part, B, T, C, k, padl, max_rows, s, bn);
     return run_dw_fused<float>(inop, (const float*)dy, (const float*)x, w, (float*)dx, part, B, T, C, k, padl, max_rows, s, bn);
+}
+
+// the weight gradient of the two-pass backward, grid = (C / 128, splits): the partial rows written to `part` ([splits][(k + 1) * C], dw then
+// dbias; summed by the caller), 0 when the sums went into dw / dbias with atomics (DWW_TILE_ATOMIC: part == nullptr)
+int launch_dwconv_wgrad(DwWgrad kind, int dt, int inop, const void* dy, const void* x, float* dw, float* dbias, float* part, int B, int T, int C, int k, int padl, hipStream_t s) {
+    const int cblocks = (C + DW_CT - 1) / DW_CT, ntt = (T + DWG_TT - 1) / DWG_TT;
+    const int splits = max(1, min(B * ntt, (part ? DWG_BLOCKS : 1024) / cblocks));
+    dim3 grid(cblocks, splits);
+#define DWW(TT, KK) hipLaunchKernelGGL((dwconv_wgrad_win_kernel<TT, KK>), grid, dim3(256), 0, s, (const TT*)dy, (const TT*)x, part, B, T, C, padl, inop)
+#define DWWK(TT) switch (k) { case 3: DWW(TT, 3); break; case 5: DWW(TT, 5); break; case 11: DWW(TT, 11); break; default: DWW(TT, 15); break; }
+    if (kind == DWW_WIN) { if (dt == DT_BF16) { DWWK(bf16) } else { DWWK(float) } }
+    else if (dt == DT_BF16) hipLaunchKernelGGL(dwconv_wgrad_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)x, dw, dbias, part, B, T, C, k, padl, inop);
+    else hipLaunchKernelGGL(dwconv_wgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, dw, dbias, part, B, T, C, k, padl, inop);
+#undef DWWK
+#undef DWW
+    return part ? splits : 0;
 }

@@ -1,5 +1,5 @@
 // The Keras get_model hybrid family: the layer graph get_model(...) builds (conv-hybrid-model.ipynb c7:12-65), its workspace plan and
-// the forward / backward orchestration over the kernels in gemm_nt.hip, gemm_tn.hip, elementwise.hip, attention.hip and ctc.hip.  confconv_fwd / _bwd
+// the forward / backward orchestration over the kernels in gemm_nt.hip, gemm_tn.hip, norm_rows.hip, dwconv.hip, bn_gate.hip, attention.hip and ctc.hip.  confconv_fwd / _bwd
 // also serve the torch families, ln_as_prologue and classifier_fwd the operator entry points (api_ops.hip).
 #include "model_types.h"
 #include <stdlib.h>

@@ -147,7 +147,7 @@ int launch_make_shadow(int dtM, const float* W, int K, int N, void* Wt, int ldt,
 struct ShadowDesc { const float* W; void* Wt; void* Wn; int K, N, ldt, ldn, tile0, tiles_n; };   // tile0: first 32x32 tile (block) of this weight
 int launch_make_shadow_batched(int dtM, const ShadowDesc* tab, int ntab, int total_tiles, hipStream_t s);
 
-// ---- normalisation / conv / small ops (elementwise.hip) ---------------------------
+// ---- row-wise passes: log-softmax, LayerNorm (norm_rows.hip; launch_map_rows is declared further down) ------------
 int launch_log_softmax_fwd(const float* x, float* y, int M, int C, int ld, hipStream_t s);
 int launch_log_softmax_bwd(const float* dy, const float* y, float* dx, int M, int C, int ld, hipStream_t s);
 int launch_layernorm_fwd(int dt, const void* x, const float* gamma, const float* beta, float eps,
@@ -159,7 +159,11 @@ int launch_layernorm_bwd(int dt, const void* dy, const void* x, const float* mea
                          const float* gamma, const void* resid, void* dx, float* dgamma, float* dbeta,
                          float* scratch, int M, int C, hipStream_t s);
 
+// ---- depthwise conv (dwconv.hip: forward kernels, routes, launchers; dwconv_bwd.hip: one-pass backward, weight gradients) ------------
 enum : int { DWIN_NONE = 0, DWIN_SWISH = 1, DWIN_GLU = 2 };
+#define DW_CT 128          // channels per workgroup of the LDS-tiled kernels
+#define DW_MAXK 31         // largest kernel size
+#define DWG_BLOCKS 512     // most partial rows a backward kernel writes: dwconv_bwd_scratch_floats (the model sizes its arenas by it)
 // y[b,t,c] = bias[c] + sum_j w[j,c] * in(x)[b, t - padl + j, c]; x has Cin = C (or 2C for GLU).
 // stats: ssum/ssq [B,C] = per-sample sum_t y, sum_t y^2 (fp32 atomics; zero them first; nullptr = off).
 // ssum / ssq: per-sample channel sums of y and y^2 [B, C] (or nullptr).  `part`: scratch of dwconv_fwd_scratch_floats(B, T, C)
@@ -182,11 +186,25 @@ int launch_dwconv_bwd_bn(int dt, int inop, const void* dy, const DwBnArgs& bn, c
                          float* dw, float* dbias, float* scratch, int B, int T, int C, int k, int padl, hipStream_t s);
 int launch_dwconv_bwd(int dt, int inop, const void* dy, const void* x, const float* w, void* dx,
                       float* dw, float* dbias, float* scratch, int B, int T, int C, int k, int padl, hipStream_t s);
-// the one-pass kernel behind the two launchers above (dwconv_bwd.hip): partial rows into `part`, summed by the caller
-bool dwconv_bwd_fused_ok(int dt, int C, int k, int padl);
+// The kernel a call runs on (dwconv.hip: the one place that decides and that reads g_force_dw_lds / ISHARA_NO_DW_STREAM); the launchers
+// and the name functions are switches over it.  stats: ssum is wanted; part / scratch: the caller gave the scratch; bn: DwBnArgs.h is set
+enum DwFwdRoute { DWF_REFUSED, DWF_STREAM, DWF_REG8, DWF_REG, DWF_TILE };
+DwFwdRoute dwconv_fwd_route(int dt, int B, int T, int C, int k, bool stats, bool part);
+enum DwBwdKind { DWB_REFUSED, DWB_FUSED_BN, DWB_FUSED, DWB_TWO_PASS };      // FUSED_BN only when bn was asked for; otherwise what launch_dwconv_bwd runs
+enum DwDgrad { DWD_REG, DWD_TILE };
+enum DwWgrad { DWW_WIN, DWW_TILE_PART, DWW_TILE_ATOMIC };
+struct DwBwdRoute { DwBwdKind kind; DwDgrad dgrad; DwWgrad wgrad; };         // dgrad, wgrad: the two kernels of DWB_TWO_PASS
+DwBwdRoute dwconv_bwd_route(int dt, int C, int k, int padl, bool scratch, bool bn);
+// the prefix of the kernel's rocprof name ("" when refused; a two-pass backward as "dgrad+wgrad")
+const char* dwconv_fwd_kernel_name(int dt, int B, int T, int C, int k, bool stats, bool part);
+const char* dwconv_bwd_kernel_name(int dt, int C, int k, int padl, bool scratch, bool bn);
+// the kernels of dwconv_bwd.hip behind the two backward launchers.  The one-pass kernel: partial rows into `part`, summed by the caller
 int launch_dwconv_bwd_fused(int dt, int inop, const void* dy, const void* x, const float* w, void* dx, float* part,
                             int B, int T, int C, int k, int padl, int max_rows, hipStream_t s, const DwBnArgs& bn);
+// the weight gradient of the two-pass backward (kind: which kernel; DWW_WIN takes k in {3, 5, 11, 15}): the partial rows written to `part`, 0 with part == nullptr (atomics into dw / dbias)
+int launch_dwconv_wgrad(DwWgrad kind, int dt, int inop, const void* dy, const void* x, float* dw, float* dbias, float* part, int B, int T, int C, int k, int padl, hipStream_t s);
 
+// ---- BatchNorm / ECA / Squeeze-Excite and the passes that apply them (bn_gate.hip) ---------------------------------
 // BN finalize from per-sample sums ssum/ssq [nb,C] (count = rows they cover): mean, rstd,
 // a = gamma*rstd, b = beta - mean*a ; moving statistics update when training
 int launch_bn_finalize(const float* ssum, const float* ssq, int nb, float count, const float* gamma, const float* beta,
@@ -209,7 +227,7 @@ int launch_sample_affine(int dt, const void* x, const float* P, const float* Q, 
 // y = x*a[c] + b[c]
 int launch_col_affine(int dt, const void* x, const float* a, const float* b, void* y, int M, int C, hipStream_t s);
 enum : int { MAP_SWISH = 0, MAP_ROWSCALE = 1, MAP_DROPMASK = 2 };
-// y = swish(x) | x * rs[row / T] | x * dropmask(row, col)   — one streaming pass over [M, C]
+// y = swish(x) | x * rs[row / T] | x * dropmask(row, col)   — one streaming pass over [M, C] (norm_rows.hip)
 int launch_map_rows(int dt, int op, const void* x, void* y, const float* rs, DropSpec drop, int M, int T, int C, hipStream_t s);
 // per-sample reductions over t: S1[b,c] = sum_t dy ; S2[b,c] = sum_t dy * other   (other optional,
 // normalised as (other-mean[c])*rstd[c] when mean != nullptr)

@@ -176,7 +176,7 @@ def _dw_ref(x, w, bias, inop, padl, C_):
     return F.conv1d(up, w.t().unsqueeze(1), bias, groups=C_).transpose(1, 2)
 
 
-# (route, B, T, C, k, inop, causal, stats, entry): route conditions at elementwise.hip dw_stream_ok / dw_reg8_ok / dw_reg_ok
+# (route, B, T, C, k, inop, causal, stats, entry): route conditions at dwconv.hip dwconv_fwd_route
 #   stream: B > 8, k 11 / 15, C % 128 == 0, T >= 64, statistics only through the caller's scratch (_ex)
 #   reg8:   k 3 / 5, C / 8 in {32, 64, 128, 256}, statistics only through scratch (or none)
 #   reg:    k 3 / 5, C / 4 a power of two <= 256 (the plain entry point with statistics, or C / 8 < 32)

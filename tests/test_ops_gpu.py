@@ -310,12 +310,14 @@ def _dwconv(lib, dt, B, T, Cc, k, inop, causal, variant):
 
 @pytest.mark.parametrize("dt", ["bf16"])
 @pytest.mark.parametrize("B,T,Cc,k,inop,causal", [(9, 384, 512, 11, 1, True), (9, 384, 512, 15, 1, True), (10, 384, 256, 15, 2, False), (9, 200, 128, 11, 0, True),
-                                                 (12, 72, 128, 15, 2, False), (9, 512, 1024, 11, 1, True)])
+                                                 (12, 72, 128, 15, 2, False), (9, 512, 1024, 11, 1, True),
+                                                 (9, 1100, 128, 11, 1, True), (9, 1100, 256, 15, 2, False)])      # T = 1100: 8 ranges of 160 rows, the last one empty
 def test_dwconv_streaming_forward(lib, dt, B, T, Cc, k, inop, causal):
-    """The streaming K = 11 / 15 forward kernel (elementwise.hip dwconv_stream_kernel: 64-row LDS ring per 128 channels, lane-pair 16-byte
+    """The streaming K = 11 / 15 forward kernel (dwconv.hip dwconv_stream_kernel: 64-row LDS ring per 128 channels, lane-pair 16-byte
     stores, time ranges per sample) — reached only with caller scratch and more than 8 samples, i.e. the model's own call: outputs and the
-    per-sample statistics against the fp64 reference, causal and 'same' padding, ragged T (partial last chunk, ranges that do not divide T),
-    GLU input (2C channels) and bias; and bit-identical outputs to the tile kernel it replaces wherever both apply."""
+    per-sample statistics against the fp64 reference, causal and 'same' padding, ragged T (partial last chunk, ranges that do not divide T,
+    a last range that is empty), GLU input (2C channels) and bias; and bit-identical outputs to the tile kernel it replaces wherever both
+    apply.  The scratch starts as NaNs (0xFF bytes): a partial statistics row that no workgroup wrote fails the sums loudly."""
     code, tdt = DT[dt]
     g = torch.Generator().manual_seed(T + k + Cc)
     Cin = 2 * Cc if inop == 2 else Cc
@@ -327,7 +329,7 @@ def test_dwconv_streaming_forward(lib, dt, B, T, Cc, k, inop, causal):
     bd = dev(bias) if bias is not None else None
     y = torch.empty(B, T, Cc, dtype=tdt, device="cuda")
     ssum, ssq = torch.zeros(B, Cc, device="cuda"), torch.zeros(B, Cc, device="cuda")
-    sc = torch.empty(int(lib.ishara_op_dwconv_fwd_scratch_bytes(B, T, Cc)) + 256, dtype=torch.uint8, device="cuda")
+    sc = torch.full((int(lib.ishara_op_dwconv_fwd_scratch_bytes(B, T, Cc)) + 256,), 0xFF, dtype=torch.uint8, device="cuda")
     scp = C.c_void_p(sc.data_ptr() + (-sc.data_ptr()) % 256)
     _lib.check(lib.ishara_op_dwconv_fwd_ex(code, inop, _lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(y), _lib.ptr(ssum), _lib.ptr(ssq), scp, B, T, Cc, k, padl, stream()))
     ref = _dw_ref(x.double(), w.double(), bias.double() if bias is not None else None, inop, padl, Cc)

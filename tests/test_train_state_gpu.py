@@ -357,7 +357,7 @@ def test_resume_is_bit_identical(batches, tmp_path):
     alike differed after ONE step of the default path (max |difference| of `grads` 2.4e-7, of opt_m 3.0e-8), and the resumed run left
     the uninterrupted one by params 5.2e-10 .. 3.7e-9, opt_m 1.9e-9, opt_v 9.1e-13 .. 1.8e-12, opt_slow 1.5e-10 after steps 4 - 6, although
     load_state had restored every bit (test_load_state_restores_every_bit).  That kernel now writes partial rows that are summed in a
-    fixed order (csrc/elementwise.hip, dwconv_wgrad_kernel)."""
+    fixed order (csrc/dwconv_bwd.hip, dwconv_wgrad_kernel)."""
     a = _fresh(3)
     for i in range(6):
         a.train_on_batch(*batches[i % 3])

@@ -335,6 +335,19 @@ int64_t ishara_op_dwconv_scratch_bytes(int32_t C, int32_t k);
 int ishara_op_dwconv_bwd(int32_t dt, int32_t inop, const void* dy, const void* x, const float* w, void* dx,
                          float* dw, float* dbias, void* scratch, int32_t B, int32_t T, int32_t C, int32_t k,
                          int32_t padl, ishara_stream s);
+/* the BatchNorm backward as a launch of its own: dx [B,T,C] (dt) = a[c] * (dy * sg[b,c] + E[b or 0, c] - (h - mean[c]) * rstd[c] * Fc[c]); h the
+ * BatchNorm input, mean / rstd / a / Fc [C] f32, E [B,C] (e_per_sample 1) or [C] (0), sg [B,C] or NULL (= 1) */
+int ishara_op_bn_bwd_apply(int32_t dt, const void* dy, const void* h, const float* mean, const float* rstd, const float* a, const float* sg,
+                           const float* E, int32_t e_per_sample, const float* Fc, void* dx, int32_t B, int32_t T, int32_t C, ishara_stream s);
+/* ishara_op_dwconv_bwd on the gradient of a BatchNorm output dy, h being the conv's forward output, as the model's conv modules run it:
+ * returns 1 when the one-pass kernel applied the BatchNorm backward to every dy row on its way in (tmp untouched), 0 when
+ * ishara_op_bn_bwd_apply into tmp [B,T,C] (dt) and ishara_op_dwconv_bwd on tmp ran instead, < 0 on error.  sg, dbias and scratch may be NULL.
+ * All three refuse, before any GPU work and each with its own message: ISHARA_F16, B or T < 1, B > 65535, C no positive multiple of 8, k outside
+ * 1..31, padl outside [0, k), a NULL required operand, an operand off a 16-byte boundary. */
+int ishara_op_dwconv_bwd_bn(int32_t dt, int32_t inop, const void* dy, const void* h, const float* mean, const float* rstd, const float* a,
+                            const float* sg, const float* E, int32_t e_per_sample, const float* Fc, const void* x, const float* w, void* dx,
+                            float* dw, float* dbias, void* scratch, void* tmp, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl,
+                            ishara_stream s);
 /* attention on packed qkv [B*T, 3*H*dh] (head-major packing): o [B*T, H*dh]; scratch (256-byte aligned) holds q,k,vt,lse,delta,maskw.
  * ISHARA_F16: rate 0 only.  impl: 0 lane-split (f32 / bf16 / f16; head dim 8, 16, 24, 32, 48, 64; any T), 1 MFMA (bf16 and, forward only, f16;
  * head dim 32 / 64; T % 8 == 0; every other dtype / head dim runs the lane-split kernels) with the dropout keep bits cached in the scratch,

@@ -314,10 +314,54 @@ extern "C" int ishara_op_dwconv_fwd_ex(int32_t dt, int32_t inop, const void* x, 
     return launch_dwconv_fwd(dt, inop, x, w, bias, y, ssum, ssq, (float*)scratch, B, T, C, k, padl, (hipStream_t)s);
 }
 extern "C" int64_t ishara_op_dwconv_scratch_bytes(int32_t C, int32_t k) { return (int64_t)(dwconv_bwd_scratch_floats(C, k) * sizeof(float)); }
+// the depthwise-conv backward operators: everything a launch would fault or fail on is refused here, before any HIP call, each with a
+// message of its own.  `required` / `optional`: operands that must not / may be NULL; all of them 16-byte aligned (vector loads and stores)
+static int dwconv_bwd_refused(const char* me, int dt, int B, int T, int C, int k, int padl, std::initializer_list<const void*> required,
+                              std::initializer_list<const char*> names, std::initializer_list<const void*> optional) {
+    if (B < 1 || T < 1) { ishara_set_error("%s: B=%d T=%d: B and T must be >= 1", me, B, T); return -1; }
+    if (B > 65535) { ishara_set_error("%s: B=%d too large (B <= 65535: one grid row per sample)", me, B); return -1; }
+    if (C < 8 || C % 8 != 0) { ishara_set_error("%s: C=%d must be a positive multiple of 8", me, C); return -1; }
+    if (dwconv_bwd_route(dt, C, k, 0, false, false).kind == DWB_REFUSED) { ishara_set_error("%s: kernel size %d unsupported (1..%d)", me, k, DW_MAXK); return -1; }
+    if (padl < 0 || padl >= k) { ishara_set_error("%s: padl=%d outside 0..%d (the left padding of a %d-tap kernel)", me, padl, k - 1, k); return -1; }
+    for (size_t i = 0; i < required.size(); ++i) if (!required.begin()[i]) { ishara_set_error("%s: null %s", me, names.begin()[i]); return -1; }
+    for (size_t i = 0; i < required.size(); ++i)
+        if ((uintptr_t)required.begin()[i] % 16) { ishara_set_error("%s: misaligned %s: 16-byte aligned operands (vector loads and stores)", me, names.begin()[i]); return -1; }
+    uintptr_t opt = 0;
+    for (const void* p : optional) opt |= (uintptr_t)p;
+    if (opt % 16) { ishara_set_error("%s: misaligned optional operand (dbias / scratch / sg): 16-byte aligned operands (vector loads and stores)", me); return -1; }
+    return 0;
+}
 extern "C" int ishara_op_dwconv_bwd(int32_t dt, int32_t inop, const void* dy, const void* x, const float* w, void* dx, float* dw, float* dbias,
                                     void* scratch, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, ishara_stream s) {
     OP_DT("ishara_op_dwconv_bwd", dt, false);
+    if (dwconv_bwd_refused("ishara_op_dwconv_bwd", dt, B, T, C, k, padl, {dy, x, w, dx, dw}, {"dy", "x", "w", "dx", "dw"}, {dbias, scratch})) return -1;
     return launch_dwconv_bwd(dt, inop, dy, x, w, dx, dw, dbias, (float*)scratch, B, T, C, k, padl, (hipStream_t)s);
+}
+// dx [B,T,C] (dt) = a[c] * (dy * sg[b,c] + E[b or 0, c] - (h - mean[c]) * rstd[c] * Fc[c]): the BatchNorm backward as a launch of its own
+extern "C" int ishara_op_bn_bwd_apply(int32_t dt, const void* dy, const void* h, const float* mean, const float* rstd, const float* a, const float* sg,
+                                      const float* E, int32_t e_per_sample, const float* Fc, void* dx, int32_t B, int32_t T, int32_t C, ishara_stream s) {
+    const char* me = "ishara_op_bn_bwd_apply";
+    OP_DT(me, dt, false);
+    if (dwconv_bwd_refused(me, dt, B, T, C, 1, 0, {dy, h, mean, rstd, a, E, Fc, dx}, {"dy", "h", "mean", "rstd", "a", "E", "Fc", "dx"}, {sg})) return -1;
+    return launch_bn_bwd_apply(dt, dy, h, mean, rstd, a, sg, E, e_per_sample ? 1 : 0, Fc, dx, B, T, C, (hipStream_t)s);
+}
+// the conv backward behind a BatchNorm, as convblock_bwd and the Conformer conv module's backward run it: the one-pass kernel with the
+// BatchNorm backward folded into its row load where the route has one (returns 1), else ishara_op_bn_bwd_apply into tmp [B,T,C] (dt) and the
+// plain backward on tmp (returns 0); < 0 on error.  sg and dbias may be NULL
+extern "C" int ishara_op_dwconv_bwd_bn(int32_t dt, int32_t inop, const void* dy, const void* h, const float* mean, const float* rstd, const float* a, const float* sg,
+                                       const float* E, int32_t e_per_sample, const float* Fc, const void* x, const float* w, void* dx, float* dw, float* dbias,
+                                       void* scratch, void* tmp, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, ishara_stream st) {
+    const char* me = "ishara_op_dwconv_bwd_bn";
+    OP_DT(me, dt, false);
+    if (dwconv_bwd_refused(me, dt, B, T, C, k, padl, {dy, h, mean, rstd, a, E, Fc, x, w, dx, dw, tmp}, {"dy", "h", "mean", "rstd", "a", "E", "Fc", "x", "w", "dx", "dw", "tmp"},
+                           {sg, dbias, scratch})) return -1;
+    hipStream_t s = (hipStream_t)st;
+    DwBnArgs bn; bn.h = h; bn.mean = mean; bn.rstd = rstd; bn.a = a; bn.sg = sg; bn.E = E; bn.Fc = Fc; bn.e_per_sample = e_per_sample ? 1 : 0;
+    const int fused = launch_dwconv_bwd_bn(dt, inop, dy, bn, x, w, dx, dw, dbias, (float*)scratch, B, T, C, k, padl, s);
+    if (fused != 0) return fused < 0 ? fused : 1;
+    CK(launch_bn_bwd_apply(dt, dy, h, mean, rstd, a, sg, E, bn.e_per_sample, Fc, tmp, B, T, C, s));
+    CK(launch_dwconv_bwd(dt, inop, tmp, x, w, dx, dw, dbias, (float*)scratch, B, T, C, k, padl, s));
+    return 0;
 }
 // scratch layout: q | k | vt | lse | delta | maskw (q, k, vt sized for 4-byte elements whatever the dtype)
 struct AttnScratch {

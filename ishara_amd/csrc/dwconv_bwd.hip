@@ -225,13 +225,13 @@ __global__ __launch_bounds__(256, (DwCfg<K, BN>::WPS)) void dwconv_bwd_fused_ker
 // weight gradient, LDS tile + per-thread tap accumulators: thread = 4 channels x all K taps x 4 consecutive time steps
 // of a 32-step tile; the in(x) window slides through registers, so an item costs 2 LDS reads per K*4 FMAs (the older
 // tap-lane mapping below needs 5 reads per 16 FMAs and is LDS-bound).  Accumulators live across the items of the
-// workgroup; lanes are combined with LDS atomics and one partial row per workgroup goes to `part`.
+// workgroup; the time lanes are combined in LDS in a fixed order and one partial row per workgroup goes to `part`.
 template <typename T, int K>
 __global__ __launch_bounds__(256) void dwconv_wgrad_win_kernel(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ part,
                                                                int B, int Tn, int C, int padl, int inop) {
     __shared__ __attribute__((aligned(16))) float xt[(DWG_TT + K - 1) * DW_CT];
     __shared__ __attribute__((aligned(16))) float dt_[DWG_TT * DW_CT];
-    __shared__ float red[(K + 1) * DW_CT];
+    __shared__ __attribute__((aligned(16))) float red[(K + 1) * DW_CT];
     const int tid = threadIdx.x;
     const int c0 = blockIdx.x * DW_CT;
     const int Cin = (inop == DWIN_GLU) ? 2 * C : C;
@@ -299,13 +299,24 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_win_kernel(const T* __restri
         }
     }
     __syncthreads();
+    // the 8 time lanes one after the other: a fixed order of summation, so the gradient repeats bit for bit (LDS float atomics would add
+    // in whatever order the lanes arrive)
+    for (int l = 0; l < 8; ++l) {
+        if (tl == l) {
 #pragma unroll
-    for (int j = 0; j < K; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) atomicAdd(red + j * DW_CT + cl * 4 + e, acc[j][e]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) atomicAdd(red + K * DW_CT + cl * 4 + e, accb[e]);
-    __syncthreads();
+            for (int j = 0; j < K; ++j) {
+                float4* p = reinterpret_cast<float4*>(red + j * DW_CT + cl * 4);
+                float4 v = *p;
+                v.x += acc[j][0]; v.y += acc[j][1]; v.z += acc[j][2]; v.w += acc[j][3];
+                *p = v;
+            }
+            float4* p = reinterpret_cast<float4*>(red + K * DW_CT + cl * 4);
+            float4 v = *p;
+            v.x += accb[0]; v.y += accb[1]; v.z += accb[2]; v.w += accb[3];
+            *p = v;
+        }
+        __syncthreads();
+    }
     // part[(blockIdx.y)][K+1][C]
     float* dst = part + (size_t)blockIdx.y * (K + 1) * C;
     for (int q = tid; q < (K + 1) * DW_CT; q += 256) {

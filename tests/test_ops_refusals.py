@@ -26,6 +26,8 @@ def _ops():
         "ishara_op_dwconv_fwd": lambda L, dt: L.ishara_op_dwconv_fwd(dt, 1, N, N, N, N, N, N, 2, 64, 128, 11, 10, N),
         "ishara_op_dwconv_fwd_ex": lambda L, dt: L.ishara_op_dwconv_fwd_ex(dt, 1, N, N, N, N, N, N, N, 2, 64, 128, 11, 10, N),
         "ishara_op_dwconv_bwd": lambda L, dt: L.ishara_op_dwconv_bwd(dt, 1, N, N, N, N, N, N, N, 2, 64, 128, 11, 10, N),
+        "ishara_op_bn_bwd_apply": lambda L, dt: L.ishara_op_bn_bwd_apply(dt, N, N, N, N, N, N, N, 0, N, N, 2, 64, 128, N),
+        "ishara_op_dwconv_bwd_bn": lambda L, dt: L.ishara_op_dwconv_bwd_bn(dt, 1, N, N, N, N, N, N, N, 0, N, N, N, N, N, N, N, N, 2, 64, 128, 11, 10, N),
         "ishara_op_attn_fwd": lambda L, dt: L.ishara_op_attn_fwd(dt, N, N, 1, 4, 64, 32, f(0.1), 1, 2, f(0.0), 1, N, N),
         "ishara_op_attn_bwd": lambda L, dt: L.ishara_op_attn_bwd(dt, N, N, N, 1, 4, 64, 32, f(0.1), 1, 2, f(0.0), 1, N, N),
         "ishara_op_qkv_fwd": lambda L, dt: L.ishara_op_qkv_fwd(dt, N, N, N, f(1e-6), N, N, N, N, N, 1, 64, 4, 32, 1, N, N),
@@ -62,7 +64,7 @@ def _r4_call(L, name, dt=F32, ptrs=None, mode=4, **kw):
 
 
 CTC_LOSS = ["ishara_ctc_loss", "ishara_op_ctc_loss"]
-BACKWARD = ["ishara_op_dense_bwd", "ishara_op_layernorm_bwd", "ishara_op_dwconv_bwd", "ishara_op_attn_bwd"]
+BACKWARD = ["ishara_op_dense_bwd", "ishara_op_layernorm_bwd", "ishara_op_dwconv_bwd", "ishara_op_bn_bwd_apply", "ishara_op_dwconv_bwd_bn", "ishara_op_attn_bwd"]
 
 
 def _refused(lib, rc, name, *words):
@@ -220,6 +222,61 @@ def test_attention_scratch_layout_is_consistent_and_refuses_bad_shapes(lib):
         assert lo % 256 == do % 256 == mo % 256 == total % 256 == 0 and total - (mo + me) < 256 and do - (lo + le) < 256 and mo - (do + de) < 256
     _refused(lib, lib.ishara_op_attn_scratch_layout_bytes(1, 3, 0, 32, (C.c_int64 * 6)()), "ishara_op_attn_scratch_layout_bytes", ">= 1")
     _refused(lib, lib.ishara_op_attn_scratch_layout_bytes(1, 3, 8, 32, None), "ishara_op_attn_scratch_layout_bytes", "null")
+
+
+# ---- the depthwise-conv backward operators: ishara_op_dwconv_bwd, ishara_op_dwconv_bwd_bn and ishara_op_bn_bwd_apply refuse shapes, a padl
+# outside the kernel and null or misaligned operands before any HIP call
+DWB_OPERANDS = {      # name -> (required operands in call order, optional ones)
+    "ishara_op_dwconv_bwd": (("dy", "x", "w", "dx", "dw"), ("dbias", "scratch")),
+    "ishara_op_bn_bwd_apply": (("dy", "h", "mean", "rstd", "a", "E", "Fc", "dx"), ("sg",)),
+    "ishara_op_dwconv_bwd_bn": (("dy", "h", "mean", "rstd", "a", "E", "Fc", "x", "w", "dx", "dw", "tmp"), ("sg", "dbias", "scratch")),
+}
+
+
+def _dwb_call(L, name, dt=BF16, ptrs=None, **kw):
+    """one call with made-up aligned addresses (a refused call dereferences nothing); `ptrs` replaces single operands by name, `kw` single
+    values of the default shape"""
+    v = dict(B=2, T=64, C=128, k=11, padl=10)
+    assert set(kw) <= set(v), kw
+    v.update(kw)
+    req, opt = DWB_OPERANDS[name]
+    p = {n: C.c_void_p(4096 * (i + 1)) for i, n in enumerate(req + opt)}
+    p.update(ptrs or {})
+    if name == "ishara_op_bn_bwd_apply":
+        return L.ishara_op_bn_bwd_apply(dt, p["dy"], p["h"], p["mean"], p["rstd"], p["a"], p["sg"], p["E"], 0, p["Fc"], p["dx"], v["B"], v["T"], v["C"], N)
+    shape = (v["B"], v["T"], v["C"], v["k"], v["padl"], N)
+    if name == "ishara_op_dwconv_bwd":
+        return L.ishara_op_dwconv_bwd(dt, 1, p["dy"], p["x"], p["w"], p["dx"], p["dw"], p["dbias"], p["scratch"], *shape)
+    return L.ishara_op_dwconv_bwd_bn(dt, 1, p["dy"], p["h"], p["mean"], p["rstd"], p["a"], p["sg"], p["E"], 0, p["Fc"], p["x"], p["w"], p["dx"], p["dw"], p["dbias"],
+                                     p["scratch"], p["tmp"], *shape)
+
+
+DWB_SHAPES = [(dict(B=0), ">= 1"), (dict(B=-3), ">= 1"), (dict(T=0), ">= 1"), (dict(T=-1), ">= 1"), (dict(B=65536), "too large"),
+              (dict(C=0), "multiple of 8"), (dict(C=12), "multiple of 8"), (dict(C=-8), "multiple of 8")]
+DWB_KERNELS = [(dict(k=0, padl=0), "kernel size 0"), (dict(k=32, padl=0), "kernel size 32"), (dict(k=-1, padl=0), "kernel size -1"),
+               (dict(padl=-1), "padl=-1"), (dict(padl=11), "padl=11"), (dict(k=1, padl=1), "padl=1"), (dict(k=5, padl=5), "padl=5")]
+
+
+DWB_ROWS = [(n, kw, word) for n in sorted(DWB_OPERANDS) for kw, word in DWB_SHAPES + (DWB_KERNELS if n != "ishara_op_bn_bwd_apply" else [])]      # (the BatchNorm backward has no kernel size)
+
+
+@pytest.mark.parametrize("name,kw,word", DWB_ROWS, ids=lambda v: "-".join(f"{k}{x}" for k, x in v.items()) if isinstance(v, dict) else None)
+def test_dwconv_backward_refuses_shapes_and_paddings(lib, name, kw, word):
+    _refused(lib, _dwb_call(lib, name, **kw), name, word)
+
+
+@pytest.mark.parametrize("name", sorted(DWB_OPERANDS))
+def test_dwconv_backward_refuses_null_and_misaligned_buffers(lib, name):
+    req, opt = DWB_OPERANDS[name]
+    for i, n in enumerate(req):      # the message names the operand at fault
+        _refused(lib, _dwb_call(lib, name, ptrs={n: N}), name, "null " + n)
+        for off in (2, 4, 8):
+            _refused(lib, _dwb_call(lib, name, ptrs={n: C.c_void_p(4096 * (i + 1) + off)}), name, "misaligned " + n + ":", "16-byte")
+    for n in opt:                    # optional operands may be NULL (the call then gets as far as the next check) but not off 16 bytes
+        _refused(lib, _dwb_call(lib, name, ptrs={n: C.c_void_p(1 << 20 | 8)}), name, "misaligned optional", "16-byte")
+        _refused(lib, _dwb_call(lib, name, ptrs={n: N, req[0]: N}), name, "null " + req[0])
+    for dt in (F32, BF16):           # the checks do not depend on the dtype
+        _refused(lib, _dwb_call(lib, name, dt=dt, ptrs={req[-1]: N}), name, "null " + req[-1])
 
 
 # (dt, M, K, C, route): shapes / dtypes the named route has no kernel for

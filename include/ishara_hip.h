@@ -166,6 +166,17 @@ int ishara_profile_report(ishara_model* m, char* buf, int32_t cap);
  * 1 <= T <= 4096, C >= 1, 0 <= blank < C, no null buffer; anything else is refused with a message before any HIP call. */
 int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank,
                          int32_t* out_idx, int32_t* out_len, ishara_stream s);
+/* Per-clip frame counts: the four *_ex entry points below take their sibling's arguments plus frame_len [B] int32 in device memory (4-byte
+ * aligned; NULL: every sample has T frames and the outputs are bit-equal to the sibling's).  The buffer's T stays the stride of every
+ * array and sizes the workspace; sample b uses its first Tb = frame_len[b] frames only and computes, bit for bit, what its sibling computes
+ * when launched on that sample alone at T = Tb.  Rows t >= Tb of the logits are not read (they may hold NaN).  Past the sample's end
+ * out_idx is -1, frame_pos is -1 and dlogits is +0.  A frame_len[b] outside [1, T] is never used as an index or a bound: the sample has no
+ * frames (greedy: out_len 0; beam: every slot len -1, score -inf; align: the no-alignment constants; loss: nll 1e30, dlogits +0) and the
+ * other samples' outputs are bit-identical to a launch without it.  Everything the sibling refuses is refused, in the same way; nothing is
+ * read on the host, so the calls are graph-capturable.
+ * ishara_greedy_decode_ex: the run that is never emitted is the one that ends at frame Tb - 1. */
+int ishara_greedy_decode_ex(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank,
+                            int32_t* out_idx, int32_t* out_len, const int32_t* frame_len, ishara_stream s);
 /* pre_process1(*pre_process00(x)) of the TFLite wrapper (c3:61-115, c13:9-15): raw [max_frames,276] landmarks with NaNs
  * (SEL_COLS order, c1:22-26), clip length read from device memory (*n_frames), mean/std [276] in output order
  * -> out [T,276].  One kernel, graph-capturable. */
@@ -195,6 +206,10 @@ int64_t ishara_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t C, int32_t
 int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
                            const float* lm, float alpha, float beta, void* workspace,
                            int32_t* out_idx, int32_t* out_len, float* out_score, ishara_stream s);
+/* with per-clip frame counts (see ishara_greedy_decode_ex); workspace as for ishara_ctc_beam_decode at the buffer's T */
+int ishara_ctc_beam_decode_ex(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
+                              const float* lm, float alpha, float beta, void* workspace,
+                              int32_t* out_idx, int32_t* out_len, float* out_score, const int32_t* frame_len, ishara_stream s);
 
 /* CTC forced alignment (Viterbi) of known labels; the semantics of ishara_amd/ctc_align.py.  logits [B,T,C] fp32, labels [B,L] int64 padded
  * with blank (the label of a row ends at its first blank).  The path maximises the sum of the raw logits along it, carried in fp64, ties
@@ -209,6 +224,10 @@ int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T, int32_t C,
 int64_t ishara_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t L);
 int ishara_ctc_align(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
                      void* ws, int32_t* frame_pos, int32_t* start, int32_t* end, float* conf, float* score, ishara_stream s);
+/* with per-clip frame counts (see ishara_greedy_decode_ex): feasibility is Tb >= len + repeats; ws as for ishara_ctc_align at the buffer's T */
+int ishara_ctc_align_ex(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                        void* ws, int32_t* frame_pos, int32_t* start, int32_t* end, float* conf, float* score,
+                        const int32_t* frame_len, ishara_stream s);
 
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */
@@ -242,6 +261,15 @@ int64_t ishara_ctc_workspace_bytes(int32_t B, int32_t T, int32_t L);
 int ishara_ctc_loss(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C,
                     int32_t L, int32_t blank, float* nll, float* dlogits, float grad_scale,
                     void* ws, ishara_stream s);
+/* with per-clip frame counts (see ishara_greedy_decode_ex): logit_length = frame_len[b], torch's input_lengths.  A sample whose label does
+ * not fit its own Tb (Tb < len + repeats) is infeasible as above on its Tb rows; dlogits[b, t >= Tb] = +0 always.  sample_scale [B] f32 in
+ * device memory (4-byte aligned, may be NULL) multiplies grad_scale for that sample's dlogits, not its nll: a reduction's per-sample weight.
+ * flags: ISHARA_CTC_ZERO_INFEASIBLE makes every dlogits row of an infeasible sample +0 (torch's zero_infinity); nll stays 1e30.  Unknown
+ * flag bits are refused.  ws = ishara_ctc_workspace_bytes(B, T, L). */
+enum { ISHARA_CTC_ZERO_INFEASIBLE = 1 };
+int ishara_ctc_loss_ex(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C,
+                       int32_t L, int32_t blank, float* nll, float* dlogits, float grad_scale,
+                       void* ws, const int32_t* frame_len, const float* sample_scale, uint32_t flags, ishara_stream s);
 /* The dropout mask the kernels draw for (seed, site): out [rows, cols] f32 (0 or 1/(1-rate)). */
 int ishara_dropout_mask(uint32_t seed, uint32_t site, int32_t rows, int32_t cols, float rate,
                         float* out, ishara_stream s);

@@ -82,16 +82,20 @@ SIGNATURES = {
     "ishara_profile_enable": (C.c_int, [_P, _I32]),
     "ishara_profile_report": (C.c_int, [_P, C.c_char_p, _I32]),
     "ishara_greedy_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "ishara_greedy_decode_ex": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "ishara_preprocess": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _P]),
     "ishara_preprocess_batch": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _I32, _P]),
     "ishara_edit_distance": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P]),
     "ishara_ctc_beam_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_ctc_beam_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "ishara_ctc_beam_decode_ex": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "ishara_ctc_align_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_ctc_align": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "ishara_ctc_align_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ishara_clip_batch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "ishara_ctc_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_ctc_loss": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P]),
+    "ishara_ctc_loss_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P, _P, _U32, _P]),
     "ishara_op_ctc_loss": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P, _P]),
     "ishara_dropout_mask": (C.c_int, [_U32, _U32, _I32, _I32, _F, _P, _P]),
     "ishara_debug_set_as_flags": (C.c_int, [_I32]),

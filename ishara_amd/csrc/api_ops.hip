@@ -28,8 +28,13 @@ __global__ void qkv_split_kernel(const T* qkv, T* q, T* k, T* vt, int B, int H, 
 
 // ------------------------------------------------------------------ stand-alone entry points
 // CTC loss and greedy decode: what a launch would fault or fail on is refused here, before any HIP call, each with a message of its own
-extern "C" int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t* out_idx, int32_t* out_len, ishara_stream s) {
-    const char* me = "ishara_greedy_decode";
+// the *_ex entry points (per-sample frame counts) refuse what their fixed-T siblings refuse, through the same checks, plus a misaligned length array
+static bool len_misaligned(const char* me, const char* what, const void* p) {
+    if ((uintptr_t)p % 4) { ishara_set_error("%s: %s must be 4-byte aligned", me, what); return true; }
+    return false;
+}
+static int greedy_decode_checked(const char* me, const float* logits, int B, int T, int C, int blank, int* out_idx, int* out_len, bool ex,
+                                 const int* frame_len, hipStream_t s) {
     if (B < 0) { ishara_set_error("%s: B=%d < 0", me, B); return -1; }
     if (T < 1) { ishara_set_error("%s: T=%d < 1", me, T); return -1; }
     if (T > 4096) { ishara_set_error("%s: T=%d too large (max 4096: one LDS word per frame)", me, T); return -1; }
@@ -37,11 +42,21 @@ extern "C" int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, i
     if (blank < 0 || blank >= C) { ishara_set_error("%s: blank %d outside 0..%d", me, blank, C - 1); return -1; }
     if (B == 0) return 0;
     if (!logits || !out_idx || !out_len) { ishara_set_error("%s: null logits / out_idx / out_len", me); return -1; }
-    return launch_greedy_decode(logits, B, T, C, blank, out_idx, out_len, (hipStream_t)s);
+    if (len_misaligned(me, "frame_len", frame_len)) return -1;
+    return ex ? launch_greedy_decode_len(logits, B, T, C, blank, out_idx, out_len, frame_len, s)
+              : launch_greedy_decode(logits, B, T, C, blank, out_idx, out_len, s);
+}
+extern "C" int ishara_greedy_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t* out_idx, int32_t* out_len, ishara_stream s) {
+    return greedy_decode_checked("ishara_greedy_decode", logits, B, T, C, blank, out_idx, out_len, false, nullptr, (hipStream_t)s);
+}
+extern "C" int ishara_greedy_decode_ex(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t* out_idx, int32_t* out_len,
+                                       const int32_t* frame_len, ishara_stream s) {
+    return greedy_decode_checked("ishara_greedy_decode_ex", logits, B, T, C, blank, out_idx, out_len, true, frame_len, (hipStream_t)s);
 }
 extern "C" int64_t ishara_ctc_workspace_bytes(int32_t B, int32_t T, int32_t L) { return (int64_t)(ctc_workspace_floats(B, T, L) * sizeof(float)); }
 static int ctc_loss_checked(const char* me, const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank,
-                            float* nll, float* dlogits, float grad_scale, void* ws, hipStream_t s, void* dlb) {
+                            float* nll, float* dlogits, float grad_scale, void* ws, hipStream_t s, void* dlb, bool ex = false,
+                            const int* frame_len = nullptr, const float* sample_scale = nullptr, uint32_t flags = 0) {
     if (B < 0) { ishara_set_error("%s: B=%d < 0", me, B); return -1; }
     if (T < 1) { ishara_set_error("%s: T=%d < 1", me, T); return -1; }
     if (L < 1 || L > 255) { ishara_set_error("%s: L=%d outside 1..255 (2L+1 lattice states in at most 8 registers of a 64-lane wave)", me, L); return -1; }
@@ -52,11 +67,21 @@ static int ctc_loss_checked(const char* me, const float* logits, const int64_t* 
                          me, T, L, ctc_lds_bytes(T, L), ctc_lds_limit(), (ctc_lds_limit() - ctc_lds_bytes(0, L)) / 4);
         return -1;
     }
+    if (flags & ~(uint32_t)ISHARA_CTC_ZERO_INFEASIBLE) { ishara_set_error("%s: unknown flag bits 0x%x (known: ISHARA_CTC_ZERO_INFEASIBLE = 1)", me, flags & ~(uint32_t)ISHARA_CTC_ZERO_INFEASIBLE); return -1; }
     if (B == 0) return 0;
     if (!logits || !labels || !nll || !ws) { ishara_set_error("%s: null logits / labels / nll / ws (dlogits may be NULL)", me); return -1; }
     if ((uintptr_t)ws % 8) { ishara_set_error("%s: ws must be 8-byte aligned (fp64 lattices)", me); return -1; }
     if ((uintptr_t)dlb % 4) { ishara_set_error("%s: dlb must be 4-byte aligned (packed bf16 pairs)", me); return -1; }
+    if (len_misaligned(me, "frame_len", frame_len) || len_misaligned(me, "sample_scale", sample_scale)) return -1;
+    if (ex) return launch_ctc_len(logits, labels, B, T, C, L, blank, nll, dlogits, grad_scale, (float*)ws, frame_len, sample_scale,
+                                  (flags & ISHARA_CTC_ZERO_INFEASIBLE) ? 1 : 0, s);
     return launch_ctc(logits, labels, B, T, C, L, blank, nll, dlogits, grad_scale, (float*)ws, s, dlb);
+}
+extern "C" int ishara_ctc_loss_ex(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                                  float* nll, float* dlogits, float grad_scale, void* ws, const int32_t* frame_len, const float* sample_scale,
+                                  uint32_t flags, ishara_stream s) {
+    return ctc_loss_checked("ishara_ctc_loss_ex", logits, labels, B, T, C, L, blank, nll, dlogits, grad_scale, ws, (hipStream_t)s, nullptr, true,
+                            frame_len, sample_scale, flags);
 }
 extern "C" int ishara_ctc_loss(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
                                float* nll, float* dlogits, float grad_scale, void* ws, ishara_stream s) {
@@ -107,27 +132,40 @@ extern "C" int64_t ishara_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t
     if (B < 0 || T < 1 || T > 4096 || beam_width < 1 || beam_width > 32) return -1;
     return (int64_t)B * (int64_t)ctc_beam_workspace_words(T, beam_width) * 4;
 }
+static int ctc_beam_checked(const char* me, const float* logits, int B, int T, int C, int blank, int beam_width, int nbest, const float* lm,
+                            float alpha, float beta, void* workspace, int* out_idx, int* out_len, float* out_score, bool ex, const int* frame_len,
+                            hipStream_t s) {
+    if (C < 2 || C > 64) { ishara_set_error("%s: C=%d unsupported (2..64: one lane per class)", me, C); return -1; }
+    if (blank < 0 || blank >= C) { ishara_set_error("%s: blank %d outside 0..%d", me, blank, C - 1); return -1; }
+    if (beam_width < 1 || beam_width > 32) { ishara_set_error("%s: beam_width %d unsupported (1..32)", me, beam_width); return -1; }
+    if (nbest < 1 || nbest > beam_width) { ishara_set_error("%s: nbest %d outside 1..beam_width=%d", me, nbest, beam_width); return -1; }
+    if (B < 0 || B > 2147483647 / 2 || T < 1 || T > 4096) { ishara_set_error("%s: B=%d T=%d unsupported (B >= 0, 1 <= T <= 4096)", me, B, T); return -1; }
+    if (!(alpha == alpha && beta == beta) || alpha - alpha != 0.0f || beta - beta != 0.0f) { ishara_set_error("%s: alpha and beta must be finite", me); return -1; }
+    if (B > 0 && (!logits || !workspace || !out_idx || !out_len || !out_score)) { ishara_set_error("%s: null argument", me); return -1; }
+    if ((uintptr_t)workspace % 4) { ishara_set_error("%s: workspace must be 4-byte aligned", me); return -1; }
+    if (len_misaligned(me, "frame_len", frame_len)) return -1;
+    return ex ? launch_ctc_beam_len(logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len, out_score, frame_len, s)
+              : launch_ctc_beam(logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len, out_score, s);
+}
 extern "C" int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
                                       const float* lm, float alpha, float beta, void* workspace,
                                       int32_t* out_idx, int32_t* out_len, float* out_score, ishara_stream s) {
-    if (C < 2 || C > 64) { ishara_set_error("ishara_ctc_beam_decode: C=%d unsupported (2..64: one lane per class)", C); return -1; }
-    if (blank < 0 || blank >= C) { ishara_set_error("ishara_ctc_beam_decode: blank %d outside 0..%d", blank, C - 1); return -1; }
-    if (beam_width < 1 || beam_width > 32) { ishara_set_error("ishara_ctc_beam_decode: beam_width %d unsupported (1..32)", beam_width); return -1; }
-    if (nbest < 1 || nbest > beam_width) { ishara_set_error("ishara_ctc_beam_decode: nbest %d outside 1..beam_width=%d", nbest, beam_width); return -1; }
-    if (B < 0 || B > 2147483647 / 2 || T < 1 || T > 4096) { ishara_set_error("ishara_ctc_beam_decode: B=%d T=%d unsupported (B >= 0, 1 <= T <= 4096)", B, T); return -1; }
-    if (!(alpha == alpha && beta == beta) || alpha - alpha != 0.0f || beta - beta != 0.0f) { ishara_set_error("ishara_ctc_beam_decode: alpha and beta must be finite"); return -1; }
-    if (B > 0 && (!logits || !workspace || !out_idx || !out_len || !out_score)) { ishara_set_error("ishara_ctc_beam_decode: null argument"); return -1; }
-    if ((uintptr_t)workspace % 4) { ishara_set_error("ishara_ctc_beam_decode: workspace must be 4-byte aligned"); return -1; }
-    return launch_ctc_beam(logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len, out_score, (hipStream_t)s);
+    return ctc_beam_checked("ishara_ctc_beam_decode", logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len,
+                            out_score, false, nullptr, (hipStream_t)s);
+}
+extern "C" int ishara_ctc_beam_decode_ex(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
+                                         const float* lm, float alpha, float beta, void* workspace,
+                                         int32_t* out_idx, int32_t* out_len, float* out_score, const int32_t* frame_len, ishara_stream s) {
+    return ctc_beam_checked("ishara_ctc_beam_decode_ex", logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len,
+                            out_score, true, frame_len, (hipStream_t)s);
 }
 // CTC forced alignment: refused before any HIP call, as the loss is
 extern "C" int64_t ishara_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t L) {
     if (B < 0 || T < 1 || T > 4096 || L < 1 || L > 255) return -1;
     return (int64_t)ctc_align_workspace_bytes(B, T, L);
 }
-extern "C" int ishara_ctc_align(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
-                                void* ws, int32_t* frame_pos, int32_t* start, int32_t* end, float* conf, float* score, ishara_stream s) {
-    const char* me = "ishara_ctc_align";
+static int ctc_align_checked(const char* me, const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws,
+                             int* frame_pos, int* start, int* end, float* conf, float* score, bool ex, const int* frame_len, hipStream_t s) {
     if (B < 0) { ishara_set_error("%s: B=%d < 0", me, B); return -1; }
     if (T < 1 || T > 4096) { ishara_set_error("%s: T=%d outside 1..4096", me, T); return -1; }
     if (L < 1 || L > 255) { ishara_set_error("%s: L=%d outside 1..255 (2L+1 lattice states in at most 8 registers of a 64-lane wave)", me, L); return -1; }
@@ -138,7 +176,18 @@ extern "C" int ishara_ctc_align(const float* logits, const int64_t* labels, int3
         ishara_set_error("%s: null logits / labels / ws / frame_pos / start / end / conf / score", me); return -1;
     }
     if ((uintptr_t)ws % 16) { ishara_set_error("%s: ws must be 16-byte aligned", me); return -1; }
-    return launch_ctc_align(logits, labels, B, T, C, L, blank, ws, frame_pos, start, end, conf, score, (hipStream_t)s);
+    if (len_misaligned(me, "frame_len", frame_len)) return -1;
+    return ex ? launch_ctc_align_len(logits, labels, B, T, C, L, blank, ws, frame_pos, start, end, conf, score, frame_len, s)
+              : launch_ctc_align(logits, labels, B, T, C, L, blank, ws, frame_pos, start, end, conf, score, s);
+}
+extern "C" int ishara_ctc_align(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                                void* ws, int32_t* frame_pos, int32_t* start, int32_t* end, float* conf, float* score, ishara_stream s) {
+    return ctc_align_checked("ishara_ctc_align", logits, labels, B, T, C, L, blank, ws, frame_pos, start, end, conf, score, false, nullptr, (hipStream_t)s);
+}
+extern "C" int ishara_ctc_align_ex(const float* logits, const int64_t* labels, int32_t B, int32_t T, int32_t C, int32_t L, int32_t blank,
+                                   void* ws, int32_t* frame_pos, int32_t* start, int32_t* end, float* conf, float* score,
+                                   const int32_t* frame_len, ishara_stream s) {
+    return ctc_align_checked("ishara_ctc_align_ex", logits, labels, B, T, C, L, blank, ws, frame_pos, start, end, conf, score, true, frame_len, (hipStream_t)s);
 }
 extern "C" int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
                                  float* x, ishara_stream s) {

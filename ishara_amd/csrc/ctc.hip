@@ -49,21 +49,39 @@ DEVI double shfl_down_d(double v, int d) { return __shfl_down(v, d, 64); }
 //   phase 2 (all threads)  state posteriors exp(alpha + bsum - logp) scatter-added to classes in LDS, one frame per wave at
 //                          a time; dlogits = grad_scale * (softmax - posterior)
 // ---------------------------------------------------------------------------------------------------------------
-template <int NS>
+//
+// VL (per-sample frame counts, ishara_ctc_loss_ex): Ts, the buffer's T, stays the stride of every row offset and of the LDS layout; the sample's
+// own count Tn = frame_len[b] takes every other role, so the sample computes what a one-sample launch at T = Tn on logits[b, :Tn] computes,
+// and rows t >= Tn are not read.  dlogits[b, t >= Tn] = +0.  A frame_len[b] outside [1, Ts] is never an index or a bound: the sample has no
+// frames (nll = 1e30, every dlogits row +0).  sample_scale[b] multiplies grad_scale; zero_inf makes an infeasible sample's gradient +0.
+// With VL = false Tn is Ts and the three extra arguments are not read: the code of the fixed-T entry points.
+template <int NS, bool VL>
 __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
-                                                  int Tn, int C, int L, int blank, float* __restrict__ nll,
+                                                  int Ts, int C, int L, int blank, float* __restrict__ nll,
                                                   float* __restrict__ dlogits, float grad_scale, double* __restrict__ ws,
-                                                  uint32_t* __restrict__ dlb) {
+                                                  uint32_t* __restrict__ dlb, const int* __restrict__ frame_len,
+                                                  const float* __restrict__ sample_scale, int zero_inf) {
     constexpr int SP = 64 * NS;
     extern __shared__ float shf[];
-    float* lse = shf;                                   // [Tn]
-    int* ext = reinterpret_cast<int*>(lse + Tn);        // [SP]
+    float* lse = shf;                                   // [Ts]
+    int* ext = reinterpret_cast<int*>(lse + Ts);        // [SP]
     __shared__ int s_len, s_bad;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const float* lg = logits + (size_t)b * Tn * C;
+    int Tn = Ts;
+    if (VL) {
+        if (frame_len) Tn = frame_len[b];
+        if (Tn < 1 || Tn > Ts) {                        // no frames (workgroup-uniform): the sentinel and a zero gradient
+            if (tid == 0) nll[b] = 1e30f;
+            if (dlogits)
+                for (size_t i = tid; i < (size_t)Ts * C; i += 256) dlogits[(size_t)b * Ts * C + i] = 0.f;
+            return;
+        }
+        if (sample_scale) grad_scale *= sample_scale[b];
+    }
+    const float* lg = logits + (size_t)b * Ts * C;
     const int64_t* lab = labels + (size_t)b * L;
-    double* Gw = ws + (size_t)b * 2 * Tn * SP;          // [Tn][SP] alpha
-    double* Hw = Gw + (size_t)Tn * SP;                  // [Tn][SP] bsum
+    double* Gw = ws + (size_t)b * 2 * Ts * SP;          // [Ts][SP] alpha
+    double* Hw = Gw + (size_t)Ts * SP;                  // [Ts][SP] bsum
     __shared__ double s_logp;
 
     // a label outside [0, C) makes the sample infeasible (header comment); it enters ext as blank, so nothing below indexes with it
@@ -248,8 +266,14 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
         constexpr int U = 4;
         __shared__ float cls[4][U][64];
         const double logp = s_logp;
-        float* dl = dlogits + (size_t)b * Tn * C;
+        float* dl = dlogits + (size_t)b * Ts * C;
         const int wv = tid >> 6;
+        if (VL) {
+            const bool dead = zero_inf && !(logp > -1e29);        // zero_infinity: an infeasible sample's rows are +0 as well
+            const int t0 = dead ? 0 : Tn;
+            for (size_t i = (size_t)t0 * C + tid; i < (size_t)Ts * C; i += 256) dl[i] = 0.f;
+            if (dead) return;
+        }
         for (int t0 = wv; t0 < Tn; t0 += 4 * U) {
             double al[U][NS], bs[U][NS];
             float lgv[U];
@@ -285,24 +309,37 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
                     const float lo = __shfl(gv, (2 * lane) & 63, 64), hi = __shfl(gv, (2 * lane + 1) & 63, 64);
                     typedef __attribute__((ext_vector_type(2))) __bf16 ctc_bf2;
                     ctc_bf2 pk; pk[0] = (__bf16)(lane < 32 ? lo : 0.f); pk[1] = (__bf16)(lane < 32 ? hi : 0.f);
-                    dlb[((size_t)b * Tn + t) * 64 + lane] = __builtin_bit_cast(uint32_t, pk);
+                    dlb[((size_t)b * Ts + t) * 64 + lane] = __builtin_bit_cast(uint32_t, pk);
                 }
             }
         }
     }
 }
 
+#define CTC_L(NS, VL, FL, SS, ZI) hipLaunchKernelGGL((ctc_kernel<NS, VL>), dim3(B), dim3(256), shmem, s, logits, labels, T, C, L, blank, nll, dlogits, grad_scale, reinterpret_cast<double*>(ws), reinterpret_cast<uint32_t*>(dlb), FL, SS, ZI)
+#define CTC_NS(VL, FL, SS, ZI) switch (ns) { case 1: CTC_L(1, VL, FL, SS, ZI); break; case 2: CTC_L(2, VL, FL, SS, ZI); break; case 3: CTC_L(3, VL, FL, SS, ZI); break; \
+                  case 4: CTC_L(4, VL, FL, SS, ZI); break; case 5: CTC_L(5, VL, FL, SS, ZI); break; case 6: CTC_L(6, VL, FL, SS, ZI); break; \
+                  case 7: CTC_L(7, VL, FL, SS, ZI); break; default: CTC_L(8, VL, FL, SS, ZI); break; }
 int launch_ctc(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank,
                float* nll, float* dlogits, float grad_scale, float* ws, hipStream_t s, void* dlb) {
     if (2 * L + 1 > 512 || C > 64) { ishara_set_error("ctc: L=%d (max 255) or C=%d (max 64) unsupported", L, C); return -1; }
     const int ns = ctc_ns(L);
     const size_t shmem = ctc_lds_bytes(T, L);
-#define CTC_L(NS) hipLaunchKernelGGL(ctc_kernel<NS>, dim3(B), dim3(256), shmem, s, logits, labels, T, C, L, blank, nll, dlogits, grad_scale, reinterpret_cast<double*>(ws), reinterpret_cast<uint32_t*>(dlb))
-    switch (ns) { case 1: CTC_L(1); break; case 2: CTC_L(2); break; case 3: CTC_L(3); break; case 4: CTC_L(4); break;
-                  case 5: CTC_L(5); break; case 6: CTC_L(6); break; case 7: CTC_L(7); break; default: CTC_L(8); break; }
-#undef CTC_L
+    CTC_NS(false, (const int*)nullptr, (const float*)nullptr, 0)
     return launch_rc();
 }
+// per-sample frame counts (the VL instantiations): frame_len [B] int32 and sample_scale [B] f32 on the device, either may be NULL
+int launch_ctc_len(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, float* nll, float* dlogits,
+                   float grad_scale, float* ws, const int* frame_len, const float* sample_scale, int zero_inf, hipStream_t s) {
+    if (2 * L + 1 > 512 || C > 64) { ishara_set_error("ctc: L=%d (max 255) or C=%d (max 64) unsupported", L, C); return -1; }
+    const int ns = ctc_ns(L);
+    const size_t shmem = ctc_lds_bytes(T, L);
+    void* dlb = nullptr;
+    CTC_NS(true, frame_len, sample_scale, zero_inf)
+    return launch_rc();
+}
+#undef CTC_NS
+#undef CTC_L
 
 __global__ void mean_kernel(const float* __restrict__ v, float* __restrict__ out, int n, float scale) {
     __shared__ float red[4];
@@ -320,13 +357,18 @@ int launch_mean(const float* v, float* out, int n, float scale, hipStream_t s) {
 
 // greedy decode: argmax per frame (first max on ties), keep x[i] (i <= T-2) where
 // x[i] != x[i+1], drop blanks (the reference never emits the final run, c8:7-9).
-__global__ __launch_bounds__(256) void greedy_decode_kernel(const float* __restrict__ logits, int Tn, int C, int blank,
-                                                            int* __restrict__ out_idx, int* __restrict__ out_len) {
-    extern __shared__ int shi[];   // am[Tn]
+// VL: the sample has Tn = frame_len[b] frames of the buffer's Ts (the stride, and the width of the -1 padding); outside [1, Ts]: none.
+template <bool VL>
+__global__ __launch_bounds__(256) void greedy_decode_kernel(const float* __restrict__ logits, int Ts, int C, int blank,
+                                                            int* __restrict__ out_idx, int* __restrict__ out_len,
+                                                            const int* __restrict__ frame_len) {
+    extern __shared__ int shi[];   // am[Ts]
     int* am = shi;
     __shared__ int s_wcnt[4], s_base;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const float* lg = logits + (size_t)b * Tn * C;
+    int Tn = Ts;
+    if (VL && frame_len) { Tn = frame_len[b]; if (Tn < 1 || Tn > Ts) Tn = 0; }
+    const float* lg = logits + (size_t)b * Ts * C;
     for (int t = tid; t < Tn; t += blockDim.x) {
         float best = lg[(size_t)t * C];
         int bi = 0;
@@ -352,17 +394,21 @@ __global__ __launch_bounds__(256) void greedy_decode_kernel(const float* __restr
         __syncthreads();
         int off = s_base;
         for (int w = 0; w < wid; ++w) off += s_wcnt[w];
-        if (keep) out_idx[(size_t)b * Tn + off + before] = am[t];
+        if (keep) out_idx[(size_t)b * Ts + off + before] = am[t];
         __syncthreads();
         if (tid == 0) s_base += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
         __syncthreads();
     }
     const int n = s_base;
     if (tid == 0) out_len[b] = n;
-    for (int t = n + tid; t < Tn; t += blockDim.x) out_idx[(size_t)b * Tn + t] = -1;      // the -1 padding (was a fill launch of its own)
+    for (int t = n + tid; t < Ts; t += blockDim.x) out_idx[(size_t)b * Ts + t] = -1;      // the -1 padding (was a fill launch of its own)
 }
 
 int launch_greedy_decode(const float* logits, int B, int T, int C, int blank, int* out_idx, int* out_len, hipStream_t s) {
-    hipLaunchKernelGGL(greedy_decode_kernel, dim3(B), dim3(256), T * sizeof(int), s, logits, T, C, blank, out_idx, out_len);
+    hipLaunchKernelGGL(greedy_decode_kernel<false>, dim3(B), dim3(256), T * sizeof(int), s, logits, T, C, blank, out_idx, out_len, (const int*)nullptr);
+    return launch_rc();
+}
+int launch_greedy_decode_len(const float* logits, int B, int T, int C, int blank, int* out_idx, int* out_len, const int* frame_len, hipStream_t s) {
+    hipLaunchKernelGGL(greedy_decode_kernel<true>, dim3(B), dim3(256), T * sizeof(int), s, logits, T, C, blank, out_idx, out_len, frame_len);
     return launch_rc();
 }

@@ -39,21 +39,27 @@ DEVI double wave_ror1(double v) {
     return __hiloint2double(hi, lo);
 }
 
-template <int NS, bool BPLDS>
-__global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int Tn, int C, int L,
+// VL (ishara_ctc_align_ex): the sample has Tn = frame_len[b] frames of the buffer's Ts; Ts stays the stride of the logits, of frame_pos, of
+// the back-pointer workspace and of the LDS layout, Tn takes every other role and frame_pos[b, t >= Tn] = -1.  A frame_len[b] outside
+// [1, Ts] is a sample without an alignment.
+template <int NS, bool BPLDS, bool VL>
+__global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int Ts, int C, int L,
                                                         int blank, uint16_t* __restrict__ ws, int* __restrict__ frame_pos, int* __restrict__ start,
-                                                        int* __restrict__ end, float* __restrict__ conf, float* __restrict__ score) {
+                                                        int* __restrict__ end, float* __restrict__ conf, float* __restrict__ score,
+                                                        const int* __restrict__ frame_len) {
     constexpr int SP = 64 * NS;
     extern __shared__ float2 sh_ms[];
-    float2* ms = sh_ms;                                          // [Tn] (m_t, sum_c expf(x_c - m_t)); phase 2 puts the emitted symbol's softmax in .x
-    int* ext = reinterpret_cast<int*>(ms + Tn);                  // [SP]
-    uint16_t* bp = BPLDS ? reinterpret_cast<uint16_t*>(ext + SP) : ws + (size_t)blockIdx.x * Tn * 64;      // [Tn][64]
+    float2* ms = sh_ms;                                          // [Ts] (m_t, sum_c expf(x_c - m_t)); phase 2 puts the emitted symbol's softmax in .x
+    int* ext = reinterpret_cast<int*>(ms + Ts);                  // [SP]
+    uint16_t* bp = BPLDS ? reinterpret_cast<uint16_t*>(ext + SP) : ws + (size_t)blockIdx.x * Ts * 64;      // [Ts][64]
     __shared__ int s_len;
     __shared__ double s_red[2][4], s_v;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* lg = logits + (size_t)b * Tn * C;
+    int Tn = Ts;
+    if (VL && frame_len) { Tn = frame_len[b]; if (Tn < 1 || Tn > Ts) Tn = 0; }
+    const float* lg = logits + (size_t)b * Ts * C;
     const int64_t* lab = labels + (size_t)b * L;
-    int* fpos = frame_pos + (size_t)b * Tn;
+    int* fpos = frame_pos + (size_t)b * Ts;
     int* st = start + (size_t)b * L;
     int* en = end + (size_t)b * L;
     float* cf = conf + (size_t)b * L;
@@ -68,12 +74,14 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict_
     const int rep = __syncthreads_count(tid >= 1 && tid < len && mine == lab[tid >= 1 ? tid - 1 : 0]);
     const int bad = __syncthreads_or(tid < len && (mine < 0 || mine >= C));
     if (tid < L) { st[tid] = -1; en[tid] = -1; }
-    if (bad || Tn < len + rep) {                                 // no alignment (workgroup-uniform): the contract's constants
-        for (int t = tid; t < Tn; t += 256) fpos[t] = -1;
+    if (bad || Tn < len + rep || (VL && Tn == 0)) {              // no alignment (workgroup-uniform): the contract's constants
+        for (int t = tid; t < Ts; t += 256) fpos[t] = -1;
         if (tid < L) cf[tid] = 0.f;
         if (tid == 0) score[b] = -1e30f;
         return;
     }
+    if (VL)
+        for (int t = Tn + tid; t < Ts; t += 256) fpos[t] = -1;
     for (int s = tid; s < SP; s += 256) {
         const int64_t v = ((s & 1) && (s >> 1) < len) ? lab[s >> 1] : (int64_t)blank;
         ext[s] = (v < 0 || v >= C) ? blank : (int)v;
@@ -237,8 +245,9 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict_
     }
 }
 
-int launch_ctc_align(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws, int* frame_pos, int* start,
-                     int* end, float* conf, float* score, hipStream_t s) {
+template <bool VL>
+static int launch_ctc_align_t(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws, int* frame_pos, int* start,
+                              int* end, float* conf, float* score, const int* frame_len, hipStream_t s) {
     const int ns = align_ns(L);
     if (ns < 1 || ns > 8 || C > 64) { ishara_set_error("ctc_align: L=%d (max 255) or C=%d (max 64) unsupported", L, C); return -1; }
     const bool fast = ctc_align_bp_in_lds(T, L);
@@ -247,15 +256,15 @@ int launch_ctc_align(const float* logits, const int64_t* labels, int B, int T, i
         if (shmem + ALIGN_LDS_STATIC > ALIGN_LDS_DEFAULT) {      /* more than every launch is granted: raise the kernel's limit once */ \
             static bool raised = false; \
             if (!raised) { \
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_align_kernel<NS, F>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_align_kernel<NS, F, VL>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                         (int)(ALIGN_LDS_MAX - ALIGN_LDS_STATIC)) != hipSuccess) { \
                     ishara_set_error("ctc_align: cannot reserve %zu bytes of LDS", shmem); return -2; \
                 } \
                 raised = true; \
             } \
         } \
-        hipLaunchKernelGGL((ctc_align_kernel<NS, F>), dim3(B), dim3(256), shmem, s, logits, labels, T, C, L, blank, reinterpret_cast<uint16_t*>(ws), \
-                           frame_pos, start, end, conf, score); \
+        hipLaunchKernelGGL((ctc_align_kernel<NS, F, VL>), dim3(B), dim3(256), shmem, s, logits, labels, T, C, L, blank, reinterpret_cast<uint16_t*>(ws), \
+                           frame_pos, start, end, conf, score, frame_len); \
     } while (0)
 #define ALIGN_NS(NS) do { if (fast) ALIGN_L(NS, true); else ALIGN_L(NS, false); } while (0)
     switch (ns) { case 1: ALIGN_NS(1); break; case 2: ALIGN_NS(2); break; case 3: ALIGN_NS(3); break; case 4: ALIGN_NS(4); break;
@@ -263,4 +272,12 @@ int launch_ctc_align(const float* logits, const int64_t* labels, int B, int T, i
 #undef ALIGN_NS
 #undef ALIGN_L
     return launch_rc();
+}
+int launch_ctc_align(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws, int* frame_pos, int* start,
+                     int* end, float* conf, float* score, hipStream_t s) {
+    return launch_ctc_align_t<false>(logits, labels, B, T, C, L, blank, ws, frame_pos, start, end, conf, score, nullptr, s);
+}
+int launch_ctc_align_len(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws, int* frame_pos, int* start,
+                         int* end, float* conf, float* score, const int* frame_len, hipStream_t s) {
+    return launch_ctc_align_t<true>(logits, labels, B, T, C, L, blank, ws, frame_pos, start, end, conf, score, frame_len, s);
 }

@@ -87,10 +87,13 @@ struct BmState {
     int nb;
 };
 
-__global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* __restrict__ logits, int Tn, int C, int blank, int W, int nbest,
+// VL (ishara_ctc_beam_decode_ex): the clip has Tn = frame_len[b] frames of the buffer's Ts; Ts stays the stride of the logits, of the trie
+// workspace and of out_idx (padded with -1 to Ts).  A frame_len[b] outside [1, Ts] is no clip: every n-best slot len -1, score -inf.
+template <bool VL>
+__global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* __restrict__ logits, int Ts, int C, int blank, int W, int nbest,
                                                                   const float* __restrict__ lm, float alpha, float beta,
                                                                   int* __restrict__ ws, int* __restrict__ out_idx, int* __restrict__ out_len,
-                                                                  float* __restrict__ out_score) {
+                                                                  float* __restrict__ out_score, const int* __restrict__ frame_len) {
     __shared__ float s_lm[BM_MAXC * BM_MAXC];
     __shared__ float s_lp[BM_CHUNK][BM_MAXC];
     __shared__ BmState s_st[2];
@@ -102,8 +105,10 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
     const bool use_lm = lm != nullptr && alpha != 0.0f;
-    const float* x = logits + (size_t)b * Tn * C;
-    int* trie = ws + (size_t)b * ctc_beam_workspace_words(Tn, W);
+    int Tn = Ts;
+    if (VL && frame_len) { Tn = frame_len[b]; if (Tn < 1 || Tn > Ts) Tn = 0; }
+    const float* x = logits + (size_t)b * Ts * C;
+    int* trie = ws + (size_t)b * ctc_beam_workspace_words(Ts, W);
 
     if (use_lm)
         for (int k = tid; k < C * C; k += blockDim.x) s_lm[(k / C) * BM_MAXC + k % C] = lm[k];
@@ -296,7 +301,7 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
         const int nb = S.nb;
         float fin = BM_NEG;
         u64 key = 0;
-        if (lane < nb) {
+        if (lane < nb && !(VL && Tn == 0)) {
             const int last = S.last[lane];
             fin = __fadd_rn(bm_lse(S.pb[lane], S.pnb[lane]), S.bonus[lane]);
             if (use_lm) fin = __fadd_rn(fin, __fmul_rn(alpha, s_lm[(last >= 0 ? last : blank) * BM_MAXC + blank]));
@@ -313,7 +318,7 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
                 out_score[o] = (float)(zoff + qoff + (double)fr);
                 s_olen[lane] = len;
                 int node = S.node[r];
-                int* dst = out_idx + o * Tn;
+                int* dst = out_idx + o * Ts;
                 for (int k = len - 1; k >= 0; --k) {
                     const int wd = trie[node];
                     dst[k] = wd >> 24;
@@ -328,8 +333,8 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
     }
     __syncthreads();
     for (int n = 0; n < nbest; ++n) {
-        int* dst = out_idx + ((size_t)b * nbest + n) * Tn;
-        for (int k = s_olen[n] + tid; k < Tn; k += blockDim.x) dst[k] = -1;
+        int* dst = out_idx + ((size_t)b * nbest + n) * Ts;
+        for (int k = s_olen[n] + tid; k < Ts; k += blockDim.x) dst[k] = -1;
     }
 }
 
@@ -338,7 +343,16 @@ int launch_ctc_beam(const float* logits, int B, int T, int C, int blank, int W, 
     if (B == 0) return 0;
     int nw = 1;
     while (nw < W && nw < BM_MAXNW) nw <<= 1;
-    hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm, alpha, beta, (int*)ws, out_idx,
-                       out_len, out_score);
+    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm, alpha, beta, (int*)ws, out_idx,
+                       out_len, out_score, (const int*)nullptr);
+    return launch_rc();
+}
+int launch_ctc_beam_len(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm, float alpha, float beta,
+                        void* ws, int* out_idx, int* out_len, float* out_score, const int* frame_len, hipStream_t s) {
+    if (B == 0) return 0;
+    int nw = 1;
+    while (nw < W && nw < BM_MAXNW) nw <<= 1;
+    hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm, alpha, beta, (int*)ws, out_idx,
+                       out_len, out_score, frame_len);
     return launch_rc();
 }

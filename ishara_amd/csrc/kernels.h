@@ -284,9 +284,14 @@ size_t ctc_lds_limit();
 // logits [B,T,C] f32; labels [B,L] int64 (padded with blank); nll [B]; dlogits = grad_scale * d nll_b / d logits
 int launch_ctc(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank,
                float* nll, float* dlogits, float grad_scale, float* ws, hipStream_t s, void* dlb = nullptr);
+// per-sample frame counts (device frame_len [B] int32 or NULL: T each; outside [1, T]: a sample without frames), a per-sample factor on
+// grad_scale (sample_scale [B] f32 or NULL) and zero_inf: an infeasible sample's gradient is +0.  T stays the stride (contract: ishara_hip.h)
+int launch_ctc_len(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, float* nll, float* dlogits,
+                   float grad_scale, float* ws, const int* frame_len, const float* sample_scale, int zero_inf, hipStream_t s);
 int launch_fill_u32(void* p, size_t n_words, uint32_t v, hipStream_t s);   // model.hip
 int launch_mean(const float* v, float* out, int n, float scale, hipStream_t s);
 int launch_greedy_decode(const float* logits, int B, int T, int C, int blank, int* out_idx, int* out_len, hipStream_t s);
+int launch_greedy_decode_len(const float* logits, int B, int T, int C, int blank, int* out_idx, int* out_len, const int* frame_len, hipStream_t s);
 
 // ---- inference preprocessing (preprocess.hip): raw [max_frames,276] (+ device clip length) -> [T,276]; mean/std [276] in OUTPUT order
 int launch_preprocess(const float* raw, const int* n_frames, int max_frames, const float* mean, const float* stdv, float* out, int T, hipStream_t s);
@@ -300,11 +305,15 @@ int launch_edit_distance(const int* out_idx, const int* out_len, int B, int T, c
 __host__ __device__ size_t ctc_beam_workspace_words(int T, int W);
 int launch_ctc_beam(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm, float alpha, float beta,
                     void* ws, int* out_idx, int* out_len, float* out_score, hipStream_t s);
+int launch_ctc_beam_len(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm, float alpha, float beta,
+                        void* ws, int* out_idx, int* out_len, float* out_score, const int* frame_len, hipStream_t s);
 // ---- CTC forced alignment (ctc_align.hip): the best path of a known label, per-symbol frame spans and confidences (ishara_amd/ctc_align.py)
 bool ctc_align_bp_in_lds(int T, int L);                          // the back-pointers (T * 128 bytes) fit in LDS: the workspace is not used
 size_t ctc_align_workspace_bytes(int B, int T, int L);
 int launch_ctc_align(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws, int* frame_pos, int* start,
                      int* end, float* conf, float* score, hipStream_t s);
+int launch_ctc_align_len(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws, int* frame_pos, int* start,
+                         int* end, float* conf, float* score, const int* frame_len, hipStream_t s);
 // ---- training input batch (input_batch.hip): device store of raw clips + per-clip augmentation table -> x [B,T,F]
 #define CLIP_MAX_T 4096
 int launch_clip_batch(const float* raw, const ishara_clip_aug* clips, int B, int T, int layout, float* x, hipStream_t s);

@@ -165,8 +165,27 @@ def workspace_bytes(lib, B: int, T: int, L: int) -> int:
     return n
 
 
-def launch(lib, logits, labels, B: int, T: int, C: int, L: int, blank: int, ws, frame_pos, start, end, conf, score, stream) -> None:
-    """One ishara_ctc_align launch on `stream` (graph-capturable)."""
+def launch(lib, logits, labels, B: int, T: int, C: int, L: int, blank: int, ws, frame_pos, start, end, conf, score, stream,
+           frame_len=None, ex: bool = False) -> None:
+    """One ishara_ctc_align launch on `stream` (graph-capturable).  With frame_len (int32 [B] on the device: the frames of each clip) or
+    ex, the launch is ishara_ctc_align_ex."""
     from . import _lib
+    if frame_len is not None or ex:
+        _lib.check(lib.ishara_ctc_align_ex(_lib.ptr(logits), _lib.ptr(labels), B, T, C, L, blank, _lib.ptr(ws), _lib.ptr(frame_pos), _lib.ptr(start),
+                                           _lib.ptr(end), _lib.ptr(conf), _lib.ptr(score), _lib.ptr(frame_len), stream), "ishara_ctc_align_ex")
+        return
     _lib.check(lib.ishara_ctc_align(_lib.ptr(logits), _lib.ptr(labels), B, T, C, L, blank, _lib.ptr(ws), _lib.ptr(frame_pos), _lib.ptr(start),
                                     _lib.ptr(end), _lib.ptr(conf), _lib.ptr(score), stream), "ishara_ctc_align")
+
+
+# `ishara_amd.ctc_align` names this module (the semantics, the host reference, launch) and is also the call of the public surface,
+# `ishara_amd.ctc_align(logits, labels, lengths)`, next to ctc_loss / ctc_greedy_decode / ctc_beam_decode: the module is callable.
+class _Module(type(np)):
+    def __call__(self, *args, **kw):
+        from .ctc import ctc_align
+        return ctc_align(*args, **kw)
+
+
+import sys as _sys  # noqa: E402
+
+_sys.modules[__name__].__class__ = _Module

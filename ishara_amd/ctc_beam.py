@@ -250,10 +250,17 @@ def workspace_bytes(lib, B: int, T: int, C: int, beam_width: int) -> int:
 
 
 def launch(lib, logits, B: int, T: int, C: int, beam_width: int, nbest: int, lm_dev, alpha: float, beta: float, ws, out_idx, out_len,
-           out_score, stream) -> None:
-    """One ishara_ctc_beam_decode launch on `stream` (graph-capturable); blank = C - 1 as for the greedy decoder."""
+           out_score, stream, frame_len=None, ex: bool = False) -> None:
+    """One ishara_ctc_beam_decode launch on `stream` (graph-capturable); blank = C - 1 as for the greedy decoder.  With frame_len (int32
+    [B] on the device: the frames of each clip) or ex, the launch is ishara_ctc_beam_decode_ex."""
     import ctypes as C_
     from . import _lib
+    if frame_len is not None or ex:
+        _lib.check(lib.ishara_ctc_beam_decode_ex(_lib.ptr(logits), B, T, C, C - 1, beam_width, nbest,
+                                                 _lib.ptr(lm_dev) if lm_dev is not None else None, C_.c_float(alpha), C_.c_float(beta),
+                                                 _lib.ptr(ws), _lib.ptr(out_idx), _lib.ptr(out_len), _lib.ptr(out_score), _lib.ptr(frame_len), stream),
+                   "ishara_ctc_beam_decode_ex")
+        return
     _lib.check(lib.ishara_ctc_beam_decode(_lib.ptr(logits), B, T, C, C - 1, beam_width, nbest,
                                           _lib.ptr(lm_dev) if lm_dev is not None else None, C_.c_float(alpha), C_.c_float(beta),
                                           _lib.ptr(ws), _lib.ptr(out_idx), _lib.ptr(out_len), _lib.ptr(out_score), stream),

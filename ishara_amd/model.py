@@ -548,14 +548,21 @@ class Model(Handle):
         _lib.check(self._lib.ishara_debug_module_backward(self._h, i, _lib.ptr(dy), B, _lib.ptr(dx), _stream()), "ishara_debug_module_backward")
         return dx
 
-    def ctc_loss(self, y, logits) -> torch.Tensor:
-        """CTCLoss(labels, logits) (c6:1-13) on the GPU; returns per-sample nll [B]."""
+    def ctc_loss(self, y, logits, frame_lengths=None) -> torch.Tensor:
+        """CTCLoss(labels, logits) (c6:1-13) on the GPU; returns per-sample nll [B].  frame_lengths [B] (1..T): clip b has that many
+        frames (logit_length of tf.nn.ctc_loss); a label that does not fit its clip gives the kernel's sentinel 1e30."""
         logits = logits.to(self.device, torch.float32).contiguous()
         y = torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(self.device, torch.int64).contiguous()
         B, T, Cc = logits.shape
         L = y.shape[1]
         ws = torch.empty(int(self._lib.ishara_ctc_workspace_bytes(B, T, L)), dtype=torch.uint8, device=self.device)
         nll = torch.empty(B, dtype=torch.float32, device=self.device)
+        if frame_lengths is not None:
+            from . import ctc
+            fl = ctc._lengths(frame_lengths, B, T, 1, "frame_lengths", self.device)
+            _lib.check(self._lib.ishara_ctc_loss_ex(_lib.ptr(logits), _lib.ptr(y), B, T, Cc, L, Cc - 1, _lib.ptr(nll), None, C.c_float(1.0),
+                                                    _lib.ptr(ws), _lib.ptr(fl), None, 0, _stream()), "ishara_ctc_loss_ex")
+            return nll
         _lib.check(self._lib.ishara_ctc_loss(_lib.ptr(logits), _lib.ptr(y), B, T, Cc, L, Cc - 1, _lib.ptr(nll), None,
                                              C.c_float(1.0), _lib.ptr(ws), _stream()), "ishara_ctc_loss")
         return nll
@@ -569,9 +576,13 @@ class Model(Handle):
         return tot / max(n, 1)
 
     # ------------------------------------------------------------------ decode
-    def decode_batch(self, logits: torch.Tensor) -> List[np.ndarray]:
-        """decode_batch_predictions (c8:15-20) -> list of index arrays (decode_phrase, c8:4-12)."""
+    def decode_batch(self, logits: torch.Tensor, frame_lengths=None) -> List[np.ndarray]:
+        """decode_batch_predictions (c8:15-20) -> list of index arrays (decode_phrase, c8:4-12).  frame_lengths [B] (1..T): clip b is
+        decoded as logits[b, :frame_lengths[b]]."""
         logits = logits.to(self.device, torch.float32).contiguous()
+        if frame_lengths is not None:
+            from . import ctc
+            return ctc.ctc_greedy_decode(logits, frame_lengths)
         B, T, Cc = logits.shape
         idx = torch.empty((B, T), dtype=torch.int32, device=self.device)
         ln = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -581,8 +592,8 @@ class Model(Handle):
         return [idx[b, :ln[b]].astype(np.int64) for b in range(B)]
 
 
-    def beam_decode(self, logits, beam_width: int = 16, nbest: int = 1, lm=None, alpha: float = 0.0, beta: float = 0.0
-                    ) -> List[List[Tuple[np.ndarray, float]]]:
+    def beam_decode(self, logits, beam_width: int = 16, nbest: int = 1, lm=None, alpha: float = 0.0, beta: float = 0.0,
+                    frame_lengths=None) -> List[List[Tuple[np.ndarray, float]]]:
         """CTC prefix beam search (ishara_amd/ctc_beam.py semantics, blank = C - 1) of logits [B, T, C] on the device -> per clip a list
         of (indices int64, score), best first, at most nbest entries.  lm: a [C, C] log-probability table (e.g. CharBigramLM) or None.
         Unlike decode_batch it uses the last frame too.  The workspace of the latest shape is kept for the next call; the call waits for
@@ -591,6 +602,9 @@ class Model(Handle):
         logits = torch.as_tensor(logits).to(self.device, torch.float32).contiguous()
         if logits.ndim != 3:
             raise ValueError(f"logits must be [B, T, C], got {tuple(logits.shape)}")
+        if frame_lengths is not None:                       # clip b is logits[b, :frame_lengths[b]]
+            from . import ctc
+            return ctc.ctc_beam_decode(logits, frame_lengths, beam_width, nbest, lm, alpha, beta, workspace=getattr(self, "_beam_ws", None))
         B, T, Cc = logits.shape
         ctc_beam.check_device_args(Cc, T, beam_width, nbest)
         lm_dev = ctc_beam.lm_to_device(lm, Cc, self.device)
@@ -605,12 +619,15 @@ class Model(Handle):
         idx, ln, sc = idx.cpu().numpy(), ln.cpu().numpy(), sc.cpu().numpy()
         return [[(idx[b, n, :ln[b, n]].astype(np.int64), float(sc[b, n])) for n in range(nbest) if ln[b, n] >= 0] for b in range(B)]
 
-    def align(self, logits, y) -> list:
+    def align(self, logits, y, frame_lengths=None) -> list:
         """CTC forced alignment (ishara_amd/ctc_align.py semantics, blank = C - 1) of logits [B, T, C] to the labels y [B, L] (padded with
         C - 1) on the device -> per clip an Alignment: the label index every frame emits, the log-probability of the best path and one
         (symbol, start, end, conf) span per symbol.  The workspace is kept for the next call, as beam_decode keeps its own."""
         from . import ctc_align
         logits = torch.as_tensor(logits).to(self.device, torch.float32).contiguous()
+        if frame_lengths is not None:                       # clip b is logits[b, :frame_lengths[b]]; frame_pos is -1 past it
+            from . import ctc
+            return ctc.ctc_align(logits, y, frame_lengths, workspace=getattr(self, "_align_ws", None))
         y = torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(self.device, torch.int64).contiguous()
         if logits.ndim != 3 or y.ndim != 2 or y.shape[0] != logits.shape[0]:
             raise ValueError(f"logits must be [B, T, C] and y [B, L], got {tuple(logits.shape)} and {tuple(y.shape)}")

@@ -151,7 +151,9 @@ class Squeezeformer:
     layer `fc = nn.Linear(encoder_dim, num_classes, bias=False)` (:431) and `log_softmax` (:449).  `model(inputs, input_lengths)` returns
     `(log_probs [B, T_out, num_classes], output_lengths)` like the reference's forward (:437-450) and is differentiable end to end (the
     encoder through `ishara_encoder_backward`, the head through the library's dense / log-softmax operators), so that
-    `torch.nn.functional.ctc_loss(log_probs.transpose(0, 1), ...)` or the library's own CTC kernel train it.  state_dict keys:
+    `ishara_amd.ctc_loss(log_probs, targets, output_lengths, target_lengths)` (the library's own CTC kernel: batch-first, per-clip lengths)
+    or `torch.nn.functional.ctc_loss(log_probs.transpose(0, 1), ...)` train it; output_lengths stays on the device of the input_lengths it
+    was computed from, so a device tensor goes from the data loader to the loss kernel without a host round trip.  state_dict keys:
     `encoder.<the encoder's keys>` and `fc.weight` [num_classes, encoder_dim]."""
 
     def __init__(self, num_classes: int, input_dim: int = 80, encoder_dim: int = 512, num_encoder_layers: int = 16, reduce_layer_index: int = 7,

@@ -286,6 +286,10 @@ const char* ishara_debug_dense_kernel_name(int32_t dt, int32_t M, int32_t K, int
  * for these arguments under the current switches: the prefix of its profiler name, a two-pass backward as "dgrad+wgrad", "" for a refused
  * call.  flags: 1 statistics wanted, 2 scratch given, 4 BatchNorm backward folded in.  Host only, launches nothing; valid until the next call */
 const char* ishara_debug_dwconv_kernel_name(int32_t dt, int32_t backward, int32_t B, int32_t T, int32_t C, int32_t k, int32_t padl, int32_t flags);
+/* the same for the attention: the kernel behind ishara_op_attn_fwd (backward != 0: ishara_op_attn_bwd) and the models' attention, with its template
+ * arguments, a kernel pair as "dq + dkv<...>", "" for a refused call.  impl: 0 lane-split, 1 MFMA where there is one.  flags: 1 dropout active,
+ * 2 keep-bit buffer given, 4 head-major dqkv.  Host only, launches nothing; valid until the next call */
+const char* ishara_debug_attn_kernel_name(int32_t dt, int32_t backward, int32_t T, int32_t dh, int32_t impl, int32_t flags);
 /* 0: never use the 256 x 256 two-operand tile GEMM (gemm_big.hip) — A/B runs against the A-stationary kernel inside one process; 1: library default */
 int ishara_debug_set_nt_big(int32_t on);
 int ishara_debug_force_regstage(int32_t on);

@@ -265,6 +265,14 @@ extern "C" const char* ishara_debug_dwconv_kernel_name(int32_t dt, int32_t backw
     if (backward) return dwconv_bwd_kernel_name(dt, C, k, padl, (flags & 2) != 0, (flags & 4) != 0);
     return dwconv_fwd_kernel_name(dt, B, T, C, k, (flags & 1) != 0, (flags & 2) != 0);
 }
+// the same for the attention: the kernel launch_attn_fwd (backward != 0: launch_attn_bwd) runs for these arguments under the current switches,
+// with its template arguments, a kernel pair as "dq + dkv<...>", "" for a refused call.  impl: 0 / 1 as the launchers take it.  flags: 1 dropout
+// active, 2 keep-bit buffer given, 4 head-major dqkv.  Host only: nothing is launched.  The answer is valid until the next call
+extern "C" const char* ishara_debug_attn_kernel_name(int32_t dt, int32_t backward, int32_t T, int32_t dh, int32_t impl, int32_t flags) {
+    if (!op_dt_ok("ishara_debug_attn_kernel_name", dt, true) || T < 1) return "";
+    if (backward) return attn_bwd_kernel_name(dt, T, dh, impl, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0);
+    return attn_fwd_kernel_name(dt, T, dh, impl, (flags & 1) != 0, (flags & 2) != 0);
+}
 extern "C" int ishara_op_dense_bwd(int32_t dt, const void* x, const float* Wm, const void* dy, void* dx, float* dW, float* db,
                                    int32_t M, int32_t K, int32_t N, void* scratch, ishara_stream st) {
     OP_DT("ishara_op_dense_bwd", dt, false);
@@ -441,14 +449,17 @@ extern "C" int ishara_op_attn_scratch_layout_bytes(int32_t B, int32_t H, int32_t
 }
 // impl: 0 lane-split, 1 MFMA with the keep bits cached in the scratch (DM 2), 2 MFMA with no keep-bit buffer: the backward kernels hash again
 // (DM 1, the product's ISHARA_NO_ATTN_BITS route).  Everything a launch would fault or fail on is refused here, before any HIP call.
-static bool attn_takes_mfma(int dt, int dh, int impl) { return impl >= 1 && dt == DT_BF16 && (dh == 32 || dh == 64); }
-static int attn_op_refused(const char* me, int dt, int B, int H, int T, int dh, float rate, int impl, std::initializer_list<const void*> operands,
+// Which kernel a call would run on is asked of attn_fwd_route / attn_bwd_route (attention.hip), as the launchers ask them.
+static int attn_op_refused(const char* me, bool backward, int dt, int B, int H, int T, int dh, float rate, int impl, std::initializer_list<const void*> operands,
                            std::initializer_list<const char*> operand_names, const void* scratch) {
     if (B < 1 || H < 1 || T < 1) { ishara_set_error("%s: B=%d H=%d T=%d: B, H and T must be >= 1", me, B, H, T); return -1; }
     if (dh != 8 && dh != 16 && dh != 24 && dh != 32 && dh != 48 && dh != 64) { ishara_set_error("%s: head dim %d unsupported (8, 16, 24, 32, 48, 64)", me, dh); return -1; }
     if (impl < 0 || impl > 2) { ishara_set_error("%s: unknown impl %d (0 lane-split, 1 MFMA with cached keep bits, 2 MFMA hashing again in the backward)", me, impl); return -1; }
-    if (impl == 2 && !attn_takes_mfma(dt, dh, impl)) { ishara_set_error("%s: impl 2 has MFMA kernels only: ISHARA_BF16 and head dim 32 / 64 (dtype %d, head dim %d)", me, dt, dh); return -1; }
-    if (attn_takes_mfma(dt, dh, impl) && T % 8 != 0) { ishara_set_error("%s: T=%d: the MFMA kernels need T %% 8 == 0 (16-byte pieces of the V^T rows)", me, T); return -1; }
+    const AttnRoute r = backward ? attn_bwd_route(dt, T, dh, impl >= 1, rate > 0.f, impl == 1, true) : attn_fwd_route(dt, T, dh, impl >= 1, rate > 0.f, impl == 1);
+    const bool takes_bits = r.kind == ATT_MFMA || r.kind == ATT_BWD_TWO_KERNEL || r.kind == ATT_BWD_FUSED;      // a kernel that has the dropout modes 1 and 2
+    if (impl == 2 && !takes_bits && r.kind != ATT_REFUSED) { ishara_set_error("%s: impl 2 has MFMA kernels only: ISHARA_BF16 and head dim 32 / 64 (dtype %d, head dim %d)", me, dt, dh); return -1; }
+    // the caller checked the dtype (OP_DT) and the head dim passed above: what the route still refuses is a T the MFMA kernels do not take
+    if (r.kind == ATT_REFUSED) { ishara_set_error("%s: T=%d: the MFMA kernels need T %% 8 == 0 (16-byte pieces of the V^T rows)", me, T); return -1; }
     if (!(rate >= 0.f && rate < 1.f)) { ishara_set_error("%s: rate %g outside [0, 1)", me, rate); return -1; }
     if ((int64_t)B * H > 65535 || (int64_t)B * H * T * dh * 3 > 2147483647LL) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d: shape too large (B*H <= 65535: one grid row per head; 3*B*H*T*dh < 2^31)", me, B, H, T, dh); return -1; }
     for (size_t i = 0; i < operands.size(); ++i) if (!operands.begin()[i]) { ishara_set_error("%s: null %s", me, operand_names.begin()[i]); return -1; }
@@ -462,7 +473,7 @@ extern "C" int ishara_op_attn_fwd(int32_t dt, const void* qkv, void* o, int32_t 
                                   uint32_t seed, uint32_t site, float rate, int32_t impl, void* scratch, ishara_stream st) {
     OP_DT("ishara_op_attn_fwd", dt, true);
     if (dt == DT_F16 && rate > 0.f) { ishara_set_error("ishara_op_attn_fwd: ISHARA_F16 is inference-only: no attention dropout (rate %g)", rate); return -1; }
-    if (attn_op_refused("ishara_op_attn_fwd", dt, B, H, T, dh, rate, impl, {qkv, o}, {"qkv", "o"}, scratch)) return -1;
+    if (attn_op_refused("ishara_op_attn_fwd", false, dt, B, H, T, dh, rate, impl, {qkv, o}, {"qkv", "o"}, scratch)) return -1;
     hipStream_t s = (hipStream_t)st;
     const AttnScratch a((char*)scratch, B, H, T, dh);
     if (dt == DT_BF16) hipLaunchKernelGGL(qkv_split_kernel<bf16>, dim3(1024), dim3(256), 0, s, (const bf16*)qkv, (bf16*)a.q, (bf16*)a.k, (bf16*)a.vt, B, H, T, dh);
@@ -473,7 +484,7 @@ extern "C" int ishara_op_attn_fwd(int32_t dt, const void* qkv, void* o, int32_t 
 extern "C" int ishara_op_attn_bwd(int32_t dt, const void* o, const void* dout, void* dqkv, int32_t B, int32_t H, int32_t T, int32_t dh, float scale,
                                   uint32_t seed, uint32_t site, float rate, int32_t impl, void* scratch, ishara_stream st) {
     OP_DT("ishara_op_attn_bwd", dt, false);
-    if (attn_op_refused("ishara_op_attn_bwd", dt, B, H, T, dh, rate, impl, {o, dout, dqkv}, {"o", "dout", "dqkv"}, scratch)) return -1;
+    if (attn_op_refused("ishara_op_attn_bwd", true, dt, B, H, T, dh, rate, impl, {o, dout, dqkv}, {"o", "dout", "dqkv"}, scratch)) return -1;
     hipStream_t s = (hipStream_t)st;
     const AttnScratch a((char*)scratch, B, H, T, dh);
     return launch_attn_bwd(dt, a.q, a.k, a.vt, o, dout, a.lse, a.delta, dqkv, B, H, T, dh, scale, make_drop_attn(seed, site, rate, true), 1, impl == 2 ? 1 : impl,

@@ -9,7 +9,6 @@
 // (24 and 48 — e.g. the reference's d384 / 8-head sibling model — have no MFMA kernel and run here in bf16 mode too).
 #include "kernels.h"
 
-
 DEVI float quad_sum(float v) {
     v += __shfl_xor(v, 1, 64);
     v += __shfl_xor(v, 2, 64);
@@ -219,41 +218,98 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
     }
 }
 
-#define ATT_DISPATCH(KERNEL, TT, ...)                                                                    \
-    do {                                                                                                  \
-        dim3 grid((T + 63) / 64, B * H);                                                                  \
-        switch (dh) {                                                                                     \
-            case 8: hipLaunchKernelGGL((KERNEL<TT, 2>), grid, dim3(256), 0, s, __VA_ARGS__); break;        \
-            case 16: hipLaunchKernelGGL((KERNEL<TT, 4>), grid, dim3(256), 0, s, __VA_ARGS__); break;       \
-            case 24: hipLaunchKernelGGL((KERNEL<TT, 6>), grid, dim3(256), 0, s, __VA_ARGS__); break;       \
-            case 32: hipLaunchKernelGGL((KERNEL<TT, 8>), grid, dim3(256), 0, s, __VA_ARGS__); break;       \
-            case 48: hipLaunchKernelGGL((KERNEL<TT, 12>), grid, dim3(256), 0, s, __VA_ARGS__); break;      \
-            case 64: hipLaunchKernelGGL((KERNEL<TT, 16>), grid, dim3(256), 0, s, __VA_ARGS__); break;      \
-            default: ishara_set_error("attention: head dim %d unsupported (8,16,24,32,48,64)", dh); return -1;  \
-        }                                                                                                 \
-    } while (0)
-
-int launch_attn_fwd(int dt, const void* q, const void* k, const void* vt, void* o, float* lse,
-                    int B, int H, int T, int dh, float scale, DropSpec drop, int impl, uint32_t* maskbits, hipStream_t s) {
-    if (impl == 1 && dt == DT_BF16 && (dh == 32 || dh == 64)) return launch_attn_fwd_mfma(q, k, vt, o, lse, B, H, T, dh, scale, drop, maskbits, s);
-    if (impl == 1 && dt == DT_F16 && (dh == 32 || dh == 64) && drop.thr == 0 && T % 8 == 0) return launch_attn_fwd_mfma_f16(q, k, vt, o, lse, B, H, T, dh, scale, s);
-    if (dt == DT_BF16) { ATT_DISPATCH(attn_fwd_kernel, bf16, (const bf16*)q, (const bf16*)k, (const bf16*)vt, (bf16*)o, lse, B, H, T, scale, drop); }
-    else if (dt == DT_F16) { ATT_DISPATCH(attn_fwd_kernel, f16, (const f16*)q, (const f16*)k, (const f16*)vt, (f16*)o, lse, B, H, T, scale, drop); }
-    else { ATT_DISPATCH(attn_fwd_kernel, float, (const float*)q, (const float*)k, (const float*)vt, (float*)o, lse, B, H, T, scale, drop); }
-    return launch_rc();
+// ---- Which kernel runs.  attn_fwd_route / attn_bwd_route decide, here and nowhere else: they alone read the switches (g_attn_bwd_two_pass,
+// ISHARA_NO_ATTN_BITS) and hold the applicability tests; the launchers launch what they return and attn_*_kernel_name names it.
+// A new kernel gets an enumerator, its test in the route (in priority order) and a case in the launcher's switch and the name's switch.
+int g_attn_bwd_two_pass = 0;     // tests / tools: 1 forces the two-kernel backward
+// the MFMA kernels: bf16 (the forward also fp16 without dropout), head dim 32 / 64, T in 16-byte pieces of the V^T rows
+static bool att_mfma_ok(int impl, int dh) { return impl == 1 && (dh == 32 || dh == 64); }
+// keep-bit cache of the attention-probability dropout (the forward writes it, the backward reads it); ISHARA_NO_ATTN_BITS=1: both passes hash
+// instead (A/B switch).  Measured per layer (B256 H8 T384 dh32): hash fwd 155 + bwd 452 us, cached bits 168 + 361 us
+static int att_dm(bool drop, bool bits) {
+    static const bool off_env = getenv("ISHARA_NO_ATTN_BITS") != nullptr;
+    const bool maskbits = bits && !off_env;
+    return !drop ? 0 : (maskbits ? 2 : 1);
+}
+// the lane-split kernels: every dtype (what is neither bf16 nor fp16 runs as fp32) at the head dims they are instantiated for
+static AttnRoute att_lane_route(int dh) {
+    static char why[64];
+    if (dh == 8 || dh == 16 || dh == 24 || dh == 32 || dh == 48 || dh == 64) return {ATT_LANE, ""};
+    snprintf(why, sizeof why, "attention: head dim %d unsupported (8,16,24,32,48,64)", dh);
+    return {ATT_REFUSED, why};
+}
+// An asymmetry kept as it was: bf16 at T % 8 != 0 is refused where fp16 falls back to the lane-split kernel
+AttnRoute attn_fwd_route(int dt, int T, int dh, int impl, bool drop, bool bits) {
+    if (att_mfma_ok(impl, dh) && dt == DT_BF16) return T % 8 != 0 ? AttnRoute{ATT_REFUSED, "attn_fwd_mfma: T % 8 != 0"} : AttnRoute{ATT_MFMA, "", att_dm(drop, bits)};
+    if (att_mfma_ok(impl, dh) && dt == DT_F16 && !drop && T % 8 == 0) return {ATT_MFMA_F16, ""};
+    return att_lane_route(dh);
+}
+AttnRoute attn_bwd_route(int dt, int T, int dh, int impl, bool drop, bool bits, bool head_major) {
+    if (dt == DT_F16) return {ATT_REFUSED, "attn_bwd: ISHARA_F16 is inference-only: no backward kernels"};
+    if (!(att_mfma_ok(impl, dh) && dt == DT_BF16 && head_major)) return att_lane_route(dh);
+    if (T % 8 != 0) return {ATT_REFUSED, "attn_bwd_mfma: T % 8 != 0"};
+    AttnRoute r = {ATT_BWD_TWO_KERNEL, "", att_dm(drop, bits)};
+    if (dh == 32 && T <= 384 && !g_attn_bwd_two_pass) {          // one-pass backward: S, dP and the elementwise pass computed once
+        r.kind = ATT_BWD_FUSED;
+        r.nw = T <= 128 ? 8 : (T <= 192 ? 12 : (T <= 256 ? 8 : 12));      // (waves, key tiles per wave): 12 waves = 3 per SIMD wherever T allows it with <= 2 tiles
+        r.nt = T <= 192 ? 1 : 2;
+        r.full = T == 16 * r.nw * r.nt;
+    }
+    return r;
 }
 
+// the prefix of the rocprof name of the kernel launch_attn_fwd / launch_attn_bwd launches for the same arguments, with its template arguments
+static const char* att_dt_name(int dt) { return dt == DT_BF16 ? "bf16" : (dt == DT_F16 ? "f16" : "float"); }
+const char* attn_fwd_kernel_name(int dt, int T, int dh, int impl, bool drop, bool bits) {
+    static char name[64];
+    const AttnRoute r = attn_fwd_route(dt, T, dh, impl, drop, bits);
+    switch (r.kind) {
+        case ATT_MFMA: snprintf(name, sizeof name, "attn_fwd_mfma_kernel<%d,%d>", dh, r.dm); return name;
+        case ATT_MFMA_F16: snprintf(name, sizeof name, "attn_fwd_mfma_kernel<%d,0,f16>", dh); return name;
+        case ATT_LANE: snprintf(name, sizeof name, "attn_fwd_kernel<%s,%d>", att_dt_name(dt), dh / 4); return name;
+        default: return "";
+    }
+}
+const char* attn_bwd_kernel_name(int dt, int T, int dh, int impl, bool drop, bool bits, bool head_major) {
+    static char name[96];
+    const AttnRoute r = attn_bwd_route(dt, T, dh, impl, drop, bits, head_major);
+    switch (r.kind) {
+        case ATT_BWD_FUSED: snprintf(name, sizeof name, "attn_bwd_fused_kernel<%d,%d,%d,%s>", r.nw, r.nt, r.dm, r.full ? "FULL" : "ragged"); return name;
+        case ATT_BWD_TWO_KERNEL: snprintf(name, sizeof name, "attn_bwd_dq_mfma_kernel + attn_bwd_dkv_mfma_kernel<%d,%d>", dh, r.dm); return name;
+        case ATT_LANE: snprintf(name, sizeof name, "attn_bwd_dq_kernel + attn_bwd_dkv_kernel<%s,%d>", att_dt_name(dt), dh / 4); return name;
+        default: return "";
+    }
+}
+
+// ---- kernel launches.  att_lane: fn(E{}, att_int<DHL>{}) in the storage type (fp16: the forward only) and at DHL = dh / 4, which the route has passed
+template <bool F16, typename F> static int att_lane(int dt, int dh, F fn) {
+    auto at = [&](auto e) {
+        dh == 8 ? fn(e, att_int<2>{}) : dh == 16 ? fn(e, att_int<4>{}) : dh == 24 ? fn(e, att_int<6>{}) : dh == 32 ? fn(e, att_int<8>{}) : dh == 48 ? fn(e, att_int<12>{}) : fn(e, att_int<16>{});
+        return launch_rc();
+    };
+    if constexpr (F16) if (dt == DT_F16) return at(f16{});
+    return dt == DT_BF16 ? at(bf16{}) : at(float{});
+}
+int launch_attn_fwd(int dt, const void* q, const void* k, const void* vt, void* o, float* lse,
+                    int B, int H, int T, int dh, float scale, DropSpec drop, int impl, uint32_t* maskbits, hipStream_t s) {
+    const AttnRoute r = attn_fwd_route(dt, T, dh, impl, drop.thr != 0, maskbits != nullptr);
+    switch (r.kind) {
+        case ATT_MFMA: return launch_attn_fwd_mfma(r.dm, q, k, vt, o, lse, B, H, T, dh, scale, drop, maskbits, s);
+        case ATT_MFMA_F16: return launch_attn_fwd_mfma_f16(q, k, vt, o, lse, B, H, T, dh, scale, s);
+        case ATT_LANE: return att_lane<true>(dt, dh, [&](auto e, auto l) { using E = decltype(e);
+            hipLaunchKernelGGL((attn_fwd_kernel<E, decltype(l)::v>), dim3((T + 63) / 64, B * H), dim3(256), 0, s, (const E*)q, (const E*)k, (const E*)vt, (E*)o, lse, B, H, T, scale, drop); });
+        default: ishara_set_error("%s", r.why); return -1;
+    }
+}
 int launch_attn_bwd(int dt, const void* q, const void* k, const void* vt, const void* o, const void* dout,
                     const float* lse, float* delta, void* dqkv, int B, int H, int T, int dh, float scale,
                     DropSpec drop, int head_major, int impl, uint32_t* maskbits, hipStream_t s) {
-    if (impl == 1 && dt == DT_BF16 && (dh == 32 || dh == 64) && head_major)
-        return launch_attn_bwd_mfma(q, k, vt, o, dout, lse, delta, dqkv, B, H, T, dh, scale, drop, maskbits, s);
-    if (dt == DT_BF16) {
-        ATT_DISPATCH(attn_bwd_dq_kernel, bf16, (const bf16*)q, (const bf16*)k, (const bf16*)vt, (const bf16*)o, (const bf16*)dout, lse, delta, (bf16*)dqkv, B, H, T, scale, drop, head_major);
-        ATT_DISPATCH(attn_bwd_dkv_kernel, bf16, (const bf16*)q, (const bf16*)k, (const bf16*)vt, (const bf16*)dout, lse, (const float*)delta, (bf16*)dqkv, B, H, T, scale, drop, head_major);
-    } else {
-        ATT_DISPATCH(attn_bwd_dq_kernel, float, (const float*)q, (const float*)k, (const float*)vt, (const float*)o, (const float*)dout, lse, delta, (float*)dqkv, B, H, T, scale, drop, head_major);
-        ATT_DISPATCH(attn_bwd_dkv_kernel, float, (const float*)q, (const float*)k, (const float*)vt, (const float*)dout, lse, (const float*)delta, (float*)dqkv, B, H, T, scale, drop, head_major);
+    const AttnRoute r = attn_bwd_route(dt, T, dh, impl, drop.thr != 0, maskbits != nullptr, head_major != 0);
+    switch (r.kind) {
+        case ATT_BWD_FUSED: case ATT_BWD_TWO_KERNEL: return launch_attn_bwd_mfma(r, q, k, vt, o, dout, lse, delta, dqkv, B, H, T, dh, scale, drop, maskbits, s);
+        case ATT_LANE: return att_lane<false>(dt, dh, [&](auto e, auto l) { using E = decltype(e); const dim3 grid((T + 63) / 64, B * H);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<E, decltype(l)::v>), grid, dim3(256), 0, s, (const E*)q, (const E*)k, (const E*)vt, (const E*)o, (const E*)dout, lse, delta, (E*)dqkv, B, H, T, scale, drop, head_major);
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<E, decltype(l)::v>), grid, dim3(256), 0, s, (const E*)q, (const E*)k, (const E*)vt, (const E*)dout, lse, (const float*)delta, (E*)dqkv, B, H, T, scale, drop, head_major); });
+        default: ishara_set_error("%s", r.why); return -1;
     }
-    return launch_rc();
 }

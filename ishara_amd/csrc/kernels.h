@@ -258,7 +258,7 @@ int launch_se_bwd(const float* dse, const float* gap, float invT, const float* W
                   const float* hid_pre, const float* se, float* dW1, float* db1, float* dW2, float* db2,
                   float* dgapT, float* scr /* B*(C+2R) floats */, int B, int C, int R, hipStream_t s);
 
-// ---- attention (attention.hip) -----------------------------------------------------
+// ---- attention (attention.hip: lane-split kernels, routes, launchers; attention_mfma.hip / attention_bwd_mfma.hip: the MFMA kernels) ----
 // q,k [B,H,T,dh], vt [B,H,dh,T]; o [B*T, H*dh]; lse [B,H,T]
 // maskbits: attn_mask_words(B, H, T) dwords where the MFMA forward kernel stores the dropout keep flags for the backward
 // kernels (nullptr: the backward kernels hash again; the lane-split kernels always hash)
@@ -269,11 +269,23 @@ int launch_attn_fwd(int dt, const void* q, const void* k, const void* vt, void* 
 int launch_attn_bwd(int dt, const void* q, const void* k, const void* vt, const void* o, const void* dout,
                     const float* lse, float* delta, void* dqkv, int B, int H, int T, int dh, float scale,
                     DropSpec drop, int head_major, int impl, uint32_t* maskbits, hipStream_t s);
-// the MFMA kernels behind impl == 1 (attention_mfma.hip)
-int launch_attn_fwd_mfma(const void* q, const void* k, const void* vt, void* o, float* lse,
+// The kernel a call runs on (attention.hip: the one place that decides and that reads g_attn_bwd_two_pass / ISHARA_NO_ATTN_BITS); the
+// launchers and the name functions are switches over it.  impl: 0 lane-split, 1 MFMA where there is one; drop: dropout is active
+// (DropSpec.thr != 0); bits: the caller gave a keep-bit buffer; head_major: the dqkv packing
+enum AttnKind { ATT_REFUSED, ATT_LANE, ATT_MFMA, ATT_MFMA_F16, ATT_BWD_TWO_KERNEL, ATT_BWD_FUSED };      // ATT_LANE: attn_fwd_kernel, or the attn_bwd_dq / _dkv pair
+// why: the refusal's message; dm: the MFMA kernels' dropout mode 0 / 1 / 2; nw, nt, full: waves, key tiles per wave and T == 16 nw nt of ATT_BWD_FUSED
+struct AttnRoute { AttnKind kind; const char* why; int dm, nw, nt; bool full; };
+AttnRoute attn_fwd_route(int dt, int T, int dh, int impl, bool drop, bool bits);
+AttnRoute attn_bwd_route(int dt, int T, int dh, int impl, bool drop, bool bits, bool head_major);
+// the kernel's rocprof name with its template arguments ("" when refused; a kernel pair as "dq + dkv<...>"); valid until the next call
+const char* attn_fwd_kernel_name(int dt, int T, int dh, int impl, bool drop, bool bits);
+const char* attn_bwd_kernel_name(int dt, int T, int dh, int impl, bool drop, bool bits, bool head_major);
+template <int N> struct att_int { static constexpr int v = N; };      // a template argument chosen at run time: fn(att_int<N>{})
+// the MFMA kernels behind ATT_MFMA / ATT_MFMA_F16 (attention_mfma.hip) and ATT_BWD_TWO_KERNEL / ATT_BWD_FUSED (attention_bwd_mfma.hip)
+int launch_attn_fwd_mfma(int dm, const void* q, const void* k, const void* vt, void* o, float* lse,
                          int B, int H, int T, int dh, float scale, DropSpec drop, uint32_t* maskbits, hipStream_t s);
 int launch_attn_fwd_mfma_f16(const void* q, const void* k, const void* vt, void* o, float* lse, int B, int H, int T, int dh, float scale, hipStream_t s);
-int launch_attn_bwd_mfma(const void* q, const void* k, const void* vt, const void* o, const void* dout, const float* lse,
+int launch_attn_bwd_mfma(const AttnRoute& r, const void* q, const void* k, const void* vt, const void* o, const void* dout, const float* lse,
                          float* delta, void* dqkv, int B, int H, int T, int dh, float scale, DropSpec drop, uint32_t* maskbits, hipStream_t s);
 
 // ---- CTC / decode (ctc.hip) ----------------------------------------------------------

@@ -1,5 +1,5 @@
 """Helpers of tests/test_attn_gpu.py and tests/test_attn_mutants.py: the cases, the inputs, the fp64 reference, the metrics and the bounds of the
-training attention operators (attention.hip's lane-split kernels and attention_mfma.hip's MFMA kernels) through ishara_op_attn_fwd / _bwd.
+training attention operators (attention.hip's lane-split kernels, attention_mfma.hip's and attention_bwd_mfma.hip's MFMA kernels) through ishara_op_attn_fwd / _bwd.
 
 Reference: test_ops_gpu._attn_ref (softmax(q.k^T * scale) * mask . v on the packed head-major qkv) in fp64 under autograd, on the operands the
 kernel receives (drawn in the storage dtype); the dropout mask is oracle/rng.py's scaled_mask_attn with row key (b*H + h)*T + i.  dqkv is
@@ -32,6 +32,9 @@ KC = {"mfma": 64, "lane": 32}       # keys per staged chunk (AF_KC, ATT_KC)
 QB = {"mfma": 128, "lane": 64}      # queries per workgroup (AF_QB, 64)
 TENSORS = ("o", "lse", "dq", "dk", "dv", "delta")
 ROUNDED = ("o", "dq", "dk", "dv")   # stored in the storage dtype
+F32, BF16 = 0, 1
+DROP, BITS, HEAD_MAJOR = 1, 2, 4    # flag bits of ishara_debug_attn_kernel_name
+TWO_PASS = 1 << 16                  # ishara_debug_force_regstage: the two-kernel attention backward instead of the one-pass kernel
 
 # route: "mfma" (impl 1 / 2, bf16) or "lane" (impl 0); dm: 0 no dropout, 1 hashed again in the backward (impl 2), 2 cached keep bits (impl 1);
 # two_pass: the two-kernel MFMA backward forced (bit 16 of ishara_debug_force_regstage); regime: see inputs()
@@ -50,18 +53,19 @@ def impl(c):
     return 0 if c.route == "lane" else (2 if c.dm == 1 else 1)
 
 
-def bwd_kernel(c):
-    """the backward instantiation launch_attn_bwd / launch_attn_bwd_mfma select for the case (the dispatch code restated; DESIGN.md §2 quotes it)"""
-    if c.route == "lane":
-        return f"attn_bwd_dq_kernel + attn_bwd_dkv_kernel<{'bf16' if c.dtype == 'bf16' else 'float'},{c.dh // 4}>"
-    if c.dh == 32 and c.T <= 384 and not c.two_pass:
-        nw, nt = (8, 1) if c.T <= 128 else (12, 1) if c.T <= 192 else (8, 2) if c.T <= 256 else (12, 2)
-        return f"attn_bwd_fused_kernel<{nw},{nt},{c.dm},{'FULL' if c.T == 16 * nw * nt else 'ragged'}>"
-    return f"attn_bwd_dq_mfma_kernel + attn_bwd_dkv_mfma_kernel<{c.dh},{c.dm}>"
+def bwd_kernel(lib, c):
+    """the backward instantiation launch_attn_bwd runs for the case as ishara_op_attn_bwd calls it (head-major dqkv; impl 1: the keep-bit buffer
+    given), read from the route itself (ishara_debug_attn_kernel_name: host only, nothing is launched); "" for a refused call"""
+    flags = (DROP if c.rate > 0 and int(rng.threshold8(c.rate)) else 0) | (BITS if impl(c) == 1 else 0) | HEAD_MAJOR
+    lib.ishara_debug_force_regstage(TWO_PASS if c.two_pass else 0)
+    try:
+        return lib.ishara_debug_attn_kernel_name(BF16 if c.dtype == "bf16" else F32, 1, c.T, c.dh, min(impl(c), 1), flags).decode()
+    finally:
+        lib.ishara_debug_force_regstage(0)
 
 
-def writes_delta(c):
-    return not bwd_kernel(c).startswith("attn_bwd_fused")
+def writes_delta(lib, c):
+    return not bwd_kernel(lib, c).startswith("attn_bwd_fused")
 
 
 MAIN = "std4"
@@ -72,7 +76,7 @@ REGIMES = ("std1", "std4", "std12", "q0", "late", "early")
 
 def _mfma_shapes():
     s = [(1, 3, T, 32, False) for T in MFMA_T32]
-    s += [(1, 3, T, 32, True) for T in MFMA_T32 if T <= 384]
+    s += [(1, 3, T, 32, True) for T in MFMA_T32[:-1]]      # forced where the one-pass kernel is the default: every T but the last
     s += [(1, 3, T, 64, False) for T in MFMA_T64]
     s += [(2, 8, T, 32, False) for T in (136, 264, 392)] + [(2, 8, 136, 64, False)]
     return s

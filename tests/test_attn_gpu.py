@@ -1,4 +1,4 @@
-"""The training attention kernels (attention.hip's lane-split kernels, attention_mfma.hip's MFMA forward, its one-pass backward in all eight
+"""The training attention kernels (attention.hip's lane-split kernels, attention_mfma.hip's MFMA forward, attention_bwd_mfma.hip's one-pass backward in all eight
 (waves, tiles, FULL / ragged) forms and its two-kernel backward at dh 32 and 64) against fp64 through ishara_op_attn_fwd / _bwd, at the tile
 edges of each: the cases, the reference and the bounds are tests/attn_parity.py's (f32 at the operator bound, bf16 at 2x observed once
 measured; tests/test_attn_mutants.py shows that the bounds reject ordinary mistakes).  Compared: o, lse, dq, dk, dv and, on the routes that store it,
@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 DT = {"f32": (_lib.F32, torch.float32), "bf16": (_lib.BF16, torch.bfloat16)}
 GUARD = 4096
 GUARD_BYTE, NAN_BYTE = 0xA5, 0xFF      # 0xFFFF is a bf16 NaN, 0xFFFFFFFF an fp32 NaN
-TWO_PASS = 1 << 16                     # ishara_debug_force_regstage: the two-kernel attention backward instead of the one-pass kernel
+TWO_PASS = A.TWO_PASS
 
 
 class Guarded:
@@ -63,6 +63,7 @@ def run(lib, c):
     o, dqkv, sc = Guarded(B * T * d * es), Guarded(B * T * 3 * d * es), Guarded(total)
     seed, f = A.seed_of(c), C.c_float
     args = (B, H, T, dh, f(A.scale_of(c)), seed, A.SITE, f(c.rate), A.impl(c), sc.ptr, _lib.stream())
+    assert A.bwd_kernel(lib, c), "the route refuses the backward call"
     lib.ishara_debug_force_regstage(TWO_PASS if c.two_pass else 0)
     try:
         _lib.check(lib.ishara_op_attn_fwd(code, _lib.ptr(qd), o.ptr, *args), "ishara_op_attn_fwd")
@@ -81,17 +82,18 @@ def run(lib, c):
     o_t, dqkv_t = o.view(tdt, B * T * d), dqkv.view(tdt, B * T * 3 * d)
     dq, dk, dv = A.split(host(dqkv_t), shp)
     got = dict(o=host(o_t).reshape(B, T, d), lse=host(sc.view(torch.float32, B * H * T, lay["lse"][0])).reshape(B, H, T), dq=dq, dk=dk, dv=dv)
-    if A.writes_delta(c):
+    if A.writes_delta(lib, c):
         got["delta"] = host(sc.view(torch.float32, B * H * T, lay["delta"][0])).reshape(B, H, T)
     return got, dict(o=o_t.clone(), dqkv=dqkv_t.clone())
 
 
-def _log(c, obs, **extra):
-    print(A.case_id(c), A.bwd_kernel(c), {k: f"{v:.3g}" for k, v in obs.items()}, extra or "")
+def _log(lib, c, obs, **extra):
+    kernel = A.bwd_kernel(lib, c)
+    print(A.case_id(c), kernel, {k: f"{v:.3g}" for k, v in obs.items()}, extra or "")
     path = os.environ.get("ISHARA_ATTN_LOG")
     if path:
         with open(path, "a") as f:
-            f.write(json.dumps(dict(case=A.case_id(c), kernel=A.bwd_kernel(c), **c._asdict(), **obs, **extra)) + "\n")
+            f.write(json.dumps(dict(case=A.case_id(c), kernel=kernel, **c._asdict(), **obs, **extra)) + "\n")
 
 
 _raw = {}      # case -> raw o / dqkv of the cases other cases are compared with bit by bit
@@ -109,7 +111,7 @@ def test_attention_matches_fp64(lib, c):
     _raw[c] = raw
     ref = dict(A.reference(c))
     names = ["o", "lse", "dq", "dk", "dv"]
-    if A.writes_delta(c):
+    if A.writes_delta(lib, c):
         assert np.isfinite(got["o"]).all(), "o is not finite"
         ref["delta"] = A.delta_from(got["o"], A.inputs(c)[1], A.shape(c))      # delta is defined on the kernel's own (rounded) o
         names.append("delta")
@@ -135,7 +137,7 @@ def test_attention_matches_fp64(lib, c):
         # every P is exp(0) = 1, exact in bf16: what is left is the fp32 sum (2e-5, as for lse) and, in bf16, o's own rounding: half an ulp is
         # 2^-9 |o|, allowed twice
         assert bool((err <= 2e-5 + (2.0 ** -8 if c.dtype == "bf16" else 0.0) * np.abs(vbar[:, None])).all()), "o of a uniform softmax is not the mean of v"
-    _log(c, obs, **extra)
+    _log(lib, c, obs, **extra)
     assert not bad, "\n".join(bad)
 
 

@@ -125,8 +125,8 @@ def test_chosen_seeds_draw_the_mask_share_the_gpu_test_asserts():
     assert A.mask_of(A.shape(A.TINY_RATE_CASE), 4242, A.TINY_RATE_CASE.rate) is None      # thr8 = 0: no mask at all
 
 
-def test_case_list_reaches_every_backward_instantiation():
-    kernels = {A.bwd_kernel(c) for c in A.CASES}
+def test_case_list_reaches_every_backward_instantiation(lib):
+    kernels = {A.bwd_kernel(lib, c) for c in A.CASES}
     for nw, nt in ((8, 1), (12, 1), (8, 2), (12, 2)):
         for dm in (0, 1, 2):
             for form in ("FULL", "ragged"):

@@ -104,6 +104,24 @@ int ishara_forward(ishara_model* m, const float* x, int32_t B, float* logits, in
  * loss (device scalar) = mean_b nll_b; gradients of loss*loss_scale fill grads[0,trainable). */
 int ishara_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B,
                          float* loss, float* nll, float loss_scale, ishara_stream s);
+/* The same pair with per-clip frame lengths: the padding mask the reference's layers were written for (Masking(0.0), conv-hybrid-model.ipynb c7;
+ * its own get_model loses the mask at x + pe).  frame_len: device int32 [B], 4-byte aligned; clip b has n_b = frame_len[b] real frames, frames
+ * t >= n_b are padding; clamped to [0,T] on the device, never read by the host (no synchronise, graph-capturable).  Exactly the three
+ * operations the reference's layers mask are masked: the keys j >= n_b of every MultiHeadSelfAttention (c5:109-112), the time mean of the ECA
+ * gate of every Conv1DBlock (c5:8-9) and of the Squeeze-Excite gate of the Squeezeformer ConvModule (c5:129-130), each with its backward.
+ * Dense, LayerNorm, the depthwise convolutions, BatchNorm (statistics over all B*T rows, as Keras's BatchNormalization ignores the mask), the
+ * positional encoding, the head and the CTC loss (logit_length = T, c6:3) see the padded frames as without lengths.  n_b = 0: the clip's
+ * attention output and both means are 0 (Keras: NaN).  The caller owns the array and passes it again to ishara_loss_backward_ex; the library
+ * keeps only whether the last training forward had lengths and refuses a backward call that disagrees.  frame_len == NULL: the plain calls
+ * above, bit for bit, on the kernels they launch.  ISHARA_F16 with lengths and the encoder-only families are refused before any GPU work. */
+int ishara_forward_ex(ishara_model* m, const float* x, int32_t B, float* logits, int32_t training, uint32_t seed, const int32_t* frame_len,
+                      ishara_stream s);
+int ishara_loss_backward_ex(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale,
+                            const int32_t* frame_len, ishara_stream s);
+/* frame lengths of a zero-padded batch x [B,T,F] f32 (device): out_len[b] (device int32 [B]) = 1 + the index of the last frame of clip b that
+ * has any non-zero feature, 0 if there is none.  The prefix reading of Masking(0.0): an all-zero frame INSIDE a clip stays valid, where Keras
+ * masks that frame too.  One workgroup per clip; B, T, F > 0. */
+int ishara_frame_lengths(const float* x, int32_t B, int32_t T, int32_t F, int32_t* out_len, ishara_stream s);
 /* ConformerEncoder.forward (conformer/conformer.py:84-87) for an ISHARA_FAMILY_TORCH_CONFORMER handle: x, y [B,T,dim] f32.
  * training=1: Dropout active (seed), BatchNorm1d uses batch statistics and updates running_mean / running_var, the
  * activations the backward pass needs stay in the workspace. */
@@ -325,6 +343,11 @@ int ishara_debug_module_forward(ishara_model* m, int32_t i, const float* x, int3
 int ishara_debug_module_backward(ishara_model* m, int32_t i, const float* dy, int32_t B, float* dx, ishara_stream s);
 int ishara_debug_head_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll,
                                     float loss_scale, float* dx, ishara_stream s);
+/* the probe with per-clip frame lengths (ishara_forward_ex): frame_len device int32 [B] or NULL (= the plain probe); the backward call must be
+ * given lengths exactly when its training forward was.  Modules without a masked operation (stem, ffn, the Conformer block's conv, head) ignore them. */
+int ishara_debug_module_forward_ex(ishara_model* m, int32_t i, const float* x, int32_t B, float* y, int32_t training, uint32_t seed,
+                                   const int32_t* frame_len, ishara_stream s);
+int ishara_debug_module_backward_ex(ishara_model* m, int32_t i, const float* dy, int32_t B, float* dx, const int32_t* frame_len, ishara_stream s);
 
 /* ---- single-operator entry points (parity tests of the individual kernels) ------------ */
 /* dt: ISHARA_F32 / ISHARA_BF16 / ISHARA_F16; the backward operators refuse ISHARA_F16 (inference only), every operator refuses an unknown

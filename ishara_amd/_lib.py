@@ -68,6 +68,9 @@ SIGNATURES = {
     "ishara_bind": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64]),
     "ishara_sync_weights": (C.c_int, [_P, _P]),
     "ishara_forward": (C.c_int, [_P, _P, _I32, _P, _I32, _U32, _P]),
+    "ishara_forward_ex": (C.c_int, [_P, _P, _I32, _P, _I32, _U32, _P, _P]),
+    "ishara_loss_backward_ex": (C.c_int, [_P, _P, _P, _I32, _P, _P, _F, _P, _P]),
+    "ishara_frame_lengths": (C.c_int, [_P, _I32, _I32, _I32, _P, _P]),
     "ishara_encoder_forward": (C.c_int, [_P, _P, _I32, _P, _I32, _U32, _P]),
     "ishara_encoder_backward": (C.c_int, [_P, _P, _I32, _P, _P]),
     "ishara_encoder_forward_ex": (C.c_int, [_P, _P, _I32, _P, _I32, _U32, _P, _P, _P]),
@@ -111,6 +114,8 @@ SIGNATURES = {
     "ishara_debug_module_forward": (C.c_int, [_P, _I32, _P, _I32, _P, _I32, _U32, _P]),
     "ishara_debug_module_backward": (C.c_int, [_P, _I32, _P, _I32, _P, _P]),
     "ishara_debug_head_loss_backward": (C.c_int, [_P, _P, _P, _I32, _P, _P, _F, _P, _P]),
+    "ishara_debug_module_forward_ex": (C.c_int, [_P, _I32, _P, _I32, _P, _I32, _U32, _P, _P]),
+    "ishara_debug_module_backward_ex": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _P]),
     "ishara_op_scratch_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_op_dense_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "ishara_op_dense_fwd_ex": (C.c_int, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),

@@ -405,9 +405,65 @@ __global__ __launch_bounds__(1024) void eca_bn_bwd_channel_kernel(const float* _
     }
 }
 
+// step 2 with per-clip frame lengths (frame_mask.hip): the gate pooled BN(h2) over the n_b valid frames, so `gap` holds that masked MEAN
+// (at n_b = 0 the pooled value is the constant 0) and the gate's gradient reaches the valid frames only.  The constant of the unmasked kernel splits in two:
+// E[b,c] <- dgn / n_b (frames t < n_b) and Ecol[c] = -dbeta / Mtot (every frame); dgamma, dbeta, Fc as above
+__global__ __launch_bounds__(1024) void eca_bn_bwd_channel_len_kernel(const float* __restrict__ S1, const float* __restrict__ S2, const float* __restrict__ gap,
+                                          const float* __restrict__ sg, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                          float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ E, float* __restrict__ Ecol, float* __restrict__ Fc,
+                                          const float* __restrict__ dw5part, int nparts5, float* __restrict__ dw5, const int* __restrict__ frame_len, int B, int Tn, int C) {
+    __shared__ double rg_[FIN_NW][FIN_CL], rb_[FIN_NW][FIN_CL];
+    if (blockIdx.x == 0 && threadIdx.x < 5 * 64) {      // ECA tap gradient, as in the unmasked kernel
+        const int j = threadIdx.x >> 6, l = threadIdx.x & 63;
+        float a = 0.f;
+        for (int b = l; b < nparts5; b += 64) a += dw5part[(size_t)b * 8 + j];
+        a = wave_sum(a);
+        if (l == 0) dw5[j] += a;
+    }
+    const int cl = threadIdx.x & (FIN_CL - 1), bl = threadIdx.x / FIN_CL, wv = threadIdx.x >> 6;
+    const int c = blockIdx.x * FIN_CL + cl;
+    const bool act = c < C;
+    const float mu = act ? mean[c] : 0.f, rs = act ? rstd[c] : 0.f;
+    double dg = 0.0, db = 0.0;
+    if (act)
+        for (int b = bl; b < B; b += FIN_BL) {
+            const size_t i = (size_t)b * C + c;
+            const float ghat = (gap[i] - mu) * rs;
+            const float ev = attn_key_count(frame_len, b, Tn) > 0 ? E[i] : 0.f;      // n_b = 0: the pooled value is the constant 0, its gradient reaches nothing
+            dg += (double)(sg[i] * S2[i] + ev * ghat);
+            db += (double)(sg[i] * S1[i] + ev);
+        }
+    dg = fin_fold(dg); db = fin_fold(db);
+    if ((threadIdx.x & 63) < FIN_CL) { rg_[wv][cl] = dg; rb_[wv][cl] = db; }
+    __syncthreads();
+    const float mtot = (float)B * (float)Tn;
+    if (bl == 0 && act) {
+        for (int i = 1; i < FIN_NW; ++i) { dg += rg_[i][cl]; db += rb_[i][cl]; }
+        dgamma[c] += (float)dg;
+        dbeta[c] += (float)db;
+        Fc[c] = (float)dg / mtot;
+        Ecol[c] = -((float)db / mtot);
+    }
+    if (act)
+        for (int b = bl; b < B; b += FIN_BL) {
+            const int n = attn_key_count(frame_len, b, Tn);
+            const size_t i = (size_t)b * C + c;
+            E[i] = n > 0 ? E[i] * (1.f / (float)n) : 0.f;
+        }
+}
+
 int launch_eca_bn_bwd_finalize(float* S1, float* S2, const float* gap, const float* gn, const float* sgate,
                                const float* w5, const float* gamma, const float* beta, const float* mean, const float* rstd,
-                               float* dgamma, float* dbeta, float* dw5, float* E, float* Fc, float* dw5part, int B, int T, int C, hipStream_t s, const PsaStats* ps) {
+                               float* dgamma, float* dbeta, float* dw5, float* E, float* Fc, float* dw5part, int B, int T, int C, hipStream_t s, const PsaStats* ps,
+                               const int* frame_len, float* Ecol) {
+    if (frame_len) {
+        if (ps || !Ecol) { ishara_set_error("eca_bn_bwd_finalize: frame lengths go with S1 / S2 from memory and an Ecol array"); return -1; }
+        const int CCl = (C > 256 && C % 256 == 0 && C / 256 <= ECA_MAX_CHUNKS) ? 256 : C, nchunkl = C / CCl;
+        hipLaunchKernelGGL(eca_bwd_sample_kernel, dim3(B, nchunkl), dim3(256), (size_t)(2 * (CCl + 4) + 2 * (CCl + 16)) * sizeof(float), s, S1, S2, gn, sgate, w5, gamma, beta, E, dw5part, C, CCl, PsaStats{});
+        hipLaunchKernelGGL(eca_bn_bwd_channel_len_kernel, dim3((C + FIN_CL - 1) / FIN_CL), dim3(FIN_CL * FIN_BL), 0, s, S1, S2, gap, sgate, mean, rstd, dgamma, dbeta, E, Ecol, Fc,
+                           dw5part, B * nchunkl, dw5, frame_len, B, T, C);
+        return launch_rc();
+    }
     PsaStats p = ps ? *ps : PsaStats{};
     if (p.G && (C % 8 != 0 || p.ldt % 8 != 0 || ((uintptr_t)p.Wt) % 16 != 0)) { ishara_set_error("eca_bn_bwd_finalize: PsaStats needs C %% 8 == 0 and 16-byte aligned weight rows"); return -1; }
     const int CC = (C > 256 && C % 256 == 0 && C / 256 <= ECA_MAX_CHUNKS) ? 256 : C, nchunk = C / CC;      // dw5part: B * nchunk * 8 floats

@@ -265,8 +265,12 @@ static int conv_fwd(ishara_model* m, ConvBlock& cb, const Run& r, const void* x)
     CK(gemm_fwd(m, cb.W1, x, dt, m->W(cb.z1), dt, r.M, OP_NONE, no, e1));
     // inference: the partial statistic rows of the depthwise conv are summed, and the BatchNorm constants formed from the moving statistics,
     // inside eca_fwd (4 launches per Conv1DBlock instead of 6: at B = 1 every launch is ~9 us of latency)
+    // Frame lengths (r.key_len; DESIGN §2 "Frame lengths"): the ECA gate pools BN(h2) over the clip's n_b valid frames (c5:8-9).  BatchNorm's statistics
+    // stay over all B*T rows, so the depthwise conv's statistics pass runs as without lengths; a masked time mean of h2 (a kernel of its own) then
+    // feeds eca_fwd_len (g = 0 at n_b = 0).  The fused inference form and the psa weight gradient assume the all-T sums: not taken.
+    const int* fl = r.key_len;
     int prows = 0;
-    const bool infer_fused = !r.training && getenv("ISHARA_NO_INFER_FUSION") == nullptr;
+    const bool infer_fused = !r.training && !fl && getenv("ISHARA_NO_INFER_FUSION") == nullptr;
     static const bool no_train_fusion = getenv("ISHARA_NO_STATS_FUSION") != nullptr;
     const bool train_fused = r.training && !no_train_fusion;
     CKP(m, "dwconv_fwd", 3.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_dwconv_fwd(dt, DWIN_SWISH, m->W(cb.z1), m->P(cb.dw), nullptr, m->W(cb.h2), m->Wf(cb.ssum), m->Wf(cb.ssq), m->Wf(m->slab), B, T, c, cb.k, cb.k - 1, m->s,
@@ -290,7 +294,10 @@ static int conv_fwd(ishara_model* m, ConvBlock& cb, const Run& r, const void* x)
                     gemm_tn_bias_rowscale_ok(dt, dt, dt, r.M, cb.W2.K, cb.W2.N, T);
         e2.rowscale_bias = cb.folded ? 1 : 0;
     }
-    if (infer_fused && prows > 0)
+    if (fl) {
+        CKP(m, "masked_time_mean", 1.0 * r.M * c * (double)dt_size(dt), 0, launch_masked_time_mean(dt, m->W(cb.h2), fl, m->Wf(cb.ssum), B, T, c, m->s));
+        CKP(m, "eca_fwd_len", 0, 0, launch_eca_fwd_len(m->Wf(cb.ssum), m->Wf(cb.a), m->Wf(cb.bsh), m->P(cb.eca), fl, T, m->Wf(cb.gn), m->Wf(cb.sg), m->Wf(cb.P), m->Wf(cb.Q), B, c, m->s, ds.thr ? m->Wf(cb.rs) : nullptr, ds, cb.folded ? 1 : 0));
+    } else if (infer_fused && prows > 0)
         CKP(m, "eca_fwd", 0, 0, launch_eca_fwd_infer(m->Wf(m->slab), prows, m->P(cb.bn.mm), m->P(cb.bn.mv), m->P(cb.bn.gamma), m->P(cb.bn.beta), 1e-3f, m->P(cb.eca), 1.f / T,
                                                        m->Wf(cb.gn), m->Wf(cb.sg), m->Wf(cb.P), m->Wf(cb.Q), B, c, m->s));
     else if (train_fused && prows > 0)
@@ -306,7 +313,7 @@ static int conv_fwd(ishara_model* m, ConvBlock& cb, const Run& r, const void* x)
         if (gemm_nt_as_prologue_ok(dt, dt, dt, r.M, cb.W2.N, cb.W2.K, cb.W2.ldt, probe)) {
             // training: h4 is written only when the backward pass needs it in memory — not when the project conv's weight-gradient GEMM applies
             // P, Q itself (gemm_tn.hip TnPsa: whole samples per M-split; the drop-path scale, if any, must be the folded one)
-            cb.psa = r.training && m->psa_on && (!ds.thr || cb.folded) && gemm_tn_psa_ok(dt, dt, dt, r.M, cb.W2.K, cb.W2.N, T);
+            cb.psa = r.training && m->psa_on && !fl && (!ds.thr || cb.folded) && gemm_tn_psa_ok(dt, dt, dt, r.M, cb.W2.K, cb.W2.N, T);
             e2.pa_P = m->Wf(cb.P); e2.pa_Q = m->Wf(cb.Q); e2.T = T; e2.pro_out = (r.training && !cb.psa) ? m->W(cb.h4) : nullptr;
             CK(gemm_fwd(m, cb.W2, m->W(cb.h2), dt, m->W(cb.out), dt, r.M, OP_NONE, no, e2));
             return 0;
@@ -341,7 +348,7 @@ static int mhsa_fwd(ishara_model* m, MHSA& a, const Run& r, const void* x) {
     CK(gemm_fwd(m, a.Wqkv, ain, dt, nullptr, dt, r.M, OP_NONE, no, eq));
     const float scale = 1.0f / sqrtf((float)m->d);     // self.scale = dim ** -0.5 (c5:95)
     CKP(m, "attn_fwd", 4.0 * r.M * m->d * (double)dt_size(m->dt), 4.0 * r.B * m->H * (double)m->T * m->T * m->dh, launch_attn_fwd(dt, m->W(a.q), m->W(a.k), m->W(a.vt), m->W(a.o), m->Wf(a.lse), r.B, m->H, m->T, m->dh, scale,
-                       dspec_attn(r, a.site_attn, a.rate), m->cfg.attn_impl, reinterpret_cast<uint32_t*>(m->W(a.maskw)), m->s));
+                       dspec_attn(r, a.site_attn, a.rate), m->cfg.attn_impl, reinterpret_cast<uint32_t*>(m->W(a.maskw)), m->s, nullptr, r.key_len));      // frame lengths: keys j >= n_b excluded (c5:109-112)
     EpiArgs ep; ep.resid = x;
     if (a.has_out_drop) ep.drop = dspec(r, a.site_out, m->cfg.dropout_rate);
     CK(gemm_fwd(m, a.Wp, m->W(a.o), dt, m->W(a.out), dt, r.M, OP_NONE, no, ep));
@@ -359,8 +366,11 @@ static int sqzconv_fwd(ishara_model* m, SqzConv& c, const Run& r, const void* x)
     CKP(m, "dwconv_fwd", 3.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_dwconv_fwd(dt, DWIN_SWISH, m->W(c.zc), m->P(c.dw), nullptr, m->W(c.zd), nullptr, nullptr, nullptr, B, T, de, c.k, c.k - 1, m->s));
     CKP(m, "map_rows", 2.0 * r.M * de * (double)dt_size(m->dt), 0, launch_map_rows(dt, MAP_SWISH, m->W(c.zd), m->W(c.hd), nullptr, DropSpec{0, 0, 1.f}, r.M, T, de, m->s));
     CK(gemm_fwd(m, c.Wc3, m->W(c.hd), dt, m->W(c.u3), dt, r.M, OP_NONE, no, e0));
+    // frame lengths: z = mean of u3 over the valid frames (c5:129-130): c.gap holds the masked mean, the SE kernels run with invT = 1
+    if (r.key_len) CKP(m, "masked_time_mean", 1.0 * r.M * d * (double)dt_size(dt), 0, launch_masked_time_mean(dt, m->W(c.u3), r.key_len, m->Wf(c.gap), B, T, d, m->s));
+    else
     CKP(m, "sample_reduce", 2.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_sample_reduce(dt, m->W(c.u3), nullptr, nullptr, nullptr, m->Wf(c.gap), nullptr, B, T, d, m->s));
-    CKP(m, "se_fwd", 0, 0, launch_se_fwd(m->Wf(c.gap), 1.f / T, m->P(c.seW1), m->P(c.seb1), m->P(c.seW2), m->P(c.seb2), m->Wf(c.hid), m->Wf(c.se), B, d, c.R, m->s));
+    CKP(m, "se_fwd", 0, 0, launch_se_fwd(m->Wf(c.gap), r.key_len ? 1.f : 1.f / T, m->P(c.seW1), m->P(c.seb1), m->P(c.seW2), m->P(c.seb2), m->Wf(c.hid), m->Wf(c.se), B, d, c.R, m->s));
     CKP(m, "sample_affine", 4.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_sample_affine(dt, m->W(c.u3), m->Wf(c.se), nullptr, x, m->W(c.out), B, T, d, m->s));
     return 0;
 }
@@ -454,16 +464,26 @@ static int head_fwd(ishara_model* m, const Run& r, const void* h, float* logits)
     return 0;
 }
 
-extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float* logits, int32_t training, uint32_t seed, ishara_stream st) {
-    if (!m->ws) { ishara_set_error("ishara_forward: model is not bound"); return -1; }
-    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("ishara_forward: this handle is an encoder-only family; use ishara_encoder_forward"); return -1; }
-    if (B <= 0 || B > m->Bmax) { ishara_set_error("ishara_forward: batch %d outside 1..%d", B, m->Bmax); return -1; }
+// what every entry point that takes frame lengths refuses before any GPU work (frame_len == NULL: nothing to refuse)
+static bool frame_len_ok(const ishara_model* m, const char* fn, const int32_t* frame_len) {
+    if (!frame_len) return true;
+    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("%s: frame lengths are for ISHARA_FAMILY_KERAS_HYBRID only (family %d)", fn, m->family); return false; }
+    if (m->dt == DT_F16) { ishara_set_error("%s: ISHARA_F16 takes no frame lengths (the fp16 model is the TFLite export, whose graph has no mask)", fn); return false; }
+    if ((uintptr_t)frame_len % 4 != 0) { ishara_set_error("%s: frame_len must be 4-byte aligned", fn); return false; }
+    return true;
+}
+static int keras_forward(const char* fn, ishara_model* m, const float* x, int32_t B, float* logits, int32_t training, uint32_t seed, const int32_t* frame_len, ishara_stream st) {
+    if (!frame_len_ok(m, fn, frame_len)) return -1;      // (with lengths: family, storage type and alignment before anything else)
+    if (!m->ws) { ishara_set_error("%s: model is not bound", fn); return -1; }
+    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("%s: this handle is an encoder-only family; use ishara_encoder_forward", fn); return -1; }
+    if (B <= 0 || B > m->Bmax) { ishara_set_error("%s: batch %d outside 1..%d", fn, B, m->Bmax); return -1; }
     if (m->dt == DT_F16 && training) {
-        ishara_set_error("ishara_forward: ISHARA_F16 is an inference-only storage type (the reference's fp16 is the TFLite export, c14:1-5; it reports NaNs when TRAINING in fp16)");
+        ishara_set_error("%s: ISHARA_F16 is an inference-only storage type (the reference's fp16 is the TFLite export, c14:1-5; it reports NaNs when TRAINING in fp16)", fn);
         return -1;
     }
     m->s = (hipStream_t)st;
     Run r{B, B * m->T, training, seed};
+    r.key_len = frame_len;
     CK(stem_fwd(m, r, x));
     const void* h = m->W(m->stem_out);
     for (const Layer& L : m->layers) {
@@ -483,8 +503,14 @@ extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float*
         }
     }
     CK(head_fwd(m, r, h, logits));
-    m->lastB = B; m->last_training = training; m->last_seed = seed; m->last_x = x; m->probe_mod = -1;
+    m->lastB = B; m->last_training = training; m->last_seed = seed; m->last_x = x; m->probe_mod = -1; m->last_masked = frame_len ? 1 : 0;
     return 0;
+}
+extern "C" int ishara_forward(ishara_model* m, const float* x, int32_t B, float* logits, int32_t training, uint32_t seed, ishara_stream st) {
+    return keras_forward("ishara_forward", m, x, B, logits, training, seed, nullptr, st);
+}
+extern "C" int ishara_forward_ex(ishara_model* m, const float* x, int32_t B, float* logits, int32_t training, uint32_t seed, const int32_t* frame_len, ishara_stream st) {
+    return keras_forward("ishara_forward_ex", m, x, B, logits, training, seed, frame_len, st);
 }
 
 // ------------------------------------------------------------------ module backward
@@ -522,7 +548,12 @@ static int conv_bwd(ishara_model* m, ConvBlock& cb, const Run& r, const void* x,
     if (cb.psa) { pst.G = m->Wf(m->psaG); pst.Rpart = m->Wf(m->psaR); pst.nparts = cb.W2.N / 64; pst.Wt = m->ws + cb.W2.wt; pst.ldt = cb.W2.ldt; pst.N = cb.W2.N;
                   pst.rs = ds.thr ? m->Wf(cb.rs) : nullptr; pst.mean = m->Wf(cb.mean); pst.rstd = m->Wf(cb.rstd); }
     CKP(m, "eca_bn_bwd_finalize", 0, 0, launch_eca_bn_bwd_finalize(m->Wf(m->S1), m->Wf(m->S2), m->Wf(cb.ssum), m->Wf(cb.gn), m->Wf(cb.sg), m->P(cb.eca), m->P(cb.bn.gamma), m->P(cb.bn.beta),
-                                  m->Wf(cb.mean), m->Wf(cb.rstd), m->G(cb.bn.gamma), m->G(cb.bn.beta), m->G(cb.eca), m->Wf(m->E), m->Wf(m->Fc), m->Wf(m->ecap), B, T, c, m->s, cb.psa ? &pst : nullptr));
+                                  m->Wf(cb.mean), m->Wf(cb.rstd), m->G(cb.bn.gamma), m->G(cb.bn.beta), m->G(cb.eca), m->Wf(m->E), m->Wf(m->Fc), m->Wf(m->ecap), B, T, c, m->s, cb.psa ? &pst : nullptr, r.key_len, m->Wf(m->Ecol)));
+    if (r.key_len) {      // frame lengths: the gate's gradient E[b,c] = dgn / n_b reaches the frames t < n_b only, Ecol[c] = -dbeta / Mtot every frame.  The two-kernel
+        // path: the BatchNorm-carrying depthwise backward takes one constant per (sample, channel) (DESIGN §2 "Frame lengths": routes)
+        CKP(m, "bn_bwd_apply_len", 6.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_bn_bwd_apply_len(dt, m->W(m->t1), m->W(cb.h2), m->Wf(cb.mean), m->Wf(cb.rstd), m->Wf(cb.a), m->Wf(cb.sg), m->Wf(m->E), m->Wf(m->Ecol), m->Wf(m->Fc), r.key_len, m->W(m->t1), B, T, c, m->s));
+        CK(dwconv_bwd_deferred(m, r, 8.0, DWIN_SWISH, m->W(m->t1), nullptr, m->W(cb.z1), cb.dw, -1, m->W(m->t2), c, cb.k, cb.k - 1));
+    } else {
     // BatchNorm backward applied inside the depthwise-conv backward (one pass over dh4, h2 and z1); shapes without the fused kernel
     // take the two-kernel path
     DwBnArgs bn; bn.h = m->W(cb.h2); bn.mean = m->Wf(cb.mean); bn.rstd = m->Wf(cb.rstd); bn.a = m->Wf(cb.a); bn.sg = m->Wf(cb.sg); bn.E = m->Wf(m->E); bn.Fc = m->Wf(m->Fc); bn.e_per_sample = 1;
@@ -531,6 +562,7 @@ static int conv_bwd(ishara_model* m, ConvBlock& cb, const Run& r, const void* x,
     if (!fused) {
         CKP(m, "bn_bwd_apply", 6.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_bn_bwd_apply(dt, m->W(m->t1), m->W(cb.h2), m->Wf(cb.mean), m->Wf(cb.rstd), m->Wf(cb.a), m->Wf(cb.sg), m->Wf(m->E), 1, m->Wf(m->Fc), m->W(m->t1), B, T, c, m->s));
         CK(dwconv_bwd_deferred(m, r, 8.0, DWIN_SWISH, m->W(m->t1), nullptr, m->W(cb.z1), cb.dw, -1, m->W(m->t2), c, cb.k, cb.k - 1));
+    }
     }
     EpiArgs e2; e2.resid = g;
     CK(gemm_dgrad(m, cb.W1, m->W(m->t2), dt, gn, r.M, OP_NONE, no, e2));
@@ -563,7 +595,7 @@ static int mhsa_bwd(ishara_model* m, MHSA& a, const Run& r, const void* x, const
     CK(gemm_wgrad(m, a.Wp, m->W(a.o), dt, OP_NONE, no, gs, dt, OP_NONE, no, r.M));
     const float scale = 1.0f / sqrtf((float)m->d);
     CKP(m, "attn_bwd", 8.0 * r.M * m->d * (double)dt_size(m->dt), 10.0 * r.B * m->H * (double)m->T * m->T * m->dh, launch_attn_bwd(dt, m->W(a.q), m->W(a.k), m->W(a.vt), m->W(a.o), m->W(m->t1), m->Wf(a.lse), m->Wf(m->delta), m->W(m->t2),
-                       r.B, m->H, m->T, m->dh, scale, dspec_attn(r, a.site_attn, a.rate), 1, m->cfg.attn_impl, reinterpret_cast<uint32_t*>(m->W(a.maskw)), m->s));
+                       r.B, m->H, m->T, m->dh, scale, dspec_attn(r, a.site_attn, a.rate), 1, m->cfg.attn_impl, reinterpret_cast<uint32_t*>(m->W(a.maskw)), m->s, nullptr, r.key_len));
     CK(gemm_dgrad(m, a.Wqkv, m->W(m->t2), dt, m->W(m->t1), r.M, OP_NONE, no, e0));            // dxn
     CK(gemm_wgrad(m, a.Wqkv, m->W(a.xn), dt, OP_NONE, no, m->W(m->t2), dt, OP_NONE, no, r.M));
     return layernorm_bwd_deferred(m, r, m->W(m->t1), x, a.mean, a.rstd, a.ln, g, gn);
@@ -573,8 +605,11 @@ static int sqzconv_bwd(ishara_model* m, SqzConv& c, const Run& r, const void* x,
     const int dt = m->dt, d = m->d, de = c.Wc1.N, B = r.B, T = m->T;
     OpArgs no; EpiArgs e0;
     CKP(m, "sample_reduce", 2.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_sample_reduce(dt, g, m->W(c.u3), nullptr, nullptr, m->Wf(m->S1), m->Wf(m->dse), B, T, d, m->s));   // dse = sum_t g*u3
-    CKP(m, "se_bwd", 0, 0, launch_se_bwd(m->Wf(m->dse), m->Wf(c.gap), 1.f / T, m->P(c.seW1), m->P(c.seW2), m->Wf(c.hid), m->Wf(c.se),
+    CKP(m, "se_bwd", 0, 0, launch_se_bwd(m->Wf(m->dse), m->Wf(c.gap), r.key_len ? 1.f : 1.f / T, m->P(c.seW1), m->P(c.seW2), m->Wf(c.hid), m->Wf(c.se),
                      m->G(c.seW1), m->G(c.seb1), m->G(c.seW2), m->G(c.seb2), m->Wf(m->dgapT), m->Wf(m->E), B, d, c.R, m->s));
+    if (r.key_len)      // frame lengths: c.gap is the masked mean, dgapT its gradient; dgapT / n_b goes to the valid frames only
+    CKP(m, "sample_affine_len", 4.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_sample_affine_len(dt, g, m->Wf(c.se), m->Wf(m->dgapT), r.key_len, m->W(m->t1), B, T, d, m->s));
+    else
     CKP(m, "sample_affine", 4.0 * r.M * m->d * (double)dt_size(m->dt), 0, launch_sample_affine(dt, g, m->Wf(c.se), m->Wf(m->dgapT), nullptr, m->W(m->t1), B, T, d, m->s));           // du3
     EpiArgs e1; e1.dact = DACT_SWISH; e1.aux = m->W(c.zd);
     CK(gemm_dgrad(m, c.Wc3, m->W(m->t1), dt, m->W(m->t2), r.M, OP_NONE, no, e1));                                // dzd
@@ -642,14 +677,23 @@ static int stem_bwd(ishara_model* m, const Run& r, const void* g) {
     return 0;
 }
 
-extern "C" int ishara_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, ishara_stream st) {
-    if (!m->ws || !m->grads) { ishara_set_error("ishara_loss_backward: model is not bound (grads required)"); return -1; }
-    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("ishara_loss_backward: this handle is an encoder-only family; use ishara_encoder_backward"); return -1; }
-    if (B != m->lastB || !m->last_training) { ishara_set_error("ishara_loss_backward: call ishara_forward(training=1) with the same batch first"); return -1; }
+// a backward call must be given frame lengths exactly when its training forward was (the arrays are the caller's: only that bit is kept)
+static bool frame_len_agrees(const char* fn, bool fwd_had, const int32_t* frame_len) {
+    if (fwd_had == (frame_len != nullptr)) return true;
+    ishara_set_error("%s: the training forward was %s frame lengths, this call is %s", fn, fwd_had ? "given" : "not given", frame_len ? "given some" : "given none");
+    return false;
+}
+static int keras_loss_backward(const char* fn, ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, const int32_t* frame_len, ishara_stream st) {
+    if (!frame_len_ok(m, fn, frame_len)) return -1;
+    if (!m->ws || !m->grads) { ishara_set_error("%s: model is not bound (grads required)", fn); return -1; }
+    if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("%s: this handle is an encoder-only family; use ishara_encoder_backward", fn); return -1; }
+    if (B != m->lastB || !m->last_training) { ishara_set_error("%s: call ishara_forward(training=1) with the same batch first", fn); return -1; }
+    if (!frame_len_agrees(fn, m->last_masked != 0, frame_len)) return -1;
     m->s = (hipStream_t)st;
     m->red.njobs = 0; m->red.nblocks = 0; m->red_off = 0; g_red_sink = nullptr;       // ... nor recorded column sums
     m->tn_defer.pending = false;        // a previous backward pass that returned early (error path) must not leave slab sums behind for this one to add
     Run r{B, B * m->T, 1, m->last_seed};
+    r.key_len = frame_len;      // the three masked operations only: the CTC loss below keeps logit_length = T (c6:3)
     const int T = m->T;
     float* nl = nll ? nll : m->Wf(m->nllb);
     CK(launch_fill_u32(m->grads, (size_t)m->n_train, 0u, m->s));      // a kernel, not a memset node: the whole step stays capturable (hipGraph note)
@@ -688,6 +732,13 @@ extern "C" int ishara_loss_backward(ishara_model* m, const float* logits, const 
     CK(red_flush(m));
     if (!m->bucket_ev.empty()) HIP_CHECK_RET(hipEventRecord(m->bucket_ev.back(), m->s));
     return 0;
+}
+extern "C" int ishara_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, ishara_stream st) {
+    return keras_loss_backward("ishara_loss_backward", m, logits, labels, B, loss, nll, loss_scale, nullptr, st);
+}
+extern "C" int ishara_loss_backward_ex(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, const int32_t* frame_len,
+                                       ishara_stream st) {
+    return keras_loss_backward("ishara_loss_backward_ex", m, logits, labels, B, loss, nll, loss_scale, frame_len, st);
 }
 
 // ------------------------------------------------------------------ module probe (debug aid; tests/test_modules_gpu.py)
@@ -763,16 +814,17 @@ static bool probe_ok(ishara_model* m, const char* fn, int i, int B, const std::v
     if (!m->ws || (need_grads && !m->grads)) { ishara_set_error("%s: model is not bound%s", fn, need_grads ? " (grads required)" : ""); return false; }
     return true;
 }
-extern "C" int ishara_debug_module_forward(ishara_model* m, int32_t i, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, ishara_stream st) {
-    const char* fn = "ishara_debug_module_forward";
+static int probe_module_forward(const char* fn, ishara_model* m, int32_t i, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, const int32_t* frame_len, ishara_stream st) {
     if (!probe_family_ok(m, fn)) return -1;
     const std::vector<ProbeMod> v = probe_modules(m);
+    if (!frame_len_ok(m, fn, frame_len)) return -1;
     if (!probe_ok(m, fn, i, B, v, training, false)) return -1;
     if (!x || !y) { ishara_set_error("%s: null x / y", fn); return -1; }
     m->s = (hipStream_t)st;
     m->probe_mod = -1; m->last_training = 0;      // the workspace no longer holds a whole forward pass: ishara_loss_backward refuses until the next ishara_forward
     const ProbeMod& p = v[i];
     Run r{B, B * m->T, training, seed};
+    r.key_len = frame_len;
     const void* in = nullptr;
     if (p.kind != ProbeMod::STEM) { CK(r5_from_f32(m->dt, x, m->W(p.in), (size_t)r.M * p.in_cols, m->s)); in = m->W(p.in); }
     switch (p.kind) {
@@ -785,8 +837,14 @@ extern "C" int ishara_debug_module_forward(ishara_model* m, int32_t i, const flo
     case ProbeMod::HEAD: CK(head_fwd(m, r, in, y)); break;
     }
     if (p.kind != ProbeMod::HEAD) CK(r5_to_f32(m->dt, m->W(p.out), y, (size_t)r.M * p.out_cols, m->s));
-    if (training) { m->probe_mod = i; m->probe_B = B; m->probe_seed = seed; }
+    if (training) { m->probe_mod = i; m->probe_B = B; m->probe_seed = seed; m->probe_masked = frame_len ? 1 : 0; }
     return 0;
+}
+extern "C" int ishara_debug_module_forward(ishara_model* m, int32_t i, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, ishara_stream st) {
+    return probe_module_forward("ishara_debug_module_forward", m, i, x, B, y, training, seed, nullptr, st);
+}
+extern "C" int ishara_debug_module_forward_ex(ishara_model* m, int32_t i, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, const int32_t* frame_len, ishara_stream st) {
+    return probe_module_forward("ishara_debug_module_forward_ex", m, i, x, B, y, training, seed, frame_len, st);
 }
 // zero gradients and empty deferred sums, as at the top of ishara_loss_backward
 static int probe_backward_begin(ishara_model* m) {
@@ -794,8 +852,7 @@ static int probe_backward_begin(ishara_model* m) {
     m->tn_defer.pending = false;
     return launch_fill_u32(m->grads, (size_t)m->n_train, 0u, m->s);
 }
-extern "C" int ishara_debug_module_backward(ishara_model* m, int32_t i, const float* dy, int32_t B, float* dx, ishara_stream st) {
-    const char* fn = "ishara_debug_module_backward";
+static int probe_module_backward(const char* fn, ishara_model* m, int32_t i, const float* dy, int32_t B, float* dx, const int32_t* frame_len, ishara_stream st) {
     if (!probe_family_ok(m, fn)) return -1;
     const std::vector<ProbeMod> v = probe_modules(m);
     if (!probe_ok(m, fn, i, B, v, 1, true)) return -1;
@@ -804,8 +861,10 @@ extern "C" int ishara_debug_module_backward(ishara_model* m, int32_t i, const fl
     if (p.kind == ProbeMod::HEAD) { ishara_set_error("%s: the head's backward starts at the CTC kernel: use ishara_debug_head_loss_backward", fn); return -1; }
     if (!dy) { ishara_set_error("%s: null dy", fn); return -1; }
     if (p.kind == ProbeMod::STEM && dx) { ishara_set_error("%s: the stem has no input gradient: dx must be NULL", fn); return -1; }
+    if (!frame_len_ok(m, fn, frame_len) || !frame_len_agrees(fn, m->probe_masked != 0, frame_len)) return -1;
     m->s = (hipStream_t)st;
     Run r{B, B * m->T, 1, m->probe_seed};
+    r.key_len = frame_len;
     CK(probe_backward_begin(m));
     void* g = m->W(m->gA); void* gn = m->W(m->gB);
     CK(r5_from_f32(m->dt, dy, g, (size_t)r.M * p.out_cols, m->s));
@@ -823,6 +882,12 @@ extern "C" int ishara_debug_module_backward(ishara_model* m, int32_t i, const fl
     CK(red_flush(m));
     if (dx) CK(r5_to_f32(m->dt, gn, dx, (size_t)r.M * p.in_cols, m->s));
     return 0;
+}
+extern "C" int ishara_debug_module_backward(ishara_model* m, int32_t i, const float* dy, int32_t B, float* dx, ishara_stream st) {
+    return probe_module_backward("ishara_debug_module_backward", m, i, dy, B, dx, nullptr, st);
+}
+extern "C" int ishara_debug_module_backward_ex(ishara_model* m, int32_t i, const float* dy, int32_t B, float* dx, const int32_t* frame_len, ishara_stream st) {
+    return probe_module_backward("ishara_debug_module_backward_ex", m, i, dy, B, dx, frame_len, st);
 }
 extern "C" int ishara_debug_head_loss_backward(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, float* dx, ishara_stream st) {
     const char* fn = "ishara_debug_head_loss_backward";

@@ -242,7 +242,9 @@ struct PsaStats { const float* G = nullptr; const float* Rpart = nullptr; int np
 int launch_eca_bn_bwd_finalize(float* S1, float* S2, const float* gap, const float* gn, const float* sgate,
                                const float* w5, const float* gamma, const float* beta, const float* mean, const float* rstd,
                                float* dgamma, float* dbeta, float* dw5, float* E, float* Fc, float* dw5part /* B * ECA_MAX_CHUNKS * 8 floats */, int B, int T, int C, hipStream_t s,
-                               const PsaStats* ps = nullptr);
+                               const PsaStats* ps = nullptr, const int* frame_len = nullptr, float* Ecol = nullptr);
+// frame_len != nullptr (no PsaStats): `gap` is the masked mean of launch_masked_time_mean; E[b,c] = dgn / n_b is for the frames t < n_b only and
+// Ecol[c] = -dbeta / Mtot for every frame: launch_bn_bwd_apply_len applies them
 // plain BN backward finalize from per-sample S1,S2: dgamma, dbeta, E[c] = -dbeta/Mtot, Fc = dgamma/Mtot
 int launch_bn_bwd_finalize(const float* S1, const float* S2, float* dgamma, float* dbeta, float* Ecol, float* Fc,
                            int B, int T, int C, hipStream_t s);
@@ -257,6 +259,21 @@ int launch_se_fwd(const float* gap, float invT, const float* W1, const float* b1
 int launch_se_bwd(const float* dse, const float* gap, float invT, const float* W1, const float* W2,
                   const float* hid_pre, const float* se, float* dW1, float* db1, float* dW2, float* db2,
                   float* dgapT, float* scr /* B*(C+2R) floats */, int B, int C, int R, hipStream_t s);
+
+// ---- per-clip frame lengths of the Keras hybrid family (frame_mask.hip): frame_len [B] int32 on the device, clamped to [0, T] in the kernels;
+// clip b has n_b = frame_len[b] real frames, the rest is padding.  Kernels of their own: the unmasked ones above are not touched
+// out[b,c] = (sum_{t < n_b} x[b,t,c]) / n_b, 0 at n_b = 0; rows t >= n_b are not read.  The Squeeze-Excite kernels above then run with invT = 1
+int launch_masked_time_mean(int dt, const void* x, const int* frame_len, float* out, int B, int T, int C, hipStream_t s);
+// ECA fwd on [B,C] from the masked mean: g = a*mean + b (0 at n_b = 0: nothing to pool); s, P, Q and the drop-path draw as launch_eca_fwd
+int launch_eca_fwd_len(const float* mean, const float* a, const float* b, const float* w5, const int* frame_len, int T,
+                       float* gn, float* sgate, float* P, float* Q, int B, int C, hipStream_t s, float* rs = nullptr, DropSpec dp = {0, 0, 1.f}, int dp_fold = 0);
+// dx = a[c] * (dy*sg[b,c] + [t < n_b] Ev[b,c] + Ecol[c] - xhat*Fc[c])
+int launch_bn_bwd_apply_len(int dt, const void* dy, const void* x, const float* mean, const float* rstd, const float* a, const float* sg,
+                            const float* Ev, const float* Ecol, const float* Fc, const int* frame_len, void* dx, int B, int T, int C, hipStream_t s);
+// y = x*P[b,c] + [t < n_b] Q[b,c] / n_b
+int launch_sample_affine_len(int dt, const void* x, const float* P, const float* Q, const int* frame_len, void* y, int B, int T, int C, hipStream_t s);
+// out_len[b] = 1 + index of the last frame of x [B,T,F] with a non-zero feature (0: none)
+int launch_frame_lengths(const float* x, int B, int T, int F, int* out_len, hipStream_t s);
 
 // ---- attention (attention.hip: lane-split kernels, routes, launchers; attention_mfma.hip / attention_bwd_mfma.hip: the MFMA kernels) ----
 // q,k [B,H,T,dh], vt [B,H,dh,T]; o [B*T, H*dh]; lse [B,H,T]

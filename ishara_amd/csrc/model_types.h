@@ -140,7 +140,8 @@ struct ishara_model {
     std::vector<float> pe_host;
     // run state
     int lastB = 0; int last_training = 0; uint32_t last_seed = 0; const float* last_x = nullptr;
-    int last_masked = 0;            // the last ishara_encoder_forward(_ex) was given an attention mask (the arrays themselves are the caller's: no pointer is kept)
+    int last_masked = 0;            // the last ishara_encoder_forward(_ex) was given an attention mask, the last ishara_forward(_ex) frame lengths (the arrays themselves are the caller's: no pointer is kept)
+    int probe_masked = 0;           // the same bit for the module probe's last training forward
     int opt_iter = 0;
     int probe_mod = -1, probe_B = 0; uint32_t probe_seed = 0;      // module probe (ishara_debug_module_*): the last training forward of a single module
     hipStream_t s = nullptr;
@@ -186,7 +187,8 @@ struct ishara_model {
 
 
 // ------------------------------------------------------------------ shared helpers (model.hip unless noted)
-// attn_bias / key_len: the caller's attention mask arrays of this one call (ishara_encoder_forward_ex / _backward_ex), nullptr otherwise
+// attn_bias / key_len: the caller's attention mask arrays of this one call (ishara_encoder_forward_ex / _backward_ex), nullptr otherwise;
+// in the Keras hybrid family key_len is the per-clip frame count of ishara_forward_ex / ishara_loss_backward_ex (keras_hybrid.hip)
 struct Run { int B, M, training; uint32_t seed; const float* attn_bias = nullptr; const int* key_len = nullptr; };
 static inline DropSpec dspec(const Run& r, uint32_t site, float rate) { return make_drop(r.seed, site, rate, r.training != 0); }
 static inline DropSpec dspec_attn(const Run& r, uint32_t site, float rate) { return make_drop_attn(r.seed, site, rate, r.training != 0); }   // attention probabilities: common.h rng_quad

@@ -93,8 +93,9 @@ class CallbackEval:
         if self.weights_path:
             model.save_weights(self.weights_path)                                   # c9:10
         predictions, targets = [], []
-        for X, y in self.dataset:                                                   # c9:13-21
-            logits = model(X, training=False)
+        for batch in self.dataset:                                                  # c9:13-21; (X, y) or (X, y, frame_lengths)
+            X, y = batch[0], batch[1]
+            logits = model(X, training=False, **({"frame_lengths": batch[2]} if len(batch) == 3 else {}))
             for idx in model.decode_batch(logits):
                 predictions.append("".join(num_to_char_fn(idx, self.num_to_char)))
             for label in np.asarray(y.cpu() if hasattr(y, "cpu") else y):

@@ -241,17 +241,38 @@ class Model(Handle):
             raise ValueError(f"expected input [B,{self.T},{self.F}], got {tuple(x.shape)}")
         return x.to(self.device, torch.float32).contiguous()
 
-    def __call__(self, x, training: bool = False, seed: Optional[int] = None) -> torch.Tensor:
+    def _as_frame_lengths(self, frame_lengths, B: int) -> Optional[torch.Tensor]:
+        """`frame_lengths` (tensor, array or list; None passes through) as a contiguous int32 [B] tensor on the model's device.  Shape and
+        dtype are checked; the values never are (reading a device tensor would synchronise): the kernels clamp them to [0, T]."""
+        if frame_lengths is None:
+            return None
+        if self._cfg.dtype == _lib.F16:
+            raise _lib.IsharaError("frame_lengths: the f16 model takes none (it is the TFLite export's graph, which has no mask)")
+        t = frame_lengths if isinstance(frame_lengths, torch.Tensor) else torch.as_tensor(np.asarray(frame_lengths))
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool or t.ndim != 1 or t.shape[0] != B:
+            raise ValueError(f"frame_lengths must be {B} integers (one per clip of the batch), got {tuple(t.shape)} {t.dtype}")
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def __call__(self, x, training: bool = False, seed: Optional[int] = None, frame_lengths=None) -> torch.Tensor:
+        """model(x, training=...).  frame_lengths [B]: clip b has that many real frames and the rest of its T rows is padding — the
+        attention keys, the ECA mean and the Squeeze-Excite mean leave the padding out (the mask the reference's layers take, DESIGN §2
+        "Frame lengths"); everything else, BatchNorm statistics included, sees the padded frames as without lengths."""
         x = self._as_input(x)
         B = x.shape[0]
         if B > self.max_batch:
             raise ValueError(f"batch {B} > max_batch {self.max_batch}")
+        fl = self._as_frame_lengths(frame_lengths, B)
         logits = torch.empty((B, self.T, self.C), dtype=torch.float32, device=self.device)
         if seed is None:
             seed = (self._step_seed + 0x9E3779B1 * self._steps) & 0xFFFFFFFF
-        _lib.check(self._lib.ishara_forward(self._h, _lib.ptr(x), B, _lib.ptr(logits), 1 if training else 0,
-                                            C.c_uint32(seed), _stream()), "ishara_forward")
+        if fl is None:
+            _lib.check(self._lib.ishara_forward(self._h, _lib.ptr(x), B, _lib.ptr(logits), 1 if training else 0,
+                                                C.c_uint32(seed), _stream()), "ishara_forward")
+        else:
+            _lib.check(self._lib.ishara_forward_ex(self._h, _lib.ptr(x), B, _lib.ptr(logits), 1 if training else 0,
+                                                   C.c_uint32(seed), _lib.ptr(fl), _stream()), "ishara_forward_ex")
         self._last_x = x          # keep the input alive: the stem weight gradient re-reads it
+        self._last_fl = fl        # and the lengths: the backward pass is handed the same array
         return logits
 
     predict = __call__
@@ -264,15 +285,21 @@ class Model(Handle):
         return self
 
     # ------------------------------------------------------------------ training
-    def loss_and_gradients(self, x, y, seed: Optional[int] = None, loss_scale: float = 1.0):
-        """forward(training=True) + CTCLoss + backward.  Returns (loss tensor[1], logits)."""
-        logits = self(x, training=True, seed=seed)
+    def loss_and_gradients(self, x, y, seed: Optional[int] = None, loss_scale: float = 1.0, frame_lengths=None):
+        """forward(training=True) + CTCLoss + backward.  Returns (loss tensor[1], logits).  frame_lengths: as in __call__, for both passes;
+        the CTC loss keeps logit_length = T (c6:3) — a per-clip loss is ctc_loss(..., frame_lengths=)."""
+        logits = self(x, training=True, seed=seed, **_fl_kw(frame_lengths))
+        fl = self._last_fl
         y = torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(self.device, torch.int64).contiguous()
         B = logits.shape[0]
         if y.shape != (B, self._cfg.max_label_len):
             raise ValueError(f"labels must be [B,{self._cfg.max_label_len}] padded with {self.C - 1}")
-        _lib.check(self._lib.ishara_loss_backward(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf),
-                                                  _lib.ptr(self._nll_buf), C.c_float(loss_scale), _stream()), "ishara_loss_backward")
+        if fl is None:
+            _lib.check(self._lib.ishara_loss_backward(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf),
+                                                      _lib.ptr(self._nll_buf), C.c_float(loss_scale), _stream()), "ishara_loss_backward")
+        else:
+            _lib.check(self._lib.ishara_loss_backward_ex(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf), _lib.ptr(self._nll_buf),
+                                                         C.c_float(loss_scale), _lib.ptr(fl), _stream()), "ishara_loss_backward_ex")
         return self._loss_buf, logits
 
     def apply_gradients(self):
@@ -292,7 +319,7 @@ class Model(Handle):
         self.optimizer.iterations += 1
         self._steps += 1
 
-    def train_on_batch(self, x, y, seed: Optional[int] = None, allreduce: bool = True) -> torch.Tensor:
+    def train_on_batch(self, x, y, seed: Optional[int] = None, allreduce: bool = True, frame_lengths=None) -> torch.Tensor:
         """One Keras train_step (c12): forward, CTC, backward, [RCCL grad all-reduce], update.
         Returns the device loss tensor (no host sync).  `allreduce=False` skips the gradient exchange (bench.py's diagnostic
         of the exposed all-reduce time; replicas diverge — never for training).
@@ -303,14 +330,16 @@ class Model(Handle):
         every rank sees the same norm) and steps the optimizer on gradient * coef.  `_steps` and `optimizer.iterations` advance once per
         cycle; microbatch j draws its dropout masks from seed index `_steps * k + j`.  The bucketed all-reduce overlap
         (parallel.overlap_enabled) applies only when accumulate_steps == 1; otherwise the accumulator is reduced in one piece.  Still no
-        host sync: `grad_stats()` reads the record when asked."""
+        host sync: `grad_stats()` reads the record when asked.
+
+        `frame_lengths` [B]: per-clip frame counts of this (micro)batch, as in __call__; every path above takes them."""
         from . import parallel
         k, clip, skip = self.optimizer.train_options()
         if k > 1 or clip > 0.0 or skip or self._micro:
-            return self._train_microbatch(x, y, seed, allreduce, k, clip, skip)
+            return self._train_microbatch(x, y, seed, allreduce, k, clip, skip, frame_lengths)
         world = parallel.world_size()
         if not allreduce:
-            loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world)
+            loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world, **_fl_kw(frame_lengths))
             self.apply_gradients()
             return loss
         overlap = world > 1 and parallel.overlap_enabled()
@@ -320,7 +349,7 @@ class Model(Handle):
             # replicas share the weight-initialisation seed but draw independent dropout / drop-path masks for their shards,
             # like the reference's replicas (tf.distribute / nn.DataParallel keep per-replica RNG streams)
             seed = ((self._step_seed + 0x9E3779B1 * self._steps) ^ (parallel.rank() * 0x85EBCA6B)) & 0xFFFFFFFF
-        loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world)
+        loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world, **_fl_kw(frame_lengths))
         if overlap:
             parallel.allreduce_buckets_(self)          # ranges of the gradient reduced on a side stream as the backward pass finishes them
         elif world > 1:
@@ -328,7 +357,7 @@ class Model(Handle):
         self.apply_gradients()
         return loss
 
-    def _train_microbatch(self, x, y, seed, allreduce, k, clip, skip) -> torch.Tensor:
+    def _train_microbatch(self, x, y, seed, allreduce, k, clip, skip, frame_lengths=None) -> torch.Tensor:
         """microbatch `_micro` of a cycle of k; the k-th one ends the cycle with all-reduce, statistics and the step"""
         from . import parallel
         world = parallel.world_size()
@@ -341,7 +370,7 @@ class Model(Handle):
             seed = (self._step_seed + 0x9E3779B1 * (self._steps * k + self._micro)) & 0xFFFFFFFF
             if world > 1:
                 seed = (seed ^ (parallel.rank() * 0x85EBCA6B)) & 0xFFFFFFFF
-        loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world)
+        loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world, **_fl_kw(frame_lengths))
         src = self.grads[:self.n_train]
         if k > 1:
             if self._grad_acc is None:
@@ -442,7 +471,7 @@ class Model(Handle):
     def fit(self, train_dataset: Iterable, validation_data: Optional[Iterable] = None, epochs: int = 1,
             callbacks: Sequence[Callback] = (), steps_per_epoch: Optional[int] = None, verbose: int = 1, initial_epoch: int = 0) -> History:
         """model.fit(train_dataset, validation_data=, epochs=, callbacks=[...]) — c12:1-10.
-        Datasets are re-iterable objects yielding (x [B,T,F] float32, y [B,64] int64).  `initial_epoch` (Keras): the epoch to start
+        Datasets are re-iterable objects yielding (x [B,T,F] float32, y [B,64] int64) or (x, y, frame_lengths [B]).  `initial_epoch` (Keras): the epoch to start
         from when a run is resumed (after load_state); epochs initial_epoch .. epochs - 1 run.  With optimizer.global_clipnorm or
         .skip_nonfinite the epoch logs gain `grad_norm` (the last cycle's) and `skipped_steps` (in this epoch): one device read per epoch.
         With accumulate_steps = k every batch is a microbatch; an epoch whose batch count is no multiple of k leaves its last cycle open."""
@@ -457,10 +486,11 @@ class Model(Handle):
             for cb in callbacks: cb.on_epoch_begin(epoch, logs)
             tot = torch.zeros(1, dtype=torch.float32, device=self.device)
             n = 0
-            for bi, (x, y) in enumerate(train_dataset):
+            for bi, batch in enumerate(train_dataset):
                 if steps_per_epoch is not None and bi >= steps_per_epoch:
                     break
-                tot += self.train_on_batch(x, y)
+                x, y, fl = split_batch(batch)
+                tot += self.train_on_batch(x, y, **_fl_kw(fl))
                 n += 1
                 for cb in callbacks: getattr(cb, "on_train_batch_end", lambda b, logs=None: None)(bi, logs)
             logs["loss"] = float(tot.item()) / max(n, 1)
@@ -515,22 +545,28 @@ class Model(Handle):
             _lib.check(n, "ishara_debug_module_count")
         return [self._module_info(i)[0] for i in range(n)]
 
-    def module_forward(self, i: int, x, training: bool = False, seed: int = 0) -> torch.Tensor:
-        """Module i alone on x [B,T,in_cols] through the model's own orchestration -> f32 [B,T,out_cols] (the head: logits)."""
+    def module_forward(self, i: int, x, training: bool = False, seed: int = 0, frame_lengths=None) -> torch.Tensor:
+        """Module i alone on x [B,T,in_cols] through the model's own orchestration -> f32 [B,T,out_cols] (the head: logits).
+        frame_lengths [B]: as in __call__ (modules without a masked operation ignore them)."""
         _, cin, cout, _, _ = self._module_info(i)
         x = torch.as_tensor(x).to(self.device, torch.float32).contiguous()
         if x.dim() != 3 or x.shape[1:] != (self.T, cin):
             raise ValueError(f"module {i}: expected input [B,{self.T},{cin}], got {tuple(x.shape)}")
+        fl = self._as_frame_lengths(frame_lengths, x.shape[0])
         y = torch.empty((x.shape[0], self.T, cout), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.ishara_debug_module_forward(self._h, i, _lib.ptr(x), x.shape[0], _lib.ptr(y), 1 if training else 0,
-                                                         C.c_uint32(seed), _stream()), "ishara_debug_module_forward")
+        if fl is None:
+            _lib.check(self._lib.ishara_debug_module_forward(self._h, i, _lib.ptr(x), x.shape[0], _lib.ptr(y), 1 if training else 0,
+                                                             C.c_uint32(seed), _stream()), "ishara_debug_module_forward")
+        else:
+            _lib.check(self._lib.ishara_debug_module_forward_ex(self._h, i, _lib.ptr(x), x.shape[0], _lib.ptr(y), 1 if training else 0,
+                                                                C.c_uint32(seed), _lib.ptr(fl), _stream()), "ishara_debug_module_forward_ex")
         self._last_x = x          # the stem's weight gradient re-reads it
         return y
 
-    def module_backward(self, i: int, dy, labels=None, loss_scale: float = 1.0) -> Optional[torch.Tensor]:
+    def module_backward(self, i: int, dy, labels=None, loss_scale: float = 1.0, frame_lengths=None) -> Optional[torch.Tensor]:
         """Backward of module i after module_forward(i, ..., training=True): dy [B,T,out_cols] -> the gradient with respect to the module's
         input (None for the stem); the parameter gradients are in `grads`.  The head takes its logits as dy and `labels` [B,L]: CTC + head
-        backward, the loss in `_loss_buf`."""
+        backward, the loss in `_loss_buf`.  frame_lengths: the ones module_forward was given (the head takes none)."""
         _, cin, cout, _, _ = self._module_info(i)
         dy = torch.as_tensor(dy).to(self.device, torch.float32).contiguous()
         if dy.dim() != 3 or dy.shape[1:] != (self.T, cout):
@@ -545,7 +581,12 @@ class Model(Handle):
                                                                  C.c_float(loss_scale), _lib.ptr(dx), _stream()), "ishara_debug_head_loss_backward")
             return dx
         dx = None if i == 0 else torch.empty((B, self.T, cin), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.ishara_debug_module_backward(self._h, i, _lib.ptr(dy), B, _lib.ptr(dx), _stream()), "ishara_debug_module_backward")
+        fl = self._as_frame_lengths(frame_lengths, B)
+        if fl is None:
+            _lib.check(self._lib.ishara_debug_module_backward(self._h, i, _lib.ptr(dy), B, _lib.ptr(dx), _stream()), "ishara_debug_module_backward")
+        else:
+            _lib.check(self._lib.ishara_debug_module_backward_ex(self._h, i, _lib.ptr(dy), B, _lib.ptr(dx), _lib.ptr(fl), _stream()),
+                       "ishara_debug_module_backward_ex")
         return dx
 
     def ctc_loss(self, y, logits, frame_lengths=None) -> torch.Tensor:
@@ -568,9 +609,12 @@ class Model(Handle):
         return nll
 
     def evaluate(self, dataset: Iterable) -> float:
+        """Mean CTC loss over a dataset of (x, y) or (x, y, frame_lengths) batches; the lengths mask the model as in __call__, the loss
+        keeps logit_length = T like the training loss."""
         tot, n = 0.0, 0
-        for x, y in dataset:
-            logits = self(x, training=False)
+        for batch in dataset:
+            x, y, fl = split_batch(batch)
+            logits = self(x, training=False, **_fl_kw(fl))
             tot += float(self.ctc_loss(y, logits).mean().item())
             n += 1
         return tot / max(n, 1)
@@ -645,6 +689,36 @@ class Model(Handle):
         sc = torch.empty(B, dtype=torch.float32, device=self.device)
         ctc_align.launch(self._lib, logits, y, B, T, Cc, L, Cc - 1, ws, fp, st, en, cf, sc, _stream())
         return ctc_align.to_alignments(y.cpu().numpy(), *(t.cpu().numpy() for t in (fp, st, en, cf, sc)))
+
+
+def _fl_kw(frame_lengths):
+    """the frame_lengths keyword of a call, only when there are lengths: without them train_on_batch calls loss_and_gradients exactly as it
+    did before lengths existed (a wrapper or subclass with the older signature keeps working)"""
+    return {} if frame_lengths is None else {"frame_lengths": frame_lengths}
+
+
+def split_batch(batch):
+    """(x, y) or (x, y, frame_lengths) of a dataset -> (x, y, frame_lengths or None)"""
+    if len(batch) == 3:
+        return batch[0], batch[1], batch[2]
+    x, y = batch
+    return x, y, None
+
+
+def frame_lengths(x) -> torch.Tensor:
+    """Per-clip frame counts of a zero-padded batch x [B,T,F] (float32, on the GPU) -> int32 [B] on the same device: 1 + the index of the
+    last frame with any non-zero feature, 0 for an all-zero clip.  The prefix reading of Keras's Masking(0.0): an all-zero frame inside a
+    clip stays valid.  No host synchronise."""
+    x = torch.as_tensor(x)
+    if x.ndim != 3 or x.dtype != torch.float32:
+        raise ValueError(f"frame_lengths: x must be float32 [B,T,F], got {tuple(x.shape)} {x.dtype}")
+    if not x.is_cuda:
+        raise _lib.IsharaError("frame_lengths: x must be on the GPU: the kernel has no CPU path")
+    x = x.contiguous()
+    out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().ishara_frame_lengths(_lib.ptr(x), x.shape[0], x.shape[1], x.shape[2], _lib.ptr(out), _stream()), "ishara_frame_lengths")
+    return out
 
 
 def make_config(dim=256, num_conv_squeeze_blocks=2, num_conv_conform_blocks=2, kernel_sizes=(11, 5, 3),

@@ -41,10 +41,15 @@ def init_from_env(backend: str | None = None) -> tuple[int, int, int]:
     return rk, world, local
 
 
-def shard_batch(x, y, rk: int | None = None, world: int | None = None):
-    """Per-rank shard of a global batch: samples rk, rk+world, ...."""
+def shard_batch(x, y, rk: int | None = None, world: int | None = None, frame_lengths=None):
+    """Per-rank shard of a global batch: samples rk, rk+world, ....  With frame_lengths [B] (Model.train_on_batch's
+    per-clip frame counts) the shard is (x, y, frame_lengths), each cut the same way."""
     rk = rank() if rk is None else rk
     world = world_size() if world is None else world
+    if frame_lengths is not None:
+        if len(frame_lengths) != len(x):
+            raise ValueError(f"frame_lengths must be one per clip of the batch ({len(x)}), got {len(frame_lengths)}")
+        return x[rk::world], y[rk::world], frame_lengths[rk::world]
     return x[rk::world], y[rk::world]
 
 

@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from ._lib import stream as _stream
 from .model import Model
-from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS, _beam_launch, _beam_setup
+from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS, _beam_launch, _beam_setup, refuse_frame_lengths
 
 PAD_TOKEN_IDX = 59           # c1:5: the targets' padding; never a decoded index (the blank is C - 1 = 59)
 MAX_SCORE_LABEL_LEN = 64     # one wavefront lane per target symbol (ishara_edit_distance)
@@ -295,16 +295,17 @@ class BatchedTFLiteModel:
         return idx, ln, dist, tlen
 
     # ---- public surface
-    def predict_indices(self, clips) -> List[np.ndarray]:
+    def predict_indices(self, clips, frame_lengths=None) -> List[np.ndarray]:
         """The decode per clip (greedy, or the beam's top-1; before the len < 3 fallback): equal to `TFLiteModel.predict_indices` clip by clip."""
+        refuse_frame_lengths(frame_lengths, "BatchedTFLiteModel")
         res = []
         for idx, ln, _, _ in self._process(clips):
             res.extend(idx[b, :ln[b]].astype(np.int64) for b in range(idx.shape[0]))
         return res
 
-    def __call__(self, clips) -> List[Dict[str, np.ndarray]]:
+    def __call__(self, clips, frame_lengths=None) -> List[Dict[str, np.ndarray]]:
         """`TFLiteModel.__call__` per clip: {'outputs': one-hot [n_chars, 59]} after the fallback (c13:22-24), on the host as there."""
-        return [{"outputs": one_hot(apply_fallback(idx))} for idx in self.predict_indices(clips)]
+        return [{"outputs": one_hot(apply_fallback(idx))} for idx in self.predict_indices(clips, frame_lengths)]
 
     def score(self, clips, targets, char_to_num: Optional[Dict[str, int]] = None) -> Dict[str, object]:
         """The test-set loop of c18:1-15 as one call: mean of (len(target) - Levenshtein(pred, target)) / len(target) over the clips, pred

@@ -48,6 +48,14 @@ def write_inference_args(path: str = "inference_args.json") -> str:
     return path
 
 
+def refuse_frame_lengths(frame_lengths, who: str) -> None:
+    """The TFLite-shaped wrappers take a raw clip and resize it to the model's frame count (c3:61-115): their reference graph has no
+    padding and no mask, so Model's frame_lengths have no meaning here."""
+    if frame_lengths is not None:
+        raise ValueError(f"{who}: frame_lengths are refused: the wrapper resizes every clip to the model's frame count, its graph (c13:9-24) has no mask; "
+                         "use Model(x, frame_lengths=) on padded batches")
+
+
 class _BeamConfig:
     """Device state of a wrapper's beam decoder, allocated once at construction (graph replays reuse it)."""
     def __init__(self, width, lm_dev, alpha, beta, ws, score):
@@ -122,7 +130,8 @@ class TFLiteModel:
             self._launch()
         self._graph = g
 
-    def predict_indices(self, inputs) -> np.ndarray:
+    def predict_indices(self, inputs, frame_lengths=None) -> np.ndarray:
+        refuse_frame_lengths(frame_lengths, "TFLiteModel")
         x = np.asarray(inputs, dtype=np.float32)
         if x.ndim != 2 or x.shape[1] != N_COLS:
             raise ValueError(f"inputs must be [n_frames, {N_COLS}]")
@@ -139,8 +148,8 @@ class TFLiteModel:
         ln = int(self._len.item())
         return self._idx[0, :ln].cpu().numpy().astype(np.int64)
 
-    def __call__(self, inputs) -> Dict[str, np.ndarray]:
-        idx = self.predict_indices(inputs)
+    def __call__(self, inputs, frame_lengths=None) -> Dict[str, np.ndarray]:
+        idx = self.predict_indices(inputs, frame_lengths)
         if idx.shape[0] < 3:                                  # c13:22-23
             idx = FALLBACK_PHRASE
         out = np.zeros((idx.shape[0], 59), dtype=np.float32)  # tf.one_hot(x, 59): index 59 -> zero row

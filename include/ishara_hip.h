@@ -323,6 +323,11 @@ const char* ishara_debug_dwconv_kernel_name(int32_t dt, int32_t backward, int32_
  * 2 keep-bit buffer given, 4 head-major dqkv, 8 masked (an attn_bias table or key lengths given).  Host only, launches nothing; valid until the
  * next call */
 const char* ishara_debug_attn_kernel_name(int32_t dt, int32_t backward, int32_t T, int32_t dh, int32_t impl, int32_t flags);
+/* the same for a Conv1DBlock of the Keras hybrid (width d, kernel size k) at (B, T): the launch plan of its forward and backward under the current
+ * switches as "forward|backward", e.g. "part+fold+prologue+psa|psa+fused_bn" ("-" for the backward half at inference), "" for a refused dtype or
+ * shape.  flags: 1 drop-path active, 2 frame lengths given, 4 the per-sample-affine weight gradient switched on (the model: bf16 without
+ * ISHARA_NO_PSA).  Host only, launches nothing; valid until the calling thread's next call */
+const char* ishara_debug_conv_block_route_name(int32_t dt, int32_t training, int32_t B, int32_t T, int32_t d, int32_t k, int32_t flags);
 /* 0: never use the 256 x 256 two-operand tile GEMM (gemm_big.hip) — A/B runs against the A-stationary kernel inside one process; 1: library default */
 int ishara_debug_set_nt_big(int32_t on);
 int ishara_debug_force_regstage(int32_t on);

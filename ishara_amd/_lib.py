@@ -107,6 +107,7 @@ SIGNATURES = {
     "ishara_debug_dense_kernel_name": (C.c_char_p, [_I32, _I32, _I32, _I32, _I32, _I32]),
     "ishara_debug_dwconv_kernel_name": (C.c_char_p, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "ishara_debug_attn_kernel_name": (C.c_char_p, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "ishara_debug_conv_block_route_name": (C.c_char_p, [_I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "ishara_debug_set_nt_big": (C.c_int, [_I32]),
     "ishara_debug_force_regstage": (C.c_int, [_I32]),
     "ishara_debug_module_count": (_I32, [_P]),

@@ -273,6 +273,15 @@ extern "C" const char* ishara_debug_attn_kernel_name(int32_t dt, int32_t backwar
     if (backward) return attn_bwd_kernel_name(dt, T, dh, impl, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (flags & 8) != 0);
     return attn_fwd_kernel_name(dt, T, dh, impl, (flags & 1) != 0, (flags & 2) != 0, (flags & 8) != 0);
 }
+// the same for a Conv1DBlock of the Keras hybrid: the launch plan conv_fwd / conv_bwd (conv_block.hip) run for a block of width d and kernel size k
+// at (B, T) under the current switches, as "forward|backward" text (conv_block_route_name), "" for a refused dtype or shape.  flags: 1 drop-path
+// active, 2 frame lengths given, 4 the per-sample-affine weight gradient switched on (the model: bf16 and no ISHARA_NO_PSA).  The project conv's
+// shadow strides follow the model's rule (shadow_ld).  Host only: nothing is launched.  The answer is valid until this thread's next call
+extern "C" const char* ishara_debug_conv_block_route_name(int32_t dt, int32_t training, int32_t B, int32_t T, int32_t d, int32_t k, int32_t flags) {
+    if (!op_dt_ok("ishara_debug_conv_block_route_name", dt, !training) || B < 1 || T < 1 || d < 1) return "";
+    if ((dt == DT_F16 && (flags & 2)) || (!training && (flags & 1))) return "";      // no frame lengths in fp16, no drop-path at inference
+    return conv_block_route_name(conv_block_plan(dt, training != 0, B, T, d, k, shadow_ld(dt, 2 * d), shadow_ld(dt, d), (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0), training != 0);
+}
 extern "C" int ishara_op_dense_bwd(int32_t dt, const void* x, const float* Wm, const void* dy, void* dx, float* dW, float* db,
                                    int32_t M, int32_t K, int32_t N, void* scratch, ishara_stream st) {
     OP_DT("ishara_op_dense_bwd", dt, false);

@@ -579,6 +579,9 @@ static bool dw_k_unrolled(int k) { return dw_k_small(k) || dw_k_wide(k); }
 // dwconv_reg_kernel (forward and data gradient): C/4 lanes a divisor of 256.  K = 11, 15: the register window (201 / 233 VGPRs) measured
 // 94 / 103 us vs 82 / 86 us for the LDS-tiled kernel
 static bool dw_reg_ok(int C, int k) { return dw_k_small(k) && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0; }
+// dwconv_reg8_kernel's segment: a handful of samples (B = 1 inference) takes 8-step segments — four times the workgroups, a quarter of the
+// dependent steps per thread (3 workgroups of 32-step chains took 17 us at T = 384)
+static int dw_reg8_seglen(int B) { return B <= DW_SMALL_B ? DWR_SEG_SMALL : DWR_SEG; }
 
 DwFwdRoute dwconv_fwd_route(int dt, int B, int T, int C, int k, bool stats, bool part) {
     if (!dw_shape_ok(C, k)) return DWF_REFUSED;
@@ -606,6 +609,33 @@ DwBwdRoute dwconv_bwd_route(int dt, int C, int k, int padl, bool scratch, bool b
     if (dw_reg_ok(C, k)) r.dgrad = DWD_REG;
     if (scratch) r.wgrad = dw_k_unrolled(k) ? DWW_WIN : DWW_TILE_PART;      // partial rows when the caller gave room for them (DWG_BLOCKS rows), else atomics
     return r;
+}
+
+// The partial statistic rows per sample the forward kernel of `route` writes for (B, T, C), which is also the time extent of its grid: every
+// forward launcher builds its grid on this, and a caller that sums the rows itself (part_rows of launch_dwconv_fwd) knows the count before
+// the launch.  tsplit: the streaming kernel's time ranges per sample.
+int dwconv_fwd_part_rows(DwFwdRoute route, int B, int T, int C, int* tsplit) {
+    switch (route) {
+        case DWF_REFUSED: break;
+        case DWF_STREAM: {
+            // enough workgroups for ~3 rounds of the chip's 768-1024 slots, whole 32-row chunks per range
+            int ts = 1;
+            while ((C / 128) * B * ts < 2048 && T / (ts * 2) >= 128) ts *= 2;      // every extra range re-reads 16 history rows
+            if (tsplit) *tsplit = ts;
+            // The kernel rounds a range up to whole chunks (`per`, computed here as there), so the last of the tsplit ranges can begin past the end
+            // (T = 1025..1120: 8 ranges of 160 rows).  Such a range is not launched and not counted: its workgroup would return without writing its
+            // partial row.  The kernel still gets tsplit, so every launched workgroup has the range it always had.
+            const int per = ((T + ts - 1) / ts + 31) / 32 * 32;
+            return (T + per - 1) / per;
+        }
+        case DWF_REG8: {
+            const int seglen = dw_reg8_seglen(B), spw = 256 / (C / 8), nseg = (T + seglen - 1) / seglen;
+            return (nseg + spw - 1) / spw;
+        }
+        case DWF_REG: return ((T + DWR_SEG - 1) / DWR_SEG + 3) / 4;
+        case DWF_TILE: return (T + DW_TT - 1) / DW_TT;
+    }
+    return 0;
 }
 
 static const char* dw_tile_name(int k) { return k == 11 ? "dwconv_kernel<11,11>" : (k <= 15 ? "dwconv_kernel<0,15>" : "dwconv_kernel<0,31>"); }
@@ -642,14 +672,8 @@ template <typename F> static int dw_typed(int dt, F fn) { return dt == DT_F32 ? 
 template <typename F> static int dw_typed_bwd(int dt, F fn) { return dt == DT_BF16 ? fn(bf16{}) : fn(float{}); }
 template <typename T>
 static int launch_dw_stream(int k, const T* x, const float* w, const float* bias, T* y, int B, int Tn, int C, int padl, int inop, float* part, hipStream_t s) {
-    // enough workgroups for ~3 rounds of the chip's 768-1024 slots, whole 32-row chunks per range
     int tsplit = 1;
-    while ((C / 128) * B * tsplit < 2048 && Tn / (tsplit * 2) >= 128) tsplit *= 2;      // every extra range re-reads 16 history rows
-    // The kernel rounds a range up to whole chunks (`per`, computed here as there), so the last of the tsplit ranges can begin past the end
-    // (T = 1025..1120: 8 ranges of 160 rows).  Such a range is not launched and not counted: its workgroup would return without writing its
-    // partial row.  The kernel still gets tsplit, so every launched workgroup has the range it always had.
-    const int per = ((Tn + tsplit - 1) / tsplit + 31) / 32 * 32;
-    const int ranges = (Tn + per - 1) / per;
+    const int ranges = dwconv_fwd_part_rows(DWF_STREAM, B, Tn, C, &tsplit);
     const dim3 grid(C / 128, B, ranges);
 #define DWS(KK, OP) hipLaunchKernelGGL((dwconv_stream_kernel<T, KK, OP>), grid, dim3(256), 0, s, x, w, bias, y, Tn, C, padl, part, tsplit)
 #define DWSK(OP) do { if (k == 11) DWS(11, OP); else DWS(15, OP); } while (0)
@@ -661,11 +685,8 @@ static int launch_dw_stream(int k, const T* x, const float* w, const float* bias
 
 template <typename T>
 static int launch_dw_reg8(int k, const T* x, const float* w, const float* bias, T* y, int B, int Tn, int C, int padl, int inop, float* part, hipStream_t s) {
-    // a handful of samples (B = 1 inference): 8-step segments — four times the workgroups, a quarter of the dependent steps per thread
-    // (3 workgroups of 32-step chains took 17 us at T = 384)
-    const int seglen = B <= DW_SMALL_B ? DWR_SEG_SMALL : DWR_SEG;
-    const int cg = C / 8, spw = 256 / cg, nseg = (Tn + seglen - 1) / seglen;
-    const dim3 grid((nseg + spw - 1) / spw, B);
+    const int seglen = dw_reg8_seglen(B);
+    const dim3 grid(dwconv_fwd_part_rows(DWF_REG8, B, Tn, C), B);
     const size_t sh = (size_t)256 * 16 * sizeof(float);
 #define DW8(KK, OP) hipLaunchKernelGGL((dwconv_reg8_kernel<T, KK, OP>), grid, dim3(256), sh, s, x, w, bias, y, Tn, C, padl, part, seglen)
 #define DW8K(OP) do { if (k == 3) DW8(3, OP); else DW8(5, OP); } while (0)
@@ -678,18 +699,18 @@ static int launch_dw_reg8(int k, const T* x, const float* w, const float* bias, 
 template <typename T>
 static int launch_dw_reg(int k, const T* x, const float* w, const float* bias, T* y, const T* aux, float* ssum, float* ssq,
                          int B, int Tn, int C, int padl, int inop, int outop, int flip, hipStream_t s, float* part = nullptr) {
-    const int nseg = (Tn + DWR_SEG - 1) / DWR_SEG;
-    dim3 grid(((C / 4 + 63) / 64) * ((nseg + 3) / 4), B);
+    const int rows = dwconv_fwd_part_rows(DWF_REG, B, Tn, C);
+    dim3 grid(((C / 4 + 63) / 64) * rows, B);
 #define DWR(KK) hipLaunchKernelGGL((dwconv_reg_kernel<T, KK>), grid, dim3(256), 0, s, x, w, bias, y, aux, ssum, ssq, Tn, C, padl, inop, outop, flip, part)
     switch (k) { case 3: DWR(3); break; case 5: DWR(5); break; case 11: DWR(11); break; default: DWR(15); break; }
 #undef DWR
-    return (nseg + 3) / 4;
+    return rows;
 }
 
 template <typename T>
 static int launch_dw_tile(const T* x, const float* w, const float* bias, T* y, const T* aux, float* ssum, float* ssq,
                           int B, int Tn, int C, int k, int padl, int inop, int outop, int flip, hipStream_t s, float* part = nullptr) {
-    dim3 grid((Tn + DW_TT - 1) / DW_TT, (C + DW_CT - 1) / DW_CT, B);
+    dim3 grid(dwconv_fwd_part_rows(DWF_TILE, B, Tn, C), (C + DW_CT - 1) / DW_CT, B);
 #define DWK(KC, KM) hipLaunchKernelGGL((dwconv_kernel<T, KC, KM>), grid, dim3(256), 0, s, x, w, bias, y, aux, ssum, ssq, B, Tn, C, k, padl, inop, outop, flip, part)
     if (k == 11) DWK(11, 11);            // 74 -> 65 us
     else if (k <= 15) DWK(0, 15);        // K = 15 unrolled: 86 vs 78 us

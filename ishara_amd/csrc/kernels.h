@@ -190,6 +190,7 @@ int launch_dwconv_bwd(int dt, int inop, const void* dy, const void* x, const flo
 // and the name functions are switches over it.  stats: ssum is wanted; part / scratch: the caller gave the scratch; bn: DwBnArgs.h is set
 enum DwFwdRoute { DWF_REFUSED, DWF_STREAM, DWF_REG8, DWF_REG, DWF_TILE };
 DwFwdRoute dwconv_fwd_route(int dt, int B, int T, int C, int k, bool stats, bool part);
+int dwconv_fwd_part_rows(DwFwdRoute route, int B, int T, int C, int* tsplit = nullptr);      // partial statistic rows per sample that route's kernel writes
 enum DwBwdKind { DWB_REFUSED, DWB_FUSED_BN, DWB_FUSED, DWB_TWO_PASS };      // FUSED_BN only when bn was asked for; otherwise what launch_dwconv_bwd runs
 enum DwDgrad { DWD_REG, DWD_TILE };
 enum DwWgrad { DWW_WIN, DWW_TILE_PART, DWW_TILE_ATOMIC };

@@ -1,6 +1,6 @@
 // Host side of libishara_hip.so that every model family shares: the handle's life cycle (create / bind / weight shadows / gradient
 // buckets / optimizer / profiler) and the plumbing the families' graphs are written with (parameter layout, workspace plan helpers,
-// profiled GEMM wrappers, deferred parameter-gradient sums).  The families themselves: keras_hybrid.hip, conformer_r5.hip,
+// profiled GEMM wrappers, deferred parameter-gradient sums).  The families themselves: keras_graph.hip / conv_block.hip / keras_hybrid.hip / keras_probe.hip, conformer_r5.hip,
 // squeezeformer_r4.hip; the stand-alone and operator entry points: api_ops.hip.  Everything is launched on the caller's stream.
 #include "model_types.h"
 #include <algorithm>
@@ -44,13 +44,10 @@ void finish_param_layout(ishara_model* m) {
 }
 
 void plan_shadow(ishara_model* m, DenseW& w, int min_ldt, int min_ldn) {
-    const int bk = dt_is16(m->dt) ? 64 : 32;
     const size_t es = dt_size(m->dt);
-    w.ldt = (int)rup(w.K, bk);
-    if (w.ldt < min_ldt) w.ldt = min_ldt;      // zero-padded K (the shadow arena is zero-filled, the builder writes k < K)
+    w.ldt = shadow_ld(m->dt, w.K, min_ldt);      // zero-padded K (the shadow arena is zero-filled, the builder writes k < K)
     w.wt = m->alloc(rup(w.N, 128) * (size_t)w.ldt * es).off;
-    w.ldn = (int)rup(w.N, bk);
-    if (w.ldn < min_ldn) w.ldn = min_ldn;
+    w.ldn = shadow_ld(m->dt, w.N, min_ldn);
     w.wn = m->alloc(rup(w.K, 128) * (size_t)w.ldn * es).off;
     m->denses.push_back(&w);
 }

@@ -1,6 +1,7 @@
 // Shared host-side types of libishara_hip.so: the model handle, its parameter / workspace bookkeeping, the profiled-launch
-// macros and what the host units share.  Included by model.hip (handle life cycle and shared plumbing), keras_hybrid.hip (the Keras
-// get_model family), conformer_r5.hip / squeezeformer_r4.hip (the torch encoder families) and api_ops.hip (stand-alone entry points).
+// macros and what the host units share.  Included by model.hip (handle life cycle and shared plumbing), keras_graph.hip / conv_block.hip /
+// keras_hybrid.hip / keras_probe.hip (the Keras get_model family), conformer_r5.hip / squeezeformer_r4.hip (the torch encoder families) and
+// api_ops.hip (stand-alone entry points).
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -42,12 +43,20 @@ struct BNp { int gamma = -1, beta = -1, mm = -1, mv = -1; };
 
 struct Buf { size_t off = 0; };   // byte offset in the workspace
 
+// The launch plan of one Conv1DBlock call (conv_block.hip conv_block_plan: the fields and their conditions)
+enum ConvStats { ST_LEN, ST_INFER_PART, ST_TRAIN_PART, ST_SUMS };      // the ECA gate: eca_fwd_len on a masked time mean / _infer / _part on the partial rows / plain on per-sample sums
+enum ConvW2Bwd { W2_PSA, W2_FOLDED, W2_SCALED_COPY, W2_PLAIN };        // the project conv's dgrad + wgrad
+enum ConvBnBwd { BNB_LEN, BNB_FUSED, BNB_TWO_KERNEL };                 // BatchNorm + depthwise backward: bn_bwd_apply_len + plain / one kernel / bn_bwd_apply + plain
+struct ConvPlan {
+    bool ok = false;          // false: the depthwise conv refuses the shape
+    int prows = 0;            // partial statistic rows per sample of the depthwise forward
+    ConvStats stats = ST_SUMS; bool bn_from_part = false, fold = false, prologue = false, psa = false;
+    ConvW2Bwd w2_bwd = W2_PLAIN; ConvBnBwd bn_bwd = BNB_TWO_KERNEL;
+};
 struct ConvBlock {
     DenseW W1, W2; int dw = -1, eca = -1; BNp bn; int k = 0; uint32_t site = 0;
     Buf z1, h2, h4, out, ssum, ssq, mean, rstd, a, bsh, gn, sg, P, Q, rs;
-    bool folded = false;      // last training forward folded the drop-path scale into h4 (= rs[b] * (h2 P + Q)): see conv_fwd
-    bool psa = false;         // last training forward did not write h4: the project conv's weight gradient applies the per-sample affine itself
-                              // and emits the BatchNorm / ECA backward statistics (gemm_tn.hip, TnPsa)
+    ConvPlan plan;            // of the last forward: conv_bwd runs what it says
 };
 struct FFN {
     Norm ln; float eps; DenseW Wa, Wb; uint32_t site_in = 0, site_out = 0; bool has_out_drop = false;
@@ -193,6 +202,10 @@ struct Run { int B, M, training; uint32_t seed; const float* attn_bias = nullptr
 static inline DropSpec dspec(const Run& r, uint32_t site, float rate) { return make_drop(r.seed, site, rate, r.training != 0); }
 static inline DropSpec dspec_attn(const Run& r, uint32_t site, float rate) { return make_drop_attn(r.seed, site, rate, r.training != 0); }   // attention probabilities: common.h rng_quad
 void finish_param_layout(ishara_model* m);      // after the last addp: offsets, n_train, n_total
+static inline int shadow_ld(int dt, int cols, int min_ld = 0) {      // row stride of a weight shadow: whole K tiles of the MFMA kernels (zero padded)
+    const int ld = (int)rup(cols, dt_is16(dt) ? 64 : 32);
+    return ld < min_ld ? min_ld : ld;
+}
 void plan_shadow(ishara_model* m, DenseW& w, int min_ldt = 0, int min_ldn = 0);
 void plan_confconv(ishara_model* m, ConfConv& c, size_t rows, int B, int d);
 void plan_post_ln_ffn(ishara_model* m, R5FFN& f, size_t rows, int d, int de);
@@ -208,9 +221,35 @@ int red_flush(ishara_model* m);
 int layernorm_bwd_deferred(ishara_model* m, const Run& r, const void* dy, const void* x, Buf mean, Buf rstd, const Norm& ln, const void* resid, void* dx);
 int dwconv_bwd_deferred(ishara_model* m, const Run& r, double by_factor, int inop, const void* dy, const DwBnArgs* bn, const void* x, int dw, int dwb, void* dx, int C, int k, int padl);
 const void* grad_through_dropout(ishara_model* m, const Run& r, uint32_t site, float rate, const void* g, void* tmp, int T, int cols, int* rc);
-// Keras get_model hybrid family (keras_hybrid.hip); confconv_* also serve the torch families, ln_as_prologue / classifier_fwd the operator entry points
+// Keras get_model hybrid family: graph and workspace plan (keras_graph.hip)
 void keras_build_graph(ishara_model* m);
 void keras_plan_workspace(ishara_model* m);
+// its Conv1DBlock (conv_block.hip): the plan, the module, the two launch pairs it shares with the Conformer conv module, the fusion switches
+bool infer_fusion_on();       // ISHARA_NO_INFER_FUSION unset (read at every call)
+bool stats_fusion_on();       // ISHARA_NO_STATS_FUSION unset (read once per process)
+ConvPlan conv_block_plan(int dt, bool training, int B, int T, int d, int k, int ldt, int ldn, bool drop_path, bool lengths, bool psa_on);
+const char* conv_block_route_name(const ConvPlan& p, bool training);
+int conv_fwd(ishara_model* m, ConvBlock& cb, const Run& r, const void* x);
+int conv_bwd(ishara_model* m, ConvBlock& cb, const Run& r, const void* x, const void* g, void* gn);
+struct DwBnFwd { BNp bn; float eps, keep, var_corr; Buf ssum, ssq, mean, rstd, a, bsh; };      // a BatchNorm behind a depthwise conv: parameters, constants, buffers
+int dwconv_stat_rows(int dt, int B, int T, int C, int k);      // partial statistic rows per sample of a depthwise forward with statistics
+int dwconv_bn_fwd(ishara_model* m, const Run& r, int inop, const void* x, int dw, int dwb, void* y, int C, int k, int padl, const DwBnFwd& s, bool with_sums, int prows, bool finalize);
+bool dwconv_bwd_fused_bn(int dt, int C, int k, int padl);
+int dwconv_bn_bwd(ishara_model* m, const Run& r, bool fused, double by_fused, int inop, void* dy, const DwBnArgs& bn, const void* x, int dw, int dwb, void* dx, int C, int k, int padl);
+// the other modules, stem and head (keras_hybrid.hip; the module probe in keras_probe.hip runs them one at a time); confconv_* also serve the torch
+// families, ln_as_prologue / classifier_fwd the operator entry points
+int ffn_fwd(ishara_model* m, FFN& f, const Run& r, const void* x);
+int ffn_bwd(ishara_model* m, FFN& f, const Run& r, const void* x, const void* g, void* gn);
+int mhsa_fwd(ishara_model* m, MHSA& a, const Run& r, const void* x);
+int mhsa_bwd(ishara_model* m, MHSA& a, const Run& r, const void* x, const void* g, void* gn);
+int sqzconv_fwd(ishara_model* m, SqzConv& c, const Run& r, const void* x);
+int sqzconv_bwd(ishara_model* m, SqzConv& c, const Run& r, const void* x, const void* g, void* gn);
+int stem_fwd(ishara_model* m, const Run& r, const float* x);
+int stem_bwd(ishara_model* m, const Run& r, const void* g);
+int head_fwd(ishara_model* m, const Run& r, const void* h, float* logits);
+int head_bwd(ishara_model* m, const Run& r, const void* hin, void* g);
+bool frame_len_ok(const ishara_model* m, const char* fn, const int32_t* frame_len);
+bool frame_len_agrees(const char* fn, bool fwd_had, const int32_t* frame_len);
 bool ln_as_prologue(int dt, int M, int N, int K, int ldt, const float* gamma, const float* beta, float eps, float* mean, float* rstd, void* xn, EpiArgs& ea);
 enum { CLS_AUTO = 0, CLS_AS = 1, CLS_NARROW = 2, CLS_GEMM = 3 };      // routes of classifier_fwd
 int cls_route_auto(int dt, int M, int K, int C);

@@ -124,6 +124,14 @@ def _check_routes(name, kind, shape, dtype, dropout, B, variant, report):
         if B == B_NO_PSA or variant == "no_psa":
             assert PSA_KEY not in report, f"the per-sample-affine route was not refused: {report}"
             assert "sample_reduce" in report
+        if shape in SHAPES:      # the profiled keys agree with what the plan says for the case (the forced switches of a variant are set while this runs)
+            kw = SHAPES[shape]
+            flags = (1 if dropout > 0 else 0) | (0 if variant == "no_psa" else 4)
+            plan = _lib.load().ishara_debug_conv_block_route_name(1, 1, B, kw["input_shape"][0], kw["dim"], kw["kernel_sizes"][int(name[-1]) - 1], flags).decode()
+            fwd, bwd = plan.split("|")
+            assert ("+psa" in fwd) == (PSA_KEY in report) == ("sample_reduce" not in report), (plan, report)
+            assert ("+affine" in fwd) == ("sample_affine" in report) and ("+prologue" in fwd) == (2 in pro), (plan, report)
+            assert bwd.endswith("fused_bn") == ("bn_bwd_apply" not in report) and ("scaled_copy" in bwd) == ("map_rows" in report), (plan, report)
     if (kind in ("ffn", "sqzconv") or (kind == "mha" and shape == "cfg2")) and plain:      # (d512: the K = 512 QKV projection runs the LayerNorm kernel and a tile GEMM)
         assert 1 in pro, f"no A-stationary GEMM with the LayerNorm prologue in {report}"
     if variant == "regstage8192":

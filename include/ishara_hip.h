@@ -367,6 +367,40 @@ int ishara_op_dense_fwd_ex(int32_t dt, const void* x, const float* W, const floa
 /* dx = dy @ W^T ; dW += x^T dy ; db += colsum(dy) */
 int ishara_op_dense_bwd(int32_t dt, const void* x, const float* W, const void* dy, void* dx,
                         float* dW, float* db, int32_t M, int32_t K, int32_t N, void* scratch, ishara_stream s);
+/* One weight-gradient GEMM with every argument the models' backward passes give it (launch_gemm_tn through gemm_wgrad):
+ *   out [ka_valid or Ka, nb_valid or Nb] f32 += A[M, Ka]^T . B[M, Nb];  dbias [nb_valid or Nb] f32 (may be NULL) += sum_m rs[m / bias_T] * B[m, :]
+ * dtA / dtB: the operands' storage types, dtM: the MFMA operand type (ISHARA_F32 / ISHARA_BF16; an f32 operand under dtM = bf16 is rounded
+ * to bf16 while it is staged).  ka_valid / nb_valid (0: none): columns [ka_valid, Ka) of A / [nb_valid, Nb) of B are zero padding that out and
+ * dbias do not have (bf16 transposed-read kernel only; nb_valid % 4 == 0; no dbias with ka_valid).  bias_rowscale (may be NULL: rs = 1):
+ * ceil(M / bias_T) f32, bias_T % 32 == 0, transposed-read kernel only.  The per-sample-affine block is present when psa_T != 0 or any of its
+ * pointers is set: P, Q [M / psa_T, Ka] f32, W bf16 [Ka][ldw] (ldw >= Nb), outputs G [M / psa_T, Nb] and Rpart [M / psa_T][Nb / 64][Ka] f32
+ * (overwritten); then out += sum_b (P[b] (.) A_b)^T B_b + Q[b] (x) colsum(B_b), G[b, n] = sum_t B_b[t, n], Rpart[b][p][k] = sum over the 64
+ * columns n of group p of W[k, n] * (A_b^T B_b)[k, n]; a bias_rowscale beside it must have bias_T == psa_T.  A, B 16-byte aligned, every f32
+ * buffer 4-byte aligned.  The operand transforms (opA / opB) of launch_gemm_tn are not carried: no weight gradient of the models passes one. */
+typedef struct ishara_gemm_tn_call {
+    const void* A; const void* B;
+    float* out; float* dbias;
+    const float* bias_rowscale;
+    const float* P; const float* Q; const void* W;
+    float* G; float* Rpart;
+    int32_t dtA, dtB, dtM;
+    int32_t M, Ka, Nb, ka_valid, nb_valid;
+    int32_t bias_T, psa_T, ldw, reserved;
+} ishara_gemm_tn_call;
+/* bytes of ONE slab buffer that takes every call of the list (the largest gemm_tn_slab_floats); -1 for a bad list */
+int64_t ishara_op_gemm_tn_scratch_bytes(const ishara_gemm_tn_call* calls, int32_t n);
+/* runs the n calls in order on stream s, as a backward pass does.  slab: 16-byte aligned, ishara_op_gemm_tn_scratch_bytes.  defer_slab0 / 1 both
+ * NULL: every call sums its M-split partials at once (immediate mode).  Both given (each as large as slab, 16-byte aligned): the calls share one
+ * deferred-sum state over them — the partial sums of a transposed-read call ride as extra workgroups of the next one, calls on other kernels
+ * use slab — and what is still pending is summed before the entry returns (launch_gemm_tn_flush).  Before any HIP call it refuses, for every
+ * call of the list: a NULL or misaligned buffer, an unknown dtype, ISHARA_F16 (no fp16 weight gradients) and whatever launch_gemm_tn refuses,
+ * with the launcher's message. */
+int ishara_op_gemm_tn(const ishara_gemm_tn_call* calls, int32_t n, void* slab, void* defer_slab0, void* defer_slab1, ishara_stream s);
+/* what launch_gemm_tn would do with one call under the current switches, read from the code that launches: route ("TN_BIG", "TN_TR",
+ * "TN_TR_BRS", "TN_TR_PSA", "TN_REG"; "TN_REFUSED" with the launcher's message in ishara_last_error), the profiler key of the kernel
+ * (gemm_tn_kernel_name; "" for a refused call), the number of M-splits and the rows per split.  The call's pointers are only tested for NULL
+ * and alignment; out / dbias / G / Rpart need not be real.  Host only, launches nothing; the strings are static. */
+int ishara_debug_gemm_tn_plan(const ishara_gemm_tn_call* call, const char** route, const char** kernel, int32_t* splits, int32_t* rows_per_split);
 /* QKV projection of the attention module at inference: LayerNorm of x [B*T, H*dh] (gamma, beta f32; gamma NULL: none; H*dh <= 512 with it),
  * x @ W + b (W [H*dh, 3*H*dh] f32, bias [3*H*dh] or NULL) scattered to q, k [B,H,T,dh] and vt [B,H,dh,T] (dt) — head_major 1: W's columns
  * are [q|k|v] per head, 0: [q of all heads | k | v].  T, dh multiples of 8.  The LayerNorm runs inside the GEMM or as a kernel of its own

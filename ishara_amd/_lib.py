@@ -48,6 +48,17 @@ class GradStats(C.Structure):
     _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("nonfinite", C.c_int32), ("skipped", C.c_int32)]
 
 
+class GemmTnCall(C.Structure):
+    """ishara_gemm_tn_call: one weight-gradient GEMM of ishara_op_gemm_tn / ishara_debug_gemm_tn_plan (field order of the header)."""
+    _fields_ = [
+        ("A", C.c_void_p), ("B", C.c_void_p), ("out", C.c_void_p), ("dbias", C.c_void_p), ("bias_rowscale", C.c_void_p),
+        ("P", C.c_void_p), ("Q", C.c_void_p), ("W", C.c_void_p), ("G", C.c_void_p), ("Rpart", C.c_void_p),
+        ("dtA", C.c_int32), ("dtB", C.c_int32), ("dtM", C.c_int32),
+        ("M", C.c_int32), ("Ka", C.c_int32), ("Nb", C.c_int32), ("ka_valid", C.c_int32), ("nb_valid", C.c_int32),
+        ("bias_T", C.c_int32), ("psa_T", C.c_int32), ("ldw", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/ishara_hip.h declares
 _P, _I32, _I64, _U32, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 SIGNATURES = {
@@ -121,6 +132,9 @@ SIGNATURES = {
     "ishara_op_dense_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "ishara_op_dense_fwd_ex": (C.c_int, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "ishara_op_dense_bwd": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "ishara_op_gemm_tn_scratch_bytes": (_I64, [C.POINTER(GemmTnCall), _I32]),
+    "ishara_op_gemm_tn": (C.c_int, [C.POINTER(GemmTnCall), _I32, _P, _P, _P, _P]),
+    "ishara_debug_gemm_tn_plan": (C.c_int, [C.POINTER(GemmTnCall), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_I32), C.POINTER(_I32)]),
     "ishara_op_qkv_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_op_qkv_fwd": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "ishara_op_classifier_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),

@@ -683,13 +683,29 @@ bool gemm_tn_psa_ok(int dtA, int dtB, int dtM, int M, int Ka, int Nb, int T) {
     return tn_tr_takes(dtA, dtB, dtM, M, Ka, Nb) && !g_dbg_tn && tn_psa_splits(M, Ka, Nb, T) > 0;
 }
 
-// the transposed-read kernels: route is TN_BIG, TN_TR, TN_TR_BRS or TN_TR_PSA
-static int run_tn_tr(TnRoute route, const void* A, const void* B, float* out, float* dbias, float* slab, int M, int Ka, int Nb, hipStream_t s, int ka_valid, int nb_valid,
+// split plan of the plain and the weighted-bias-sum transposed-read kernel: M-splits and rows per split (whole 32-row stages, at least 8 per split
+// where M allows)
+static void tn_tr_plan(int M, int Ka, int Nb, int& splits, int& rps) {
+    const int tiles = (Ka / 128) * (Nb / 128);
+    // workgroups: one per CU for up to 8 tiles (same kernel time as two per CU, half the slab bytes: the slab sums go
+    // 9.6 -> 7.3 us), two per CU for 12+ tiles (N = 768: 61 vs 72 us); g_tn_blocks != 0 overrides (tools/tn_ablate.py)
+    const int blocks = g_tn_blocks ? g_tn_blocks : (tiles <= 8 ? 256 : 512);
+    int want = max(1, blocks / tiles);
+    const int maxs = max(1, M / 256);                     // at least 8 tiles per split
+    if (want > maxs) want = maxs;
+    if (want > 8) want &= ~7;                             // a multiple of 8 keeps the XCD-aware (tile, split) mapping: 12 tiles x 42 splits ran 102 us, x 40: see DESIGN.md
+    rps = ((M + want - 1) / want + TR_ROWS - 1) / TR_ROWS * TR_ROWS;
+    splits = (M + rps - 1) / rps;
+    while (want > 8 && (splits & 7) != 0 && rps > TR_ROWS) { rps -= TR_ROWS; splits = (M + rps - 1) / rps; if (splits > 512) break; }
+    if (splits > 512) { rps = ((M + want - 1) / want + TR_ROWS - 1) / TR_ROWS * TR_ROWS; splits = (M + rps - 1) / rps; }
+}
+
+// the transposed-read kernels: plan.route is TN_BIG, TN_TR, TN_TR_BRS or TN_TR_PSA
+static int run_tn_tr(const TnPlan& plan, const void* A, const void* B, float* out, float* dbias, float* slab, int M, int Ka, int Nb, hipStream_t s, int ka_valid, int nb_valid,
                      const float* brs, int brsT, TnDefer* defer, const TnPsa* psa) {
-    if (route == TN_BIG) {
+    if (plan.route == TN_BIG) {
         // config #4's shapes (Ka, Nb >= 512 in whole 256-wide tiles, M >= 32768): the 256 x 256 tile kernel of gemm_big.hip, sums right behind it
-        int bsplits = 0;
-        gemm_tn_big_plan(M, Ka, Nb, &bsplits);
+        int bsplits = plan.splits;
         launch_gemm_tn_flush(defer, s);
         if (g_tn_phase != 2) {
             const int rc = launch_gemm_tn_big(A, B, slab, dbias ? 1 : 0, M, Ka, Nb, &bsplits, (brs && dbias) ? brs : nullptr, brsT, s);
@@ -701,22 +717,8 @@ static int run_tn_tr(TnRoute route, const void* A, const void* B, float* out, fl
     }
     const int tiles = (Ka / 128) * (Nb / 128);
     const TnPsa nopsa = {};
-    // workgroups: one per CU for up to 8 tiles (same kernel time as two per CU, half the slab bytes: the slab sums go
-    // 9.6 -> 7.3 us), two per CU for 12+ tiles (N = 768: 61 vs 72 us); g_tn_blocks != 0 overrides (tools/tn_ablate.py)
-    const int blocks = g_tn_blocks ? g_tn_blocks : (tiles <= 8 ? 256 : 512);
-    int want = max(1, blocks / tiles);
-    const int maxs = max(1, M / 256);                     // at least 8 tiles per split
-    if (want > maxs) want = maxs;
-    if (want > 8) want &= ~7;                             // a multiple of 8 keeps the XCD-aware (tile, split) mapping: 12 tiles x 42 splits ran 102 us, x 40: see DESIGN.md
-    int rps = ((M + want - 1) / want + TR_ROWS - 1) / TR_ROWS * TR_ROWS;
-    int splits = (M + rps - 1) / rps;
-    while (want > 8 && (splits & 7) != 0 && rps > TR_ROWS) { rps -= TR_ROWS; splits = (M + rps - 1) / rps; if (splits > 512) break; }
-    if (splits > 512) { rps = ((M + want - 1) / want + TR_ROWS - 1) / TR_ROWS * TR_ROWS; splits = (M + rps - 1) / rps; }
-    if (psa) {
-        splits = tn_psa_splits(M, Ka, Nb, psa->T);
-        if (splits <= 0 || g_dbg_tn) { ishara_set_error("gemm_tn: no per-sample-affine plan for M=%d T=%d (gemm_tn_psa_ok)", M, psa->T); return -1; }
-        rps = M / splits;
-    }
+    const int splits = plan.splits, rps = plan.rps;
+    if (splits <= 0 || rps <= 0) { ishara_set_error("gemm_tn: internal error: no split plan for the route gemm_tn_route chose (M=%d Ka=%d Nb=%d)", M, Ka, Nb); return -2; }
     if (defer && g_tn_phase == 0 && !g_dbg_tn && tiles * splits > 256 && !psa) {
         // a launch that fills the chip twice over (12+ tiles at two workgroups per CU) neither carries riders nor defers its own sums: the riders
         // would queue behind 512 workgroups and its slabs (2 MB x 16 splits for a 1024 x 512 weight) make the next launch's riders the tail
@@ -767,10 +769,9 @@ static int run_tn_tr(TnRoute route, const void* A, const void* B, float* out, fl
 }
 
 template <typename TA, typename TB, typename TM>
-static int run_tn(int opA, int opB, const void* A, const void* B, float* out, float* dbias, float* slab,
-                  int M, int Ka, int Nb, int dtM, const OpArgs& oa, const OpArgs& ob, hipStream_t s) {
-    int splits, rps;
-    tn_plan(M, Ka, Nb, dtM, splits, rps);
+static int run_tn(const TnPlan& plan, int opA, int opB, const void* A, const void* B, float* out, float* dbias, float* slab,
+                  int M, int Ka, int Nb, const OpArgs& oa, const OpArgs& ob, hipStream_t s) {
+    const int splits = plan.splits, rps = plan.rps;
     float* bias_slab = dbias ? slab + (size_t)splits * Ka * Nb : nullptr;
     const int tiles = ((Ka + 127) / 128) * ((Nb + 127) / 128);
     const int a_ok = (((size_t)Ka * sizeof(TA)) % 16 == 0) && (((uintptr_t)A) % 16 == 0);
@@ -816,35 +817,59 @@ TnRoute gemm_tn_route(int dtA, int dtB, int dtM, int opA, int opB, int M, int Ka
     return dtM == DT_BF16 && (dtA == DT_BF16 || dtA == DT_F32) && (dtB == DT_BF16 || dtB == DT_F32) && !(dtA == DT_F32 && dtB == DT_F32) ? TN_REG : TN_REFUSED;
 }
 
-int launch_gemm_tn(int dtA, int dtB, int dtM, int opA, int opB, const void* A, const void* B,
-                   float* out, float* dbias, float* slab, int M, int Ka, int Nb,
-                   const OpArgs& oa, const OpArgs& ob, hipStream_t s, int ka_valid, int nb_valid, const float* bias_rowscale, int bias_T, TnDefer* defer, const TnPsa* psa) {
-    if (M <= 0 || Ka <= 0 || Nb <= 0) { ishara_set_error("gemm_tn: bad shape"); return -1; }
+// What launch_gemm_tn does with a call, decided here and nowhere else: every refusal with its message (route TN_REFUSED), else the route and the
+// split plan the launch uses.  Host only; A / B: the operand addresses (their alignment is checked, nothing is read)
+TnPlan gemm_tn_plan(int dtA, int dtB, int dtM, int opA, int opB, const void* A, const void* B, bool has_dbias, int M, int Ka, int Nb,
+                    int ka_valid, int nb_valid, const float* bias_rowscale, int bias_T, const TnPsa* psa) {
+    const TnPlan refused = {TN_REFUSED, 0, 0};
+    if (M <= 0 || Ka <= 0 || Nb <= 0) { ishara_set_error("gemm_tn: bad shape"); return refused; }
     const TnRoute route = gemm_tn_route(dtA, dtB, dtM, opA, opB, M, Ka, Nb, ka_valid, nb_valid, bias_rowscale != nullptr, bias_T, psa != nullptr, psa ? psa->T : 0);
     if (psa && (route != TN_TR_PSA || !psa->P || !psa->Q || !psa->W || !psa->G || !psa->Rpart)) {
-        ishara_set_error("gemm_tn: per-sample affine needs the transposed-read kernel, whole samples per split and all of P, Q, W, G, Rpart (gemm_tn_psa_ok)"); return -1;
+        ishara_set_error("gemm_tn: per-sample affine needs the transposed-read kernel, whole samples per split and all of P, Q, W, G, Rpart (gemm_tn_psa_ok)"); return refused;
     }
-    if (bias_rowscale && !gemm_tn_bias_rowscale_ok(dtA, dtB, dtM, M, Ka, Nb, bias_T)) { ishara_set_error("gemm_tn: bias row scale needs the transposed-read kernel and T %% 32 == 0"); return -1; }
+    if (bias_rowscale && !gemm_tn_bias_rowscale_ok(dtA, dtB, dtM, M, Ka, Nb, bias_T)) { ishara_set_error("gemm_tn: bias row scale needs the transposed-read kernel and T %% 32 == 0"); return refused; }
     if (ka_valid <= 0) ka_valid = Ka;
     if (nb_valid >= Nb || nb_valid < 0) nb_valid = 0;
-    if (nb_valid % 4 != 0) { ishara_set_error("gemm_tn: nb_valid %d must be a multiple of 4", nb_valid); return -1; }
+    if (nb_valid % 4 != 0) { ishara_set_error("gemm_tn: nb_valid %d must be a multiple of 4", nb_valid); return refused; }
     if ((dtA == DT_BF16 && Ka % 8 != 0) || (dtA == DT_F32 && Ka % 4 != 0) || (dtB == DT_BF16 && Nb % 8 != 0) || (dtB == DT_F32 && Nb % 4 != 0) ||
         ((uintptr_t)A) % 16 != 0 || ((uintptr_t)B) % 16 != 0) {
-        ishara_set_error("gemm_tn: operand rows must be 16-byte aligned (Ka=%d Nb=%d)", Ka, Nb); return -1;
+        ishara_set_error("gemm_tn: operand rows must be 16-byte aligned (Ka=%d Nb=%d)", Ka, Nb); return refused;
     }
+    TnPlan p = {route, 0, 0};
     switch (route) {
         case TN_REFUSED:
             if (ka_valid != Ka || nb_valid) ishara_set_error("gemm_tn: padded A columns need the bf16 transposed-read kernel (M %% 64, Ka %% 128, Nb %% 128)");
             else ishara_set_error("gemm_tn: unsupported dtype combination %d/%d/%d", dtA, dtB, dtM);
+            return refused;
+        case TN_BIG: case TN_TR: case TN_TR_BRS: case TN_TR_PSA:
+            if (ka_valid < Ka && has_dbias) { ishara_set_error("gemm_tn: padded A columns with a bias gradient"); return refused; }
+            if (route == TN_BIG) p.rps = gemm_tn_big_plan(M, Ka, Nb, &p.splits);
+            else if (route == TN_TR_PSA) { p.splits = tn_psa_splits(M, Ka, Nb, psa->T); p.rps = p.splits > 0 ? M / p.splits : 0; }
+            else tn_tr_plan(M, Ka, Nb, p.splits, p.rps);
+            break;
+        case TN_REG:
+            tn_plan(M, Ka, Nb, dtM, p.splits, p.rps);
+            break;
+    }
+    return p;
+}
+
+int launch_gemm_tn(int dtA, int dtB, int dtM, int opA, int opB, const void* A, const void* B,
+                   float* out, float* dbias, float* slab, int M, int Ka, int Nb,
+                   const OpArgs& oa, const OpArgs& ob, hipStream_t s, int ka_valid, int nb_valid, const float* bias_rowscale, int bias_T, TnDefer* defer, const TnPsa* psa) {
+    const TnPlan plan = gemm_tn_plan(dtA, dtB, dtM, opA, opB, A, B, dbias != nullptr, M, Ka, Nb, ka_valid, nb_valid, bias_rowscale, bias_T, psa);
+    if (ka_valid <= 0) ka_valid = Ka;
+    if (nb_valid >= Nb || nb_valid < 0) nb_valid = 0;
+    switch (plan.route) {
+        case TN_REFUSED:
             return -1;
         case TN_BIG: case TN_TR: case TN_TR_BRS: case TN_TR_PSA:
-            if (ka_valid < Ka && dbias) { ishara_set_error("gemm_tn: padded A columns with a bias gradient"); return -1; }
-            return run_tn_tr(route, A, B, out, dbias, slab, M, Ka, Nb, s, ka_valid, nb_valid, bias_rowscale, bias_T, defer, psa);
+            return run_tn_tr(plan, A, B, out, dbias, slab, M, Ka, Nb, s, ka_valid, nb_valid, bias_rowscale, bias_T, defer, psa);
         case TN_REG:
-            if (dtM == DT_F32) return run_tn<float, float, float>(opA, opB, A, B, out, dbias, slab, M, Ka, Nb, dtM, oa, ob, s);
-            if (dtA == DT_F32) return run_tn<float, bf16, bf16>(opA, opB, A, B, out, dbias, slab, M, Ka, Nb, dtM, oa, ob, s);
-            if (dtB == DT_F32) return run_tn<bf16, float, bf16>(opA, opB, A, B, out, dbias, slab, M, Ka, Nb, dtM, oa, ob, s);
-            return run_tn<bf16, bf16, bf16>(opA, opB, A, B, out, dbias, slab, M, Ka, Nb, dtM, oa, ob, s);
+            if (dtM == DT_F32) return run_tn<float, float, float>(plan, opA, opB, A, B, out, dbias, slab, M, Ka, Nb, oa, ob, s);
+            if (dtA == DT_F32) return run_tn<float, bf16, bf16>(plan, opA, opB, A, B, out, dbias, slab, M, Ka, Nb, oa, ob, s);
+            if (dtB == DT_F32) return run_tn<bf16, float, bf16>(plan, opA, opB, A, B, out, dbias, slab, M, Ka, Nb, oa, ob, s);
+            return run_tn<bf16, bf16, bf16>(plan, opA, opB, A, B, out, dbias, slab, M, Ka, Nb, oa, ob, s);
     }
     return -1;
 }

@@ -134,6 +134,11 @@ enum TnRoute { TN_REFUSED, TN_BIG, TN_TR, TN_TR_BRS, TN_TR_PSA, TN_REG };
 TnRoute gemm_tn_route(int dtA, int dtB, int dtM, int opA, int opB, int M, int Ka, int Nb, int ka_valid, int nb_valid, bool brs, int brsT, bool psa, int psaT);
 const char* gemm_tn_kernel_name(int dtA, int dtB, int dtM, int opA, int opB, int M, int Ka, int Nb, int ka_valid = 0, int nb_valid = 0,
                                 const float* bias_rowscale = nullptr, int bias_T = 0, const TnPsa* psa = nullptr);
+// what launch_gemm_tn does with a call: the route (TN_REFUSED: the launcher's message is set) and the split plan it launches with — M-splits and
+// rows per split.  launch_gemm_tn launches from this and ishara_debug_gemm_tn_plan reports it.  Host only; A / B: alignment only, nothing is read
+struct TnPlan { TnRoute route; int splits, rps; };
+TnPlan gemm_tn_plan(int dtA, int dtB, int dtM, int opA, int opB, const void* A, const void* B, bool has_dbias, int M, int Ka, int Nb,
+                    int ka_valid, int nb_valid, const float* bias_rowscale, int bias_T, const TnPsa* psa);
 // the 256 x 256 tile wgrad kernel (gemm_big.hip): rows per M-split (0: not a shape it takes); the launcher answers 1 for such a shape
 int gemm_tn_big_plan(int M, int Ka, int Nb, int* splits_out);
 int launch_gemm_tn_big(const void* A, const void* B, float* slab, int want_bias, int M, int Ka, int Nb, int* splits_out, const float* brs, int brsT, hipStream_t s);

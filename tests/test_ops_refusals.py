@@ -32,6 +32,7 @@ def _ops():
         "ishara_op_attn_bwd": lambda L, dt: L.ishara_op_attn_bwd(dt, N, N, N, 1, 4, 64, 32, f(0.1), 1, 2, f(0.0), 1, N, N),
         "ishara_op_qkv_fwd": lambda L, dt: L.ishara_op_qkv_fwd(dt, N, N, N, f(1e-6), N, N, N, N, N, 1, 64, 4, 32, 1, N, N),
         "ishara_op_classifier_fwd": lambda L, dt: L.ishara_op_classifier_fwd(dt, N, N, N, N, 64, 256, 60, 0, N, N),
+        "ishara_op_gemm_tn": lambda L, dt: _gemm_tn(L, dict(dtA=dt, dtB=dt, dtM=dt)),
         **{n: (lambda L, dt, n=n: _r4_call(L, n, dt=dt)) for n in R4_DEFAULTS},
     }
 
@@ -64,7 +65,27 @@ def _r4_call(L, name, dt=F32, ptrs=None, mode=4, **kw):
 
 
 CTC_LOSS = ["ishara_ctc_loss", "ishara_op_ctc_loss"]
-BACKWARD = ["ishara_op_dense_bwd", "ishara_op_layernorm_bwd", "ishara_op_dwconv_bwd", "ishara_op_bn_bwd_apply", "ishara_op_dwconv_bwd_bn", "ishara_op_attn_bwd"]
+BACKWARD = ["ishara_op_dense_bwd", "ishara_op_layernorm_bwd", "ishara_op_dwconv_bwd", "ishara_op_bn_bwd_apply", "ishara_op_dwconv_bwd_bn", "ishara_op_attn_bwd",
+            "ishara_op_gemm_tn"]
+
+
+def _gemm_tn_call(**kw):
+    """one ishara_gemm_tn_call: a plain bf16 call of the transposed-read kernel with made-up aligned addresses, `kw` replacing single fields"""
+    k = _lib.GemmTnCall()
+    v = dict(A=4096, B=8192, out=12288, dbias=16384, dtA=BF16, dtB=BF16, dtM=BF16, M=576, Ka=128, Nb=128)
+    v.update(kw)
+    for n, x in v.items():
+        setattr(k, n, x)
+    return k
+
+
+PSA_FIELDS = dict(P=20480, Q=24576, W=28672, G=32768, Rpart=36864, psa_T=128, ldw=128, M=1024)
+
+
+def _gemm_tn(L, *calls, slab=C.c_void_p(1 << 20), d0=N, d1=N):
+    """ishara_op_gemm_tn on a list of calls (dicts of field replacements) with a made-up slab and a NULL stream"""
+    arr = (_lib.GemmTnCall * len(calls))(*[_gemm_tn_call(**kw) for kw in calls])
+    return L.ishara_op_gemm_tn(arr, len(calls), slab, d0, d1, N)
 
 
 def _refused(lib, rc, name, *words):
@@ -76,8 +97,9 @@ def _refused(lib, rc, name, *words):
 
 
 def test_every_dtype_taking_operator_is_listed():
-    """every ishara_op_* with a dtype argument (first argument) is covered below; ishara_op_ctc_loss (fp32 only, no dtype argument) has
-    its refusals with ishara_ctc_loss and ishara_greedy_decode at the end of this file"""
+    """every ishara_op_* with a dtype argument (first argument; ishara_op_gemm_tn: the three dtypes of each call of its list) is covered
+    below; ishara_op_ctc_loss (fp32 only, no dtype argument) has its refusals with ishara_ctc_loss and ishara_greedy_decode at the end of
+    this file"""
     with_dt = {n for n, (_, args) in _lib.SIGNATURES.items() if n.startswith("ishara_op_") and not n.endswith("_bytes")
                and not n.startswith("ishara_op_log_softmax") and n not in CTC_LOSS}
     assert with_dt == set(_ops())
@@ -451,3 +473,65 @@ def test_greedy_decode_refuses_null_buffers_and_skips_an_empty_batch(lib):
     for k in ("logits", "out_idx", "out_len"):
         _refused(lib, _decode_call(lib, ptrs={k: N}), "ishara_greedy_decode", "null")
     assert _decode_call(lib, B=0, ptrs=dict(logits=N, out_idx=N, out_len=N)) == 0
+
+
+# ---- ishara_op_gemm_tn: the list, the slabs and every call are checked before the first launch; what launch_gemm_tn itself refuses comes back
+# with the launcher's message behind the entry's name and the call's index
+GEMM_TN_REFUSALS = [
+    (dict(A=0), ("null A / B / out",)), (dict(B=0), ("null A / B / out",)), (dict(out=0), ("null A / B / out",)),
+    (dict(out=12290), ("misaligned",)), (dict(dbias=16386), ("misaligned",)), (dict(bias_rowscale=40962, bias_T=32), ("misaligned",)),
+    (dict(A=4104), ("gemm_tn: operand rows must be 16-byte aligned",)), (dict(B=8200), ("gemm_tn: operand rows must be 16-byte aligned",)),
+    (dict(Ka=12, M=100), ("gemm_tn: operand rows must be 16-byte aligned",)),
+    (dict(M=0), ("gemm_tn: bad shape",)), (dict(Ka=-128), ("gemm_tn: bad shape",)), (dict(Nb=0), ("gemm_tn: bad shape",)),
+    (dict(dtA=F16), ("ISHARA_F16", "dtA")), (dict(dtM=F16), ("ISHARA_F16", "dtM")), (dict(dtB=5), ("unknown dtype", "dtB=5")),
+    (dict(dtA=F32, dtB=F32), ("gemm_tn: unsupported dtype combination",)), (dict(dtM=F32), ("gemm_tn: unsupported dtype combination",)),
+    (dict(bias_rowscale=40960, bias_T=48), ("gemm_tn: bias row scale needs",)), (dict(bias_rowscale=40960, bias_T=0), ("gemm_tn: bias row scale needs",)),
+    (dict(bias_rowscale=40960, bias_T=32, M=130), ("gemm_tn: bias row scale needs",)),
+    (dict(ka_valid=100, dbias=0, M=130), ("gemm_tn: padded A columns need",)), (dict(nb_valid=60, Ka=136), ("gemm_tn: padded A columns need",)),
+    (dict(ka_valid=100), ("gemm_tn: padded A columns with a bias gradient",)), (dict(nb_valid=62), ("gemm_tn: nb_valid 62 must be a multiple of 4",)),
+    (dict(PSA_FIELDS, M=11 * 128), ("gemm_tn: per-sample affine needs",)), (dict(PSA_FIELDS, psa_T=96, M=768), ("gemm_tn: per-sample affine needs",)),
+    (dict(PSA_FIELDS, G=0), ("gemm_tn: per-sample affine needs",)), (dict(PSA_FIELDS, psa_T=0), ("gemm_tn: per-sample affine needs",)),
+    (dict(PSA_FIELDS, ka_valid=100, dbias=0), ("gemm_tn: per-sample affine needs",)), (dict(PSA_FIELDS, M=1000), ("gemm_tn: per-sample affine needs",)),
+    (dict(PSA_FIELDS, bias_rowscale=40960, bias_T=64), ("gemm_tn: per-sample affine needs",)),
+    (dict(PSA_FIELDS, ldw=120), ("ldw=120",)), (dict(PSA_FIELDS, W=28673), ("misaligned",)), (dict(PSA_FIELDS, Rpart=36866), ("misaligned",)),
+]
+
+
+@pytest.mark.parametrize("kw,words", GEMM_TN_REFUSALS)
+def test_gemm_tn_refuses_buffers_dtypes_and_shapes(lib, kw, words):
+    _refused(lib, _gemm_tn(lib, kw), "ishara_op_gemm_tn", "call 0", *words)
+    # the same call behind a good one: nothing of the list is launched, and the message names the call
+    _refused(lib, _gemm_tn(lib, {}, kw), "ishara_op_gemm_tn", "call 1", *words)
+    _refused(lib, _gemm_tn(lib, kw, d0=C.c_void_p(2 << 20), d1=C.c_void_p(3 << 20)), "ishara_op_gemm_tn", "call 0", *words)
+
+
+def test_gemm_tn_refuses_a_bad_list_or_slab(lib):
+    name = "ishara_op_gemm_tn"
+    arr = (_lib.GemmTnCall * 1)(_gemm_tn_call())
+    _refused(lib, lib.ishara_op_gemm_tn(None, 1, C.c_void_p(1 << 20), N, N, N), name, "null or empty call list")
+    _refused(lib, lib.ishara_op_gemm_tn(arr, 0, C.c_void_p(1 << 20), N, N, N), name, "null or empty call list")
+    _refused(lib, _gemm_tn(lib, {}, slab=N), name, "slab")
+    _refused(lib, _gemm_tn(lib, {}, slab=C.c_void_p((1 << 20) + 8)), name, "misaligned slab")
+    _refused(lib, _gemm_tn(lib, {}, d0=C.c_void_p(2 << 20)), name, "both defer_slab0 and defer_slab1")
+    _refused(lib, _gemm_tn(lib, {}, d1=C.c_void_p(2 << 20)), name, "both defer_slab0 and defer_slab1")
+    _refused(lib, _gemm_tn(lib, {}, d0=C.c_void_p((2 << 20) + 4), d1=C.c_void_p(3 << 20)), name, "misaligned defer slab")
+    _refused(lib, _gemm_tn(lib, {}, d0=C.c_void_p(2 << 20), d1=C.c_void_p(2 << 20)), name, "three buffers")
+    _refused(lib, _gemm_tn(lib, {}, d0=C.c_void_p(1 << 20), d1=C.c_void_p(2 << 20)), name, "three buffers")
+
+
+def test_gemm_tn_scratch_query_and_plan_entry_refuse_bad_arguments(lib):
+    good = (_lib.GemmTnCall * 2)(_gemm_tn_call(), _gemm_tn_call(M=4096, Ka=512, Nb=768))
+    assert lib.ishara_op_gemm_tn_scratch_bytes(good, 2) == 512 * (512 * 768 + 768) * 4          # the larger call's slab: 512 splits' worth
+    assert lib.ishara_op_gemm_tn_scratch_bytes(good, 1) == 512 * (128 * 128 + 128) * 4
+    assert lib.ishara_op_gemm_tn_scratch_bytes(None, 1) == -1 and lib.ishara_op_gemm_tn_scratch_bytes(good, 0) == -1
+    for kw in (dict(M=0), dict(Ka=0), dict(Nb=-1), dict(dtM=F16), dict(dtM=9)):
+        assert lib.ishara_op_gemm_tn_scratch_bytes((_lib.GemmTnCall * 1)(_gemm_tn_call(**kw)), 1) == -1, kw
+    route, kernel, splits, rps = C.c_char_p(), C.c_char_p(), C.c_int32(), C.c_int32()
+    k = _gemm_tn_call()
+    _refused(lib, lib.ishara_debug_gemm_tn_plan(None, C.byref(route), C.byref(kernel), C.byref(splits), C.byref(rps)), "ishara_debug_gemm_tn_plan", "null")
+    _refused(lib, lib.ishara_debug_gemm_tn_plan(C.byref(k), None, C.byref(kernel), C.byref(splits), C.byref(rps)), "ishara_debug_gemm_tn_plan", "null")
+    assert lib.ishara_debug_gemm_tn_plan(C.byref(k), C.byref(route), C.byref(kernel), C.byref(splits), C.byref(rps)) == 0
+    assert (route.value, kernel.value, splits.value, rps.value) == (b"TN_TR", b"gemm_tn_tr_kernel<0>", 2, 288)
+    k = _gemm_tn_call(dtA=F16)
+    assert lib.ishara_debug_gemm_tn_plan(C.byref(k), C.byref(route), C.byref(kernel), C.byref(splits), C.byref(rps)) == 0
+    assert (route.value, kernel.value, splits.value, rps.value) == (b"TN_REFUSED", b"", 0, 0) and b"ISHARA_F16" in lib.ishara_last_error()

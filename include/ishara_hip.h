@@ -146,6 +146,21 @@ int ishara_encoder_backward(ishara_model* m, const float* dy, int32_t B, float* 
 int ishara_encoder_forward_ex(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, const float* attn_bias,
                               const int32_t* key_len, ishara_stream s);
 int ishara_encoder_backward_ex(ishara_model* m, const float* dy, int32_t B, float* dx, const float* attn_bias, const int32_t* key_len, ishara_stream s);
+
+/* The padding mask of the ISHARA_FAMILY_TORCH_SQUEEZEFORMER encoder (RelativeMultiHeadAttention.forward(..., mask), attention.py:75-92, in its
+ * (batch, 1, time2) form).  input_len: device int32 [B], INPUT frames per clip (not keys: the layers run at three resolutions).  The library derives
+ * the keys of each resolution on the device with the reference's own arithmetic, clamped: L to [0, frames]; n2 = clamp((L >> 2) - 1, 0, T2) after the
+ * conv2d subsampling; n3 = clamp((n2 >> 1) - 1, 0, T3) in the reduced layers; nrec = clamp(2 * n3, 0, Trec) after recovery.  In every attention layer
+ * the keys at or past the clip's length at that layer's resolution are masked, for every query and head; nothing else changes (query rows past the
+ * length are computed, the convolution module, BatchNorm statistics, subsampling and time reduction see the padded frames as before).  Dropout acts on
+ * the masked probabilities.  A clip whose length is 0 at a resolution gets an all-zero attention output there and takes no part in that layer's
+ * attention backward (the reference's -1e9 fill would average the padding uniformly; zeros are this library's convention).
+ * input_len NULL: ishara_encoder_forward / _backward, bit for bit, on the same kernels.  The library keeps no pointer: pass the array again to the
+ * backward call; a backward call that disagrees with the last training forward about lengths is refused.  The other families are refused (they take
+ * frame_len of ishara_forward_ex, key_len of ishara_encoder_forward_ex); a misaligned input_len is refused before any GPU work. */
+int ishara_encoder_forward_lengths(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed,
+                                   const int32_t* input_len, ishara_stream s);
+int ishara_encoder_backward_lengths(ishara_model* m, const float* dy, int32_t B, float* dx, const int32_t* input_len, ishara_stream s);
 /* Gradient buckets for data parallelism (replaces what tf.distribute / nn.DataParallel do inside the reference's
  * train step: nb4 c1:63-75, integration.py:1058-1060).  The backward pass completes the flat gradient from its end
  * (head) towards its start (stem); ishara_grad_bucket(i) gives range i in completion order and
@@ -488,6 +503,19 @@ int ishara_op_relattn_fwd(int32_t dt, const void* q, const void* k, const void* 
 int ishara_op_relattn_bwd(int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
                           void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
                           int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate, void* scratch, ishara_stream s);
+/* The same pair with per-clip key lengths: key_len device int32 [B], keys at this T (clamped to [0, T]); the keys j >= key_len[b] are masked.
+ * route 0: the plan's choice (ishara_debug_relattn_kernel_name reports it), 1: the fp32 lane kernels.  Same checks and messages as the pair above,
+ * then a NULL or misaligned key_len and an unknown route.  A clip with key_len 0: o = 0, dq = 0, nothing of its dO in dk / dv / du / dvb / dposp;
+ * the dk / dv rows at keys >= key_len[b] are exact zeros.  ishara_debug_relattn_kernel_name: "" for a refused dtype / head dim / T; host only. */
+int64_t ishara_relattn_len_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh);
+int ishara_relattn_len_fwd(int32_t dt, const void* q, const void* k, const void* v, const float* pe, const float* Wpos, const float* u, const float* vb,
+                           void* o, float* lse, int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
+                           const int32_t* key_len, int32_t route, void* scratch, ishara_stream s);
+int ishara_relattn_len_bwd(int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
+                           void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
+                           int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
+                           const int32_t* key_len, int32_t route, void* scratch, ishara_stream s);
+const char* ishara_debug_relattn_kernel_name(int32_t dt, int32_t backward, int32_t T, int32_t dh, int32_t masked);
 /* DepthwiseConv2dSubsampling: x [B,T0,F] f32, w1, w2 [d,9], b1, b2 [d] f32 -> sub [B*T2, d*F2] (dt), T1 = (T0-3)/2+1, T2 = (T1-3)/2+1, same
  * for F; T0, F >= 7.  The first convolution's output stays in scratch for the backward call: dsub (dt) -> dw1, db1, dw2, db2 and dx [B,T0,F]
  * f32 (NULL: not computed). */

@@ -86,6 +86,8 @@ SIGNATURES = {
     "ishara_encoder_backward": (C.c_int, [_P, _P, _I32, _P, _P]),
     "ishara_encoder_forward_ex": (C.c_int, [_P, _P, _I32, _P, _I32, _U32, _P, _P, _P]),
     "ishara_encoder_backward_ex": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P]),
+    "ishara_encoder_forward_lengths": (C.c_int, [_P, _P, _I32, _P, _I32, _U32, _P, _P]),
+    "ishara_encoder_backward_lengths": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
     "ishara_encoder_output_frames": (_I32, [_P]),
     "ishara_loss_backward": (C.c_int, [_P, _P, _P, _I32, _P, _P, _F, _P]),
     "ishara_optimizer_step": (C.c_int, [_P, _F, _F, _P]),
@@ -156,6 +158,10 @@ SIGNATURES = {
     "ishara_op_relattn_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_op_relattn_fwd": (C.c_int, [_I32] + [_P] * 9 + [_I32, _I32, _I32, _I32, _U32, _U32, _F, _P, _P]),
     "ishara_op_relattn_bwd": (C.c_int, [_I32] + [_P] * 14 + [_I32, _I32, _I32, _I32, _U32, _U32, _F, _P, _P]),
+    "ishara_relattn_len_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "ishara_relattn_len_fwd": (C.c_int, [_I32] + [_P] * 9 + [_I32, _I32, _I32, _I32, _U32, _U32, _F, _P, _I32, _P, _P]),
+    "ishara_relattn_len_bwd": (C.c_int, [_I32] + [_P] * 14 + [_I32, _I32, _I32, _I32, _U32, _U32, _F, _P, _I32, _P, _P]),
+    "ishara_debug_relattn_kernel_name": (C.c_char_p, [_I32, _I32, _I32, _I32, _I32]),
     "ishara_op_r4_subsample_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_op_r4_subsample_fwd": (C.c_int, [_I32] + [_P] * 6 + [_I32, _I32, _I32, _I32, _P, _P]),
     "ishara_op_r4_subsample_bwd": (C.c_int, [_I32] + [_P] * 10 + [_I32, _I32, _I32, _I32, _P, _P]),

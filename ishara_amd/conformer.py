@@ -83,11 +83,12 @@ def default_state_dict(shapes: "OrderedDict[str, tuple]", seed: int) -> "Ordered
 
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, flat, enc, attn_bias=None, key_len=None):
+    def forward(ctx, x, flat, enc, attn_bias=None, key_len=None, input_len=None):
         ctx.enc = enc
         ctx.attn_bias, ctx.key_len = attn_bias, key_len      # the caller's mask arrays: the library keeps no pointer, backward() passes them again
         ctx.mask_versions = tuple(None if t is None else t._version for t in (attn_bias, key_len))      # (they never require grad: not save_for_backward's business)
-        y = enc._forward(x, training=enc.training, attn_bias=attn_bias, key_len=key_len)
+        ctx.input_len, ctx.input_len_version = input_len, None if input_len is None else input_len._version      # the Squeezeformer family's padding mask
+        y = enc._forward(x, training=enc.training, attn_bias=attn_bias, key_len=key_len, input_len=input_len)
         ctx.gen = enc._gen                # the library keeps the saved activations of its LAST training forward only
         return y
 
@@ -101,8 +102,11 @@ class _EncoderFn(torch.autograd.Function):
         if ctx.mask_versions != tuple(None if t is None else t._version for t in (ctx.attn_bias, ctx.key_len)):
             raise IsharaError("attn_mask / key_lengths were modified in place between the forward pass and backward(): the gradient would belong to "
                               "another mask than the output")
-        dx = enc._backward(dy, attn_bias=ctx.attn_bias, key_len=ctx.key_len)
-        return dx, enc.grads[:enc.n_train].clone(), None, None, None
+        if ctx.input_len is not None and ctx.input_len_version != ctx.input_len._version:
+            raise IsharaError("input_lengths were modified in place between the forward pass and backward(): the gradient would belong to "
+                              "another mask than the output")
+        dx = enc._backward(dy, attn_bias=ctx.attn_bias, key_len=ctx.key_len, input_len=ctx.input_len)
+        return dx, enc.grads[:enc.n_train].clone(), None, None, None, None
 
 
 class _TorchFamilyEncoder(Handle):
@@ -186,7 +190,7 @@ class _TorchFamilyEncoder(Handle):
         self._synced_version = self.flat._version
 
     # ------------------------------------------------------------------ forward / backward
-    def _forward(self, x: torch.Tensor, training: bool, seed: Optional[int] = None, attn_bias=None, key_len=None) -> torch.Tensor:
+    def _forward(self, x: torch.Tensor, training: bool, seed: Optional[int] = None, attn_bias=None, key_len=None, input_len=None) -> torch.Tensor:
         if x.dim() == 2:
             x = x[None]
         if x.shape[1:] != (self.T, self.F_in):
@@ -202,7 +206,12 @@ class _TorchFamilyEncoder(Handle):
         if seed is None:
             seed = (self._seed + 0x9E3779B1 * self._steps) & 0xFFFFFFFF
             self._steps += 1
-        if attn_bias is None and key_len is None:
+        if input_len is not None:      # SqueezeformerEncoder(mask_padding=True): input frames per clip
+            if tuple(input_len.shape) != (B,):
+                raise ValueError(f"input_lengths: expected [{B}] (one per clip of the batch), got {tuple(input_len.shape)}")
+            _lib.check(self._lib.ishara_encoder_forward_lengths(self._h, _lib.ptr(x), B, _lib.ptr(y), 1 if training else 0, C.c_uint32(seed), _lib.ptr(input_len),
+                                                                _stream()), "ishara_encoder_forward_lengths")
+        elif attn_bias is None and key_len is None:
             _lib.check(self._lib.ishara_encoder_forward(self._h, _lib.ptr(x), B, _lib.ptr(y), 1 if training else 0, C.c_uint32(seed), _stream()),
                        "ishara_encoder_forward")
         else:
@@ -213,10 +222,13 @@ class _TorchFamilyEncoder(Handle):
         self._last_x = x
         return y
 
-    def _backward(self, dy: torch.Tensor, attn_bias=None, key_len=None) -> torch.Tensor:
+    def _backward(self, dy: torch.Tensor, attn_bias=None, key_len=None, input_len=None) -> torch.Tensor:
         dy = dy.detach().to(self.device, torch.float32).contiguous()
         dx = torch.empty((dy.shape[0], self.T, self.F_in), dtype=torch.float32, device=self.device)
-        if attn_bias is None and key_len is None:
+        if input_len is not None:
+            _lib.check(self._lib.ishara_encoder_backward_lengths(self._h, _lib.ptr(dy), dy.shape[0], _lib.ptr(dx), _lib.ptr(input_len), _stream()),
+                       "ishara_encoder_backward_lengths")
+        elif attn_bias is None and key_len is None:
             _lib.check(self._lib.ishara_encoder_backward(self._h, _lib.ptr(dy), dy.shape[0], _lib.ptr(dx), _stream()), "ishara_encoder_backward")
         else:
             _lib.check(self._lib.ishara_encoder_backward_ex(self._h, _lib.ptr(dy), dy.shape[0], _lib.ptr(dx), _lib.ptr(attn_bias), _lib.ptr(key_len), _stream()),
@@ -226,17 +238,17 @@ class _TorchFamilyEncoder(Handle):
     def _default_state(self, seed):
         return default_state_dict(self.torch_shapes(), seed)
 
-    def _apply(self, x, attn_bias=None, key_len=None):
+    def _apply(self, x, attn_bias=None, key_len=None, input_len=None):
         """Training mode with grad enabled: differentiable through `_EncoderFn` — ONE live graph per encoder (the library keeps the
         saved activations and the dropout seed of its last training forward; a stale graph's backward raises).  Eval mode returns a
         constant (inference path, nothing saved): asking for a gradient w.r.t. the input there is an error, not a silent zero."""
         x = torch.as_tensor(x)
         if torch.is_grad_enabled() and self.training:
-            return _EncoderFn.apply(x.to(self.device), self.flat, self, attn_bias, key_len)
+            return _EncoderFn.apply(x.to(self.device), self.flat, self, attn_bias, key_len, input_len)
         if torch.is_grad_enabled() and x.requires_grad:
             raise IsharaError("eval-mode forward is not differentiable (no activations are saved): call enc.train() for gradients, or "
                               "pass x.detach() / use torch.no_grad() for inference")
-        return self._forward(x, training=self.training, attn_bias=attn_bias, key_len=key_len)
+        return self._forward(x, training=self.training, attn_bias=attn_bias, key_len=key_len, input_len=input_len)
 
 
 class ConformerEncoder(_TorchFamilyEncoder):

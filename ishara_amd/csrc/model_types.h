@@ -273,8 +273,9 @@ void r4_plan_workspace(ishara_model* m);
 int r4_bind(ishara_model* m);
 void r4_destroy(ishara_model* m);
 int r4_output_frames(const ishara_model* m);
-int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, hipStream_t st);
-int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStream_t st);
+// input_len: device int32 [B], input frames per clip (ishara_encoder_forward_lengths / _backward_lengths); nullptr: the unmasked pass
+int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, hipStream_t st, const int32_t* input_len = nullptr);
+int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStream_t st, const int32_t* input_len = nullptr);
 // its launch code, shared with the operator entry points (api_ops.hip ishara_op_relattn_* / ishara_op_r4_*)
 struct R4Dims { int T1, F1, T2, F2, T3, Fr, Kp; };      // frames / features after each 3x3 stride-2 convolution, the time-reduction conv's width and its padded K
 R4Dims r4_dims(int T0, int F, int d);
@@ -283,6 +284,20 @@ int launch_relattn_fwd(int dt, const void* q, const void* k, const void* v, cons
 int launch_relattn_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
                        const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
                        int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
+// the same with per-clip key lengths (relattn_len.hip): which kernels a call runs is stated once, by relattn_route; key_len nullptr is the
+// unmasked route, the two launches above
+enum { RELATTN_REFUSED = 0, RELATTN_LANE = 1, RELATTN_LANE_LEN = 2, RELATTN_MFMA_LEN = 3 };      // MFMA_LEN: MFMA forward (relattn_mfma.hip), lane backward
+struct RelAttnRoute { int kind = RELATTN_REFUSED; const char* why = ""; };
+RelAttnRoute relattn_route(int dt, int T, int dh, bool masked);
+const char* relattn_kernel_name(const RelAttnRoute& r, bool backward);
+int launch_relattn_len_fwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
+                           const int* key_len, bool force_lane, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
+int launch_relattn_len_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
+                           const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
+                           const int* key_len, bool force_lane, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
+int launch_relattn_len_fwd_mfma(const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
+                                const int* key_len, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
+int r4_stage_len_launch(const int* L, int* out, int B, int T0, int T2, int T3, int Trec, hipStream_t s);      // int32 [3][B]: keys at T2, T3, Trec
 int r4_subsample_fwd_launch(int dt, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y1, void* sub,
                             int B, int T0, int F, int d, int T1, int F1, int T2, int F2, hipStream_t s);
 int r4_subsample_bwd_launch(int dt, const void* dsub, const void* sub, const float* y1, const float* x, const float* w1, const float* w2, float* dz1,

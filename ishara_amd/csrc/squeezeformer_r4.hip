@@ -19,13 +19,14 @@ struct RelMHSA {
     DenseW Wq, Wk, Wv, Wpos, Wo; int u = -1, v = -1; Norm ln; uint32_t site_attn = 0, site_out = 0;
     Buf q, k, vv, o, lse, posp, r, mean, rstd, out;
 };
-struct R4Layer { RelMHSA mha; R5FFN ffn1; ConfConv conv; R5FFN ffn2; int T = 0; bool wrapped = false; Buf wrap_out; int pe = 0; };
+struct R4Layer { RelMHSA mha; R5FFN ffn1; ConfConv conv; R5FFN ffn2; int T = 0; bool wrapped = false; Buf wrap_out; int pe = 0; int stage = 0; };      // stage: 0 at T2, 1 reduced (T3), 2 recovered (Trec)
 struct R4State {
     int w1 = -1, b1 = -1, w2 = -1, b2 = -1, trw = -1, trb = -1;
     DenseW Win, Wred, Wrec;
     int T0 = 0, F = 0, T1 = 0, F1 = 0, T2 = 0, F2 = 0, T3 = 0, Fr = 0, Kp = 0, Trec = 0, Tout = 0;
     int reduce = 0, recover = 0; uint32_t site_in = 0;
     Buf y1, dz1, dwred, sub, h0, trpre, trout, red, rep, crop, rec, gskip, gwrap, dsub, dqb, dkb, dvb, dposp;
+    Buf nlen;      // int32 [3][Bmax]: keys per clip at T2 / T3 / Trec, derived from the caller's input lengths by the masked pass (r4_stage_len_launch)
     std::vector<R4Layer> layers;
     std::vector<int> pe_T; std::vector<Buf> pe32, pedt; std::vector<std::vector<float>> pe_host;
 };
@@ -634,12 +635,12 @@ void r4_build_graph(ishara_model* m) {
     S->Wred = m->dense_named("time_reduction_proj.weight", "time_reduction_proj.bias", S->Fr, d);
     S->Wrec = m->dense_named("time_recover_layer.weight", "time_recover_layer.bias", d, d);
     const float factor = c.half_step_residual ? 0.5f : 1.0f;
-    int Tl = S->T2;
+    int Tl = S->T2, stage = 0;
     for (int idx = 0; idx < L; ++idx) {
-        if (idx == S->reduce) Tl = S->T3;
-        if (idx == S->recover) Tl = S->Trec;
+        if (idx == S->reduce) { Tl = S->T3; stage = 1; }
+        if (idx == S->recover) { Tl = S->Trec; stage = 2; }
         R4Layer Ly;
-        Ly.T = Tl;
+        Ly.T = Tl; Ly.stage = stage;
         Ly.wrapped = idx >= S->reduce && idx < S->recover;
         const std::string s = "layers." + std::to_string(idx) + (Ly.wrapped ? ".module" : "") + ".sequential";
         const std::string a = s + ".0.module.attention";
@@ -735,6 +736,7 @@ void r4_plan_workspace(ishara_model* m) {
     m->Fc = m->f32(maxw); m->Ecol = m->f32(maxw); m->fac = m->f32(B);
     m->slab = m->f32(slab_floats(m, Mmax, B, Tmax, maxw, S->Kp));      // K at least Kp: the padded time_reduction_proj wgrad (r4_backward)
     m->delta = m->f32((size_t)B * m->H * Tmax);
+    S->nlen = m->alloc((size_t)3 * B * sizeof(int));
     m->ws_need = m->cur;
 }
 
@@ -762,16 +764,18 @@ static int r4_mhsa_fwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, co
     CK(gemm_fwd(m, a.Wpos, m->dt == DT_F32 ? (const void*)m->Wf(S->pe32[L.pe]) : (const void*)m->W(S->pedt[L.pe]), dt, m->Wf(a.posp), DT_F32, 2 * T - 1, OP_NONE, no, e0));
     const float scale = 1.0f / sqrtf((float)m->dh);
     CKP(m, "relattn_fwd", 4.0 * r.M * d * (double)dt_size(dt), 8.0 * r.B * m->H * (double)T * T * m->dh,
-        launch_relattn_fwd(dt, m->W(a.q), m->W(a.k), m->W(a.vv), m->Wf(a.posp), m->P(a.u), m->P(a.v), m->W(a.o), m->Wf(a.lse), r.B, m->H, T, m->dh, scale,
-                           dspec_attn(r, a.site_attn, m->cfg.dropout_rate), m->s));
+        launch_relattn_len_fwd(dt, m->W(a.q), m->W(a.k), m->W(a.vv), m->Wf(a.posp), m->P(a.u), m->P(a.v), m->W(a.o), m->Wf(a.lse), r.key_len, false, r.B, m->H, T, m->dh, scale,
+                               dspec_attn(r, a.site_attn, m->cfg.dropout_rate), m->s));      // r.key_len: this layer's keys per clip (nullptr: the unmasked route)
     EpiArgs ep; ep.resid = x; ep.drop = dspec(r, a.site_out, m->cfg.dropout_rate);
     CK(gemm_fwd(m, a.Wo, m->W(a.o), dt, m->W(a.r), dt, r.M, OP_NONE, no, ep));
     return r5_ln_fwd(m, r, m->W(a.r), a.ln, m->W(a.out), a.mean, a.rstd);
 }
 
-int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, hipStream_t st) {
+int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, hipStream_t st, const int32_t* input_len) {
     R4State* S = m->r4;
     m->s = st;
+    int* nlen = nullptr;      // masked pass: the keys per clip of the three attention resolutions, on the device
+    if (input_len) { nlen = m->W<int>(S->nlen); CK(r4_stage_len_launch(input_len, nlen, B, S->T0, S->T2, S->T3, S->Trec, m->s)); }
     const int dt = m->dt, d = m->d;
     OpArgs no;
     Run r{B, B * S->T2, training, seed};
@@ -805,7 +809,8 @@ int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t tra
         }
         m->T = Tl;
         Run rl{B, B * Tl, training, seed};
-        CK(r4_mhsa_fwd(m, S, L, rl, h));
+        Run ra = rl; ra.key_len = nlen ? nlen + L.stage * B : nullptr;      // only the attention sees the lengths
+        CK(r4_mhsa_fwd(m, S, L, ra, h));
         CK(r5_ffn_fwd(m, L.ffn1, rl, m->W(L.mha.out)));
         CK(confconv_fwd(m, L.conv, rl, m->W(L.ffn1.out)));
         CK(r5_ffn_fwd(m, L.ffn2, rl, m->W(L.conv.out)));
@@ -834,9 +839,9 @@ static int r4_mhsa_bwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, co
     CK(r4_fill_f32_launch(m->Wf(S->dposp), (size_t)(2 * T - 1) * d, 0.f, m->s));
     const float scale = 1.0f / sqrtf((float)m->dh);
     CKP(m, "relattn_bwd", 12.0 * r.M * d * (double)dt_size(dt), 24.0 * r.B * m->H * (double)T * T * m->dh,
-        launch_relattn_bwd(dt, m->W(a.q), m->W(a.k), m->W(a.vv), m->Wf(a.posp), m->P(a.u), m->P(a.v), m->W(a.o), m->W(m->t1), m->Wf(a.lse), m->Wf(m->delta),
-                           m->W(S->dqb), m->W(S->dkb), m->W(S->dvb), m->G(a.u), m->G(a.v), m->Wf(S->dposp), r.B, m->H, T, m->dh, scale,
-                           dspec_attn(r, a.site_attn, m->cfg.dropout_rate), m->s));
+        launch_relattn_len_bwd(dt, m->W(a.q), m->W(a.k), m->W(a.vv), m->Wf(a.posp), m->P(a.u), m->P(a.v), m->W(a.o), m->W(m->t1), m->Wf(a.lse), m->Wf(m->delta),
+                               m->W(S->dqb), m->W(S->dkb), m->W(S->dvb), m->G(a.u), m->G(a.v), m->Wf(S->dposp), r.key_len, false, r.B, m->H, T, m->dh, scale,
+                               dspec_attn(r, a.site_attn, m->cfg.dropout_rate), m->s));
     // pos_proj weight gradient: table^T . dposp (no bias, the table itself has no gradient)
     CK(gemm_wgrad(m, a.Wpos, m->dt == DT_F32 ? (const void*)m->Wf(S->pe32[L.pe]) : (const void*)m->W(S->pedt[L.pe]), dt, OP_NONE, no, m->Wf(S->dposp), DT_F32, OP_NONE, no, 2 * T - 1));
     // the three input projections: dx = dr + dq Wq^T + dk Wk^T + dv Wv^T
@@ -852,9 +857,11 @@ static int r4_mhsa_bwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, co
     return 0;
 }
 
-int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStream_t st) {
+int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStream_t st, const int32_t* input_len) {
     R4State* S = m->r4;
     m->s = st;
+    int* nlen = nullptr;      // derived again from the caller's array: the library keeps no pointer between the two calls
+    if (input_len) { nlen = m->W<int>(S->nlen); CK(r4_stage_len_launch(input_len, nlen, B, S->T0, S->T2, S->T3, S->Trec, m->s)); }
     const int dt = m->dt, d = m->d;
     OpArgs no; EpiArgs e0;
     CK(launch_fill_u32(m->grads, (size_t)m->n_train, 0u, m->s));
@@ -881,11 +888,12 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
         const int Tl = L.T;
         m->T = Tl;
         Run rl{B, B * Tl, 1, m->last_seed};
+        Run ra = rl; ra.key_len = nlen ? nlen + L.stage * B : nullptr;
         if (L.wrapped) HIP_CHECK_RET(hipMemcpyAsync(m->W(S->gwrap), g, (size_t)rl.M * d * dt_size(dt), hipMemcpyDeviceToDevice, m->s));   // the skip branch of the wrapper
         CK(r5_ffn_bwd(m, L.ffn2, rl, m->W(L.conv.out), g, gn)); SWAP();
         CK(confconv_bwd(m, L.conv, rl, m->W(L.ffn1.out), g, gn)); SWAP();
         CK(r5_ffn_bwd(m, L.ffn1, rl, m->W(L.mha.out), g, gn)); SWAP();
-        CK(r4_mhsa_bwd(m, S, L, rl, lin[idx], g, gn)); SWAP();
+        CK(r4_mhsa_bwd(m, S, L, ra, lin[idx], g, gn)); SWAP();
         if (L.wrapped) { CK(r4_rows_launch<4>(dt, m->W(S->gwrap), g, gn, B, Tl, Tl, d, m->s)); SWAP(); }
         if (idx == S->recover) {           // g = gradient of rec = Linear(rep) + crop(recover_src)
             CK(r4_rows_launch<3>(dt, g, nullptr, m->W(S->gskip), B, S->T2, S->Trec, d, m->s));        // into the longer pre-reduction sequence
@@ -916,4 +924,37 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
                                B, S->T0, S->F, d, S->T1, S->F1, S->T2, S->F2, m->s));
     if (!m->bucket_ev.empty()) HIP_CHECK_RET(hipEventRecord(m->bucket_ev.back(), m->s));
     return 0;
+}
+
+// ------------------------------------------------------------------ the call with per-clip input lengths
+// ishara_encoder_forward_lengths / _backward_lengths: the padding mask of this family.  input_len device int32 [B], input frames per clip; the keys
+// of every attention layer at or past the clip's length AT THAT LAYER'S RESOLUTION are masked (r4_stage_len_launch), nothing else changes.
+// input_len NULL is ishara_encoder_forward / _backward, on the same kernels.  Every check is made before any GPU work
+static int r4_lengths_refused(const char* me, const ishara_model* m, const int32_t* input_len) {
+    if (m->family == ISHARA_FAMILY_TORCH_CONFORMER) { ishara_set_error("%s: input lengths are served by ISHARA_FAMILY_TORCH_SQUEEZEFORMER only: the Conformer encoder takes key_len of ishara_encoder_forward_ex", me); return -1; }
+    if (m->family != ISHARA_FAMILY_TORCH_SQUEEZEFORMER) { ishara_set_error("%s: input lengths are served by ISHARA_FAMILY_TORCH_SQUEEZEFORMER only: the Keras hybrid takes frame_len of ishara_forward_ex", me); return -1; }
+    if (m->dt == DT_F16) { ishara_set_error("%s: ISHARA_F16 is refused: the torch Squeezeformer family has no fp16 kernels", me); return -1; }
+    if (input_len && (uintptr_t)input_len % 4) { ishara_set_error("%s: misaligned input_len: an int32 array", me); return -1; }
+    return 0;
+}
+extern "C" int ishara_encoder_forward_lengths(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, const int32_t* input_len, ishara_stream st) {
+    const char* me = "ishara_encoder_forward_lengths";
+    if (r4_lengths_refused(me, m, input_len)) return -1;
+    if (!m->ws) { ishara_set_error("%s: model is not bound", me); return -1; }
+    if (B <= 0 || B > m->Bmax) { ishara_set_error("%s: batch %d outside 1..%d", me, B, m->Bmax); return -1; }
+    m->last_masked = input_len ? 1 : 0;
+    return r4_forward(m, x, B, y, training, seed, (hipStream_t)st, input_len);
+}
+extern "C" int ishara_encoder_backward_lengths(ishara_model* m, const float* dy, int32_t B, float* dx, const int32_t* input_len, ishara_stream st) {
+    const char* me = "ishara_encoder_backward_lengths";
+    if (r4_lengths_refused(me, m, input_len)) return -1;
+    if (!m->ws || !m->grads) { ishara_set_error("%s: model is not bound (grads required)", me); return -1; }
+    if (B != m->lastB || !m->last_training) { ishara_set_error("%s: call ishara_encoder_forward(training=1) with the same batch first", me); return -1; }
+    const bool masked = input_len != nullptr;
+    if (masked != (m->last_masked != 0)) {
+        ishara_set_error("%s: the last training forward pass was %s an attention mask and this call is %s one: pass the same input_len array again", me,
+                         m->last_masked ? "given" : "not given", masked ? "given" : "not given");
+        return -1;
+    }
+    return r4_backward(m, dy, B, dx, (hipStream_t)st, input_len);
 }

@@ -98,9 +98,36 @@ class SqueezeformerEncoder(_TorchFamilyEncoder):
                 out = out * 2
         return out
 
-    def __call__(self, inputs, input_lengths=None):
-        """SqueezeformerEncoder.forward(inputs, input_lengths) — encoder.py:135-166: (outputs [B, T_out, encoder_dim], output_lengths)."""
-        y = self._apply(inputs)
+    def stage_lengths(self, input_lengths: torch.Tensor):
+        """Keys per clip at the three attention resolutions (after the conv2d subsampling, in the reduced layers, after recovery), as the
+        library derives them on the device for `mask_padding=True`: the arithmetic of `output_lengths`, clamped to the planned lengths."""
+        T2 = ((self.T - 3) // 2 + 1 - 3) // 2 + 1
+        T3 = (T2 - 3) // 2 + 1
+        n2 = ((input_lengths.clamp(0, self.T) >> 2) - 1).clamp(0, T2)
+        n3 = ((n2 >> 1) - 1).clamp(0, T3)
+        return n2, n3, (2 * n3).clamp(0, 2 * T3)
+
+    def _input_len(self, input_lengths):
+        """int32 [B] on the device; a device int32 tensor is used where it is, anything else is converted and copied (no host read of device memory)"""
+        if input_lengths is None:
+            raise ValueError("mask_padding=True needs input_lengths: [B] integers, input frames per clip")
+        k = torch.as_tensor(input_lengths)
+        if k.dim() != 1 or k.dtype == torch.bool or k.is_floating_point() or k.is_complex():
+            raise ValueError(f"input_lengths: expected [B] integers, got shape {tuple(k.shape)} of {k.dtype}")
+        return k.to(self.device, torch.int32).contiguous()
+
+    def __call__(self, inputs, input_lengths=None, *, mask_padding=False):
+        """SqueezeformerEncoder.forward(inputs, input_lengths) — encoder.py:135-166: (outputs [B, T_out, encoder_dim], output_lengths).
+
+        `mask_padding=False`: the lengths only give `output_lengths`, as in the reference, whose encoder never builds the attention mask.
+        `mask_padding=True`: the padding mask of RelativeMultiHeadAttention.forward(..., mask) (attention.py:75-92, the `(batch, 1, time2)` form) built
+        from `input_lengths` ([B] integers, input frames; a device int32 tensor is used in place): in every attention layer the keys at or past the
+        clip's length at that layer's resolution (`stage_lengths`) are masked for every query and head.  Only attention keys: query rows past the
+        length are still computed, the convolution module, BatchNorm statistics, subsampling and time reduction see the padded frames as before.
+        Works in eval and in training mode (dropout acts on the masked probabilities) and is differentiable like the plain call.  A clip with no
+        key left at a resolution gets an all-zero attention output there (the reference's -1e9 fill would average its padding uniformly; zeros
+        are this library's convention).  The returned `output_lengths` are the same either way."""
+        y = self._apply(inputs, input_len=self._input_len(input_lengths)) if mask_padding else self._apply(inputs)
         if input_lengths is None:
             return y
         return y, self.output_lengths(torch.as_tensor(input_lengths).clone())
@@ -203,8 +230,9 @@ class Squeezeformer:
         elif strict:
             raise KeyError("load_state_dict: missing fc.weight")
 
-    def __call__(self, inputs, input_lengths):
-        enc_out, out_len = self.encoder(inputs, input_lengths)
+    def __call__(self, inputs, input_lengths, *, mask_padding=False):
+        """`mask_padding=True`: the encoder masks the padded attention keys (SqueezeformerEncoder.__call__); the head is per-frame and unchanged."""
+        enc_out, out_len = self.encoder(inputs, input_lengths, mask_padding=mask_padding)
         if torch.is_grad_enabled() and self.training:
             return _FcLogSoftmaxFn.apply(enc_out, self.fc_weight, self.encoder._lib), out_len
         with torch.no_grad():

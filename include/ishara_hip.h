@@ -257,6 +257,20 @@ int ishara_ctc_beam_decode(const float* logits, int32_t B, int32_t T, int32_t C,
 int ishara_ctc_beam_decode_ex(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
                               const float* lm, float alpha, float beta, void* workspace,
                               int32_t* out_idx, int32_t* out_len, float* out_score, const int32_t* frame_len, ishara_stream s);
+/* The same search with the LM as a deterministic automaton of S states (a character n-gram with backoff: ishara_amd/ctc_lm.py), both
+ * tables on the device: lm_logp [S,C] fp32, row s = the natural-log probability of every next event in state s (column c != blank: next
+ * class c; column blank: end of phrase), and lm_next [S,C] int32, the state after class c (column blank unused).  Every beam carries its
+ * state from start_state: an extension by c adds alpha * lm_logp[state][c] and moves to lm_next[state][c], the final term is
+ * alpha * lm_logp[state][blank].  The bigram table is the case S = C, start_state = blank, lm_next[s][c] = c, lm_logp = lm, and gives
+ * ishara_ctc_beam_decode_ex's bits.  Limits, outputs, workspace, total order and frame_len (may be NULL: every clip has T frames) as
+ * for ishara_ctc_beam_decode_ex; in addition 1 <= S <= 2^22, 0 <= start_state < S, both tables non-NULL and 16-byte aligned; anything
+ * else is refused with a message before any HIP call.  The tables cannot be read on the host: an lm_next value outside [0, S) is read as
+ * state 0 and is never used as an index.  One kernel (the rows of the beams' states are fetched once per frame, under the frame's merge
+ * detection), graph-capturable, no atomics, bit-identical from run to run; B = 0 is a no-op. */
+int ishara_ctc_beam_decode_lm(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
+                              const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state, float alpha, float beta,
+                              void* workspace, int32_t* out_idx, int32_t* out_len, float* out_score,
+                              const int32_t* frame_len /* may be NULL */, ishara_stream s);
 
 /* CTC forced alignment (Viterbi) of known labels; the semantics of ishara_amd/ctc_align.py.  logits [B,T,C] fp32, labels [B,L] int64 padded
  * with blank (the label of a row ends at its first blank).  The path maximises the sum of the raw logits along it, carried in fp64, ties

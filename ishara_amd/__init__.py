@@ -8,5 +8,6 @@ from .conformer import ConformerEncoder  # noqa: F401  (torch family: conformer/
 from .squeezeformer import Squeezeformer, SqueezeformerEncoder  # noqa: F401  (torch family: squeezeformer/encoder.py, model.py)
 from .tflite_batch import BatchedTFLiteModel  # noqa: F401  (batched raw-clip inference + device test-set scoring)
 from .ctc_beam import CharBigramLM, prefix_beam_search  # noqa: F401  (CTC prefix beam search: host reference, bigram LM)
+from .ctc_lm import CharNGramLM, LMAutomaton  # noqa: F401  (character n-gram LMs as automata, for the beam search's lm=)
 from . import ctc_align  # noqa: F401  (forced alignment: the module, callable as ctc_align(logits, labels, lengths))
 from .ctc import ctc_beam_decode, ctc_greedy_decode, ctc_loss  # noqa: F401  (CTC with per-clip frame counts)

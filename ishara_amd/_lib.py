@@ -107,6 +107,7 @@ SIGNATURES = {
     "ishara_ctc_beam_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_ctc_beam_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _F, _P, _P, _P, _P, _P]),
     "ishara_ctc_beam_decode_ex": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "ishara_ctc_beam_decode_lm": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _F, _F, _P, _P, _P, _P, _P, _P]),
     "ishara_ctc_align_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_ctc_align": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "ishara_ctc_align_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),

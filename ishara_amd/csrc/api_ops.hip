@@ -132,9 +132,9 @@ extern "C" int64_t ishara_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t
     if (B < 0 || T < 1 || T > 4096 || beam_width < 1 || beam_width > 32) return -1;
     return (int64_t)B * (int64_t)ctc_beam_workspace_words(T, beam_width) * 4;
 }
-static int ctc_beam_checked(const char* me, const float* logits, int B, int T, int C, int blank, int beam_width, int nbest, const float* lm,
-                            float alpha, float beta, void* workspace, int* out_idx, int* out_len, float* out_score, bool ex, const int* frame_len,
-                            hipStream_t s) {
+// the limits every beam entry point shares; -1: refused, the message is set
+static int ctc_beam_args_check(const char* me, const float* logits, int B, int T, int C, int blank, int beam_width, int nbest, float alpha, float beta,
+                             void* workspace, int* out_idx, int* out_len, float* out_score, const int* frame_len) {
     if (C < 2 || C > 64) { ishara_set_error("%s: C=%d unsupported (2..64: one lane per class)", me, C); return -1; }
     if (blank < 0 || blank >= C) { ishara_set_error("%s: blank %d outside 0..%d", me, blank, C - 1); return -1; }
     if (beam_width < 1 || beam_width > 32) { ishara_set_error("%s: beam_width %d unsupported (1..32)", me, beam_width); return -1; }
@@ -144,6 +144,12 @@ static int ctc_beam_checked(const char* me, const float* logits, int B, int T, i
     if (B > 0 && (!logits || !workspace || !out_idx || !out_len || !out_score)) { ishara_set_error("%s: null argument", me); return -1; }
     if ((uintptr_t)workspace % 4) { ishara_set_error("%s: workspace must be 4-byte aligned", me); return -1; }
     if (len_misaligned(me, "frame_len", frame_len)) return -1;
+    return 0;
+}
+static int ctc_beam_checked(const char* me, const float* logits, int B, int T, int C, int blank, int beam_width, int nbest, const float* lm,
+                            float alpha, float beta, void* workspace, int* out_idx, int* out_len, float* out_score, bool ex, const int* frame_len,
+                            hipStream_t s) {
+    if (ctc_beam_args_check(me, logits, B, T, C, blank, beam_width, nbest, alpha, beta, workspace, out_idx, out_len, out_score, frame_len)) return -1;
     return ex ? launch_ctc_beam_len(logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len, out_score, frame_len, s)
               : launch_ctc_beam(logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len, out_score, s);
 }
@@ -158,6 +164,19 @@ extern "C" int ishara_ctc_beam_decode_ex(const float* logits, int32_t B, int32_t
                                          int32_t* out_idx, int32_t* out_len, float* out_score, const int32_t* frame_len, ishara_stream s) {
     return ctc_beam_checked("ishara_ctc_beam_decode_ex", logits, B, T, C, blank, beam_width, nbest, lm, alpha, beta, workspace, out_idx, out_len,
                             out_score, true, frame_len, (hipStream_t)s);
+}
+extern "C" int ishara_ctc_beam_decode_lm(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank, int32_t beam_width, int32_t nbest,
+                                         const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state, float alpha, float beta,
+                                         void* workspace, int32_t* out_idx, int32_t* out_len, float* out_score, const int32_t* frame_len,
+                                         ishara_stream s) {
+    const char* me = "ishara_ctc_beam_decode_lm";
+    if (ctc_beam_args_check(me, logits, B, T, C, blank, beam_width, nbest, alpha, beta, workspace, out_idx, out_len, out_score, frame_len)) return -1;
+    if (S < 1 || S > (1 << 22)) { ishara_set_error("%s: S=%d states unsupported (1..2^22)", me, S); return -1; }
+    if (start_state < 0 || start_state >= S) { ishara_set_error("%s: start_state %d outside 0..%d", me, start_state, S - 1); return -1; }
+    if (B > 0 && (!lm_logp || !lm_next)) { ishara_set_error("%s: null lm_logp / lm_next (the table entry points take a NULL lm)", me); return -1; }
+    if (((uintptr_t)lm_logp | (uintptr_t)lm_next) % 16) { ishara_set_error("%s: lm_logp and lm_next must be 16-byte aligned", me); return -1; }
+    return launch_ctc_beam_lm(logits, B, T, C, blank, beam_width, nbest, lm_logp, lm_next, S, start_state, alpha, beta, workspace, out_idx, out_len,
+                              out_score, frame_len, (hipStream_t)s);
 }
 // CTC forced alignment: refused before any HIP call, as the loss is
 extern "C" int64_t ishara_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t L) {

@@ -15,6 +15,14 @@
 //      beam values stay small; the device scores agree with the fp64 host reference within 1e-3 at T = 384 (tests/test_ctc_beam_gpu.py).
 // The log-softmax of up to BM_CHUNK frames at a time is staged in LDS from logits loaded one chunk ahead; the LM table is staged once.
 // No atomics: runs are bit-reproducible.
+//
+// AUT (ishara_ctc_beam_decode_lm): the LM is a deterministic automaton, logp [S, C] f32 and next [S, C] i32 in global memory, and every beam
+// carries its state.  The 16 KB of LDS that hold the [C, C] table hold instead, per beam, the logp row and the next row of its state (32 x 64
+// f32 + 32 x 64 i32).  Wave w owns the rows of beams w, w + NW, ... (the beams whose candidates it forms in 2.): at the top of a frame it
+// issues the two coalesced row loads of each of its beams into registers, the chunk's log-softmax and merge detection (1.) run under them,
+// and the rows are written to LDS just before the barrier that ends 1.  A beam that stayed at its rank with its prefix keeps its rows (no
+// load).  The extension term is formed by bm_ext_bonus exactly as for the table, so a bigram automaton gives the table kernel's bits; the
+// table instantiations compile none of this (every statement of it is under `if constexpr (AUT)`).
 #include "kernels.h"
 
 #define BM_MAXC 64
@@ -24,6 +32,8 @@
 #define BM_PRE 4                   // frames of logits per wave loaded ahead (the chunk is min(BM_CHUNK, BM_PRE * NW) frames)
 #define BM_NEG (-__builtin_inff())
 #define BM_HASH_MUL 0x9E3779B97F4A7C15ull
+#define BM_LMPER (BM_MAXW / BM_MAXNW)                       // AUT: beams per wave at most (the launch has NW >= W or NW = BM_MAXNW)
+#define BM_LMHELD ((int)0x80000000)                         // AUT: bit 31 of BmState.lmstate
 
 typedef unsigned long long u64;
 
@@ -85,16 +95,19 @@ struct BmState {
     int last[BM_MAXW], len[BM_MAXW], node[BM_MAXW], par[BM_MAXW], msrc[BM_MAXW];   // par: trie node of the prefix without its last class
     u64 h[BM_MAXW], hp[BM_MAXW];                            // hash of the prefix / of the prefix without its last class
     int nb;
+    int lmstate[BM_MAXW];                                   // AUT only: bits 0..22 the prefix's LM state, always in [0, S); bit 31 (BM_LMHELD):
+                                                            // nothing to fetch (its rows are already in LDS, or rank without a beam)
 };
 
 // VL (ishara_ctc_beam_decode_ex): the clip has Tn = frame_len[b] frames of the buffer's Ts; Ts stays the stride of the logits, of the trie
 // workspace and of out_idx (padded with -1 to Ts).  A frame_len[b] outside [1, Ts] is no clip: every n-best slot len -1, score -inf.
-template <bool VL>
+template <bool VL, bool AUT>
 __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* __restrict__ logits, int Ts, int C, int blank, int W, int nbest,
                                                                   const float* __restrict__ lm, float alpha, float beta,
                                                                   int* __restrict__ ws, int* __restrict__ out_idx, int* __restrict__ out_len,
-                                                                  float* __restrict__ out_score, const int* __restrict__ frame_len) {
-    __shared__ float s_lm[BM_MAXC * BM_MAXC];
+                                                                  float* __restrict__ out_score, const int* __restrict__ frame_len,
+                                                                  const int* __restrict__ lm_next, int nstates, int start_state) {
+    __shared__ float s_lm[BM_MAXC * BM_MAXC];               // AUT: rows 0..31 the beams' logp rows, rows 32..63 their next rows (int bits)
     __shared__ float s_lp[BM_CHUNK][BM_MAXC];
     __shared__ BmState s_st[2];
     __shared__ float s_cpnb[BM_MAXW][BM_MAXC];              // pnb' of every candidate (lane b: the same-prefix candidate)
@@ -110,7 +123,7 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
     const float* x = logits + (size_t)b * Ts * C;
     int* trie = ws + (size_t)b * ctc_beam_workspace_words(Ts, W);
 
-    if (use_lm)
+    if (!AUT && use_lm)
         for (int k = tid; k < C * C; k += blockDim.x) s_lm[(k / C) * BM_MAXC + k % C] = lm[k];
     for (int k = tid; k < BM_MAXW * BM_MAXC; k += blockDim.x) (&s_stamp[0][0])[k] = 0;
     if (tid < BM_MAXW) {
@@ -126,6 +139,9 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
         s.h[tid] = 0;
         s.hp[tid] = 0;
         if (tid == 0) s.nb = 1;
+        if constexpr (AUT) {
+            s.lmstate[tid] = tid == 0 ? start_state : BM_LMHELD;
+        }
     }
     if (tid == 0) trie[0] = 0;
     // wave 0 keeps the clip's offsets and the trie size in registers (every lane the same value)
@@ -147,6 +163,25 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
 
     for (int t = 0; t < Tn; ++t) {
         const int f = t % chunk;
+        // AUT: the rows of this wave's beams, issued as soon as the beams are known (the barrier that ended the last frame) and waited
+        // for only where they are written to LDS, after 1.  One LDS read per beam stands between that barrier and the loads: the state
+        // word says by itself whether to fetch.
+        float lm_row[BM_LMPER];
+        int lm_nxt[BM_LMPER], lm_st[BM_LMPER];
+        if constexpr (AUT) {
+            if (use_lm) {
+#pragma unroll
+                for (int k = 0; k < BM_LMPER; ++k) lm_st[k] = w + k * nw < BM_MAXW ? s_st[cur].lmstate[w + k * nw] : BM_LMHELD;
+#pragma unroll
+                for (int k = 0; k < BM_LMPER; ++k) {
+                    if (lm_st[k] >= 0 && lane < C) {
+                        const size_t o = (size_t)lm_st[k] * C + lane;
+                        lm_row[k] = lm[o];
+                        lm_nxt[k] = lm_next[o];
+                    }
+                }
+            }
+        }
         if (f == 0) {                                       // log-softmax of this chunk, one frame per wave at a time
 #pragma unroll
             for (int k = 0; k < BM_PRE; ++k) {
@@ -184,6 +219,18 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
                 }
             }
         }
+        if constexpr (AUT) {
+            if (use_lm) {
+#pragma unroll
+                for (int k = 0; k < BM_LMPER; ++k) {
+                    const int i = w + k * nw;
+                    if (lm_st[k] >= 0 && lane < C) {
+                        s_lm[i * BM_MAXC + lane] = lm_row[k];
+                        s_lm[(BM_MAXW + i) * BM_MAXC + lane] = __int_as_float(lm_nxt[k]);
+                    }
+                }
+            }
+        }
         __syncthreads();
         // 2. candidates and the wave's running top-32
         const float lpc = s_lp[f][lane];
@@ -208,7 +255,8 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
                 key = sc > BM_NEG ? bm_key(sc, 0, i, 0) : 0;        // no alignment reaches it: not a candidate
             } else if (lane < C && s_stamp[i][lane] != t + 1) {
                 const float epnb = __fadd_rn(lane == last ? pb : tot, lpc);
-                const float eb = bm_ext_bonus(bonus, use_lm ? s_lm[(last >= 0 ? last : blank) * BM_MAXC + lane] : 0.0f, alpha, beta, use_lm);
+                const int lmr = AUT ? i : (last >= 0 ? last : blank);      // the LDS row of the beam's LM context
+                const float eb = bm_ext_bonus(bonus, use_lm ? s_lm[lmr * BM_MAXC + lane] : 0.0f, alpha, beta, use_lm);
                 s_cpnb[i][lane] = epnb;
                 const float sc = __fadd_rn(epnb, eb);
                 key = sc > BM_NEG ? bm_key(sc, 1, i, lane) : 0;
@@ -241,8 +289,19 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
             float npb = BM_NEG, npnb = BM_NEG, nbonus = 0.0f;
             int nlast = -1, nlen = 0, nnode = 0, npar = 0;
             u64 nh = 0, nhp = 0;
+            int nstate = BM_LMHELD;
             if (valid) {
                 const int slast = S.last[src];
+                const int lmr = AUT ? src : (slast >= 0 ? slast : blank);
+                if constexpr (AUT) {
+                    if (kind == 0) {
+                        nstate = S.lmstate[src] & ~BM_LMHELD;
+                        if (src == lane) nstate |= BM_LMHELD;               // same prefix at the same rank: its rows are in place
+                    } else if (use_lm) {
+                        nstate = __float_as_int(s_lm[(BM_MAXW + src) * BM_MAXC + c]);
+                        if ((unsigned)nstate >= (unsigned)nstates) nstate = 0;     // never an index: the table is not readable on the host
+                    }
+                }
                 if (kind == 0) {
                     npb = s_spb[src];
                     npnb = s_cpnb[src][blank];
@@ -255,7 +314,7 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
                     nhp = S.hp[src];
                 } else {
                     npnb = s_cpnb[src][c];
-                    nbonus = bm_ext_bonus(S.bonus[src], use_lm ? s_lm[(slast >= 0 ? slast : blank) * BM_MAXC + c] : 0.0f, alpha, beta, use_lm);
+                    nbonus = bm_ext_bonus(S.bonus[src], use_lm ? s_lm[lmr * BM_MAXC + c] : 0.0f, alpha, beta, use_lm);
                     nlast = c;
                     nlen = S.len[src] + 1;
                     npar = S.node[src];
@@ -287,6 +346,9 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
                 N.msrc[lane] = -1;
                 N.h[lane] = nh;
                 N.hp[lane] = nhp;
+                if constexpr (AUT) {
+                    N.lmstate[lane] = nstate;
+                }
             }
             const int nnb = __popcll(__ballot(valid));
             if (lane == 0) N.nb = nnb;
@@ -304,7 +366,10 @@ __global__ __launch_bounds__(BM_MAXNW * WAVE) void ctc_beam_kernel(const float* 
         if (lane < nb && !(VL && Tn == 0)) {
             const int last = S.last[lane];
             fin = __fadd_rn(bm_lse(S.pb[lane], S.pnb[lane]), S.bonus[lane]);
-            if (use_lm) fin = __fadd_rn(fin, __fmul_rn(alpha, s_lm[(last >= 0 ? last : blank) * BM_MAXC + blank]));
+            float eos = 0.0f;
+            if constexpr (AUT) { if (use_lm) eos = lm[(size_t)(S.lmstate[lane] & ~BM_LMHELD) * C + blank]; }      // the final set's rows were never staged
+            else if (use_lm) eos = s_lm[(last >= 0 ? last : blank) * BM_MAXC + blank];
+            if (use_lm) fin = __fadd_rn(fin, __fmul_rn(alpha, eos));
             key = ((u64)bm_ord(fin) << 32) | (u64)(0xFFFFFFFFu - (uint32_t)lane);
         }
         key = bm_sort64(key, lane);
@@ -343,8 +408,8 @@ int launch_ctc_beam(const float* logits, int B, int T, int C, int blank, int W, 
     if (B == 0) return 0;
     int nw = 1;
     while (nw < W && nw < BM_MAXNW) nw <<= 1;
-    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm, alpha, beta, (int*)ws, out_idx,
-                       out_len, out_score, (const int*)nullptr);
+    hipLaunchKernelGGL((ctc_beam_kernel<false, false>), dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm, alpha, beta, (int*)ws,
+                       out_idx, out_len, out_score, (const int*)nullptr, (const int*)nullptr, 0, 0);
     return launch_rc();
 }
 int launch_ctc_beam_len(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm, float alpha, float beta,
@@ -352,7 +417,22 @@ int launch_ctc_beam_len(const float* logits, int B, int T, int C, int blank, int
     if (B == 0) return 0;
     int nw = 1;
     while (nw < W && nw < BM_MAXNW) nw <<= 1;
-    hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm, alpha, beta, (int*)ws, out_idx,
-                       out_len, out_score, frame_len);
+    hipLaunchKernelGGL((ctc_beam_kernel<true, false>), dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm, alpha, beta, (int*)ws,
+                       out_idx, out_len, out_score, frame_len, (const int*)nullptr, 0, 0);
+    return launch_rc();
+}
+// the automaton LM (AUT): lm_logp / lm_next [S, C]; frame_len may be null (every clip has T frames)
+int launch_ctc_beam_lm(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm_logp, const int* lm_next, int S,
+                       int start_state, float alpha, float beta, void* ws, int* out_idx, int* out_len, float* out_score, const int* frame_len,
+                       hipStream_t s) {
+    if (B == 0) return 0;
+    int nw = 1;
+    while (nw < W && nw < BM_MAXNW) nw <<= 1;
+    if (frame_len)
+        hipLaunchKernelGGL((ctc_beam_kernel<true, true>), dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm_logp, alpha, beta,
+                           (int*)ws, out_idx, out_len, out_score, frame_len, lm_next, S, start_state);
+    else
+        hipLaunchKernelGGL((ctc_beam_kernel<false, true>), dim3(B), dim3(nw * WAVE), 0, s, logits, T, C, blank, W, nbest, lm_logp, alpha, beta,
+                           (int*)ws, out_idx, out_len, out_score, (const int*)nullptr, lm_next, S, start_state);
     return launch_rc();
 }

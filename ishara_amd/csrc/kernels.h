@@ -374,6 +374,10 @@ int launch_ctc_beam(const float* logits, int B, int T, int C, int blank, int W, 
                     void* ws, int* out_idx, int* out_len, float* out_score, hipStream_t s);
 int launch_ctc_beam_len(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm, float alpha, float beta,
                         void* ws, int* out_idx, int* out_len, float* out_score, const int* frame_len, hipStream_t s);
+// the LM as an automaton: lm_logp f32 / lm_next i32 [S,C] on the device, one state per beam; frame_len may be null
+int launch_ctc_beam_lm(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm_logp, const int* lm_next, int S,
+                       int start_state, float alpha, float beta, void* ws, int* out_idx, int* out_len, float* out_score, const int* frame_len,
+                       hipStream_t s);
 // ---- CTC forced alignment (ctc_align.hip): the best path of a known label, per-symbol frame spans and confidences (ishara_amd/ctc_align.py)
 bool ctc_align_bp_in_lds(int T, int L);                          // the back-pointers (T * 128 bytes) fit in LDS: the workspace is not used
 size_t ctc_align_workspace_bytes(int B, int T, int L);

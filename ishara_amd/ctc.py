@@ -157,7 +157,8 @@ def ctc_greedy_decode(logits, lengths=None, blank: Optional[int] = None) -> List
 def ctc_beam_decode(logits, lengths=None, beam_width: int = 16, nbest: int = 1, lm=None, alpha: float = 0.0, beta: float = 0.0,
                     workspace: Optional[torch.Tensor] = None) -> List[List[Tuple[np.ndarray, float]]]:
     """CTC prefix beam search (ishara_amd/ctc_beam.py semantics, blank = C - 1) of every clip's first `lengths[b]` frames -> per clip a
-    list of (indices int64, score), best first: what `Model.beam_decode` returns.  `workspace`: a uint8 device tensor to reuse, if large enough."""
+    list of (indices int64, score), best first: what `Model.beam_decode` returns.  lm: None, a [C, C] table / CharBigramLM, or a
+    CharNGramLM / LMAutomaton (ctc_lm.py, launched as ishara_ctc_beam_decode_lm).  `workspace`: a uint8 device tensor to reuse, if large enough."""
     from . import ctc_beam
     x, fl = _ragged(logits, lengths)
     B, T, Cc = x.shape

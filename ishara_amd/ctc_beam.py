@@ -20,6 +20,10 @@ weights alpha (LM) and beta (bonus per emitted character).  The LM term is used 
   source-beam rank; then the lower class index.  After the last frame every beam gets alpha * lm[last][b] (end of phrase); the beams are
   ranked again by (higher final score, lower beam rank) and the first nbest are returned.
 
+lm may also be an LMAutomaton or a CharNGramLM (ctc_lm.py; the device side is `ishara_ctc_beam_decode_lm`): every beam then carries an LM
+state from `start`; an extension by c adds alpha * logp[state][c] and moves to next[state][c], and the final term is
+alpha * logp[state][b].  The table is the automaton whose state is the last character, and everything else above is unchanged.
+
 Unlike `decode_phrase`, which never emits the final run of frames (the reference's quirk, kept in the greedy path), the beam search uses
 every frame: on logits that end in blank frames the two agree on confident inputs.
 """
@@ -67,6 +71,18 @@ def _lm_table(lm, C: int) -> Optional[np.ndarray]:
     return t
 
 
+def _lm_rows(lm, C: int, b: int):
+    """(logp [S, C] fp64, next [S, C] or None, start): an LMAutomaton or a CharNGramLM (ctc_lm.py) as they are, a table as the automaton
+    whose state is the last character (next = None stands for next[s, c] = c; start = blank).  (None, None, b) without an LM."""
+    from .ctc_lm import as_automaton
+    aut = as_automaton(lm)
+    if aut is None:
+        return _lm_table(lm, C), None, b
+    if aut.num_classes != C:
+        raise ValueError(f"the lm has {aut.num_classes} classes, the logits {C}")
+    return aut.logp.astype(np.float64), aut.next, aut.start
+
+
 def prefix_beam_search(logits, beam_width: int, nbest: int = 1, lm=None, alpha: float = 0.0, beta: float = 0.0,
                        blank: Optional[int] = None, return_margin: bool = False):
     """One clip: logits [T, C] -> list of (indices int64, score) in rank order, at most nbest entries (fewer when fewer distinct
@@ -84,7 +100,7 @@ def prefix_beam_search(logits, beam_width: int, nbest: int = 1, lm=None, alpha: 
         raise ValueError(f"blank {b} outside 0..{C - 1}")
     if beam_width < 1 or nbest < 1 or nbest > beam_width:
         raise ValueError(f"need 1 <= nbest ({nbest}) <= beam_width ({beam_width})")
-    table = _lm_table(lm, C)
+    table, nxt, start = _lm_rows(lm, C, b)                  # every beam carries its LM state; with a table that is its last character
     use_lm = table is not None and alpha != 0.0
     lp = log_softmax(x)
     cls = np.arange(C)
@@ -93,6 +109,7 @@ def prefix_beam_search(logits, beam_width: int, nbest: int = 1, lm=None, alpha: 
     prefixes: List[Tuple[int, ...]] = [()]
     pb, pnb = np.zeros(1), np.full(1, NEG_INF)
     lmsum, ln, last = np.zeros(1), np.zeros(1, np.int64), np.full(1, -1, np.int64)
+    state = np.full(1, start, np.int64)
     for t in range(T):
         nb = len(prefixes)
         lpt = lp[t]
@@ -114,8 +131,7 @@ def prefix_beam_search(logits, beam_width: int, nbest: int = 1, lm=None, alpha: 
         bonus = (alpha * lmsum if use_lm else 0.0) + beta * ln
         s_score = _lse(s_pb, s_pnb) + bonus
         e_pnb = np.where(cls[None, :] == last[:, None], pb[:, None], tot[:, None]) + lpt[None, :]
-        row = np.where(last >= 0, last, b)
-        e_lm = lmsum[:, None] + table[row] if use_lm else np.zeros((nb, C))
+        e_lm = lmsum[:, None] + table[state] if use_lm else np.zeros((nb, C))
         e_score = e_pnb + ((alpha * e_lm) if use_lm else 0.0) + beta * (ln[:, None] + 1)
         ok = ~merged & (e_score > NEG_INF)
         ok[:, b] = False
@@ -129,23 +145,25 @@ def prefix_beam_search(logits, beam_width: int, nbest: int = 1, lm=None, alpha: 
         if order.size > beam_width:
             margin = min(margin, _gap(score[order[beam_width - 1]], score[order[beam_width]]))
         keep = order[:beam_width]
-        n_pref, n_pb, n_pnb, n_lm, n_ln, n_last = [], [], [], [], [], []
+        n_pref, n_pb, n_pnb, n_lm, n_ln, n_last, n_state = [], [], [], [], [], [], []
         for k in keep:
             s = int(src[k])
             if kind[k] == 0:
                 n_pref.append(prefixes[s]); n_pb.append(s_pb[s]); n_pnb.append(s_pnb[s])
-                n_lm.append(lmsum[s]); n_ln.append(ln[s]); n_last.append(last[s])
+                n_lm.append(lmsum[s]); n_ln.append(ln[s]); n_last.append(last[s]); n_state.append(state[s])
             else:
                 c = int(cc[k])
                 n_pref.append(prefixes[s] + (c,)); n_pb.append(NEG_INF); n_pnb.append(e_pnb[s, c])
                 n_lm.append(e_lm[s, c] if use_lm else 0.0); n_ln.append(ln[s] + 1); n_last.append(c)
+                n_state.append(c if nxt is None else nxt[state[s], c])
         prefixes = n_pref
         pb, pnb = np.array(n_pb, np.float64), np.array(n_pnb, np.float64)
         lmsum, ln, last = np.array(n_lm, np.float64), np.array(n_ln, np.int64), np.array(n_last, np.int64)
+        state = np.array(n_state, np.int64)
 
     final = _lse(pb, pnb) + ((alpha * lmsum if use_lm else 0.0) + beta * ln)
     if use_lm:
-        final = final + alpha * table[np.where(last >= 0, last, b), b]
+        final = final + alpha * table[state, b]
     order = np.lexsort((np.arange(final.size), -final))
     for k in range(min(nbest, order.size - 1)):
         margin = min(margin, _gap(final[order[k]], final[order[k + 1]]))
@@ -232,10 +250,15 @@ def check_device_args(C: int, T: int, beam_width: int, nbest: int) -> None:
 
 
 def lm_to_device(lm, C: int, device):
-    """The LM table as a contiguous fp32 [C, C] device tensor (None stays None)."""
+    """The LM table as a contiguous fp32 [C, C] device tensor (None stays None); a CharNGramLM or an LMAutomaton as the DeviceAutomaton
+    of ctc_lm.py, which `launch` sends to ishara_ctc_beam_decode_lm."""
     import torch
+    from . import ctc_lm
     if lm is None:
         return None
+    aut = ctc_lm.as_automaton(lm)
+    if aut is not None:
+        return ctc_lm.DeviceAutomaton(aut, C, device)
     t = np.asarray(lm, dtype=np.float32)
     if t.shape != (C, C):
         raise ValueError(f"lm must be [{C}, {C}], got {t.shape}")
@@ -252,9 +275,17 @@ def workspace_bytes(lib, B: int, T: int, C: int, beam_width: int) -> int:
 def launch(lib, logits, B: int, T: int, C: int, beam_width: int, nbest: int, lm_dev, alpha: float, beta: float, ws, out_idx, out_len,
            out_score, stream, frame_len=None, ex: bool = False) -> None:
     """One ishara_ctc_beam_decode launch on `stream` (graph-capturable); blank = C - 1 as for the greedy decoder.  With frame_len (int32
-    [B] on the device: the frames of each clip) or ex, the launch is ishara_ctc_beam_decode_ex."""
+    [B] on the device: the frames of each clip) or ex, the launch is ishara_ctc_beam_decode_ex.  An lm_dev that is a DeviceAutomaton
+    goes to ishara_ctc_beam_decode_lm, with or without frame_len."""
     import ctypes as C_
     from . import _lib
+    from .ctc_lm import entry_point
+    if entry_point(lm_dev) == "ishara_ctc_beam_decode_lm":
+        _lib.check(lib.ishara_ctc_beam_decode_lm(_lib.ptr(logits), B, T, C, C - 1, beam_width, nbest, _lib.ptr(lm_dev.logp), _lib.ptr(lm_dev.next),
+                                                 lm_dev.S, lm_dev.start, C_.c_float(alpha), C_.c_float(beta), _lib.ptr(ws), _lib.ptr(out_idx),
+                                                 _lib.ptr(out_len), _lib.ptr(out_score), _lib.ptr(frame_len), stream),
+                   "ishara_ctc_beam_decode_lm")
+        return
     if frame_len is not None or ex:
         _lib.check(lib.ishara_ctc_beam_decode_ex(_lib.ptr(logits), B, T, C, C - 1, beam_width, nbest,
                                                  _lib.ptr(lm_dev) if lm_dev is not None else None, C_.c_float(alpha), C_.c_float(beta),

@@ -639,7 +639,8 @@ class Model(Handle):
     def beam_decode(self, logits, beam_width: int = 16, nbest: int = 1, lm=None, alpha: float = 0.0, beta: float = 0.0,
                     frame_lengths=None) -> List[List[Tuple[np.ndarray, float]]]:
         """CTC prefix beam search (ishara_amd/ctc_beam.py semantics, blank = C - 1) of logits [B, T, C] on the device -> per clip a list
-        of (indices int64, score), best first, at most nbest entries.  lm: a [C, C] log-probability table (e.g. CharBigramLM) or None.
+        of (indices int64, score), best first, at most nbest entries.  lm: a [C, C] log-probability table (e.g. CharBigramLM), a CharNGramLM or an
+        LMAutomaton (ctc_lm.py: ishara_ctc_beam_decode_lm), or None.
         Unlike decode_batch it uses the last frame too.  The workspace of the latest shape is kept for the next call; the call waits for
         its results, so successive calls never overlap, but calls from several threads at once on one Model would share it (not supported)."""
         from . import ctc_beam

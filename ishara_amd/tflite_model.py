@@ -63,7 +63,8 @@ class _BeamConfig:
 
 
 def _beam_setup(model: Model, batch: int, beam_width: int, lm, alpha: float, beta: float) -> Optional[_BeamConfig]:
-    """None for beam_width == 0 (greedy); else the LM table, the workspace and the top-1 score buffer on the model's device."""
+    """None for beam_width == 0 (greedy); else the LM (a table, or an automaton's two tables), the workspace and the top-1 score buffer
+    on the model's device."""
     from . import ctc_beam
     if beam_width == 0:
         if lm is not None:
@@ -87,7 +88,8 @@ class TFLiteModel:
     def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, max_frames: int = 1024, use_graph: bool = True,
                  beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0):
         """beam_width = 0: the reference's greedy decode (c8:4-12).  beam_width > 0: the CTC prefix beam search of ishara_amd/ctc_beam.py
-        (top-1, optional LM table lm [C, C] weighted by lm_alpha, lm_beta per character) replaces it inside the same graph."""
+        (top-1, optional LM weighted by lm_alpha, lm_beta per character: a table lm [C, C], or a CharNGramLM / LMAutomaton of ctc_lm.py,
+        whose device tables are built here once) replaces it inside the same graph."""
         if model.F != N_COLS:
             raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
         self.model, self.max_frames, self.T = model, max_frames, model.T

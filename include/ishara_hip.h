@@ -240,6 +240,27 @@ int ishara_preprocess_batch(const float* raw, int64_t n_total, const int64_t* of
  * (MAX_PHRASE_LENGTH, c1:28) -> dist [B], tlen [B] (symbols before the first pad).  Integer-only, deterministic. */
 int ishara_edit_distance(const int32_t* out_idx, const int32_t* out_len, int32_t B, int32_t T, const int32_t* targets, int32_t L,
                          int32_t* dist, int32_t* tlen, ishara_stream s);
+/* The alignment behind that distance: for every (prediction, target) pair the canonical minimal edit script.  Prediction a[0..na), target
+ * b[0..nb) (nb = symbols before the first 59), D the unit-cost Levenshtein table; the script is the walk from (na, nb) to (0, 0) that takes at
+ * each cell the FIRST move that applies: diagonal (i, j > 0 and D[i][j] == D[i-1][j-1] + (a[i-1] != b[j-1]): a match or a substitution,
+ * aligned[j-1] = a[i-1]), then up (i > 0 and D[i][j] == D[i-1][j] + 1: an insertion, the prediction holds a symbol the target lacks,
+ * inserted[j] += 1: slot j counts the extra symbols in front of target position j, slot nb the trailing ones), else left (a deletion:
+ * aligned[j-1] = -1).  Inputs and limits as for ishara_edit_distance (out_idx [B,T], out_len [B] clamped to 0..T, targets [B,L] pad-59,
+ * 1 <= L <= 64, 1 <= T <= 4096, B = 0 a no-op); fallback != 0 replaces a prediction with out_len < 3 by the wrapper's constant phrase first,
+ * as ishara_edit_distance does, fallback == 0 aligns the raw prediction (beam outputs, the torch families).
+ * -> ops [B,4] = (matches, substitutions, deletions, insertions); aligned [B,L], -2 at j >= nb; inserted [B,L+1], 0 at j > nb;
+ * confusion [60,60] int32 (row = target symbol, column = predicted symbol, index 59 = "nothing"), ACCUMULATED: += 1 at [t][p] per diagonal
+ * move, at [59][p] per insertion, at [t][59] per deletion; the caller zeroes it once and sums a whole test set on the device; NULL: not
+ * wanted.  A symbol outside 0..58 is counted at index 59 (indexing only: aligned keeps the symbol); nothing is written outside the matrix,
+ * and [59][59] stays 0 for predictions inside 0..58.  S + D + I is the edit distance, M + S + D = nb, M + S + I = na (after the fallback).
+ * workspace: ishara_edit_alignment_workspace_bytes(B, T) bytes (B * max(T, 11) * 16; -1 for B < 0 or T outside 1..4096), 16-byte aligned,
+ * no initialisation needed.  A null or misaligned workspace, a null buffer (other than confusion) and out-of-range L / T / B are refused
+ * with a message before any launch.  One kernel, graph-capturable, no allocation, no memset; the matrix's integer atomics are the only
+ * atomics: every output is an exact function of the inputs. */
+int64_t ishara_edit_alignment_workspace_bytes(int32_t B, int32_t T);
+int ishara_edit_alignment(const int32_t* out_idx, const int32_t* out_len, int32_t B, int32_t T, const int32_t* targets, int32_t L,
+                          int32_t fallback, int32_t* ops, int32_t* aligned, int32_t* inserted, int32_t* confusion /* may be NULL */,
+                          void* workspace, ishara_stream s);
 
 /* CTC prefix beam search (Hannun et al. 2014) with optional character-bigram shallow fusion; the semantics of ishara_amd/ctc_beam.py.
  * logits [B,T,C] fp32 (log_softmax taken on the device), blank index, beam width W, nbest <= W; lm [C,C] natural-log probabilities

@@ -104,6 +104,8 @@ SIGNATURES = {
     "ishara_preprocess": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _P]),
     "ishara_preprocess_batch": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _I32, _P]),
     "ishara_edit_distance": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P]),
+    "ishara_edit_alignment_workspace_bytes": (_I64, [_I32, _I32]),
+    "ishara_edit_alignment": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "ishara_ctc_beam_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_ctc_beam_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _F, _P, _P, _P, _P, _P]),
     "ishara_ctc_beam_decode_ex": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _F, _P, _P, _P, _P, _P, _P]),

@@ -127,6 +127,25 @@ extern "C" int ishara_edit_distance(const int32_t* out_idx, const int32_t* out_l
     if (B > 0 && (!out_idx || !out_len || !targets || !dist || !tlen)) { ishara_set_error("ishara_edit_distance: null argument"); return -1; }
     return launch_edit_distance(out_idx, out_len, B, T, targets, L, dist, tlen, (hipStream_t)s);
 }
+extern "C" int64_t ishara_edit_alignment_workspace_bytes(int32_t B, int32_t T) {
+    if (B < 0 || T < 1 || T > 4096) return -1;
+    return (int64_t)edit_alignment_workspace_bytes(B, T);
+}
+extern "C" int ishara_edit_alignment(const int32_t* out_idx, const int32_t* out_len, int32_t B, int32_t T, const int32_t* targets, int32_t L,
+                                     int32_t fallback, int32_t* ops, int32_t* aligned, int32_t* inserted, int32_t* confusion, void* workspace,
+                                     ishara_stream s) {
+    const char* me = "ishara_edit_alignment";
+    if (L < 1 || L > SCORE_MAX_L) { ishara_set_error("%s: target length L=%d unsupported (1..%d: one wavefront lane per target symbol)", me, L, SCORE_MAX_L); return -1; }
+    if (B < 0 || T < 1 || T > 4096) { ishara_set_error("%s: B=%d T=%d unsupported (B >= 0, 1 <= T <= 4096)", me, B, T); return -1; }
+    if (B == 0) return 0;
+    if (!out_idx || !out_len || !targets || !ops || !aligned || !inserted) { ishara_set_error("%s: null out_idx / out_len / targets / ops / aligned / inserted (confusion may be NULL)", me); return -1; }
+    if (!workspace) { ishara_set_error("%s: null workspace (ishara_edit_alignment_workspace_bytes)", me); return -1; }
+    if ((uintptr_t)workspace % 16) { ishara_set_error("%s: workspace must be 16-byte aligned (one 16-byte mask pair per table row)", me); return -1; }
+    if (((uintptr_t)out_idx | (uintptr_t)out_len | (uintptr_t)targets | (uintptr_t)ops | (uintptr_t)aligned | (uintptr_t)inserted | (uintptr_t)confusion) % 4) {
+        ishara_set_error("%s: int32 buffers must be 4-byte aligned", me); return -1;
+    }
+    return launch_edit_alignment(out_idx, out_len, B, T, targets, L, fallback, ops, aligned, inserted, confusion, workspace, (hipStream_t)s);
+}
 extern "C" int64_t ishara_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t C, int32_t beam_width) {
     (void)C;
     if (B < 0 || T < 1 || T > 4096 || beam_width < 1 || beam_width > 32) return -1;

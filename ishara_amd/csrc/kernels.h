@@ -368,6 +368,11 @@ int launch_preprocess_batch(const float* raw, int64_t n_total, const int64_t* of
 // ---- test-set scoring (score.hip): edit distance of greedy decodes (len < 3 -> fallback phrase) to pad-59 targets [B,L], L <= 64
 #define SCORE_MAX_L 64
 int launch_edit_distance(const int* out_idx, const int* out_len, int B, int T, const int* targets, int L, int* dist, int* tlen, hipStream_t s);
+// ---- edit-operation alignment (score_align.hip): the canonical edit script of the same pairs -> ops [B,4], aligned [B,L], inserted [B,L+1] and
+// confusion [60,60] (+=, may be null); fallback != 0 applies the len < 3 rule; ws = edit_alignment_workspace_bytes(B, T), 16-byte aligned
+size_t edit_alignment_workspace_bytes(int B, int T);
+int launch_edit_alignment(const int* out_idx, const int* out_len, int B, int T, const int* targets, int L, int fallback, int* ops, int* aligned,
+                          int* inserted, int* confusion, void* ws, hipStream_t s);
 // ---- CTC prefix beam search (ctc_beam.hip): logits [B,T,C] f32 -> n-best prefixes; ws = B * ctc_beam_workspace_words(T, W) int32 (trie)
 __host__ __device__ size_t ctc_beam_workspace_words(int T, int W);
 int launch_ctc_beam(const float* logits, int B, int T, int C, int blank, int W, int nbest, const float* lm, float alpha, float beta,

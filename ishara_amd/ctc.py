@@ -142,6 +142,13 @@ def _ragged(x, lengths) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
 def ctc_greedy_decode(logits, lengths=None, blank: Optional[int] = None) -> List[np.ndarray]:
     """decode_phrase of every clip's first `lengths[b]` frames (the run ending at the clip's last frame is never emitted, as in the
     reference) -> list of int64 index arrays, what `Model.decode_batch` returns.  blank defaults to C - 1."""
+    idx, ln = greedy_decode_device(logits, lengths, blank)
+    idx, ln = idx.cpu().numpy(), ln.cpu().numpy()
+    return [idx[b, :ln[b]].astype(np.int64) for b in range(idx.shape[0])]
+
+
+def greedy_decode_device(logits, lengths=None, blank: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The same decode left on the device: (indices int32 [B, T], lengths int32 [B]), the layout ishara_edit_distance / ishara_edit_alignment read."""
     x, fl = _ragged(logits, lengths)
     B, T, Cc = x.shape
     blank = Cc - 1 if blank is None else int(blank)
@@ -150,8 +157,7 @@ def ctc_greedy_decode(logits, lengths=None, blank: Optional[int] = None) -> List
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().ishara_greedy_decode_ex(_lib.ptr(x), B, T, Cc, blank, _lib.ptr(idx), _lib.ptr(ln), _lib.ptr(fl), _lib.stream()),
                    "ishara_greedy_decode_ex")
-    idx, ln = idx.cpu().numpy(), ln.cpu().numpy()
-    return [idx[b, :ln[b]].astype(np.int64) for b in range(B)]
+    return idx, ln
 
 
 def ctc_beam_decode(logits, lengths=None, beam_width: int = 16, nbest: int = 1, lm=None, alpha: float = 0.0, beta: float = 0.0,

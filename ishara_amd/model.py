@@ -623,17 +623,22 @@ class Model(Handle):
     def decode_batch(self, logits: torch.Tensor, frame_lengths=None) -> List[np.ndarray]:
         """decode_batch_predictions (c8:15-20) -> list of index arrays (decode_phrase, c8:4-12).  frame_lengths [B] (1..T): clip b is
         decoded as logits[b, :frame_lengths[b]]."""
+        idx, ln = self._decode_device(logits, frame_lengths)
+        idx, ln = idx.cpu().numpy(), ln.cpu().numpy()
+        return [idx[b, :ln[b]].astype(np.int64) for b in range(idx.shape[0])]
+
+    def _decode_device(self, logits: torch.Tensor, frame_lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """decode_batch's decode left on the device: (indices int32 [B, T], lengths int32 [B])."""
         logits = logits.to(self.device, torch.float32).contiguous()
         if frame_lengths is not None:
             from . import ctc
-            return ctc.ctc_greedy_decode(logits, frame_lengths)
+            return ctc.greedy_decode_device(logits, frame_lengths)
         B, T, Cc = logits.shape
         idx = torch.empty((B, T), dtype=torch.int32, device=self.device)
         ln = torch.empty(B, dtype=torch.int32, device=self.device)
         _lib.check(self._lib.ishara_greedy_decode(_lib.ptr(logits), B, T, Cc, Cc - 1, _lib.ptr(idx), _lib.ptr(ln), _stream()),
                    "ishara_greedy_decode")
-        idx, ln = idx.cpu().numpy(), ln.cpu().numpy()
-        return [idx[b, :ln[b]].astype(np.int64) for b in range(B)]
+        return idx, ln
 
 
     def beam_decode(self, logits, beam_width: int = 16, nbest: int = 1, lm=None, alpha: float = 0.0, beta: float = 0.0,

@@ -13,6 +13,10 @@ H2D copy on a copy stream, replays the graph on the current stream and copies th
 D2H copy.  Two staging slots: batch i+1 is packed and copied while batch i replays; the host waits once per batch.  A last partial batch
 fills its unused slots with empty clips (equal offsets), whose outputs are dropped.  Each clip's result equals `TFLiteModel(...)(clip)`:
 the preprocessing is bit-identical per clip, and an inference-mode forward pass has no cross-sample statistics.
+
+`score(breakdown=True)` appends ishara_edit_alignment (fallback = 1) to the captured sequence: per-clip operation counts and per-position
+records in a result buffer of their own (ops | aligned | inserted, a second D2H copy in front of the same host wait), and one 60 x 60
+confusion matrix that stays on the device for the whole test set (zeroed before the first batch, read once after the last).
 """
 from __future__ import annotations
 
@@ -24,6 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import stream as _stream
+from .evaluation import ErrorReport
 from .model import Model
 from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS, _beam_launch, _beam_setup, refuse_frame_lengths
 
@@ -177,7 +182,23 @@ class BatchedTFLiteModel:
         self._consumed = [None, None]            # event after the replay that last read a device slot
         self._done = [torch.cuda.Event() for _ in range(2)]
         self.use_graph = use_graph
-        self._graphs: Dict[Tuple[int, bool], torch.cuda.CUDAGraph] = {}
+        self._graphs: Dict[Tuple[int, bool, bool], torch.cuda.CUDAGraph] = {}
+        self._brk = None                         # score(breakdown=True)'s buffers, made on first use
+
+    def _breakdown_buffers(self):
+        """ops int32 [bs, 4] | aligned [bs, L] | inserted [bs, L + 1] with two pinned copies, the confusion matrix and the kernel's workspace."""
+        if self._brk is None:
+            bs, L, dev = self.batch_size, self.L, self.model.device
+            n = bs * (4 + L + L + 1)
+            d = torch.zeros(n, dtype=torch.int32, device=dev)
+            need = int(self.model._lib.ishara_edit_alignment_workspace_bytes(bs, self.T))
+            if need < 0:
+                raise ValueError(f"edit alignment: batch_size={bs} T={self.T} unsupported")
+            ws_owner, ws = _lib.aligned(need, dev)
+            self._brk = dict(d=d, h=[torch.empty(n, dtype=torch.int32, pin_memory=True) for _ in range(2)],
+                             ops=d[:bs * 4].view(bs, 4), aligned=d[bs * 4:bs * (4 + L)].view(bs, L), inserted=d[bs * (4 + L):].view(bs, L + 1),
+                             conf=torch.zeros((60, 60), dtype=torch.int32, device=dev), ws_owner=ws_owner, ws=ws)
+        return self._brk
 
     # ---- views of a staging buffer (host or device)
     def _off(self, buf):
@@ -190,7 +211,7 @@ class BatchedTFLiteModel:
         return buf[self._raw_at:].view(torch.float32).view(self._cap, N_COLS)
 
     # ---- device work of one batch
-    def _launch(self, slot: int, scoring: bool):
+    def _launch(self, slot: int, scoring: bool, breakdown: bool = False):
         lib, m, d, bs = self.model._lib, self.model, self._d_in[slot], self.batch_size
         st = _stream()
         _lib.check(lib.ishara_preprocess_batch(_lib.ptr(self._raw(d)), self._cap, _lib.ptr(self._off(d)), bs, self.max_frames,
@@ -204,28 +225,45 @@ class BatchedTFLiteModel:
         if scoring:
             _lib.check(lib.ishara_edit_distance(_lib.ptr(self._idx), _lib.ptr(self._len), bs, self.T, _lib.ptr(self._tgt(d)), self.L,
                                                 _lib.ptr(self._dist), _lib.ptr(self._tlen), st), "ishara_edit_distance")
+        if breakdown:
+            self._launch_alignment(slot, bs)
 
-    def _graph(self, slot: int, scoring: bool):
-        key = (slot, scoring)
+    def _launch_alignment(self, slot: int, n: int):
+        """ishara_edit_alignment (fallback = 1) of the first n clips of the batch in device slot `slot`, adding to the object's matrix."""
+        k = self._breakdown_buffers()
+        _lib.check(self.model._lib.ishara_edit_alignment(_lib.ptr(self._idx), _lib.ptr(self._len), n, self.T, _lib.ptr(self._tgt(self._d_in[slot])),
+                                                         self.L, 1, _lib.ptr(k["ops"]), _lib.ptr(k["aligned"]), _lib.ptr(k["inserted"]),
+                                                         _lib.ptr(k["conf"]), k["ws"], _stream()), "ishara_edit_alignment")
+
+    def _graph(self, slot: int, scoring: bool, breakdown: bool = False):
+        key = (slot, scoring, breakdown)
         if key not in self._graphs:              # as TFLiteModel._capture: warm-up outside the capture, then capture once
+            conf = self._breakdown_buffers()["conf"].clone() if breakdown else None      # the warm-up launch adds to the matrix: put it back
             side = torch.cuda.Stream(device=self.model.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._launch(slot, scoring)
+                self._launch(slot, scoring, breakdown)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._launch(slot, scoring)
+                self._launch(slot, scoring, breakdown)
+            if breakdown:
+                self._brk["conf"].copy_(conf)
             self._graphs[key] = g
         return self._graphs[key]
 
-    def _run(self, slot: int, scoring: bool):
-        """The device sequence on the current stream, on the inputs already in device slot `slot`."""
+    def _run(self, slot: int, scoring: bool, breakdown: bool = False, n: Optional[int] = None):
+        """The device sequence on the current stream, on the inputs already in device slot `slot`.  With breakdown, n < batch_size clips (the
+        last, partial batch): the empty padding slots must not reach the confusion matrix, so the alignment is launched for n clips behind
+        the sequence without it."""
+        whole = breakdown and (n is None or n == self.batch_size)
         if self.use_graph:
-            self._graph(slot, scoring).replay()
+            self._graph(slot, scoring, whole).replay()
         else:
-            self._launch(slot, scoring)
+            self._launch(slot, scoring, whole)
+        if breakdown and not whole:
+            self._launch_alignment(slot, n)
 
     # ---- host pipeline
     def _batches(self, clips):
@@ -251,8 +289,9 @@ class BatchedTFLiteModel:
                 part = clips[b0:b0 + bs]
                 yield (lambda raw, out_off, part=part: pack_clips(part, raw, out_off)), len(part)
 
-    def _process(self, clips, targets=None):
-        """Run every batch; returns the host results per batch: (indices [n, T], lengths, dist, tlen)."""
+    def _process(self, clips, targets=None, breakdown: bool = False):
+        """Run every batch; returns the host results per batch: (indices [n, T], lengths, dist, tlen), with breakdown followed by
+        (ops [n, 4], aligned [n, L], inserted [n, L + 1])."""
         scoring = targets is not None
         bs = self.batch_size
         cur = torch.cuda.current_stream()
@@ -273,25 +312,31 @@ class BatchedTFLiteModel:
                 d[:nbytes].copy_(h[:nbytes], non_blocking=True)
                 self._copied[s].record(self._copy_stream)
             cur.wait_event(self._copied[s])
-            self._run(s, scoring)
+            self._run(s, scoring, breakdown, n)
             ev = torch.cuda.Event()
             ev.record(cur)
             self._consumed[s] = ev
             self._h_res[s].copy_(self._d_res, non_blocking=True)
+            if breakdown:
+                self._brk["h"][s].copy_(self._brk["d"], non_blocking=True)
             self._done[s].record(cur)
             if pending is not None:
                 out.append(self._collect(*pending))
-            pending = (s, n)
+            pending = (s, n, breakdown)
         if pending is not None:
             out.append(self._collect(*pending))
         return out
 
-    def _collect(self, s: int, n: int):
+    def _collect(self, s: int, n: int, breakdown: bool = False):
         self._done[s].synchronize()                  # the one host wait of a batch
         r = self._h_res[s].numpy()
         bs, T = self.batch_size, self.T
         idx = r[:bs * T].reshape(bs, T)[:n].copy()
         ln, dist, tlen = (r[bs * T + k * bs: bs * T + k * bs + n].copy() for k in range(3))
+        if breakdown:
+            k, L = self._brk["h"][s].numpy(), self.L
+            return (idx, ln, dist, tlen, k[:bs * 4].reshape(bs, 4)[:n].copy(), k[bs * 4:bs * (4 + L)].reshape(bs, L)[:n].copy(),
+                    k[bs * (4 + L):].reshape(bs, L + 1)[:n].copy())
         return idx, ln, dist, tlen
 
     # ---- public surface
@@ -307,16 +352,27 @@ class BatchedTFLiteModel:
         """`TFLiteModel.__call__` per clip: {'outputs': one-hot [n_chars, 59]} after the fallback (c13:22-24), on the host as there."""
         return [{"outputs": one_hot(apply_fallback(idx))} for idx in self.predict_indices(clips, frame_lengths)]
 
-    def score(self, clips, targets, char_to_num: Optional[Dict[str, int]] = None) -> Dict[str, object]:
+    def score(self, clips, targets, char_to_num: Optional[Dict[str, int]] = None, breakdown: bool = False) -> Dict[str, object]:
         """The test-set loop of c18:1-15 as one call: mean of (len(target) - Levenshtein(pred, target)) / len(target) over the clips, pred
         the wrapper's output (fallback applied).  targets: strings (encoded through char_to_num) or index sequences, one per clip.  The
-        distances are computed on the device; the scores in float64 on the host from the integer distances and target lengths."""
+        distances are computed on the device; the scores in float64 on the host from the integer distances and target lengths.
+        breakdown: also align every pair on the device (ishara_edit_alignment after the same fallback) and add `report` (an ErrorReport over
+        all clips), `ops` [n, 4] (matches, substitutions, deletions, insertions), `aligned` [n, L] and `inserted` [n, L + 1]."""
         enc = np.stack([encode_phrase(t, char_to_num, self.L) for t in targets]) if len(targets) else np.zeros((0, self.L), np.int32)
         n_clips = (np.asarray(clips[1]).shape[0] - 1) if (isinstance(clips, tuple) and len(clips) == 2 and np.ndim(clips[1]) == 1) else len(clips)
         if enc.shape[0] != n_clips:
             raise ValueError(f"{enc.shape[0]} targets for {n_clips} clips")
-        parts = self._process(clips, enc)
+        if breakdown:
+            self._breakdown_buffers()["conf"].zero_()      # on the current stream, outside the graph (a capture's warm-up leaves it as it was)
+        parts = self._process(clips, enc, breakdown)
         dist = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, np.int32)
         tlen = np.concatenate([p[3] for p in parts]) if parts else np.zeros(0, np.int32)
         mean, scores = normalized_scores(dist, tlen)
-        return dict(mean_score=mean, scores=scores, distances=dist.astype(np.int64))
+        res = dict(mean_score=mean, scores=scores, distances=dist.astype(np.int64))
+        if breakdown:
+            L = self.L
+            ops, aligned, inserted = (np.concatenate([p[k] for p in parts]) if parts else np.zeros((0, w), np.int32)
+                                      for k, w in ((4, 4), (5, L), (6, L + 1)))
+            conf = self._brk["conf"].cpu().numpy()   # the test set's matrix, read once
+            res.update(report=ErrorReport.from_arrays(ops, aligned, inserted, conf, enc), ops=ops, aligned=aligned, inserted=inserted)
+        return res

@@ -451,6 +451,42 @@ int ishara_op_gemm_tn(const ishara_gemm_tn_call* calls, int32_t n, void* slab, v
  * (gemm_tn_kernel_name; "" for a refused call), the number of M-splits and the rows per split.  The call's pointers are only tested for NULL
  * and alignment; out / dbias / G / Rpart need not be real.  Host only, launches nothing; the strings are static. */
 int ishara_debug_gemm_tn_plan(const ishara_gemm_tn_call* call, const char** route, const char** kernel, int32_t* splits, int32_t* rows_per_split);
+/* One forward / dgrad GEMM on the tile kernels of gemm_nt.hip with the arguments the models pass (launch_gemm_nt):
+ *   C [M, N] (dtC) = epi( op(A) [M, K] (dtA) . Bt [N, K]^T (dtM) )
+ * Bt is the CALLER-BUILT weight shadow [bt_rows][ldb] in dtM: bt_rows >= roundup(N, 128), ldb >= roundup(K, K tile) and whole 16-byte pieces
+ * (K tile: 32 bf16 / 16 f32 on the LDS-DMA kernels, 64 / 32 on the register-staged one).  Rows n >= N are read and discarded (any value);
+ * columns k in [K, ldb) must be zero (the register-staged kernel multiplies them with its zero-filled A tail).
+ * op: 0 none, 1 swish(A), 2 A * c1[k] + c0[k] (c1, c0 f32, readable up to roundup(K, K tile) floats), 4 A * dropout mask(op_seed, op_site,
+ * op_rate) — the mask of ishara_dropout_mask over [M, K]; 3 (row scale) is not carried.
+ * Epilogue, in this order (each part optional): + bias[n] (* rowscale[m / T] when rowscale_bias) ; + addtab[(m % tab_period), n] ; pre_out = the
+ * value so far ; act (0 none, 1 swish, 2 ReLU) ; * dropout mask(drop_seed, drop_site, drop_rate) over [M, N] ; * rowscale[m / T] (when not
+ * rowscale_bias) ; dact (1: * swish'(aux), 2: 0 where aux <= 0) ; + resid ; then mode 0 stores C, mode 1 (QKV split; C may be NULL) scatters to
+ * q, k [M / T, H, T, dh] and vt [M / T, H, dh, T] — head_major 1: columns are [q|k|v] per head, 0: [q of all heads | k | v]; N == 3 * H * dh, T and
+ * dh multiples of 8, M a multiple of T.  pre_out, aux, resid, q, k, vt are dtC; bias, addtab, rowscale f32.  A, Bt 16-byte aligned; dtC buffers
+ * 16-byte aligned (8-byte for 16-bit dtC on the 128 x 128 tile kernel); addtab 16-byte aligned on that kernel, f32 vectors 4-byte aligned. */
+typedef struct ishara_gemm_nt_call {
+    const void* A; const void* Bt; void* C;
+    const float* c1; const float* c0;
+    const float* bias; const float* addtab; void* pre_out;
+    const float* rowscale; const void* aux; const void* resid;
+    void* q; void* k; void* vt;
+    int32_t dtA, dtM, dtC, op;
+    int32_t M, N, K, bt_rows, ldb;
+    uint32_t op_seed, op_site; float op_rate;
+    int32_t tab_period, act;
+    uint32_t drop_seed, drop_site; float drop_rate;
+    int32_t T, rowscale_bias, dact, mode, H, dh, head_major;
+} ishara_gemm_nt_call;
+/* runs the call on stream s: exactly one kernel launch, nothing else.  Before any HIP call it refuses, with a message that names the field:
+ * unknown dtypes / op / act / dact / mode, a NULL A / Bt / C, a misaligned buffer, a shadow smaller than the contract above, addtab with
+ * tab_period < 1, rowscale with T < 1, dact without aux, an incomplete or inconsistent QKV split, a rate outside [0, 1), a call that lands on
+ * another kernel family than the three tile kernels (ishara_debug_force_regstage 8192 / 8 / 1 selects them), and whatever launch_gemm_nt
+ * refuses, with the launcher's message. */
+int ishara_op_gemm_nt(const ishara_gemm_nt_call* call, ishara_stream s);
+/* where ishara_op_gemm_nt would run the call under the current switches, read from the code that launches: route ("NT_TILE_T", "NT_GLDS",
+ * "NT_REG"; "NT_REFUSED" for every call the entry refuses, with the reason in ishara_last_error) and the profiler key of the kernel
+ * (gemm_nt_kernel_name; "" for a refused call).  Pointers are only tested for NULL and alignment.  Host only, launches nothing; the strings are static. */
+int ishara_debug_gemm_nt_route(const ishara_gemm_nt_call* call, const char** route, const char** kernel);
 /* QKV projection of the attention module at inference: LayerNorm of x [B*T, H*dh] (gamma, beta f32; gamma NULL: none; H*dh <= 512 with it),
  * x @ W + b (W [H*dh, 3*H*dh] f32, bias [3*H*dh] or NULL) scattered to q, k [B,H,T,dh] and vt [B,H,dh,T] (dt) — head_major 1: W's columns
  * are [q|k|v] per head, 0: [q of all heads | k | v].  T, dh multiples of 8.  The LayerNorm runs inside the GEMM or as a kernel of its own

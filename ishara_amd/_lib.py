@@ -59,6 +59,22 @@ class GemmTnCall(C.Structure):
     ]
 
 
+class GemmNtCall(C.Structure):
+    """ishara_gemm_nt_call: one forward / dgrad GEMM of ishara_op_gemm_nt / ishara_debug_gemm_nt_route (field order of the header)."""
+    _fields_ = [
+        ("A", C.c_void_p), ("Bt", C.c_void_p), ("C", C.c_void_p), ("c1", C.c_void_p), ("c0", C.c_void_p),
+        ("bias", C.c_void_p), ("addtab", C.c_void_p), ("pre_out", C.c_void_p), ("rowscale", C.c_void_p), ("aux", C.c_void_p), ("resid", C.c_void_p),
+        ("q", C.c_void_p), ("k", C.c_void_p), ("vt", C.c_void_p),
+        ("dtA", C.c_int32), ("dtM", C.c_int32), ("dtC", C.c_int32), ("op", C.c_int32),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("bt_rows", C.c_int32), ("ldb", C.c_int32),
+        ("op_seed", C.c_uint32), ("op_site", C.c_uint32), ("op_rate", C.c_float),
+        ("tab_period", C.c_int32), ("act", C.c_int32),
+        ("drop_seed", C.c_uint32), ("drop_site", C.c_uint32), ("drop_rate", C.c_float),
+        ("T", C.c_int32), ("rowscale_bias", C.c_int32), ("dact", C.c_int32), ("mode", C.c_int32), ("H", C.c_int32), ("dh", C.c_int32),
+        ("head_major", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/ishara_hip.h declares
 _P, _I32, _I64, _U32, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 SIGNATURES = {
@@ -140,6 +156,8 @@ SIGNATURES = {
     "ishara_op_gemm_tn_scratch_bytes": (_I64, [C.POINTER(GemmTnCall), _I32]),
     "ishara_op_gemm_tn": (C.c_int, [C.POINTER(GemmTnCall), _I32, _P, _P, _P, _P]),
     "ishara_debug_gemm_tn_plan": (C.c_int, [C.POINTER(GemmTnCall), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_I32), C.POINTER(_I32)]),
+    "ishara_op_gemm_nt": (C.c_int, [C.POINTER(GemmNtCall), _P]),
+    "ishara_debug_gemm_nt_route": (C.c_int, [C.POINTER(GemmNtCall), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
     "ishara_op_qkv_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_op_qkv_fwd": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "ishara_op_classifier_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),

@@ -147,7 +147,7 @@ def test_dense_big_tile_kernel(lib, M, K, N, act, with_resid):
     the A-stationary / tile kernels it replaces there (ishara_debug_set_nt_big(0)) on every element, and against the fp64 reference on
     sampled rows.  Same MFMA instruction and the same ascending order over K, so the fp32 accumulators agree bit for bit and the outputs
     differ by at most one bf16 rounding of the epilogue arithmetic.  K = 640: an uneven split of K steps between main loop and tail;
-    M = 34816: a row-tile count that is not a multiple of 8 (the plain workgroup order)."""
+    M = 34816: 272 row tiles of 128 and 136 of 256, both multiples of 8, so that shape runs the XCD-aware workgroup order."""
     code, tdt = DT["bf16"]
     g = torch.Generator().manual_seed(M + N + K + act)
     x = torch.randn(M, K, generator=g).to(tdt)

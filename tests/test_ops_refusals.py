@@ -33,6 +33,7 @@ def _ops():
         "ishara_op_qkv_fwd": lambda L, dt: L.ishara_op_qkv_fwd(dt, N, N, N, f(1e-6), N, N, N, N, N, 1, 64, 4, 32, 1, N, N),
         "ishara_op_classifier_fwd": lambda L, dt: L.ishara_op_classifier_fwd(dt, N, N, N, N, 64, 256, 60, 0, N, N),
         "ishara_op_gemm_tn": lambda L, dt: _gemm_tn(L, dict(dtA=dt, dtB=dt, dtM=dt)),
+        "ishara_op_gemm_nt": lambda L, dt: _gemm_nt(L, dtA=dt, dtM=dt, dtC=dt),
         **{n: (lambda L, dt, n=n: _r4_call(L, n, dt=dt)) for n in R4_DEFAULTS},
     }
 
@@ -86,6 +87,29 @@ def _gemm_tn(L, *calls, slab=C.c_void_p(1 << 20), d0=N, d1=N):
     """ishara_op_gemm_tn on a list of calls (dicts of field replacements) with a made-up slab and a NULL stream"""
     arr = (_lib.GemmTnCall * len(calls))(*[_gemm_tn_call(**kw) for kw in calls])
     return L.ishara_op_gemm_tn(arr, len(calls), slab, d0, d1, N)
+
+
+def _gemm_nt_call(**kw):
+    """one ishara_gemm_nt_call: a plain bf16 call of the 128 x 128 tile kernel (bias + residual) with made-up aligned addresses, `kw` replacing
+    single fields"""
+    k = _lib.GemmNtCall()
+    v = dict(A=4096, Bt=8192, C=12288, bias=16384, resid=20480, dtA=BF16, dtM=BF16, dtC=BF16, M=200, N=132, K=64, bt_rows=256, ldb=64, tab_period=1,
+             T=1, H=1, dh=1, head_major=1)
+    v.update(kw)
+    for n, x in v.items():
+        setattr(k, n, x)
+    return k
+
+
+def _gemm_nt(L, **kw):
+    return L.ishara_op_gemm_nt(C.byref(_gemm_nt_call(**kw)), N)
+
+
+def _gemm_nt_route(L, **kw):
+    """(rc, route, kernel) of ishara_debug_gemm_nt_route"""
+    route, kernel = C.c_char_p(), C.c_char_p()
+    rc = L.ishara_debug_gemm_nt_route(C.byref(_gemm_nt_call(**kw)), C.byref(route), C.byref(kernel))
+    return rc, route.value, kernel.value
 
 
 def _refused(lib, rc, name, *words):
@@ -535,3 +559,70 @@ def test_gemm_tn_scratch_query_and_plan_entry_refuse_bad_arguments(lib):
     k = _gemm_tn_call(dtA=F16)
     assert lib.ishara_debug_gemm_tn_plan(C.byref(k), C.byref(route), C.byref(kernel), C.byref(splits), C.byref(rps)) == 0
     assert (route.value, kernel.value, splits.value, rps.value) == (b"TN_REFUSED", b"", 0, 0) and b"ISHARA_F16" in lib.ishara_last_error()
+
+
+# ---- ishara_op_gemm_nt / ishara_debug_gemm_nt_route: everything a launch would fault on is refused before any HIP call with a message that names
+# the field; what launch_gemm_nt itself refuses comes back with the launcher's message behind the entry's name.  The route entry answers
+# "NT_REFUSED" with the same message
+QKV_FIELDS = dict(mode=1, q=24576, k=28672, vt=32768, C=0, resid=0, T=40, H=2, dh=32, M=160, N=192, bt_rows=256)
+GEMM_NT_REFUSALS = [
+    (dict(dtA=5), ("unknown dtype", "dtA=5")), (dict(dtM=-1), ("unknown dtype", "dtM=-1")), (dict(dtC=3), ("unknown dtype", "dtC=3")),
+    (dict(op=5), ("unknown op=5",)), (dict(op=-1), ("unknown op=-1",)), (dict(op=3), ("OP_ROWSCALE",)), (dict(op=2), ("OP_COLAFFINE", "c1 / c0")),
+    (dict(act=3), ("unknown act=3",)), (dict(dact=3), ("unknown dact=3",)), (dict(mode=2), ("unknown mode=2",)), (dict(head_major=2), ("head_major=2",)),
+    (dict(rowscale_bias=2), ("rowscale_bias=2",)), (dict(drop_rate=1.0), ("drop_rate",)), (dict(op_rate=-0.5), ("op_rate",)), (dict(drop_rate=float("nan")), ("drop_rate",)),
+    (dict(A=0), ("null A",)), (dict(Bt=0), ("null Bt",)), (dict(C=0), ("null C",)),
+    (dict(A=4104), ("gemm_nt: A rows must be 16-byte aligned",)), (dict(Bt=8200), ("misaligned Bt", "16-byte")),
+    (dict(C=12292), ("misaligned C", "8-byte")), (dict(C=12296, dtC=F32), ("misaligned C", "16-byte")), (dict(resid=20484), ("misaligned resid",)),
+    (dict(pre_out=40964), ("misaligned pre_out",)), (dict(dact=2, aux=40962), ("misaligned aux",)), (dict(bias=16386), ("misaligned bias", "4-byte")),
+    (dict(addtab=40968), ("misaligned addtab", "16-byte")), (dict(rowscale=40961, T=8), ("misaligned rowscale",)),
+    (dict(op=2, c1=40960, c0=45058, K=72, ldb=128), ("misaligned c0",)),
+    (dict(bt_rows=255), ("bt_rows=255", "roundup(N=132, 128)")), (dict(bt_rows=128), ("bt_rows=128",)), (dict(bt_rows=0), ("bt_rows=0",)),
+    (dict(K=72, ldb=72), ("ldb=72", "roundup(K=72, 64)")), (dict(K=72, ldb=64), ("ldb=64",)), (dict(dtA=F32, dtM=F32, dtC=F32, K=36, ldb=36), ("ldb=36", "roundup(K=36, 32)")),
+    (dict(K=128, ldb=64), ("ldb=64", "roundup(K=128, 32)")), (dict(K=72, ldb=132), ("ldb=132", "16-byte")),
+    (dict(addtab=40960, tab_period=0), ("addtab", "tab_period=0")), (dict(addtab=40960, tab_period=-3), ("tab_period=-3",)),
+    (dict(rowscale=40960, T=0), ("rowscale", "T=0")), (dict(dact=2), ("dact=2 without aux",)), (dict(dact=1), ("dact=1 without aux",)),
+    (dict(QKV_FIELDS, q=0), ("QKV", "q, k, vt")), (dict(QKV_FIELDS, k=0), ("QKV", "q, k, vt")), (dict(QKV_FIELDS, vt=0), ("QKV", "q, k, vt")),
+    (dict(QKV_FIELDS, T=0), ("QKV", "T=0")), (dict(QKV_FIELDS, M=170), ("QKV", "M=170", "T=40")), (dict(QKV_FIELDS, N=128, bt_rows=128), ("QKV", "N=128", "3 * H * dh")),
+    (dict(QKV_FIELDS, H=0), ("QKV", "H=0")), (dict(QKV_FIELDS, vt=32772), ("misaligned vt",)),
+    (dict(QKV_FIELDS, T=20), ("gemm_nt: QKV split needs T, dh multiples of 8",)), (dict(QKV_FIELDS, dh=12, H=4, N=144), ("gemm_nt: QKV split needs",)),
+    (dict(M=0), ("gemm_nt: bad shape",)), (dict(N=-4), ("gemm_nt: bad shape",)), (dict(K=0), ("gemm_nt: bad shape",)),
+    (dict(K=12), ("gemm_nt: A rows must be 16-byte aligned",)), (dict(dtA=F32, dtM=F32, dtC=F32, K=6), ("gemm_nt: A rows must be 16-byte aligned",)),
+    (dict(dtC=F32, dtM=F32), ("gemm_nt: unsupported dtype combination",)), (dict(dtA=F32, dtC=F32), ("gemm_nt: unsupported dtype combination",)),
+    (dict(dtA=F16, dtM=F16, dtC=F16, op=4), ("gemm_nt: f16 operands take no operand transform",)), (dict(dtA=F16, dtM=F16, dtC=BF16), ("gemm_nt: unsupported f16 dtype combination",)),
+    (dict(dtA=F32, dtM=BF16, dtC=BF16, op=1), ("gemm_nt: unsupported dtype combination",)),
+    (dict(M=34816, N=768, K=640, bt_rows=768, ldb=640), ("route NT_BIG", "only the tile kernels")),
+]
+
+
+@pytest.mark.parametrize("kw,words", GEMM_NT_REFUSALS)
+def test_gemm_nt_refuses_buffers_dtypes_and_shapes(lib, kw, words):
+    _refused(lib, _gemm_nt(lib, **kw), "ishara_op_gemm_nt", *words)
+    rc, route, kernel = _gemm_nt_route(lib, **kw)
+    assert (rc, route, kernel) == (0, b"NT_REFUSED", b"")
+    _refused(lib, -1, "ishara_debug_gemm_nt_route", *words)
+
+
+def test_gemm_nt_null_arguments_and_accepted_calls(lib):
+    _refused(lib, lib.ishara_op_gemm_nt(None, N), "ishara_op_gemm_nt", "null call")
+    route, kernel = C.c_char_p(), C.c_char_p()
+    k = _gemm_nt_call()
+    _refused(lib, lib.ishara_debug_gemm_nt_route(None, C.byref(route), C.byref(kernel)), "ishara_debug_gemm_nt_route", "null")
+    _refused(lib, lib.ishara_debug_gemm_nt_route(C.byref(k), None, C.byref(kernel)), "ishara_debug_gemm_nt_route", "null")
+    _refused(lib, lib.ishara_debug_gemm_nt_route(C.byref(k), C.byref(route), None), "ishara_debug_gemm_nt_route", "null")
+    # what the refusal rows vary, unvaried, is taken: each row is refused for its own field
+    assert _gemm_nt_route(lib) == (0, b"NT_TILE_T", b"gemm_nt_t_kernel<bf16,bf16>")
+    assert _gemm_nt_route(lib, **QKV_FIELDS) == (0, b"NT_TILE_T", b"gemm_nt_t_kernel<bf16,bf16>")
+    assert _gemm_nt_route(lib, C=12296) == (0, b"NT_TILE_T", b"gemm_nt_t_kernel<bf16,bf16>")          # 8-byte aligned 16-bit C: the 128 x 128 kernel stores 4 elements
+    assert _gemm_nt_route(lib, N=130, bt_rows=256) == (0, b"NT_GLDS", b"gemm_nt_glds_kernel<bf16,bf16>")
+    _refused(lib, _gemm_nt(lib, N=130, C=12296), "ishara_op_gemm_nt", "misaligned C", "16-byte", "NT_GLDS")
+    assert _gemm_nt_route(lib, K=72, ldb=128) == (0, b"NT_REG", b"gemm_nt_kernel<bf16,bf16,bf16>")
+    assert _gemm_nt_route(lib, addtab=40964, K=72, ldb=128) == (0, b"NT_REG", b"gemm_nt_kernel<bf16,bf16,bf16>")      # 4-byte aligned table off the 128 x 128 kernel
+    try:      # the switches steer the answer, as they steer the launcher
+        lib.ishara_debug_force_regstage(8)
+        assert _gemm_nt_route(lib)[1] == b"NT_GLDS"
+        lib.ishara_debug_force_regstage(1)
+        assert _gemm_nt_route(lib)[1] == b"NT_REG"
+        lib.ishara_debug_force_regstage(8192)
+        assert _gemm_nt_route(lib, M=34816, N=768, K=640, bt_rows=768, ldb=640)[1] == b"NT_TILE_T"
+    finally:
+        lib.ishara_debug_force_regstage(0)

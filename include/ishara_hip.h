@@ -359,8 +359,8 @@ int ishara_dropout_mask(uint32_t seed, uint32_t site, int32_t rows, int32_t cols
 /* tests/ablation: bit0 register-staged NT GEMM, bit1 register-transposing TN GEMM, bit2 LDS-tiled depthwise conv
  * (defaults: LDS-DMA NT, transposed-read TN, register-window depthwise conv); bits 4-11 ablation switches */
 /* switches of the A-stationary GEMM family, the bits of ISHARA_AS_FLAGS: 1 paired half-line stores, 2 non-temporal side outputs, 16 / 32 the
- * chunked form at K = 256 / 512, 64 the C-stationary kernel (gemm_cs.hip) for bf16 K = 512 -> N = 256 at M > 49152 rows, 128 that kernel at
- * any M (tests).  -1 = library default (115); 51 and 3 select the A-stationary kernels alone, as before bit 64 existed */
+ * chunked form at K = 256 / 512, 64 the C-stationary kernel (gemm_cs.hip) for bf16 K = 512 -> N = 256 (and K = 768 -> N = 256 without an
+ * epilogue operand) at M > 49152 rows, 128 that kernel at any M (tests), 256 K = 768 stays on the tile kernel.  -1 = library default (115); 51 and 3 select the A-stationary kernels alone, as before bit 64 existed */
 int ishara_debug_set_as_flags(int32_t flags);
 /* the kernel (profiler key) ishara_op_dense_fwd_ex would run for these arguments, with a bias, under the current switches; host only, launches nothing */
 const char* ishara_debug_dense_kernel_name(int32_t dt, int32_t M, int32_t K, int32_t N, int32_t act, int32_t with_resid);

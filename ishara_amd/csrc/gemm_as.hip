@@ -334,11 +334,14 @@ DEVI void as_pass(const as_t* __restrict__ A, const as_t* __restrict__ Bt, TC* _
 #pragma unroll
                 for (int q = 0; q < NG; ++q) rs[i][q] = *reinterpret_cast<const as_u32x4*>(resid + eoff[i] + n0 + 4 * GW * q);
         }
+        // (act': the last use of a saved pre-activation, yet an ordinary load.  Four lanes take 64 bytes of a row per column step and the other half
+        // of the 128-byte line is asked for one step, ~2 us, later: with the non-temporal hint the first half had left L2 by then and every line
+        // came from memory twice — FETCH_SIZE 240 MB per launch of <8,10,0> against 154 MB without it, 69.9 -> 64.7 us: DESIGN 7e)
         if (f_dact) {
 #pragma unroll
             for (int i = 0; i < RT; ++i)
 #pragma unroll
-                for (int q = 0; q < NG; ++q) au[i][q] = __builtin_nontemporal_load(reinterpret_cast<const as_u32x4*>(aux + eoff[i] + n0 + 4 * GW * q));      // last use of a saved pre-activation
+                for (int q = 0; q < NG; ++q) au[i][q] = *reinterpret_cast<const as_u32x4*>(aux + eoff[i] + n0 + 4 * GW * q);
         }
         if (sync && sg + R - 1 < nstages && !(dbg & 8)) issue(slot == 0 ? (R - 1) * STAGE : slot - STAGE);
         // ---- MFMA: acc[j][i] = sum_k Bt[row(j), k] * A[16i + .., k]

@@ -1,6 +1,10 @@
-// gemm_cs.hip — "C-stationary" NT GEMM for the K = 512 -> N = 256 projections of the encoder at training-size M (gfx950).
+// gemm_cs.hip — "C-stationary" NT GEMM for the K = 512 -> N = 256 projections of the encoder at training-size M (gfx950), and for the
+// K = 768 -> N = 256 dgrad of the QKV projection (plain epilogue only).
 //
-//   C[M,256] = epi( pro(A)[M,512] . Bt[256,512]^T ),  bf16 operands and output, fp32 accumulate.
+//   C[M,256] = epi( pro(A)[M,K] . Bt[256,K]^T ),  K = 64 NST in {512, 768}, bf16 operands and output, fp32 accumulate.
+//
+// Nothing below but the number of K chunks depends on K: the accumulator registers, the LDS ring and the wait classes of cs_stage are the same
+// for NST = 8 and NST = 12 (gemm_nt_cs_kernel<0,0,12>: 79 -> 56 us per launch against the 128 x 128 tile kernel).
 //
 // The A-stationary kernels (gemm_as.hip) keep a wave's rows x full K in registers: at K = 512 that is 128 VGPRs, loaded in one burst that
 // nothing overlaps, followed by a column loop that only writes.  At N = 256 the roles can be swapped: the fp32 accumulators of 32 rows x ALL
@@ -18,8 +22,8 @@
 //
 // BUILD CHECK.  The A chunks and residual rows in flight are outputs of asm loads: hipcc believes them valid from the load on, so one spill
 // or copy of such a register between cs_ld16 and cs_pin corrupts data silently.  The Makefile therefore compiles this file with
-// -Rpass-analysis=kernel-resource-usage and fails when any kernel has scratch; re-check that, the VGPR counts (226 / 246 / 253 / 245 /
-// 248 of 256 for <0,0> <1,0> <9,0> <1,2> <17,2>) and the ISA between every asm load and its wait whenever ROCm is bumped.
+// -Rpass-analysis=kernel-resource-usage and fails when any kernel has scratch; re-check that, the VGPR counts (226 / 246 / 253 / 244 /
+// 248 / 224 of 256 for <0,0> <1,0> <9,0> <1,2> <17,2> <0,0,12>) and the ISA between every asm load and its wait whenever ROCm is bumped.
 // The library default of as_flags is stated twice: CS_DEFAULT_FLAGS below and 51 in gemm_as.hip's as_default_flags() (that file ignores bits
 // 64 / 128, and both read ISHARA_AS_FLAGS): whoever changes a default bit of the A-stationary kernels changes both.
 //
@@ -35,14 +39,13 @@
 #include "kernels.h"
 
 enum { CS_RESID = 1, CS_DROP = 8, CS_ROWSCALE = 16 };          // the epilogue feature bits of gemm_as.hip (AS_RESID, AS_DROP, AS_ROWSCALE)
-#define CS_K 512
 #define CS_N 256
 #define CS_ROWS 384          // rows per workgroup: 256 + 128
-#define CS_NST 8             // K chunks / weight stages per pass (64 k each)
+// NST = K / 64: K chunks / weight stages per pass (64 k each): 8 (K = 512, every mask) or 12 (K = 768, the plain mask: the QKV projection's dgrad)
 #define CS_RING 4
 #define CS_STAGE 32768       // 256 weight rows x 128 bytes
 #define CS_DPW 4             // 1 KB DMA instructions per wave and stage (32 per stage, 8 waves)
-#define CS_LDS (CS_RING * CS_STAGE + CS_N * 4 + 2 * CS_K * 4)      // ring | bias | P, Q of the per-sample affine
+#define CS_LDS(K) (CS_RING * CS_STAGE + CS_N * 4 + 2 * (K) * 4)      // ring | bias | P, Q of the per-sample affine
 // library default of as_flags as this file reads them: the A-stationary kernels' 51 | 64, the route on (14.50 -> 14.15 ms/step by same-box alternation,
 // every mask of the step faster than its old kernel: DESIGN 7d); ISHARA_AS_FLAGS=51 / ishara_debug_set_as_flags(51) turn it off
 #define CS_DEFAULT_FLAGS 115
@@ -92,11 +95,11 @@ template <int RT> struct CsRows {
     int mrow[RT];                 // clamped row
     cs_u32x4 a[3][RT][2];         // three K chunks: two in flight, one consumed
 };
-template <int RT> DEVI void cs_rows_init(CsRows<RT>& r, const bf16* __restrict__ A, int M, int mw, const CsLane& L) {
+template <int RT, int K> DEVI void cs_rows_init(CsRows<RT>& r, const bf16* __restrict__ A, int M, int mw, const CsLane& L) {
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
         r.mrow[i] = min(mw + 16 * i + L.c, M - 1);
-        r.ap[i] = A + (size_t)r.mrow[i] * CS_K + L.g * 8;
+        r.ap[i] = A + (size_t)r.mrow[i] * K + L.g * 8;
     }
 }
 // A chunk S -> buffer S % 3: lane (c, g) of row tile i takes row 16i + c, k = 64 S + 32 kt + 8 g .. +7
@@ -127,23 +130,26 @@ template <int RT> DEVI void cs_prefetch(CsRows<RT>& r, const CsLane& L, char* sm
 }
 #define CS_PREFETCH_OPS(RT) (2 * 2 * (RT) + 3 * CS_DPW)
 
-// K chunk / weight stage S of a pass.  VM operations of a wave, in issue order (NA = 2 RT loads per A chunk, D = 4 DMAs per stage, P = NA
-// stores of the prologue's rows when they are written, E = stores of the previous pass's epilogue):
+// K chunk / weight stage S of a pass of NST stages.  VM operations of a wave, in issue order (NA = 2 RT loads per A chunk, D = 4 DMAs per
+// stage, P = NA stores of the prologue's rows when they are written, E = stores of the previous pass's epilogue), at NST = 8:
 //     A0 A1 D0 D1 D2 [E] | A2 D3 P0 | A3 D4 P1 | A4 D5 P2 | A5 D6 P3 | A6 D7 P4 | A7 P5 | P6 | P7
-// Stage S needs A(S) and D(S): everything younger than the later of the two may stay in flight.
-template <int MASK, int PRO, int RT, int E, int S>
+// and at NST = 12 four more middle stages `A(S+2) D(S+3) P(S)`.  Stage S needs A(S) and D(S): everything younger than the later of the two
+// may stay in flight.  From S = 2 on the later one is A(S), issued by stage S - 2 in front of D(S+1) P(S-2) | A(S+1) D(S+2) P(S-1), of which
+// D(S+2) is missing at S = NST - 2 and all but the stores at S = NST - 1: the five classes below do not depend on NST otherwise.
+template <int MASK, int PRO, int NST, int RT, int E, int S>
 DEVI void cs_stage(CsRows<RT>& r, const CsLane& L, char* smem, const float* pq_s, f32x4 (&acc)[8][2][RT], bf16* pro_out, int M, int mw,
                    bool full, bool pout, bool nt_side) {
-    constexpr int NA = 2 * RT, D = CS_DPW;
+    constexpr int NA = 2 * RT, D = CS_DPW, K = 64 * NST;
+    static_assert(NST >= 5 && S < NST, "the wait classes below need a middle stage");
     if constexpr (S == 0) cs_wait<2 * D + E, 2 * D + E>(full, pout);
     else if constexpr (S == 1) cs_wait<2 * D + E + NA, 2 * D + E + NA + NA>(full, pout);
-    else if constexpr (S <= 5) cs_wait<2 * D + NA, 2 * D + NA + 2 * NA>(full, pout);
-    else if constexpr (S == 6) cs_wait<D + NA, D + NA + 2 * NA>(full, pout);
+    else if constexpr (S <= NST - 3) cs_wait<2 * D + NA, 2 * D + NA + 2 * NA>(full, pout);
+    else if constexpr (S == NST - 2) cs_wait<D + NA, D + NA + 2 * NA>(full, pout);
     else cs_wait<0, 2 * NA>(full, pout);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();          // stage S has landed for every wave; every wave is done reading stage S - 1
-    if constexpr (S + 2 < CS_NST) cs_load_a<RT, S + 2>(r);
-    if constexpr (S + 3 < CS_NST) cs_issue_w<S + 3>(L, smem);        // into the slot of stage S - 1
+    if constexpr (S + 2 < NST) cs_load_a<RT, S + 2>(r);
+    if constexpr (S + 3 < NST) cs_issue_w<S + 3>(L, smem);        // into the slot of stage S - 1
     constexpr int B = S % 3;
 #pragma unroll
     for (int i = 0; i < RT; ++i) { cs_pin(r.a[B][i][0]); cs_pin(r.a[B][i][1]); }
@@ -152,7 +158,7 @@ DEVI void cs_stage(CsRows<RT>& r, const CsLane& L, char* smem, const float* pq_s
         for (int kt = 0; kt < 2; ++kt) {
             const float* cp = pq_s + 64 * S + 32 * kt + 8 * L.g;
             const f32x4 w0 = *reinterpret_cast<const f32x4*>(cp), w1 = *reinterpret_cast<const f32x4*>(cp + 4);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(cp + CS_K), b1 = *reinterpret_cast<const f32x4*>(cp + CS_K + 4);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(cp + K), b1 = *reinterpret_cast<const f32x4*>(cp + K + 4);
             float wv[8], bv[8];
 #pragma unroll
             for (int e = 0; e < 4; ++e) { wv[e] = w0[e]; wv[4 + e] = w1[e]; bv[e] = b0[e]; bv[4 + e] = b1[e]; }
@@ -165,7 +171,7 @@ DEVI void cs_stage(CsRows<RT>& r, const CsLane& L, char* smem, const float* pq_s
                 for (int e = 0; e < 8; ++e) t[e] = (bf16)(v[e] * wv[e] + bv[e]);
                 r.a[B][i][kt] = __builtin_bit_cast(cs_u32x4, t);
                 if (pout && (full || mw + 16 * i + L.c < M))
-                    cs_st_pk(pro_out + (size_t)r.mrow[i] * CS_K + L.g * 8 + 64 * S + 32 * kt, t, nt_side);
+                    cs_st_pk(pro_out + (size_t)r.mrow[i] * K + L.g * 8 + 64 * S + 32 * kt, t, nt_side);
             }
         }
     }
@@ -192,10 +198,18 @@ DEVI void cs_stage(CsRows<RT>& r, const CsLane& L, char* smem, const float* pq_s
     }
 }
 
+// stages S .. NST - 1 of a pass, in order (the K loop, fully unrolled)
+template <int MASK, int PRO, int NST, int RT, int E, int S>
+DEVI void cs_stages(CsRows<RT>& r, const CsLane& L, char* smem, const float* pq_s, f32x4 (&acc)[8][2][RT], bf16* pro_out, int M, int mw,
+                    bool full, bool pout, bool nt_side) {
+    cs_stage<MASK, PRO, NST, RT, E, S>(r, L, smem, pq_s, acc, pro_out, M, mw, full, pout, nt_side);
+    if constexpr (S + 1 < NST) cs_stages<MASK, PRO, NST, RT, E, S + 1>(r, L, smem, pq_s, acc, pro_out, M, mw, full, pout, nt_side);
+}
+
 // One pass over the rows [m_base, m_base + 128 RT) (wave w: 16 RT rows from m_base + 16 RT w); started with cs_prefetch under way and E
 // stores of the previous pass younger than it.  `hand` requests the next pass's prefetch; it runs after the K loop (the ring is free) and
 // before this pass's stores.  HOPS: the VM operations it issues (0: last pass).
-template <int MASK, int PRO, int RT, int E, typename HAND>
+template <int MASK, int PRO, int NST, int RT, int E, typename HAND>
 DEVI void cs_pass(CsRows<RT>& r, const CsLane& L, bf16* __restrict__ C, int M, const EpiArgs& ea, char* smem, const float* bias_s, const float* pq_s,
                   int m_base, float rsc, int hops, HAND hand) {
     const int mw = m_base + L.wid * 16 * RT;
@@ -205,14 +219,7 @@ DEVI void cs_pass(CsRows<RT>& r, const CsLane& L, bf16* __restrict__ C, int M, c
     constexpr bool f_resid = (MASK & CS_RESID) != 0, f_drop = (MASK & CS_DROP) != 0, f_rowscale = (MASK & CS_ROWSCALE) != 0;
     f32x4 acc[8][2][RT];          // (first written by stage 0's MFMAs: acc = 0 + W . A)
     bf16* po = reinterpret_cast<bf16*>(ea.pro_out);
-    cs_stage<MASK, PRO, RT, E, 0>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
-    cs_stage<MASK, PRO, RT, E, 1>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
-    cs_stage<MASK, PRO, RT, E, 2>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
-    cs_stage<MASK, PRO, RT, E, 3>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
-    cs_stage<MASK, PRO, RT, E, 4>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
-    cs_stage<MASK, PRO, RT, E, 5>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
-    cs_stage<MASK, PRO, RT, E, 6>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
-    cs_stage<MASK, PRO, RT, E, 7>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
+    cs_stages<MASK, PRO, NST, RT, E, 0>(r, L, smem, pq_s, acc, po, M, mw, full, pout, nt_side);
 
     asm volatile("s_nop 15");          // the last MFMAs' results -> the compiler's epilogue code
     // residual rows first (the A chunk registers are free), then the next pass's prefetch, then the stores
@@ -278,8 +285,9 @@ DEVI void cs_pass(CsRows<RT>& r, const CsLane& L, bf16* __restrict__ C, int M, c
     }
 }
 
-template <int MASK, int PRO>
-__global__ __launch_bounds__(512, 1) void gemm_nt_cs_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bt, bf16* __restrict__ C, int M, int ldb, EpiArgs ea) {
+template <int MASK, int PRO, int NST>
+DEVI void cs_body(const bf16* __restrict__ A, const bf16* __restrict__ Bt, bf16* __restrict__ C, int M, int ldb, const EpiArgs& ea) {
+    constexpr int K = 64 * NST;
     extern __shared__ __attribute__((aligned(16))) char cs_smem[];
     float* bias_s = reinterpret_cast<float*>(cs_smem + CS_RING * CS_STAGE);
     float* pq_s = bias_s + CS_N;
@@ -288,9 +296,9 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_cs_kernel(const bf16* __restri
     const int bsm = min(m_base, M - 1) / max(ea.T, 1);          // PRO 2 / row scale: the workgroup's rows lie in ONE sample (launcher)
     for (int n = tid; n < CS_N; n += 512) bias_s[n] = ea.bias ? ea.bias[n] : 0.f;
     if constexpr (PRO == 2) {
-        const float* c0 = ea.pa_P + (size_t)bsm * CS_K;
-        const float* c1 = ea.pa_Q + (size_t)bsm * CS_K;
-        for (int x = tid; x < CS_K; x += 512) { pq_s[x] = c0[x]; pq_s[CS_K + x] = c1[x]; }
+        const float* c0 = ea.pa_P + (size_t)bsm * K;
+        const float* c1 = ea.pa_Q + (size_t)bsm * K;
+        for (int x = tid; x < K; x += 512) { pq_s[x] = c0[x]; pq_s[K + x] = c1[x]; }
     }
     float rsc = 1.f;
     if constexpr ((MASK & CS_ROWSCALE) != 0) rsc = ea.rowscale[bsm];
@@ -313,16 +321,27 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_cs_kernel(const bf16* __restri
     const bool two = m_base + 256 < M;
     CsRows<2> r1;
     CsRows<1> r2;
-    cs_rows_init<2>(r1, A, M, m_base + L.wid * 32, L);
+    cs_rows_init<2, K>(r1, A, M, m_base + L.wid * 32, L);
     cs_prefetch<2>(r1, L, cs_smem);
-    cs_pass<MASK, PRO, 2, 0>(r1, L, C, M, ea, cs_smem, bias_s, pq_s, m_base, rsc, two ? CS_PREFETCH_OPS(1) : 0, [&]() {
+    cs_pass<MASK, PRO, NST, 2, 0>(r1, L, C, M, ea, cs_smem, bias_s, pq_s, m_base, rsc, two ? CS_PREFETCH_OPS(1) : 0, [&]() {
         if (two) {
-            cs_rows_init<1>(r2, A, M, m_base + 256 + L.wid * 16, L);
+            cs_rows_init<1, K>(r2, A, M, m_base + 256 + L.wid * 16, L);
             cs_prefetch<1>(r2, L, cs_smem);
         }
     });
     // the first pass was full when there is a second one: E = its 2 x 8 stores per lane
-    if (two) cs_pass<MASK, PRO, 1, 16>(r2, L, C, M, ea, cs_smem, bias_s, pq_s, m_base + 256, rsc, 0, []() {});
+    if (two) cs_pass<MASK, PRO, NST, 1, 16>(r2, L, C, M, ea, cs_smem, bias_s, pq_s, m_base + 256, rsc, 0, []() {});
+}
+// Two overloads, not one template with a defaulted NST: the K = 512 kernels keep their two-argument rocprof names gemm_nt_cs_kernel<MASK, PRO>,
+// the K = 768 one is gemm_nt_cs_kernel<0, 0, 12>.
+template <int MASK, int PRO>
+__global__ __launch_bounds__(512, 1) void gemm_nt_cs_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bt, bf16* __restrict__ C, int M, int ldb, EpiArgs ea) {
+    cs_body<MASK, PRO, 8>(A, Bt, C, M, ldb, ea);
+}
+template <int MASK, int PRO, int NST>
+__global__ __launch_bounds__(512, 1) void gemm_nt_cs_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bt, bf16* __restrict__ C, int M, int ldb, EpiArgs ea) {
+    static_assert(NST != 8, "K = 512 is the two-argument overload");
+    cs_body<MASK, PRO, NST>(A, Bt, C, M, ldb, ea);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
@@ -331,38 +350,45 @@ static int cs_mask_of(const EpiArgs& ea) {      // as gemm_as.hip's as_mask_of
            (ea.pre_out ? 32 : 0) | (ea.mode == EPI_QKV ? 64 : 0) | (ea.addtab ? 128 : 0);
 }
 // as_flags as this route reads them: the per-call value, else ishara_debug_set_as_flags, else ISHARA_AS_FLAGS, else the library default
-// CS_DEFAULT_FLAGS.  115 = 51 (the A-stationary kernels' switches, gemm_as.hip) | 64 (this route on); 128: ignore the row threshold (tests)
+// CS_DEFAULT_FLAGS.  115 = 51 (the A-stationary kernels' switches, gemm_as.hip) | 64 (this route on); 128: ignore the row threshold (tests);
+// 256: K = 768 stays on the 128 x 128 tile kernel (A/B runs of the QKV projection's dgrad inside one build)
 static int cs_flags(const EpiArgs& ea) {
     static const int v = getenv("ISHARA_AS_FLAGS") ? atoi(getenv("ISHARA_AS_FLAGS")) : CS_DEFAULT_FLAGS;
     return ea.as_flags >= 0 ? ea.as_flags : (g_as_flags_override >= 0 ? g_as_flags_override : v);
 }
 bool gemm_nt_cs_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs& ea) {
-    if (dtC != DT_BF16 || K != CS_K || N != CS_N || M < 1 || ldb < CS_K || ldb % 8 != 0) return false;
+    if (dtC != DT_BF16 || (K != 512 && K != 768) || N != CS_N || M < 1 || ldb < K || ldb % 8 != 0) return false;
     const int flags = cs_flags(ea);
     if (!(flags & 64)) return false;
+    if (K == 768 && ((flags & 256) || ea.pa_P || cs_mask_of(ea) != 0)) return false;          // K = 768: the plain mask alone (<0,0,12>)
     if (ea.n_valid || ea.dbg || (ea.ldc && ea.ldc != CS_N) || ea.ln_gamma) return false;
     if (!(flags & 128) && M < CS_MIN_M) return false;
     const int mask = cs_mask_of(ea);
     if (ea.pa_P) return ea.pa_Q && ea.T > 0 && ea.T % CS_ROWS == 0 && (mask == CS_RESID || mask == (CS_RESID | CS_ROWSCALE));
     return mask == 0 || mask == CS_RESID || mask == (CS_RESID | CS_DROP);
 }
-const char* gemm_nt_cs_name(const EpiArgs& ea) {
+const char* gemm_nt_cs_name(int K, const EpiArgs& ea) {
     static std::map<int, std::string> names;
-    const int mask = cs_mask_of(ea), pro = ea.pa_P ? 2 : 0;
-    auto it = names.find(mask | pro << 8);
+    const int mask = cs_mask_of(ea), pro = ea.pa_P ? 2 : 0, key = mask | pro << 8 | (K == 768) << 12;
+    auto it = names.find(key);
     if (it == names.end()) {
         char buf[64];
-        snprintf(buf, sizeof buf, "gemm_nt_cs_kernel<%d,%d>", mask, pro);
-        it = names.emplace(mask | pro << 8, buf).first;
+        if (K == 768) snprintf(buf, sizeof buf, "gemm_nt_cs_kernel<%d,%d,12>", mask, pro);
+        else snprintf(buf, sizeof buf, "gemm_nt_cs_kernel<%d,%d>", mask, pro);
+        it = names.emplace(key, buf).first;
     }
     return it->second.c_str();
 }
-template <int MASK, int PRO>
+typedef void (*cs_kernel_t)(const bf16*, const bf16*, bf16*, int, int, EpiArgs);
+template <int MASK, int PRO, int NST = 8>
 static int cs_launch(const void* A, const void* Bt, void* C, int M, int ldb, const EpiArgs& ea, hipStream_t s) {
+    cs_kernel_t kern;
+    if constexpr (NST == 8) kern = gemm_nt_cs_kernel<MASK, PRO>; else kern = gemm_nt_cs_kernel<MASK, PRO, NST>;
+    constexpr int lds = CS_LDS(64 * NST);
     static int ready = 0;          // dynamic LDS above 64 KB needs the attribute once per kernel
-    if (!ready) ready = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_cs_kernel<MASK, PRO>), hipFuncAttributeMaxDynamicSharedMemorySize, CS_LDS) == hipSuccess ? 1 : -1;
-    if (ready < 0) { ishara_set_error("gemm_nt_cs: %d bytes of LDS refused", CS_LDS); return -1; }
-    hipLaunchKernelGGL((gemm_nt_cs_kernel<MASK, PRO>), dim3((M + CS_ROWS - 1) / CS_ROWS), dim3(512), CS_LDS, s, (const bf16*)A, (const bf16*)Bt, (bf16*)C, M, ldb, ea);
+    if (!ready) ready = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess ? 1 : -1;
+    if (ready < 0) { ishara_set_error("gemm_nt_cs: %d bytes of LDS refused", lds); return -1; }
+    hipLaunchKernelGGL(kern, dim3((M + CS_ROWS - 1) / CS_ROWS), dim3(512), lds, s, (const bf16*)A, (const bf16*)Bt, (bf16*)C, M, ldb, ea);
     return launch_rc();
 }
 // returns 1 when the call is not one this kernel takes
@@ -371,6 +397,7 @@ int launch_gemm_nt_cs(int dtC, const void* A, const void* Bt, void* C, int M, in
     EpiArgs ea = ea_in;
     ea.as_flags = cs_flags(ea_in);
     const int mask = cs_mask_of(ea);
+    if (K == 768) return cs_launch<0, 0, 12>(A, Bt, C, M, ldb, ea, s);
     if (ea.pa_P) return mask == CS_RESID ? cs_launch<CS_RESID, 2>(A, Bt, C, M, ldb, ea, s) : cs_launch<CS_RESID | CS_ROWSCALE, 2>(A, Bt, C, M, ldb, ea, s);
     if (mask == 0) return cs_launch<0, 0>(A, Bt, C, M, ldb, ea, s);
     if (mask == CS_RESID) return cs_launch<CS_RESID, 0>(A, Bt, C, M, ldb, ea, s);

@@ -582,7 +582,7 @@ NtRoute gemm_nt_route(int dtA, int dtM, int dtC, int op, const void* A, int M, i
     if (g_force_regstage == 0 && gemm_nt_big_applicable(dtA, dtM, dtC, op, A, M, N, K, ldb, ea)) return NT_BIG;       // config #4's compute-heavy shapes: the 256 x 256 two-operand tile (gemm_big.hip)
     const int bk = dtM == DT_BF16 ? 32 : 16;     // K tile of the LDS-DMA kernels
     const bool dma_ok = op == OP_NONE && dtA == dtM && K % bk == 0 && ldb % (2 * bk) == 0 && ((uintptr_t)A) % 16 == 0;
-    if (dma_ok && g_force_regstage == 0 && dtM == DT_BF16 && gemm_nt_cs_applicable(dtC, M, N, K, ldb, ea)) return NT_CS;                  // K = 512 -> N = 256 at training-size M: the C-stationary kernel (gemm_cs.hip)
+    if (dma_ok && g_force_regstage == 0 && dtM == DT_BF16 && gemm_nt_cs_applicable(dtC, M, N, K, ldb, ea)) return NT_CS;                  // K = 512 / 768 -> N = 256 at training-size M: the C-stationary kernel (gemm_cs.hip)
     if (dma_ok && g_force_regstage == 0 && dtM == DT_BF16 && gemm_nt_as_applicable(dtC, M, N, K, ldb, ea)) return NT_AS;
     const bool dma_dt = (dtM == DT_F32 && dtC == DT_F32) || (dtM == DT_BF16 && (dtC == DT_BF16 || dtC == DT_F32));       // the output types the LDS-DMA tile kernels are compiled for
     if (dma_ok && dma_dt && (g_force_regstage == 0 || g_force_regstage == 3) && N % 4 == 0 && (ea.mode != EPI_QKV || ea.dh % 4 == 0)) return NT_TILE_T;
@@ -640,7 +640,7 @@ const char* gemm_nt_kernel_name(int dtA, int dtM, int dtC, int op, const void* A
     if (dtM == DT_F16) return "gemm_nt_kernel<f16>";
     switch (route) {
         case NT_BIG: return "gemm_nt_big_kernel<bf16>";
-        case NT_CS: return gemm_nt_cs_name(ea);
+        case NT_CS: return gemm_nt_cs_name(K, ea);
         case NT_AS: return gemm_nt_as_name(dtC, K, ea, M, N);
         case NT_TILE_T: return dtM == DT_F32 ? "gemm_nt_t_kernel<f32,f32>" : (dtC == DT_F32 ? "gemm_nt_t_kernel<bf16,f32>" : "gemm_nt_t_kernel<bf16,bf16>");
         case NT_GLDS: return dtM == DT_F32 ? "gemm_nt_glds_kernel<f32,f32>" : (dtC == DT_F32 ? "gemm_nt_glds_kernel<bf16,f32>" : "gemm_nt_glds_kernel<bf16,bf16>");

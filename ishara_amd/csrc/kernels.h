@@ -75,9 +75,10 @@ bool gemm_nt_as_prologue_ok(int dtA, int dtM, int dtC, int M, int N, int K, int 
 const char* gemm_nt_as_name(int dtC, int K, const EpiArgs& ea, int M, int N);
 int launch_gemm_nt_as(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);
 int launch_gemm_nt_as_f16(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);   // gemm_as_f16.hip
-// the C-stationary kernel of the K = 512 -> N = 256 projections at training-size M (gemm_cs.hip; as_flags bit 6 turns the route on, bit 7 drops the row threshold)
+// the C-stationary kernel of the K = 512 -> N = 256 projections and the K = 768 -> N = 256 plain dgrad at training-size M (gemm_cs.hip; as_flags bit 6 turns
+// the route on, bit 7 drops the row threshold, bit 8 keeps K = 768 on the tile kernel)
 bool gemm_nt_cs_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);
-const char* gemm_nt_cs_name(const EpiArgs& ea);
+const char* gemm_nt_cs_name(int K, const EpiArgs& ea);
 int launch_gemm_nt_cs(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);
 bool gemm_nt_big_applicable(int dtA, int dtM, int dtC, int op, const void* A, int M, int N, int K, int ldb, const EpiArgs& ea);              // gemm_big.hip
 int launch_gemm_nt_big(int dtA, int dtM, int dtC, int op, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);

@@ -6,7 +6,8 @@ memory the chip has not touched for NB-1 launches — what a launch sees inside 
     python tools/gemm_cold.py [--as-flags 51,115] [--nt-only] [--shape 98304,512,256]
 
 --as-flags: ishara_debug_set_as_flags values to time the NT GEMMs under, one line each (51 the A-stationary kernels, 115 with the
-C-stationary route for K = 512 -> N = 256: the decision gate of gemm_cs.hip); default: the library default alone."""
+C-stationary route for K = 512 -> N = 256: the decision gate of gemm_cs.hip; 371 = 115 | 256 keeps K = 768 -> N = 256 on the tile kernel:
+`--nt-only --shape 98304,768,256 --as-flags 371,115` is that shape's gate); default: the library default alone."""
 import argparse, ctypes as C, sys, torch
 sys.path.insert(0, ".")
 from ishara_amd import _lib
@@ -16,6 +17,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--as-flags", default="-1")
 ap.add_argument("--nt-only", action="store_true")
 ap.add_argument("--shape", default="", help="M,K,N: this shape alone")
+ap.add_argument("--repeats", type=int, default=3, help="cold repeats per line: the minimum and max - min are printed")
 args = ap.parse_args()
 FLAGS = [int(f) for f in args.as_flags.split(",")]
 NB = 12
@@ -41,9 +43,10 @@ for (M, K, N) in SHAPES:
             f = lambda i, rot: lib.ishara_op_dense_fwd_ex(1, _lib.ptr(xs[i % NB if rot else 0]), _lib.ptr(W), _lib.ptr(b), _lib.ptr(rs[i % NB if rot else 0]) if resid else None,
                                                           _lib.ptr(ys[i % NB if rot else 0]), M, K, N, act, scp, st())
             w = min(timeit(lambda i: f(i, False), 24) for _ in range(3))
-            c = min(timeit(lambda i: f(i, True), 24) for _ in range(3))
-            out[name] = (w, c)
-        print(f"NT  M{M} K{K} N{N} as_flags {flags}: " + "  ".join(f"{k}: warm {w:.1f} cold {c:.1f} us" for k, (w, c) in out.items()), flush=True)
+            cs = [timeit(lambda i: f(i, True), 24) for _ in range(args.repeats)]
+            out[name] = (w, min(cs), max(cs) - min(cs))
+        kern = lib.ishara_debug_dense_kernel_name(1, M, K, N, 0, 0).decode()
+        print(f"NT  M{M} K{K} N{N} as_flags {flags} ({kern}): " + "  ".join(f"{k}: warm {w:.1f} cold {c:.1f} us (spread of {args.repeats} repeats {sp:.1f})" for k, (w, c, sp) in out.items()), flush=True)
     lib.ishara_debug_set_as_flags(-1)
     if args.nt_only:
         del xs, ys, rs

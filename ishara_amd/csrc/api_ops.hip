@@ -538,7 +538,7 @@ extern "C" int ishara_op_attn_bwd(int32_t dt, const void* o, const void* dout, v
                            impl == 2 ? nullptr : a.maskw, s);
 }
 
-// ---- operator tests: the torch Squeezeformer family's own kernels (squeezeformer_r4.hip), through the launch code the encoder uses.
+// ---- operator tests: the torch Squeezeformer family's own kernels (r4_subsample.hip, relattn_len.hip), through the launch code the encoder uses.
 // The family has no fp16 kernels: every entry point refuses ISHARA_F16.  Shapes, null and alignment are checked before any HIP call;
 // every output, the parameter gradients included, is overwritten.
 static bool op_r4_dt_ok(const char* op, int dt) {
@@ -561,7 +561,7 @@ struct RelAttnScratch {
     }
 };
 static const char* relattn_shape_error(int B, int H, int T, int dh, float rate) {
-    if (dh != 8 && dh != 16 && dh != 32 && dh != 64) return "head dim unsupported (8, 16, 32, 64)";
+    if (!relattn_head_dim_ok(dh)) return "head dim unsupported (" RELATTN_HEAD_DIMS ")";
     if (B < 1 || H < 1 || T < 1) return "B, H and T must be >= 1";
     if ((int64_t)B * H > 65535 || (int64_t)B * H * T * dh > 2147483647LL || (2 * (int64_t)T - 1) * H * dh > 2147483647LL) return "shape too large (B*H <= 65535, B*H*T*dh < 2^31)";
     if (!(rate >= 0.f && rate < 1.f)) return "rate outside [0, 1)";
@@ -571,14 +571,24 @@ extern "C" int64_t ishara_op_relattn_scratch_bytes(int32_t B, int32_t H, int32_t
     if (relattn_shape_error(B, H, T, dh, 0.f)) return -1;
     return (int64_t)RelAttnScratch(B, H, T, dh).total;
 }
-extern "C" int ishara_op_relattn_fwd(int32_t dt, const void* q, const void* k, const void* v, const float* pe, const float* Wpos, const float* u, const float* vb,
-                                     void* o, float* lse, int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate, void* scratch, ishara_stream st) {
-    const char* me = "ishara_op_relattn_fwd";
+// ---- the two pairs of entry points, one body each.  ishara_op_relattn_fwd / _bwd: no lengths (key_len NULL: every key).  ishara_relattn_len_fwd /
+// _bwd: key_len device int32 [B], the keys j >= clamp(key_len[b], 0, T) of clip b are masked for every query and head; route: 0 the plan's
+// choice (relattn_route), 1 the fp32 lane kernels.  The checks and messages are the same, then key_len and route where lengths are taken.
+// The second pair is named outside the ishara_op_ prefix: it takes key lengths, which no other operator entry point does
+static int relattn_len_refused(const char* me, const int32_t* key_len, int32_t route) {
+    if (!key_len || (uintptr_t)key_len % 4) { ishara_set_error("%s: null or misaligned key_len: an int32 array [B]", me); return -1; }
+    if (route != 0 && route != 1) { ishara_set_error("%s: route %d unknown (0 the plan's choice, 1 the fp32 lane kernels)", me, route); return -1; }
+    return 0;
+}
+static int relattn_fwd_op(const char* me, bool lengths, int32_t dt, const void* q, const void* k, const void* v, const float* pe, const float* Wpos, const float* u, const float* vb,
+                          void* o, float* lse, int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
+                          const int32_t* key_len, int32_t route, void* scratch, ishara_stream st) {
     OP_R4_DT(me, dt);
     if (const char* why = relattn_shape_error(B, H, T, dh, rate)) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d rate=%g: %s", me, B, H, T, dh, rate, why); return -1; }
     if (op_any_null({q, k, v, pe, Wpos, u, vb, o, scratch}) || op_misaligned({q, k, v, pe, Wpos, u, vb, o, lse, scratch})) {
         ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only lse may be NULL)", me); return -1;
     }
+    if (lengths && relattn_len_refused(me, key_len, route)) return -1;
     hipStream_t s = (hipStream_t)st;
     const int d = H * dh, R = 2 * T - 1;
     const OpShadow sh(dt, d, d, R);
@@ -590,85 +600,21 @@ extern "C" int ishara_op_relattn_fwd(int32_t dt, const void* q, const void* k, c
     else HIP_CHECK_RET(hipMemcpyAsync(sc + a.pedt, pe, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, s));
     OpArgs no; EpiArgs e0;
     CK(launch_gemm_nt(dt, dt, DT_F32, OP_NONE, sc + a.pedt, sc + sh.wt, sc + a.posp, R, d, d, sh.ldt, no, e0, s));      // r4_mhsa_fwd's pos_proj
-    CK(launch_relattn_fwd(dt, q, k, v, (const float*)(sc + a.posp), u, vb, o, (float*)(sc + a.lse), B, H, T, dh, 1.0f / sqrtf((float)dh), make_drop_attn(seed, site, rate, true), s));
-    if (lse) HIP_CHECK_RET(hipMemcpyAsync(lse, sc + a.lse, (size_t)B * H * T * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
-extern "C" int ishara_op_relattn_bwd(int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
-                                     void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
-                                     int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate, void* scratch, ishara_stream st) {
-    const char* me = "ishara_op_relattn_bwd";
-    OP_R4_DT(me, dt);
-    if (const char* why = relattn_shape_error(B, H, T, dh, rate)) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d rate=%g: %s", me, B, H, T, dh, rate, why); return -1; }
-    if (op_any_null({q, k, v, u, vb, o, dO, dq, dk, dv, du, dvb, dWpos, scratch}) || op_misaligned({q, k, v, u, vb, o, dO, dq, dk, dv, du, dvb, dWpos, dposp, scratch})) {
-        ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only dposp may be NULL)", me); return -1;
-    }
-    hipStream_t s = (hipStream_t)st;
-    const int d = H * dh, R = 2 * T - 1;
-    const OpShadow sh(dt, d, d, R);
-    const RelAttnScratch a(B, H, T, dh);
-    char* sc = (char*)scratch;
-    float* dp = (float*)(sc + a.dposp);
-    CK(r4_fill_f32_launch(dp, (size_t)R * d, 0.f, s));
-    CK(r4_fill_f32_launch(du, (size_t)d, 0.f, s));
-    CK(r4_fill_f32_launch(dvb, (size_t)d, 0.f, s));
-    CK(r4_fill_f32_launch(dWpos, (size_t)d * d, 0.f, s));
-    CK(launch_relattn_bwd(dt, q, k, v, (const float*)(sc + a.posp), u, vb, o, dO, (const float*)(sc + a.lse), (float*)(sc + a.delta), dq, dk, dv, du, dvb, dp,
-                          B, H, T, dh, 1.0f / sqrtf((float)dh), make_drop_attn(seed, site, rate, true), s));
-    OpArgs no;
-    CK(launch_gemm_tn(dt, DT_F32, dt, OP_NONE, OP_NONE, sc + a.pedt, dp, dWpos, nullptr, (float*)(sc + sh.slab), R, d, d, no, no, s));      // r4_mhsa_bwd's pos_proj weight gradient
-    if (dposp) HIP_CHECK_RET(hipMemcpyAsync(dposp, dp, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
-
-// ---- the same pair with per-clip key lengths (relattn_len.hip): key_len device int32 [B], the keys j >= clamp(key_len[b], 0, T) of clip b are
-// masked for every query and head.  route: 0 the plan's choice (relattn_route), 1 the fp32 lane kernels.  The checks and messages of the pair
-// above, then key_len and route.  Named outside the ishara_op_ prefix: these take key lengths, which no other operator entry point does
-extern "C" int64_t ishara_relattn_len_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh) { return ishara_op_relattn_scratch_bytes(B, H, T, dh); }
-extern "C" const char* ishara_debug_relattn_kernel_name(int32_t dt, int32_t backward, int32_t T, int32_t dh, int32_t masked) {
-    return relattn_kernel_name(relattn_route(dt, T, dh, masked != 0), backward != 0);
-}
-static int relattn_len_refused(const char* me, const int32_t* key_len, int32_t route) {
-    if (!key_len || (uintptr_t)key_len % 4) { ishara_set_error("%s: null or misaligned key_len: an int32 array [B]", me); return -1; }
-    if (route != 0 && route != 1) { ishara_set_error("%s: route %d unknown (0 the plan's choice, 1 the fp32 lane kernels)", me, route); return -1; }
-    return 0;
-}
-extern "C" int ishara_relattn_len_fwd(int32_t dt, const void* q, const void* k, const void* v, const float* pe, const float* Wpos, const float* u, const float* vb,
-                                      void* o, float* lse, int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
-                                      const int32_t* key_len, int32_t route, void* scratch, ishara_stream st) {
-    const char* me = "ishara_relattn_len_fwd";
-    OP_R4_DT(me, dt);
-    if (const char* why = relattn_shape_error(B, H, T, dh, rate)) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d rate=%g: %s", me, B, H, T, dh, rate, why); return -1; }
-    if (op_any_null({q, k, v, pe, Wpos, u, vb, o, scratch}) || op_misaligned({q, k, v, pe, Wpos, u, vb, o, lse, scratch})) {
-        ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only lse may be NULL)", me); return -1;
-    }
-    if (relattn_len_refused(me, key_len, route)) return -1;
-    hipStream_t s = (hipStream_t)st;
-    const int d = H * dh, R = 2 * T - 1;
-    const OpShadow sh(dt, d, d, R);
-    const RelAttnScratch a(B, H, T, dh);
-    char* sc = (char*)scratch;
-    CK(sh.build(dt, Wpos, d, d, sc, s));
-    if (dt != DT_F32) CK(r5_from_f32(dt, pe, sc + a.pedt, (size_t)R * d, s));
-    else HIP_CHECK_RET(hipMemcpyAsync(sc + a.pedt, pe, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-    OpArgs no; EpiArgs e0;
-    CK(launch_gemm_nt(dt, dt, DT_F32, OP_NONE, sc + a.pedt, sc + sh.wt, sc + a.posp, R, d, d, sh.ldt, no, e0, s));
     CK(launch_relattn_len_fwd(dt, q, k, v, (const float*)(sc + a.posp), u, vb, o, (float*)(sc + a.lse), key_len, route == 1, B, H, T, dh, 1.0f / sqrtf((float)dh),
                               make_drop_attn(seed, site, rate, true), s));
     if (lse) HIP_CHECK_RET(hipMemcpyAsync(lse, sc + a.lse, (size_t)B * H * T * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
 }
-extern "C" int ishara_relattn_len_bwd(int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
-                                      void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
-                                      int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
-                                      const int32_t* key_len, int32_t route, void* scratch, ishara_stream st) {
-    const char* me = "ishara_relattn_len_bwd";
+static int relattn_bwd_op(const char* me, bool lengths, int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
+                          void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
+                          int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
+                          const int32_t* key_len, int32_t route, void* scratch, ishara_stream st) {
     OP_R4_DT(me, dt);
     if (const char* why = relattn_shape_error(B, H, T, dh, rate)) { ishara_set_error("%s: B=%d H=%d T=%d dh=%d rate=%g: %s", me, B, H, T, dh, rate, why); return -1; }
     if (op_any_null({q, k, v, u, vb, o, dO, dq, dk, dv, du, dvb, dWpos, scratch}) || op_misaligned({q, k, v, u, vb, o, dO, dq, dk, dv, du, dvb, dWpos, dposp, scratch})) {
         ishara_set_error("%s: null or misaligned buffer (all 16-byte aligned; only dposp may be NULL)", me); return -1;
     }
-    if (relattn_len_refused(me, key_len, route)) return -1;
+    if (lengths && relattn_len_refused(me, key_len, route)) return -1;
     hipStream_t s = (hipStream_t)st;
     const int d = H * dh, R = 2 * T - 1;
     const OpShadow sh(dt, d, d, R);
@@ -680,11 +626,35 @@ extern "C" int ishara_relattn_len_bwd(int32_t dt, const void* q, const void* k, 
     CK(r4_fill_f32_launch(dvb, (size_t)d, 0.f, s));
     CK(r4_fill_f32_launch(dWpos, (size_t)d * d, 0.f, s));
     CK(launch_relattn_len_bwd(dt, q, k, v, (const float*)(sc + a.posp), u, vb, o, dO, (const float*)(sc + a.lse), (float*)(sc + a.delta), dq, dk, dv, du, dvb, dp,
-                              key_len, route == 1, B, H, T, dh, 1.0f / sqrtf((float)dh), make_drop_attn(seed, site, rate, true), s));
+                              key_len, B, H, T, dh, 1.0f / sqrtf((float)dh), make_drop_attn(seed, site, rate, true), s));      // the route's one backward
     OpArgs no;
-    CK(launch_gemm_tn(dt, DT_F32, dt, OP_NONE, OP_NONE, sc + a.pedt, dp, dWpos, nullptr, (float*)(sc + sh.slab), R, d, d, no, no, s));
+    CK(launch_gemm_tn(dt, DT_F32, dt, OP_NONE, OP_NONE, sc + a.pedt, dp, dWpos, nullptr, (float*)(sc + sh.slab), R, d, d, no, no, s));      // r4_mhsa_bwd's pos_proj weight gradient
     if (dposp) HIP_CHECK_RET(hipMemcpyAsync(dposp, dp, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
+}
+extern "C" int ishara_op_relattn_fwd(int32_t dt, const void* q, const void* k, const void* v, const float* pe, const float* Wpos, const float* u, const float* vb,
+                                     void* o, float* lse, int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate, void* scratch, ishara_stream st) {
+    return relattn_fwd_op("ishara_op_relattn_fwd", false, dt, q, k, v, pe, Wpos, u, vb, o, lse, B, H, T, dh, seed, site, rate, nullptr, 0, scratch, st);
+}
+extern "C" int ishara_op_relattn_bwd(int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
+                                     void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
+                                     int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate, void* scratch, ishara_stream st) {
+    return relattn_bwd_op("ishara_op_relattn_bwd", false, dt, q, k, v, u, vb, o, dO, dq, dk, dv, du, dvb, dWpos, dposp, B, H, T, dh, seed, site, rate, nullptr, 0, scratch, st);
+}
+extern "C" int64_t ishara_relattn_len_scratch_bytes(int32_t B, int32_t H, int32_t T, int32_t dh) { return ishara_op_relattn_scratch_bytes(B, H, T, dh); }
+extern "C" const char* ishara_debug_relattn_kernel_name(int32_t dt, int32_t backward, int32_t T, int32_t dh, int32_t masked) {
+    return relattn_kernel_name(relattn_route(dt, T, dh, masked != 0), backward != 0);
+}
+extern "C" int ishara_relattn_len_fwd(int32_t dt, const void* q, const void* k, const void* v, const float* pe, const float* Wpos, const float* u, const float* vb,
+                                      void* o, float* lse, int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
+                                      const int32_t* key_len, int32_t route, void* scratch, ishara_stream st) {
+    return relattn_fwd_op("ishara_relattn_len_fwd", true, dt, q, k, v, pe, Wpos, u, vb, o, lse, B, H, T, dh, seed, site, rate, key_len, route, scratch, st);
+}
+extern "C" int ishara_relattn_len_bwd(int32_t dt, const void* q, const void* k, const void* v, const float* u, const float* vb, const void* o, const void* dO,
+                                      void* dq, void* dk, void* dv, float* du, float* dvb, float* dWpos, float* dposp,
+                                      int32_t B, int32_t H, int32_t T, int32_t dh, uint32_t seed, uint32_t site, float rate,
+                                      const int32_t* key_len, int32_t route, void* scratch, ishara_stream st) {
+    return relattn_bwd_op("ishara_relattn_len_bwd", true, dt, q, k, v, u, vb, o, dO, dq, dk, dv, du, dvb, dWpos, dposp, B, H, T, dh, seed, site, rate, key_len, route, scratch, st);
 }
 
 // DepthwiseConv2dSubsampling.  scratch: y1 | dz1, both [B, d, T1, F1] f32

@@ -266,7 +266,7 @@ int r5_to_f32(int dt, const void* x, float* y, size_t n, hipStream_t s);
 int r5_validate(const ishara_config& c);
 void r5_build_graph(ishara_model* m);
 void r5_plan_workspace(ishara_model* m);
-// torch Squeezeformer family (squeezeformer_r4.hip)
+// torch Squeezeformer family (squeezeformer_r4.hip; its kernels: r4_subsample.hip, relattn_len.hip, relattn_mfma.hip)
 int r4_validate(const ishara_config& c);
 void r4_build_graph(ishara_model* m);
 void r4_plan_workspace(ishara_model* m);
@@ -276,27 +276,27 @@ int r4_output_frames(const ishara_model* m);
 // input_len: device int32 [B], input frames per clip (ishara_encoder_forward_lengths / _backward_lengths); nullptr: the unmasked pass
 int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t training, uint32_t seed, hipStream_t st, const int32_t* input_len = nullptr);
 int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStream_t st, const int32_t* input_len = nullptr);
-// its launch code, shared with the operator entry points (api_ops.hip ishara_op_relattn_* / ishara_op_r4_*)
-struct R4Dims { int T1, F1, T2, F2, T3, Fr, Kp; };      // frames / features after each 3x3 stride-2 convolution, the time-reduction conv's width and its padded K
-R4Dims r4_dims(int T0, int F, int d);
-int launch_relattn_fwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
-                       int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
-int launch_relattn_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
-                       const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
-                       int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
-// the same with per-clip key lengths (relattn_len.hip): which kernels a call runs is stated once, by relattn_route; key_len nullptr is the
-// unmasked route, the two launches above
-enum { RELATTN_REFUSED = 0, RELATTN_LANE = 1, RELATTN_LANE_LEN = 2, RELATTN_MFMA_LEN = 3 };      // MFMA_LEN: MFMA forward (relattn_mfma.hip), lane backward
+// its launch code, shared with the operator entry points (api_ops.hip ishara_op_relattn_* / ishara_relattn_len_* / ishara_op_r4_*)
+// relative-position attention (relattn_len.hip, relattn_mfma.hip).  The head dims the kernels are instantiated for, stated once
+#define RELATTN_HEAD_DIMS "8, 16, 32, 64"
+inline bool relattn_head_dim_ok(int dh) { return dh == 8 || dh == 16 || dh == 32 || dh == 64; }
+// which kernels a call runs is stated once, by relattn_route; key_len nullptr (masked = false) is the call without lengths: every key
+enum { RELATTN_REFUSED = 0, RELATTN_LANE = 1, RELATTN_MFMA_LEN = 3 };      // LANE: the fp32 lane kernels; MFMA_LEN: MFMA forward (relattn_mfma.hip), lane backward
 struct RelAttnRoute { int kind = RELATTN_REFUSED; const char* why = ""; };
 RelAttnRoute relattn_route(int dt, int T, int dh, bool masked);
 const char* relattn_kernel_name(const RelAttnRoute& r, bool backward);
+// force_lane: the lane forward where the route would choose the MFMA one (the backward has one route)
 int launch_relattn_len_fwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
                            const int* key_len, bool force_lane, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
 int launch_relattn_len_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
                            const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
-                           const int* key_len, bool force_lane, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
+                           const int* key_len, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
 int launch_relattn_len_fwd_mfma(const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
                                 const int* key_len, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s);
+// subsampling, time reduction, row maps and stage lengths (r4_subsample.hip)
+struct R4Dims { int T1, F1, T2, F2, T3, Fr, Kp; };      // frames / features after each 3x3 stride-2 convolution, the time-reduction conv's width and its padded K
+R4Dims r4_dims(int T0, int F, int d);
+enum { R4_ROWS_RECOVER = 0, R4_ROWS_CROP = 1, R4_ROWS_RECOVER_BWD = 2, R4_ROWS_CROP_BWD = 3, R4_ROWS_ADD = 4 };      // r4_rows_mode_launch's modes; the integers are the ABI of ishara_op_r4_rows
 int r4_stage_len_launch(const int* L, int* out, int B, int T0, int T2, int T3, int Trec, hipStream_t s);      // int32 [3][B]: keys at T2, T3, Trec
 int r4_subsample_fwd_launch(int dt, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y1, void* sub,
                             int B, int T0, int F, int d, int T1, int F1, int T2, int F2, hipStream_t s);

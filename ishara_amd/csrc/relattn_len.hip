@@ -1,39 +1,25 @@
-// Relative-position attention of the torch Squeezeformer family WITH PER-CLIP KEY LENGTHS (the padding mask of
-// RelativeMultiHeadAttention.forward(..., mask), attention.py:75-92, in its (batch, 1, time2) form): the keys j >= n[b] of clip b are masked for
-// every query and head, n[b] = clamp(key_len[b], 0, T).  The reference fills those scores with -1e9; in fp32 exp underflows to exactly 0 for a
-// clip with at least one valid key, so the kernels SKIP the keys instead: every key loop sweeps ceil(n[b] / RL_KT) chunks only and no K / V row
-// at or past n[b] is read into a sum (they are staged as zero).  Query rows past n[b] are computed like any other: only keys are masked.
+// The fp32 lane kernels of the torch Squeezeformer family's relative-position attention (RelativeMultiHeadAttention.forward, attention.py:75-92),
+// forward and three backward passes: one thread per query (forward, dq) / key (dk, dv) / table row (dpos), the other side streamed through LDS
+// in chunks, no [T, T] matrix in memory; the backward passes recompute the probabilities from the saved log-sum-exp.
+//   q, k, v [B*T, d] (head h in columns h*DH ..), posp [2T-1, d] f32 (pos_proj of the table), u, vb [d] f32.
+//   score(i,j) = scale * ((q_i+u).k_j + (q_i+vb).posp[T-1-i+j]) (`_relative_shift`, attention.py:102-110, in closed form); softmax over j;
+//   inverted dropout on the probabilities (row key (b*H+h)*T+i, column = key, 8-bit threshold).
+// PER-CLIP KEY LENGTHS (the padding mask in its (batch, 1, time2) form): the keys j >= n[b] of clip b are masked for every query and head,
+// n[b] = clamp(key_len[b], 0, T); a null key_len means every key, n[b] = T (attn_key_count, kernels.h): the call without lengths runs these same
+// kernels.  The reference fills the masked scores with -1e9; in fp32 exp underflows to exactly 0 for a clip with at least one valid key, so the
+// kernels SKIP the keys instead: every key loop sweeps ceil(n[b] / RL_KT) chunks only and no K / V row at or past n[b] is read into a sum (they
+// are staged as zero).  Query rows past n[b] are computed like any other: only keys are masked.
 //   n[b] = 0 (a dead clip): o = 0, lse = ATT_DEAD_LSE, dq = 0, and its dO reaches neither dk / dv nor du / dvb / dposp.  The reference's fill
 //   would average the padding uniformly there; zeros are this library's convention ("Fully masked rows").
 //   Every output is overwritten: the dk / dv rows of the keys >= n[b] are exact zeros (a workgroup holding only such keys sweeps nothing).
-// The four kernels are the fp32 lane kernels of squeezeformer_r4.hip (one thread per query / key / table row, the other side streamed through
-// LDS, same arithmetic in the same order, same dropout hash: row key (b*H+h)*T+i, column = key, 8-bit threshold) with the bound n[b] in place of
-// T on the key side: at n[b] = T they compute bit for bit what relattn_fwd / _bwd_dq / _bwd_dkv compute (tests/test_relattn_len_gpu.py).
-// du / dvb / dposp are fp32 atomics into zero-filled buffers, as in the parent kernels.
-// Which kernels a call runs is stated once, by relattn_route below; the unmasked call keeps its route and its kernels.
+// du / dvb / dposp are fp32 atomics into buffers the caller has zero-filled.
+// Which kernels a call runs is stated once, by relattn_route below; the MFMA forward of the masked bf16 call is relattn_mfma.hip.
 #include "model_types.h"
 
-#define RL_QB 64      // threads per workgroup = queries / keys / table rows per workgroup (RA_QB of squeezeformer_r4.hip)
-#define RL_KT 32      // rows of the streamed side per chunk (RA_KT)
+#define RL_QB 64      // threads per workgroup = queries / keys / table rows per workgroup
+#define RL_KT 32      // rows of the streamed side per chunk
 
 template <typename T> DEVI float rl_ldf(const T* p) { return to_f(*p); }
-
-// ------------------------------------------------------------------ stage lengths
-// input frames L[b] -> keys of each attention resolution, the reference's own arithmetic, clamped, on the device (the host never reads them):
-//   n2 = clamp((L >> 2) - 1, 0, T2) (convolution.py:68-71), n3 = clamp((n2 >> 1) - 1, 0, T3) (:266-268), nrec = clamp(2 * n3, 0, Trec) (encoder.py:162)
-// out int32 [3][B]
-__global__ void r4_stage_len_kernel(const int* __restrict__ L, int* __restrict__ out, int B, int T0, int T2, int T3, int Trec) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int l = min(max(L[b], 0), T0);
-    const int n2 = min(max((l >> 2) - 1, 0), T2);
-    const int n3 = min(max((n2 >> 1) - 1, 0), T3);
-    out[b] = n2; out[B + b] = n3; out[2 * B + b] = min(max(2 * n3, 0), Trec);
-}
-int r4_stage_len_launch(const int* L, int* out, int B, int T0, int T2, int T3, int Trec, hipStream_t s) {
-    hipLaunchKernelGGL(r4_stage_len_kernel, dim3((B + 63) / 64), dim3(64), 0, s, L, out, B, T0, T2, T3, Trec);
-    return launch_rc();
-}
 
 // ------------------------------------------------------------------ forward
 template <typename T, int DH>
@@ -225,7 +211,7 @@ __global__ __launch_bounds__(RL_QB) void relattn_len_bwd_dkv_kernel(const T* __r
 }
 
 // ------------------------------------------------------------------ dposp: one thread per table row, the (i, j) pairs with T-1-i+j == r and j < n[b]
-// A length-aware fp32 gather kernel, like its parent (there is no MFMA dposp yet)
+// A length-aware fp32 gather kernel (there is no MFMA dposp yet)
 template <typename T, int DH>
 __global__ __launch_bounds__(RL_QB) void relattn_len_bwd_dpos_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const float* __restrict__ posp,
                                                                      const float* __restrict__ u, const float* __restrict__ vb, const T* __restrict__ dO,
@@ -280,24 +266,21 @@ __global__ __launch_bounds__(RL_QB) void relattn_len_bwd_dpos_kernel(const T* __
 }
 
 // ------------------------------------------------------------------ the route, stated once
-// masked = per-clip key lengths given.  The unmasked call runs the four relattn_* kernels of squeezeformer_r4.hip, as before this file existed.
-// The masked call: bf16 at head dim 32 / 64 runs the MFMA forward of relattn_mfma.hip and the length-aware lane backward above; everything else
-// the family has (f32, bf16 at dh 8 / 16, any T >= 1) runs the length-aware lane kernels, forward too.  MFMA dq / dkv / dposp: DESIGN.md §8
+// masked = per-clip key lengths given.  The masked bf16 call at head dim 32 / 64 runs the MFMA forward of relattn_mfma.hip and the lane backward
+// above; everything else the family has (the call without lengths at any dtype and head dim, f32, bf16 at dh 8 / 16, any T >= 1) runs the lane
+// kernels, forward too.  MFMA dq / dkv / dposp: DESIGN.md §8
 RelAttnRoute relattn_route(int dt, int T, int dh, bool masked) {
     RelAttnRoute r;
     if (dt != DT_F32 && dt != DT_BF16) { r.kind = RELATTN_REFUSED; r.why = "relative attention: f32 / bf16 only"; return r; }
-    if (dh != 8 && dh != 16 && dh != 32 && dh != 64) { r.kind = RELATTN_REFUSED; r.why = "relative attention: head dim unsupported (8, 16, 32, 64)"; return r; }
+    if (!relattn_head_dim_ok(dh)) { r.kind = RELATTN_REFUSED; r.why = "relative attention: head dim unsupported (" RELATTN_HEAD_DIMS ")"; return r; }
     if (T < 1) { r.kind = RELATTN_REFUSED; r.why = "relative attention: T must be >= 1"; return r; }
-    r.kind = !masked ? RELATTN_LANE : ((dt == DT_BF16 && (dh == 32 || dh == 64)) ? RELATTN_MFMA_LEN : RELATTN_LANE_LEN);
+    r.kind = (masked && dt == DT_BF16 && (dh == 32 || dh == 64)) ? RELATTN_MFMA_LEN : RELATTN_LANE;
     return r;
 }
 const char* relattn_kernel_name(const RelAttnRoute& r, bool backward) {
-    switch (r.kind) {
-        case RELATTN_LANE: return backward ? "relattn_bwd_dq_kernel+relattn_bwd_dkv_kernel+relattn_bwd_dpos_kernel" : "relattn_fwd_kernel";
-        case RELATTN_LANE_LEN: return backward ? "relattn_len_bwd_dq_kernel+relattn_len_bwd_dkv_kernel+relattn_len_bwd_dpos_kernel" : "relattn_len_fwd_kernel";
-        case RELATTN_MFMA_LEN: return backward ? "relattn_len_bwd_dq_kernel+relattn_len_bwd_dkv_kernel+relattn_len_bwd_dpos_kernel" : "relattn_len_fwd_mfma_kernel";
-        default: return "";
-    }
+    if (r.kind != RELATTN_LANE && r.kind != RELATTN_MFMA_LEN) return "";
+    if (backward) return "relattn_len_bwd_dq_kernel+relattn_len_bwd_dkv_kernel+relattn_len_bwd_dpos_kernel";
+    return r.kind == RELATTN_MFMA_LEN ? "relattn_len_fwd_mfma_kernel" : "relattn_len_fwd_kernel";
 }
 
 #define RL_DISPATCH(KERNEL, TT, grid, s, ...)                                                                           \
@@ -305,48 +288,36 @@ const char* relattn_kernel_name(const RelAttnRoute& r, bool backward) {
         case 8: hipLaunchKernelGGL((KERNEL<TT, 8>), grid, dim3(RL_QB), 0, s, __VA_ARGS__); break;                        \
         case 16: hipLaunchKernelGGL((KERNEL<TT, 16>), grid, dim3(RL_QB), 0, s, __VA_ARGS__); break;                      \
         case 32: hipLaunchKernelGGL((KERNEL<TT, 32>), grid, dim3(RL_QB), 0, s, __VA_ARGS__); break;                      \
-        default: hipLaunchKernelGGL((KERNEL<TT, 64>), grid, dim3(RL_QB), 0, s, __VA_ARGS__); break;                      \
+        case 64: hipLaunchKernelGGL((KERNEL<TT, 64>), grid, dim3(RL_QB), 0, s, __VA_ARGS__); break;                      \
+        default: ishara_set_error("relative attention: head dim %d unsupported (" RELATTN_HEAD_DIMS ")", dh); return -1; \
     }
 
-// key_len NULL: the unmasked route (the parent's launch).  force_lane: the operator entry points' `route` = 1, the lane kernels where the plan
-// would choose the MFMA forward
+// key_len NULL: every key.  force_lane: the operator entry points' `route` = 1, the lane kernels where the route would choose the MFMA forward
 int launch_relattn_len_fwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
                            const int* key_len, bool force_lane, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s) {
-    RelAttnRoute r = relattn_route(dt, T, dh, key_len != nullptr);
-    if (force_lane && r.kind == RELATTN_MFMA_LEN) r.kind = RELATTN_LANE_LEN;
-    switch (r.kind) {
-        case RELATTN_MFMA_LEN: return launch_relattn_len_fwd_mfma(q, k, v, posp, u, vb, o, lse, key_len, B, H, T, dh, scale, drop, s);
-        case RELATTN_LANE: return launch_relattn_fwd(dt, q, k, v, posp, u, vb, o, lse, B, H, T, dh, scale, drop, s);
-        case RELATTN_LANE_LEN: {
-            const dim3 grid((T + RL_QB - 1) / RL_QB, B * H);
-            if (dt == DT_BF16) { RL_DISPATCH(relattn_len_fwd_kernel, bf16, grid, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (bf16*)o, lse, key_len, H, T, scale, drop) }
-            else { RL_DISPATCH(relattn_len_fwd_kernel, float, grid, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (float*)o, lse, key_len, H, T, scale, drop) }
-            return launch_rc();
-        }
-        default: ishara_set_error("%s", r.why); return -1;
-    }
+    const RelAttnRoute r = relattn_route(dt, T, dh, key_len != nullptr);
+    if (r.kind == RELATTN_REFUSED) { ishara_set_error("%s", r.why); return -1; }
+    if (r.kind == RELATTN_MFMA_LEN && !force_lane) return launch_relattn_len_fwd_mfma(q, k, v, posp, u, vb, o, lse, key_len, B, H, T, dh, scale, drop, s);
+    const dim3 grid((T + RL_QB - 1) / RL_QB, B * H);
+    if (dt == DT_BF16) { RL_DISPATCH(relattn_len_fwd_kernel, bf16, grid, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (bf16*)o, lse, key_len, H, T, scale, drop) }
+    else { RL_DISPATCH(relattn_len_fwd_kernel, float, grid, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (float*)o, lse, key_len, H, T, scale, drop) }
+    return launch_rc();
 }
+// one backward for every route: the lane kernels
 int launch_relattn_len_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
                            const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
-                           const int* key_len, bool force_lane, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s) {
+                           const int* key_len, int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s) {
     const RelAttnRoute r = relattn_route(dt, T, dh, key_len != nullptr);
-    (void)force_lane;      // one masked backward: the lane kernels
-    switch (r.kind) {
-        case RELATTN_LANE: return launch_relattn_bwd(dt, q, k, v, posp, u, vb, o, dO, lse, delta, dq, dk, dv, du, dvb, dposp, B, H, T, dh, scale, drop, s);
-        case RELATTN_MFMA_LEN:
-        case RELATTN_LANE_LEN: {
-            const dim3 gq((T + RL_QB - 1) / RL_QB, B * H), gp((2 * T - 1 + RL_QB - 1) / RL_QB, B * H);
-            if (dt == DT_BF16) {
-                RL_DISPATCH(relattn_len_bwd_dq_kernel, bf16, gq, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)o, (const bf16*)dO, lse, delta, (bf16*)dq, du, dvb, key_len, H, T, scale, drop)
-                RL_DISPATCH(relattn_len_bwd_dkv_kernel, bf16, gq, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)dO, lse, (const float*)delta, (bf16*)dk, (bf16*)dv, key_len, H, T, scale, drop)
-                RL_DISPATCH(relattn_len_bwd_dpos_kernel, bf16, gp, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)dO, lse, (const float*)delta, dposp, key_len, H, T, scale, drop)
-            } else {
-                RL_DISPATCH(relattn_len_bwd_dq_kernel, float, gq, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)o, (const float*)dO, lse, delta, (float*)dq, du, dvb, key_len, H, T, scale, drop)
-                RL_DISPATCH(relattn_len_bwd_dkv_kernel, float, gq, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)dO, lse, (const float*)delta, (float*)dk, (float*)dv, key_len, H, T, scale, drop)
-                RL_DISPATCH(relattn_len_bwd_dpos_kernel, float, gp, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)dO, lse, (const float*)delta, dposp, key_len, H, T, scale, drop)
-            }
-            return launch_rc();
-        }
-        default: ishara_set_error("%s", r.why); return -1;
+    if (r.kind == RELATTN_REFUSED) { ishara_set_error("%s", r.why); return -1; }
+    const dim3 gq((T + RL_QB - 1) / RL_QB, B * H), gp((2 * T - 1 + RL_QB - 1) / RL_QB, B * H);
+    if (dt == DT_BF16) {
+        RL_DISPATCH(relattn_len_bwd_dq_kernel, bf16, gq, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)o, (const bf16*)dO, lse, delta, (bf16*)dq, du, dvb, key_len, H, T, scale, drop)
+        RL_DISPATCH(relattn_len_bwd_dkv_kernel, bf16, gq, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)dO, lse, (const float*)delta, (bf16*)dk, (bf16*)dv, key_len, H, T, scale, drop)
+        RL_DISPATCH(relattn_len_bwd_dpos_kernel, bf16, gp, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)dO, lse, (const float*)delta, dposp, key_len, H, T, scale, drop)
+    } else {
+        RL_DISPATCH(relattn_len_bwd_dq_kernel, float, gq, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)o, (const float*)dO, lse, delta, (float*)dq, du, dvb, key_len, H, T, scale, drop)
+        RL_DISPATCH(relattn_len_bwd_dkv_kernel, float, gq, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)dO, lse, (const float*)delta, (float*)dk, (float*)dv, key_len, H, T, scale, drop)
+        RL_DISPATCH(relattn_len_bwd_dpos_kernel, float, gp, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)dO, lse, (const float*)delta, dposp, key_len, H, T, scale, drop)
     }
+    return launch_rc();
 }

@@ -1,8 +1,8 @@
 // The torch Squeezeformer family of the reference (squeezeformer/{attention,modules,convolution,encoder}.py):
 //   R1  RelativeMultiHeadAttention (attention.py:25-110): Transformer-XL attention — content score (q + u_bias) . k plus positional score
 //       (q + v_bias) . p with p = pos_proj(RelPositionalEncoding); `_relative_shift` (:102-110) in closed form: the key j of query i
-//       reads row T-1-i+j of the [2T-1, d] table.  Flash-style kernels below (no [T, T] matrix in memory), forward and three backward
-//       passes (dq + du/dv, dk/dv, dpos) that recompute the probabilities from the saved log-sum-exp.
+//       reads row T-1-i+j of the [2T-1, d] table.  Flash-style kernels (relattn_len.hip, relattn_mfma.hip; no [T, T] matrix in memory),
+//       forward and three backward passes (dq + du/dv, dk/dv, dpos) that recompute the probabilities from the saved log-sum-exp.
 //   R2  RelPositionalEncoding (modules.py:59-108): table built on the host at create time (fp32 sin / cos, positions T-1 .. -(T-1)).
 //   R3  ConvModule (convolution.py:199-238): the ConfConv composition of keras_hybrid.hip with Swish after the BatchNorm, no depthwise bias.
 //   R4  post-LN SqueezeformerBlock (encoder.py:208-247) with the half-step FFN residual, DepthwiseConv2dSubsampling
@@ -10,6 +10,8 @@
 //       (encoder.py:135-166) with its ResidualConnectionModule around the reduced-rate blocks (:88-103).
 // Parameter entries carry the reference's state_dict keys, in state_dict order, arrays in the kernels' layout (Linear / pointwise
 // weights [in,out], 3x3 kernels [C,9], depthwise [k,d], u/v bias [d]); ishara_amd/squeezeformer.py converts to and from torch's.
+// This file is the encoder itself: state, graph, workspace plan, bind, forward, backward and the entry points with per-clip lengths.  Its own
+// kernels are in r4_subsample.hip (subsampling, time reduction, row maps, stage lengths) and relattn_len.hip / relattn_mfma.hip (attention).
 #include "model_types.h"
 
 static const float R4_EPS = 1e-5f;
@@ -31,566 +33,6 @@ struct R4State {
     std::vector<int> pe_T; std::vector<Buf> pe32, pedt; std::vector<std::vector<float>> pe_host;
 };
 
-// ------------------------------------------------------------------ small kernels
-template <typename T> DEVI float ldf(const T* p) { return to_f(*p); }
-
-// x [B,T0,F] f32 -> y1 [B,d,T1,F1] f32 = relu(conv3x3 s2)        (convolution.py:56)
-__global__ void r4_sub1_fwd(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ y1,
-                            int B, int T0, int F, int d, int T1, int F1) {
-    const size_t n = (size_t)B * d * T1 * F1;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int f1 = (int)(i % F1), t1 = (int)((i / F1) % T1), c = (int)((i / ((size_t)F1 * T1)) % d), bb = (int)(i / ((size_t)F1 * T1 * d));
-        float acc = b[c];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) acc += w[c * 9 + a * 3 + e] * x[((size_t)bb * T0 + 2 * t1 + a) * F + 2 * f1 + e];
-        y1[i] = fmaxf(acc, 0.f);
-    }
-}
-// y1 -> sub [B*T2, d*F2] (storage type) = relu(depthwise conv3x3 s2), channel-major features   (:58-66)
-template <typename T>
-__global__ void r4_sub2_fwd(const float* __restrict__ y1, const float* __restrict__ w, const float* __restrict__ b, T* __restrict__ sub,
-                            int B, int d, int T1, int F1, int T2, int F2) {
-    const size_t n = (size_t)B * T2 * d * F2;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int f2 = (int)(i % F2), c = (int)((i / F2) % d), t2 = (int)((i / ((size_t)F2 * d)) % T2), bb = (int)(i / ((size_t)F2 * d * T2));
-        float acc = b[c];
-        const float* src = y1 + (((size_t)bb * d + c) * T1) * F1;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) acc += w[c * 9 + a * 3 + e] * src[(size_t)(2 * t2 + a) * F1 + 2 * f2 + e];
-        sub[i] = from_f<T>(fmaxf(acc, 0.f));
-    }
-}
-// backward of the depthwise conv: dz2 = dsub * (sub > 0); dw2, db2 (atomics) and dy1 (scatter-free gather form)
-template <typename T>
-__global__ void r4_sub2_bwd_w(const T* __restrict__ dsub, const T* __restrict__ sub, const float* __restrict__ y1, float* __restrict__ dw, float* __restrict__ db,
-                              int B, int d, int T1, int F1, int T2, int F2) {
-    // one workgroup per channel: 10 sums over (b, t2, f2)
-    const int c = blockIdx.x;
-    float acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int n = B * T2 * F2;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int f2 = i % F2, t2 = (i / F2) % T2, bb = i / (F2 * T2);
-        const size_t o = (((size_t)bb * T2 + t2) * d + c) * F2 + f2;
-        const float g = ldf(sub + o) > 0.f ? ldf(dsub + o) : 0.f;
-        const float* src = y1 + (((size_t)bb * d + c) * T1) * F1;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) acc[a * 3 + e] += g * src[(size_t)(2 * t2 + a) * F1 + 2 * f2 + e];
-        acc[9] += g;
-    }
-    __shared__ float red[10][256];
-    for (int q = 0; q < 10; ++q) red[q][threadIdx.x] = acc[q];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) for (int q = 0; q < 10; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 9) dw[c * 9 + threadIdx.x] += red[threadIdx.x][0];
-    if (threadIdx.x == 9) db[c] += red[9][0];
-}
-template <typename T>
-__global__ void r4_sub2_bwd_x(const T* __restrict__ dsub, const T* __restrict__ sub, const float* __restrict__ w, const float* __restrict__ y1, float* __restrict__ dz1,
-                              int B, int d, int T1, int F1, int T2, int F2) {
-    // dz1[b,c,t1,f1] = (y1 > 0) * sum_{a,e: (t1-a)/2, (f1-e)/2 integral and in range} w[c,a,e] * dz2[b, (t1-a)/2, c, (f1-e)/2]
-    const size_t n = (size_t)B * d * T1 * F1;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int f1 = (int)(i % F1), t1 = (int)((i / F1) % T1), c = (int)((i / ((size_t)F1 * T1)) % d), bb = (int)(i / ((size_t)F1 * T1 * d));
-        float acc = 0.f;
-        if (y1[i] > 0.f) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const int tt = t1 - a;
-                if (tt < 0 || (tt & 1) || (tt >> 1) >= T2) continue;
-#pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    const int ff = f1 - e;
-                    if (ff < 0 || (ff & 1) || (ff >> 1) >= F2) continue;
-                    const size_t o = (((size_t)bb * T2 + (tt >> 1)) * d + c) * F2 + (ff >> 1);
-                    if (ldf(sub + o) > 0.f) acc += w[c * 9 + a * 3 + e] * ldf(dsub + o);
-                }
-            }
-        }
-        dz1[i] = acc;
-    }
-}
-// first conv backward: dw1[c,9], db1[c] from dz1 and x (one workgroup per channel); dx optional (atomic-free gather over channels is O(d): skipped unless asked)
-__global__ void r4_sub1_bwd_w(const float* __restrict__ dz1, const float* __restrict__ x, float* __restrict__ dw, float* __restrict__ db,
-                              int B, int T0, int F, int d, int T1, int F1) {
-    const int c = blockIdx.x;
-    float acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int n = B * T1 * F1;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int f1 = i % F1, t1 = (i / F1) % T1, bb = i / (F1 * T1);
-        const float g = dz1[(((size_t)bb * d + c) * T1 + t1) * F1 + f1];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) acc[a * 3 + e] += g * x[((size_t)bb * T0 + 2 * t1 + a) * F + 2 * f1 + e];
-        acc[9] += g;
-    }
-    __shared__ float red[10][256];
-    for (int q = 0; q < 10; ++q) red[q][threadIdx.x] = acc[q];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) for (int q = 0; q < 10; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 9) dw[c * 9 + threadIdx.x] += red[threadIdx.x][0];
-    if (threadIdx.x == 9) db[c] += red[9][0];
-}
-__global__ void r4_sub1_bwd_x(const float* __restrict__ dz1, const float* __restrict__ w, float* __restrict__ dx, int B, int T0, int F, int d, int T1, int F1) {
-    const size_t n = (size_t)B * T0 * F;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int f = (int)(i % F), t = (int)((i / F) % T0), bb = (int)(i / ((size_t)F * T0));
-        float acc = 0.f;
-        for (int a = 0; a < 3; ++a) {
-            const int tt = t - a;
-            if (tt < 0 || (tt & 1) || (tt >> 1) >= T1) continue;
-            for (int e = 0; e < 3; ++e) {
-                const int ff = f - e;
-                if (ff < 0 || (ff & 1) || (ff >> 1) >= F1) continue;
-                for (int c = 0; c < d; ++c) acc += w[c * 9 + a * 3 + e] * dz1[(((size_t)bb * d + c) * T1 + (tt >> 1)) * F1 + (ff >> 1)];
-            }
-        }
-        dx[i] = acc;
-    }
-}
-
-// TimeReductionLayer (convolution.py:241-269): one 3x3 stride-2 kernel over the (time, feature) plane of h [B,Tin,d], Swish;
-// out [B*Tr, Kp] (columns >= Fr are zero padding of the following Linear's K), pre [B,Tr,Fr] f32 saved for the backward pass
-template <typename T>
-__global__ void r4_tred_fwd(const T* __restrict__ h, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ pre, T* __restrict__ out,
-                            int B, int Tin, int d, int Tr, int Fr, int Kp) {
-    const size_t n = (size_t)B * Tr * Kp;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int f = (int)(i % Kp), t = (int)((i / Kp) % Tr), bb = (int)(i / ((size_t)Kp * Tr));
-        if (f >= Fr) { out[i] = from_f<T>(0.f); continue; }
-        float acc = b[0];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) acc += w[a * 3 + e] * ldf(h + ((size_t)bb * Tin + 2 * t + a) * d + 2 * f + e);
-        pre[((size_t)bb * Tr + t) * Fr + f] = acc;
-        out[i] = from_f<T>(swishf_(acc));
-    }
-}
-template <typename T>
-__global__ void r4_tred_bwd_w(const T* __restrict__ dout, const float* __restrict__ pre, const T* __restrict__ h, float* __restrict__ dw, float* __restrict__ db,
-                              int B, int Tin, int d, int Tr, int Fr, int Kp) {
-    float acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const size_t n = (size_t)B * Tr * Fr;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int f = (int)(i % Fr), t = (int)((i / Fr) % Tr), bb = (int)(i / ((size_t)Fr * Tr));
-        const float g = ldf(dout + ((size_t)bb * Tr + t) * Kp + f) * dswishf_(pre[i]);
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) acc[a * 3 + e] += g * ldf(h + ((size_t)bb * Tin + 2 * t + a) * d + 2 * f + e);
-        acc[9] += g;
-    }
-    __shared__ float red[10][256];
-    for (int q = 0; q < 10; ++q) red[q][threadIdx.x] = acc[q];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) for (int q = 0; q < 10; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 9) atomicAdd(&dw[threadIdx.x], red[threadIdx.x][0]);
-    if (threadIdx.x == 9) atomicAdd(&db[0], red[9][0]);
-}
-// dh[b,t,f] = extra[b,t,f] (gradient arriving through the recover skip, or 0) + sum_{a,e} w[a,e] * dz[b, (t-a)/2, (f-e)/2]
-template <typename T>
-__global__ void r4_tred_bwd_x(const T* __restrict__ dout, const float* __restrict__ pre, const float* __restrict__ w, const T* __restrict__ extra, T* __restrict__ dh,
-                              int B, int Tin, int d, int Tr, int Fr, int Kp) {
-    const size_t n = (size_t)B * Tin * d;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int f = (int)(i % d), t = (int)((i / d) % Tin), bb = (int)(i / ((size_t)d * Tin));
-        float acc = extra ? ldf(extra + i) : 0.f;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const int tt = t - a;
-            if (tt < 0 || (tt & 1) || (tt >> 1) >= Tr) continue;
-#pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                const int ff = f - e;
-                if (ff < 0 || (ff & 1) || (ff >> 1) >= Fr) continue;
-                const size_t o = ((size_t)bb * Tr + (tt >> 1));
-                acc += w[a * 3 + e] * ldf(dout + o * Kp + (ff >> 1)) * dswishf_(pre[o * Fr + (ff >> 1)]);
-            }
-        }
-        dh[i] = from_f<T>(acc);
-    }
-}
-// generic row maps over [B, Tdst, d]: MODE 0 dst[b,t] = src[b, t/2] (recover_resolution, src has Tsrc rows per sample);
-// MODE 1 dst[b,t] = src[b,t] for t < Tdst (crop of a longer sequence); MODE 2 dst[b,t] = src[b,2t] + src[b,2t+1] (backward of MODE 0);
-// MODE 3 dst[b,t] = t < Tsrc ? src[b,t] : 0 (backward of the crop into the longer sequence); MODE 4 dst = a + src (same shape)
-template <typename T, int MODE>
-__global__ void r4_rows(const T* __restrict__ src, const T* __restrict__ a, T* __restrict__ dst, int B, int Tdst, int Tsrc, int d) {
-    const size_t n = (size_t)B * Tdst * d;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int e = (int)(i % d), t = (int)((i / d) % Tdst), bb = (int)(i / ((size_t)d * Tdst));
-        float v;
-        if (MODE == 0) v = ldf(src + ((size_t)bb * Tsrc + (t >> 1)) * d + e);
-        else if (MODE == 1) v = ldf(src + ((size_t)bb * Tsrc + t) * d + e);
-        else if (MODE == 2) v = ldf(src + ((size_t)bb * Tsrc + 2 * t) * d + e) + ldf(src + ((size_t)bb * Tsrc + 2 * t + 1) * d + e);
-        else if (MODE == 3) v = t < Tsrc ? ldf(src + ((size_t)bb * Tsrc + t) * d + e) : 0.f;
-        else v = ldf(a + i) + ldf(src + i);
-        dst[i] = from_f<T>(v);
-    }
-}
-__global__ void r4_axpy_f32(const float* __restrict__ x, float* __restrict__ y, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] += x[i];
-}
-__global__ void r4_fill_f32(float* p, size_t n, float v) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
-}
-static int g1d(size_t n) { const size_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-template <int MODE>
-static int r4_rows_launch(int dt, const void* src, const void* a, void* dst, int B, int Tdst, int Tsrc, int d, hipStream_t s) {
-    const int grid = g1d((size_t)B * Tdst * d);
-    if (dt == DT_BF16) hipLaunchKernelGGL((r4_rows<bf16, MODE>), dim3(grid), dim3(256), 0, s, (const bf16*)src, (const bf16*)a, (bf16*)dst, B, Tdst, Tsrc, d);
-    else hipLaunchKernelGGL((r4_rows<float, MODE>), dim3(grid), dim3(256), 0, s, (const float*)src, (const float*)a, (float*)dst, B, Tdst, Tsrc, d);
-    return launch_rc();
-}
-int r4_rows_mode_launch(int dt, int mode, const void* src, const void* a, void* dst, int B, int Tdst, int Tsrc, int d, hipStream_t s) {
-    switch (mode) {
-        case 0: return r4_rows_launch<0>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
-        case 1: return r4_rows_launch<1>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
-        case 2: return r4_rows_launch<2>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
-        case 3: return r4_rows_launch<3>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
-        case 4: return r4_rows_launch<4>(dt, src, a, dst, B, Tdst, Tsrc, d, s);
-        default: ishara_set_error("r4_rows: unknown mode %d (0..4)", mode); return -1;
-    }
-}
-
-// typed launches of the small kernels
-#define R4_TYPED(dt, CALL) do { if ((dt) == DT_BF16) { typedef bf16 TT; CALL; } else { typedef float TT; CALL; } } while (0)
-
-// ---- the launches of the subsampling and time-reduction kernels, shared by the encoder (r4_forward / r4_backward) and the operator entry
-// points (api_ops.hip ishara_op_r4_*): grids included
-R4Dims r4_dims(int T0, int F, int d) {
-    R4Dims D;
-    D.T1 = (T0 - 3) / 2 + 1; D.F1 = (F - 3) / 2 + 1;
-    D.T2 = (D.T1 - 3) / 2 + 1; D.F2 = (D.F1 - 3) / 2 + 1;
-    D.T3 = (D.T2 - 3) / 2 + 1; D.Fr = (d - 1) / 2; D.Kp = (int)rup(D.Fr, 8);
-    return D;
-}
-// x [B,T0,F] f32 -> y1 [B,d,T1,F1] f32 -> sub [B*T2, d*F2] (dt)
-int r4_subsample_fwd_launch(int dt, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y1, void* sub,
-                            int B, int T0, int F, int d, int T1, int F1, int T2, int F2, hipStream_t s) {
-    hipLaunchKernelGGL(r4_sub1_fwd, dim3(g1d((size_t)B * d * T1 * F1)), dim3(256), 0, s, x, w1, b1, y1, B, T0, F, d, T1, F1);
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_fwd<TT>), dim3(g1d((size_t)B * T2 * d * F2)), dim3(256), 0, s, y1, w2, b2, (TT*)sub, B, d, T1, F1, T2, F2));
-    return launch_rc();
-}
-// dsub -> dw2, db2, dz1 (scratch [B,d,T1,F1] f32), dw1, db1 (all four accumulated) and dx (NULL: skipped)
-int r4_subsample_bwd_launch(int dt, const void* dsub, const void* sub, const float* y1, const float* x, const float* w1, const float* w2, float* dz1,
-                            float* dw1, float* db1, float* dw2, float* db2, float* dx, int B, int T0, int F, int d, int T1, int F1, int T2, int F2, hipStream_t s) {
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_bwd_w<TT>), dim3(d), dim3(256), 0, s, (const TT*)dsub, (const TT*)sub, y1, dw2, db2, B, d, T1, F1, T2, F2));
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_sub2_bwd_x<TT>), dim3(g1d((size_t)B * d * T1 * F1)), dim3(256), 0, s, (const TT*)dsub, (const TT*)sub, w2, y1, dz1, B, d, T1, F1, T2, F2));
-    hipLaunchKernelGGL(r4_sub1_bwd_w, dim3(d), dim3(256), 0, s, dz1, x, dw1, db1, B, T0, F, d, T1, F1);
-    if (dx) hipLaunchKernelGGL(r4_sub1_bwd_x, dim3(g1d((size_t)B * T0 * F)), dim3(256), 0, s, dz1, w1, dx, B, T0, F, d, T1, F1);
-    return launch_rc();
-}
-// h [B,Tin,d] (dt) -> pre [B,Tr,Fr] f32, out [B*Tr, Kp] (dt, pad columns zero)
-int r4_tred_fwd_launch(int dt, const void* h, const float* w, const float* b, float* pre, void* out, int B, int Tin, int d, int Tr, int Fr, int Kp, hipStream_t s) {
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_fwd<TT>), dim3(g1d((size_t)B * Tr * Kp)), dim3(256), 0, s, (const TT*)h, w, b, pre, (TT*)out, B, Tin, d, Tr, Fr, Kp));
-    return launch_rc();
-}
-// weight gradient of time_reduction_proj over the padded K (the pad columns of trout are zero, so are the rows >= Fr of the product): into the
-// [Kp, d] scratch dwred, then the Fr real rows are added to dW; the bias gradient is added to db
-int r4_tred_wgrad_launch(int dt, const void* trout, const void* g, float* dwred, float* dW, float* db, float* slab, int M, int Fr, int Kp, int d, hipStream_t s) {
-    OpArgs no;
-    hipLaunchKernelGGL(r4_fill_f32, dim3(g1d((size_t)Kp * d)), dim3(256), 0, s, dwred, (size_t)Kp * d, 0.f);
-    CK(launch_gemm_tn(dt, dt, dt, OP_NONE, OP_NONE, trout, g, dwred, db, slab, M, Kp, d, no, no, s));
-    hipLaunchKernelGGL(r4_axpy_f32, dim3(g1d((size_t)Fr * d)), dim3(256), 0, s, dwred, dW, (size_t)Fr * d);
-    return launch_rc();
-}
-// dout [B*Tr, Kp] (dt: gradient of the conv output) -> dw[9], db[1] (accumulated), dh [B,Tin,d] = extra (NULL: 0) + the input gradient
-int r4_tred_bwd_launch(int dt, const void* dout, const float* pre, const void* h, const float* w, const void* extra, float* dw, float* db, void* dh,
-                       int B, int Tin, int d, int Tr, int Fr, int Kp, hipStream_t s) {
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_bwd_w<TT>), dim3(64), dim3(256), 0, s, (const TT*)dout, pre, (const TT*)h, dw, db, B, Tin, d, Tr, Fr, Kp));
-    R4_TYPED(dt, hipLaunchKernelGGL((r4_tred_bwd_x<TT>), dim3(g1d((size_t)B * Tin * d)), dim3(256), 0, s, (const TT*)dout, pre, w, (const TT*)extra, (TT*)dh, B, Tin, d, Tr, Fr, Kp));
-    return launch_rc();
-}
-int r4_fill_f32_launch(float* p, size_t n, float v, hipStream_t s) {
-    hipLaunchKernelGGL(r4_fill_f32, dim3(g1d(n)), dim3(256), 0, s, p, n, v);
-    return launch_rc();
-}
-
-// ------------------------------------------------------------------ R1: relative-position attention
-// q, k, v [B*T, d] (head h in columns h*DH ..), posp [2T-1, d] f32 (pos_proj of the table), u, vb [d] f32.  One thread per query
-// (forward, dq) / key (dk, dv) / table row (dpos); the other side streams through LDS in chunks.  score(i,j) = scale * ((q_i+u).k_j +
-// (q_i+vb).posp[T-1-i+j]); softmax over j; inverted dropout on the probabilities (keyed by (b*H+h)*T+i, j).
-#define RA_QB 64      // threads per workgroup = queries / keys / table rows per workgroup
-#define RA_KT 32      // rows of the streamed side per chunk
-
-template <typename T, int DH>
-__global__ __launch_bounds__(RA_QB) void relattn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const float* __restrict__ posp,
-                                                            const float* __restrict__ u, const float* __restrict__ vb, T* __restrict__ o, float* __restrict__ lse,
-                                                            int H, int Tn, float scale, DropSpec drop) {
-    __shared__ float Ks[RA_KT][DH + 1], Vs[RA_KT][DH + 1], Ps[RA_KT + RA_QB - 1][DH + 1];
-    const int d = H * DH, bh = blockIdx.y, b = bh / H, h = bh % H, i0 = blockIdx.x * RA_QB, i = i0 + threadIdx.x;
-    const bool act = i < Tn;
-    float qu[DH], qv[DH], acc[DH];
-    {
-        const T* qp = q + ((size_t)b * Tn + (act ? i : 0)) * d + h * DH;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) { const float x = ldf(qp + e); qu[e] = x + u[h * DH + e]; qv[e] = x + vb[h * DH + e]; acc[e] = 0.f; }
-    }
-    float mx = -3.0e38f, l = 0.f;
-    const uint32_t rk = rng_row_key(drop.key, (uint32_t)(bh * Tn + i));
-    for (int j0 = 0; j0 < Tn; j0 += RA_KT) {
-        const int rbase = Tn - 1 - (i0 + RA_QB - 1) + j0;
-        __syncthreads();
-        for (int x = threadIdx.x; x < RA_KT * DH; x += RA_QB) {
-            const int jj = x / DH, e = x % DH, j = j0 + jj;
-            Ks[jj][e] = j < Tn ? ldf(k + ((size_t)b * Tn + j) * d + h * DH + e) : 0.f;
-            Vs[jj][e] = j < Tn ? ldf(v + ((size_t)b * Tn + j) * d + h * DH + e) : 0.f;
-        }
-        for (int x = threadIdx.x; x < (RA_KT + RA_QB - 1) * DH; x += RA_QB) {
-            const int rr = x / DH, e = x % DH, r = rbase + rr;
-            Ps[rr][e] = (r >= 0 && r < 2 * Tn - 1) ? posp[(size_t)r * d + h * DH + e] : 0.f;
-        }
-        __syncthreads();
-        if (!act) continue;
-        const int pr0 = i0 + RA_QB - 1 - i;
-        for (int jj = 0; jj < RA_KT && j0 + jj < Tn; ++jj) {
-            float s = 0.f;
-#pragma unroll
-            for (int e = 0; e < DH; ++e) s += qu[e] * Ks[jj][e] + qv[e] * Ps[pr0 + jj][e];
-            s *= scale;
-            const float mn = fmaxf(mx, s), corr = __expf(mx - mn), p = __expf(s - mn);
-            l = l * corr + p;
-            const float pd = (drop.thr == 0u || rng_keep_q(rk, (uint32_t)(j0 + jj), drop.thr)) ? p * drop.scale : 0.f;
-#pragma unroll
-            for (int e = 0; e < DH; ++e) acc[e] = acc[e] * corr + pd * Vs[jj][e];
-            mx = mn;
-        }
-    }
-    if (act) {
-        const float inv = 1.f / l;
-        T* op = o + ((size_t)b * Tn + i) * d + h * DH;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) op[e] = from_f<T>(acc[e] * inv);
-        lse[(size_t)bh * Tn + i] = mx + __logf(l);
-    }
-}
-
-// dq (content + positional parts), delta_i = rowsum(dO . O), and the u_bias / v_bias gradients (workgroup sums, then one atomic each)
-template <typename T, int DH>
-__global__ __launch_bounds__(RA_QB) void relattn_bwd_dq_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const float* __restrict__ posp,
-                                                               const float* __restrict__ u, const float* __restrict__ vb, const T* __restrict__ o, const T* __restrict__ dO,
-                                                               const float* __restrict__ lse, float* __restrict__ delta, T* __restrict__ dq,
-                                                               float* __restrict__ du, float* __restrict__ dvb, int H, int Tn, float scale, DropSpec drop) {
-    __shared__ float Ks[RA_KT][DH + 1], Vs[RA_KT][DH + 1], Ps[RA_KT + RA_QB - 1][DH + 1];
-    const int d = H * DH, bh = blockIdx.y, b = bh / H, h = bh % H, i0 = blockIdx.x * RA_QB, i = i0 + threadIdx.x;
-    const bool act = i < Tn;
-    float qu[DH], qv[DH], go[DH], dqc[DH], dqp[DH];
-    float D = 0.f, L = 0.f;
-    {
-        const size_t row = ((size_t)b * Tn + (act ? i : 0)) * d + h * DH;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) {
-            const float x = ldf(q + row + e);
-            qu[e] = x + u[h * DH + e]; qv[e] = x + vb[h * DH + e];
-            go[e] = act ? ldf(dO + row + e) : 0.f;
-            D += go[e] * ldf(o + row + e);
-            dqc[e] = 0.f; dqp[e] = 0.f;
-        }
-        if (act) { L = lse[(size_t)bh * Tn + i]; delta[(size_t)bh * Tn + i] = D; }
-    }
-    const uint32_t rk = rng_row_key(drop.key, (uint32_t)(bh * Tn + i));
-    for (int j0 = 0; j0 < Tn; j0 += RA_KT) {
-        const int rbase = Tn - 1 - (i0 + RA_QB - 1) + j0;
-        __syncthreads();
-        for (int x = threadIdx.x; x < RA_KT * DH; x += RA_QB) {
-            const int jj = x / DH, e = x % DH, j = j0 + jj;
-            Ks[jj][e] = j < Tn ? ldf(k + ((size_t)b * Tn + j) * d + h * DH + e) : 0.f;
-            Vs[jj][e] = j < Tn ? ldf(v + ((size_t)b * Tn + j) * d + h * DH + e) : 0.f;
-        }
-        for (int x = threadIdx.x; x < (RA_KT + RA_QB - 1) * DH; x += RA_QB) {
-            const int rr = x / DH, e = x % DH, r = rbase + rr;
-            Ps[rr][e] = (r >= 0 && r < 2 * Tn - 1) ? posp[(size_t)r * d + h * DH + e] : 0.f;
-        }
-        __syncthreads();
-        if (!act) continue;
-        const int pr0 = i0 + RA_QB - 1 - i;
-        for (int jj = 0; jj < RA_KT && j0 + jj < Tn; ++jj) {
-            float s = 0.f, dp = 0.f;
-#pragma unroll
-            for (int e = 0; e < DH; ++e) { s += qu[e] * Ks[jj][e] + qv[e] * Ps[pr0 + jj][e]; dp += go[e] * Vs[jj][e]; }
-            const float p = __expf(s * scale - L);
-            if (!(drop.thr == 0u || rng_keep_q(rk, (uint32_t)(j0 + jj), drop.thr))) dp = 0.f; else dp *= drop.scale;
-            const float dS = p * (dp - D) * scale;
-#pragma unroll
-            for (int e = 0; e < DH; ++e) { dqc[e] += dS * Ks[jj][e]; dqp[e] += dS * Ps[pr0 + jj][e]; }
-        }
-    }
-    if (act) {
-        T* dp_ = dq + ((size_t)b * Tn + i) * d + h * DH;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) dp_[e] = from_f<T>(dqc[e] + dqp[e]);
-    }
-    // u_bias gradient = sum over queries of the content part, v_bias gradient = of the positional part
-    __syncthreads();
-    float (*red)[DH + 1] = Ps;       // RA_QB rows available
-    for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-        for (int e = 0; e < DH; ++e) red[threadIdx.x][e] = act ? (pass == 0 ? dqc[e] : dqp[e]) : 0.f;
-        __syncthreads();
-        for (int e = threadIdx.x; e < DH; e += RA_QB) {
-            float s = 0.f;
-            for (int t = 0; t < RA_QB; ++t) s += red[t][e];
-            atomicAdd(&(pass == 0 ? du : dvb)[h * DH + e], s);
-        }
-        __syncthreads();
-    }
-}
-
-// dk, dv: one thread per key, queries streamed
-template <typename T, int DH>
-__global__ __launch_bounds__(RA_QB) void relattn_bwd_dkv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const float* __restrict__ posp,
-                                                                const float* __restrict__ u, const float* __restrict__ vb, const T* __restrict__ dO,
-                                                                const float* __restrict__ lse, const float* __restrict__ delta, T* __restrict__ dk, T* __restrict__ dv,
-                                                                int H, int Tn, float scale, DropSpec drop) {
-    __shared__ float Qs[RA_KT][DH + 1], Gs[RA_KT][DH + 1], Ps[RA_KT + RA_QB - 1][DH + 1], Ls[RA_KT], Ds[RA_KT];
-    const int d = H * DH, bh = blockIdx.y, b = bh / H, h = bh % H, j0 = blockIdx.x * RA_QB, j = j0 + threadIdx.x;
-    const bool act = j < Tn;
-    float kk[DH], vv[DH], ak[DH], av[DH], uu[DH], vbv[DH];
-    float uk = 0.f;
-    {
-        const size_t row = ((size_t)b * Tn + (act ? j : 0)) * d + h * DH;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) {
-            kk[e] = ldf(k + row + e); vv[e] = ldf(v + row + e); ak[e] = 0.f; av[e] = 0.f;
-            uu[e] = u[h * DH + e]; vbv[e] = vb[h * DH + e];
-            uk += uu[e] * kk[e];
-        }
-    }
-    for (int i0 = 0; i0 < Tn; i0 += RA_KT) {
-        // rows of the table this chunk needs: r = T-1-i+j for i in [i0, i0+KT), j in [j0, j0+QB): from T-1-(i0+KT-1)+j0
-        const int rbase = Tn - 1 - (i0 + RA_KT - 1) + j0;
-        __syncthreads();
-        for (int x = threadIdx.x; x < RA_KT * DH; x += RA_QB) {
-            const int ii = x / DH, e = x % DH, i = i0 + ii;
-            Qs[ii][e] = i < Tn ? ldf(q + ((size_t)b * Tn + i) * d + h * DH + e) : 0.f;
-            Gs[ii][e] = i < Tn ? ldf(dO + ((size_t)b * Tn + i) * d + h * DH + e) : 0.f;
-        }
-        for (int x = threadIdx.x; x < RA_KT; x += RA_QB) { const int i = i0 + x; Ls[x] = i < Tn ? lse[(size_t)bh * Tn + i] : 0.f; Ds[x] = i < Tn ? delta[(size_t)bh * Tn + i] : 0.f; }
-        for (int x = threadIdx.x; x < (RA_KT + RA_QB - 1) * DH; x += RA_QB) {
-            const int rr = x / DH, e = x % DH, r = rbase + rr;
-            Ps[rr][e] = (r >= 0 && r < 2 * Tn - 1) ? posp[(size_t)r * d + h * DH + e] : 0.f;
-        }
-        __syncthreads();
-        if (!act) continue;
-        for (int ii = 0; ii < RA_KT && i0 + ii < Tn; ++ii) {
-            const int pr = (RA_KT - 1 - ii) + (int)threadIdx.x;          // (T-1-(i0+ii)+j) - rbase
-            float s = uk, dp = 0.f;
-#pragma unroll
-            for (int e = 0; e < DH; ++e) { s += Qs[ii][e] * kk[e] + (Qs[ii][e] + vbv[e]) * Ps[pr][e]; dp += Gs[ii][e] * vv[e]; }
-            const float p = __expf(s * scale - Ls[ii]);
-            const bool keep = drop.thr == 0u || rng_keep_q(rng_row_key(drop.key, (uint32_t)(bh * Tn + i0 + ii)), (uint32_t)j, drop.thr);
-            const float pd = keep ? p * drop.scale : 0.f;
-            dp = keep ? dp * drop.scale : 0.f;
-            const float dS = p * (dp - Ds[ii]) * scale;
-#pragma unroll
-            for (int e = 0; e < DH; ++e) { ak[e] += dS * (Qs[ii][e] + uu[e]); av[e] += pd * Gs[ii][e]; }
-        }
-    }
-    if (act) {
-        const size_t row = ((size_t)b * Tn + j) * d + h * DH;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) { dk[row + e] = from_f<T>(ak[e]); dv[row + e] = from_f<T>(av[e]); }
-    }
-}
-
-// dposp[r, h*DH ..] += sum over the batch and over the (i, j) pairs with T-1-i+j == r of dS_ij * (q_i + vb): one thread per table row
-template <typename T, int DH>
-__global__ __launch_bounds__(RA_QB) void relattn_bwd_dpos_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const float* __restrict__ posp,
-                                                                 const float* __restrict__ u, const float* __restrict__ vb, const T* __restrict__ dO,
-                                                                 const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dposp,
-                                                                 int H, int Tn, float scale, DropSpec drop) {
-    __shared__ float Qs[RA_KT][DH + 1], Gs[RA_KT][DH + 1], Ks[RA_KT + RA_QB - 1][DH + 1], Vs[RA_KT + RA_QB - 1][DH + 1], Ls[RA_KT], Ds[RA_KT];
-    const int d = H * DH, bh = blockIdx.y, b = bh / H, h = bh % H, r0 = blockIdx.x * RA_QB, r = r0 + threadIdx.x;
-    const bool act = r < 2 * Tn - 1;
-    float pp[DH], acc[DH], uu[DH], vbv[DH];
-#pragma unroll
-    for (int e = 0; e < DH; ++e) { pp[e] = act ? posp[(size_t)r * d + h * DH + e] : 0.f; acc[e] = 0.f; uu[e] = u[h * DH + e]; vbv[e] = vb[h * DH + e]; }
-    for (int i0 = 0; i0 < Tn; i0 += RA_KT) {
-        // keys: j = i + r - (T-1) for i in [i0, i0+KT), r in [r0, r0+QB): from jbase = i0 + r0 - (T-1)
-        const int jbase = i0 + r0 - (Tn - 1);
-        __syncthreads();
-        for (int x = threadIdx.x; x < RA_KT * DH; x += RA_QB) {
-            const int ii = x / DH, e = x % DH, i = i0 + ii;
-            Qs[ii][e] = i < Tn ? ldf(q + ((size_t)b * Tn + i) * d + h * DH + e) : 0.f;
-            Gs[ii][e] = i < Tn ? ldf(dO + ((size_t)b * Tn + i) * d + h * DH + e) : 0.f;
-        }
-        for (int x = threadIdx.x; x < RA_KT; x += RA_QB) { const int i = i0 + x; Ls[x] = i < Tn ? lse[(size_t)bh * Tn + i] : 0.f; Ds[x] = i < Tn ? delta[(size_t)bh * Tn + i] : 0.f; }
-        for (int x = threadIdx.x; x < (RA_KT + RA_QB - 1) * DH; x += RA_QB) {
-            const int jj = x / DH, e = x % DH, j = jbase + jj;
-            const bool ok = j >= 0 && j < Tn;
-            Ks[jj][e] = ok ? ldf(k + ((size_t)b * Tn + j) * d + h * DH + e) : 0.f;
-            Vs[jj][e] = ok ? ldf(v + ((size_t)b * Tn + j) * d + h * DH + e) : 0.f;
-        }
-        __syncthreads();
-        if (!act) continue;
-        for (int ii = 0; ii < RA_KT && i0 + ii < Tn; ++ii) {
-            const int jl = ii + (int)threadIdx.x, j = jbase + jl;
-            if (j < 0 || j >= Tn) continue;
-            float s = 0.f, dp = 0.f;
-#pragma unroll
-            for (int e = 0; e < DH; ++e) { s += (Qs[ii][e] + uu[e]) * Ks[jl][e] + (Qs[ii][e] + vbv[e]) * pp[e]; dp += Gs[ii][e] * Vs[jl][e]; }
-            const float p = __expf(s * scale - Ls[ii]);
-            const bool keep = drop.thr == 0u || rng_keep_q(rng_row_key(drop.key, (uint32_t)(bh * Tn + i0 + ii)), (uint32_t)j, drop.thr);
-            dp = keep ? dp * drop.scale : 0.f;
-            const float dS = p * (dp - Ds[ii]) * scale;
-#pragma unroll
-            for (int e = 0; e < DH; ++e) acc[e] += dS * (Qs[ii][e] + vbv[e]);
-        }
-    }
-    if (act) {
-#pragma unroll
-        for (int e = 0; e < DH; ++e) atomicAdd(&dposp[(size_t)r * d + h * DH + e], acc[e]);
-    }
-}
-
-#define RA_DISPATCH(KERNEL, TT, grid, s, ...)                                                                           \
-    switch (dh) {                                                                                                       \
-        case 8: hipLaunchKernelGGL((KERNEL<TT, 8>), grid, dim3(RA_QB), 0, s, __VA_ARGS__); break;                        \
-        case 16: hipLaunchKernelGGL((KERNEL<TT, 16>), grid, dim3(RA_QB), 0, s, __VA_ARGS__); break;                      \
-        case 32: hipLaunchKernelGGL((KERNEL<TT, 32>), grid, dim3(RA_QB), 0, s, __VA_ARGS__); break;                      \
-        case 64: hipLaunchKernelGGL((KERNEL<TT, 64>), grid, dim3(RA_QB), 0, s, __VA_ARGS__); break;                      \
-        default: ishara_set_error("relative attention: head dim %d unsupported (8, 16, 32, 64)", dh); return -1;         \
-    }
-
-int launch_relattn_fwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, void* o, float* lse,
-                              int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s) {
-    const dim3 grid((T + RA_QB - 1) / RA_QB, B * H);
-    if (dt == DT_BF16) { RA_DISPATCH(relattn_fwd_kernel, bf16, grid, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (bf16*)o, lse, H, T, scale, drop) }
-    else { RA_DISPATCH(relattn_fwd_kernel, float, grid, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (float*)o, lse, H, T, scale, drop) }
-    return launch_rc();
-}
-int launch_relattn_bwd(int dt, const void* q, const void* k, const void* v, const float* posp, const float* u, const float* vb, const void* o, const void* dO,
-                              const float* lse, float* delta, void* dq, void* dk, void* dv, float* du, float* dvb, float* dposp,
-                              int B, int H, int T, int dh, float scale, DropSpec drop, hipStream_t s) {
-    const dim3 gq((T + RA_QB - 1) / RA_QB, B * H), gp((2 * T - 1 + RA_QB - 1) / RA_QB, B * H);
-    if (dt == DT_BF16) {
-        RA_DISPATCH(relattn_bwd_dq_kernel, bf16, gq, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)o, (const bf16*)dO, lse, delta, (bf16*)dq, du, dvb, H, T, scale, drop)
-        RA_DISPATCH(relattn_bwd_dkv_kernel, bf16, gq, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)dO, lse, (const float*)delta, (bf16*)dk, (bf16*)dv, H, T, scale, drop)
-        RA_DISPATCH(relattn_bwd_dpos_kernel, bf16, gp, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, posp, u, vb, (const bf16*)dO, lse, (const float*)delta, dposp, H, T, scale, drop)
-    } else {
-        RA_DISPATCH(relattn_bwd_dq_kernel, float, gq, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)o, (const float*)dO, lse, delta, (float*)dq, du, dvb, H, T, scale, drop)
-        RA_DISPATCH(relattn_bwd_dkv_kernel, float, gq, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)dO, lse, (const float*)delta, (float*)dk, (float*)dv, H, T, scale, drop)
-        RA_DISPATCH(relattn_bwd_dpos_kernel, float, gp, s, (const float*)q, (const float*)k, (const float*)v, posp, u, vb, (const float*)dO, lse, (const float*)delta, dposp, H, T, scale, drop)
-    }
-    return launch_rc();
-}
-
 // ------------------------------------------------------------------ construction
 static R5FFN r4_build_ffn(ishara_model* m, const std::string& mod, const std::string& ln, float factor) {
     R5FFN f;
@@ -608,7 +50,7 @@ int r4_validate(const ishara_config& c) {
     if (c.features < 7) { ishara_set_error("SqueezeformerEncoder: input_dim (features) must be >= 7 (two 3x3 stride-2 convolutions)"); return -1; }
     if (c.frames < 7) { ishara_set_error("SqueezeformerEncoder: frames must be >= 7"); return -1; }
     const int dh = c.dim / c.num_heads;
-    if (dh != 8 && dh != 16 && dh != 32 && dh != 64) { ishara_set_error("SqueezeformerEncoder: head dim %d unsupported (8, 16, 32, 64)", dh); return -1; }
+    if (!relattn_head_dim_ok(dh)) { ishara_set_error("SqueezeformerEncoder: head dim %d unsupported (" RELATTN_HEAD_DIMS ")", dh); return -1; }
     const int L = c.num_conv_conform_blocks;
     if (c.reduce_layer_index < L && c.recover_layer_index < L && c.recover_layer_index <= c.reduce_layer_index) { ishara_set_error("SqueezeformerEncoder: recover_layer_index must follow reduce_layer_index"); return -1; }
     if (c.reduce_layer_index >= L && c.recover_layer_index < L) { ishara_set_error("SqueezeformerEncoder: recover without reduce"); return -1; }
@@ -622,11 +64,10 @@ void r4_build_graph(ishara_model* m) {
     const ishara_config& c = m->cfg;
     const int d = m->d, L = c.num_conv_conform_blocks, k = c.transformer_kernel_size;
     S->T0 = c.frames; S->F = c.features;
-    S->T1 = (S->T0 - 3) / 2 + 1; S->F1 = (S->F - 3) / 2 + 1;
-    S->T2 = (S->T1 - 3) / 2 + 1; S->F2 = (S->F1 - 3) / 2 + 1;
+    const R4Dims D = r4_dims(S->T0, S->F, d);
+    S->T1 = D.T1; S->F1 = D.F1; S->T2 = D.T2; S->F2 = D.F2; S->T3 = D.T3; S->Fr = D.Fr; S->Kp = D.Kp; S->Trec = 2 * S->T3;
     S->reduce = c.reduce_layer_index < L ? c.reduce_layer_index : L;
     S->recover = c.recover_layer_index < L ? c.recover_layer_index : L;
-    S->T3 = (S->T2 - 3) / 2 + 1; S->Fr = (d - 1) / 2; S->Kp = (int)rup(S->Fr, 8); S->Trec = 2 * S->T3;
     S->w1 = m->addp("conv_subsample.sequential.0.weight", d, 9, true); S->b1 = m->addp("conv_subsample.sequential.0.bias", d, 0, true);
     S->w2 = m->addp("conv_subsample.sequential.2.conv.weight", d, 9, true); S->b2 = m->addp("conv_subsample.sequential.2.conv.bias", d, 0, true);
     S->Win = m->dense_named("input_proj.0.weight", "input_proj.0.bias", d * S->F2, d);
@@ -765,7 +206,7 @@ static int r4_mhsa_fwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, co
     const float scale = 1.0f / sqrtf((float)m->dh);
     CKP(m, "relattn_fwd", 4.0 * r.M * d * (double)dt_size(dt), 8.0 * r.B * m->H * (double)T * T * m->dh,
         launch_relattn_len_fwd(dt, m->W(a.q), m->W(a.k), m->W(a.vv), m->Wf(a.posp), m->P(a.u), m->P(a.v), m->W(a.o), m->Wf(a.lse), r.key_len, false, r.B, m->H, T, m->dh, scale,
-                               dspec_attn(r, a.site_attn, m->cfg.dropout_rate), m->s));      // r.key_len: this layer's keys per clip (nullptr: the unmasked route)
+                               dspec_attn(r, a.site_attn, m->cfg.dropout_rate), m->s));      // r.key_len: this layer's keys per clip (nullptr: every key)
     EpiArgs ep; ep.resid = x; ep.drop = dspec(r, a.site_out, m->cfg.dropout_rate);
     CK(gemm_fwd(m, a.Wo, m->W(a.o), dt, m->W(a.r), dt, r.M, OP_NONE, no, ep));
     return r5_ln_fwd(m, r, m->W(a.r), a.ln, m->W(a.out), a.mean, a.rstd);
@@ -801,8 +242,8 @@ int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t tra
             h = m->W(S->red); Tl = S->T3;
         }
         if (idx == S->recover) {           // recover_resolution + Linear + skip (encoder.py:157-162)
-            CK(r4_rows_launch<0>(dt, h, nullptr, m->W(S->rep), B, S->Trec, S->T3, d, m->s));
-            CK(r4_rows_launch<1>(dt, recover_src, nullptr, m->W(S->crop), B, S->Trec, S->T2, d, m->s));
+            CK(r4_rows_mode_launch(dt, R4_ROWS_RECOVER, h, nullptr, m->W(S->rep), B, S->Trec, S->T3, d, m->s));
+            CK(r4_rows_mode_launch(dt, R4_ROWS_CROP, recover_src, nullptr, m->W(S->crop), B, S->Trec, S->T2, d, m->s));
             EpiArgs er; er.resid = m->W(S->crop);
             CK(gemm_fwd(m, S->Wrec, m->W(S->rep), dt, m->W(S->rec), dt, B * S->Trec, OP_NONE, no, er));
             h = m->W(S->rec); Tl = S->Trec;
@@ -815,7 +256,7 @@ int r4_forward(ishara_model* m, const float* x, int32_t B, float* y, int32_t tra
         CK(confconv_fwd(m, L.conv, rl, m->W(L.ffn1.out)));
         CK(r5_ffn_fwd(m, L.ffn2, rl, m->W(L.conv.out)));
         const void* out = m->W(L.ffn2.out);
-        if (L.wrapped) { CK(r4_rows_launch<4>(dt, h, out, m->W(L.wrap_out), B, Tl, Tl, d, m->s)); out = m->W(L.wrap_out); }      // ResidualConnectionModule around the block
+        if (L.wrapped) { CK(r4_rows_mode_launch(dt, R4_ROWS_ADD, h, out, m->W(L.wrap_out), B, Tl, Tl, d, m->s)); out = m->W(L.wrap_out); }      // ResidualConnectionModule around the block
         h = out;
     }
     m->T = keepT;
@@ -840,7 +281,7 @@ static int r4_mhsa_bwd(ishara_model* m, R4State* S, R4Layer& L, const Run& r, co
     const float scale = 1.0f / sqrtf((float)m->dh);
     CKP(m, "relattn_bwd", 12.0 * r.M * d * (double)dt_size(dt), 24.0 * r.B * m->H * (double)T * T * m->dh,
         launch_relattn_len_bwd(dt, m->W(a.q), m->W(a.k), m->W(a.vv), m->Wf(a.posp), m->P(a.u), m->P(a.v), m->W(a.o), m->W(m->t1), m->Wf(a.lse), m->Wf(m->delta),
-                               m->W(S->dqb), m->W(S->dkb), m->W(S->dvb), m->G(a.u), m->G(a.v), m->Wf(S->dposp), r.key_len, false, r.B, m->H, T, m->dh, scale,
+                               m->W(S->dqb), m->W(S->dkb), m->W(S->dvb), m->G(a.u), m->G(a.v), m->Wf(S->dposp), r.key_len, r.B, m->H, T, m->dh, scale,
                                dspec_attn(r, a.site_attn, m->cfg.dropout_rate), m->s));
     // pos_proj weight gradient: table^T . dposp (no bias, the table itself has no gradient)
     CK(gemm_wgrad(m, a.Wpos, m->dt == DT_F32 ? (const void*)m->Wf(S->pe32[L.pe]) : (const void*)m->W(S->pedt[L.pe]), dt, OP_NONE, no, m->Wf(S->dposp), DT_F32, OP_NONE, no, 2 * T - 1));
@@ -894,13 +335,13 @@ int r4_backward(ishara_model* m, const float* dy, int32_t B, float* dx, hipStrea
         CK(confconv_bwd(m, L.conv, rl, m->W(L.ffn1.out), g, gn)); SWAP();
         CK(r5_ffn_bwd(m, L.ffn1, rl, m->W(L.mha.out), g, gn)); SWAP();
         CK(r4_mhsa_bwd(m, S, L, ra, lin[idx], g, gn)); SWAP();
-        if (L.wrapped) { CK(r4_rows_launch<4>(dt, m->W(S->gwrap), g, gn, B, Tl, Tl, d, m->s)); SWAP(); }
+        if (L.wrapped) { CK(r4_rows_mode_launch(dt, R4_ROWS_ADD, m->W(S->gwrap), g, gn, B, Tl, Tl, d, m->s)); SWAP(); }
         if (idx == S->recover) {           // g = gradient of rec = Linear(rep) + crop(recover_src)
-            CK(r4_rows_launch<3>(dt, g, nullptr, m->W(S->gskip), B, S->T2, S->Trec, d, m->s));        // into the longer pre-reduction sequence
+            CK(r4_rows_mode_launch(dt, R4_ROWS_CROP_BWD, g, nullptr, m->W(S->gskip), B, S->T2, S->Trec, d, m->s));        // into the longer pre-reduction sequence
             have_skip = true;
             CK(gemm_dgrad(m, S->Wrec, g, dt, m->W(m->t1), B * S->Trec, OP_NONE, no, e0));
             CK(gemm_wgrad(m, S->Wrec, m->W(S->rep), dt, OP_NONE, no, g, dt, OP_NONE, no, B * S->Trec));
-            CK(r4_rows_launch<2>(dt, m->W(m->t1), nullptr, gn, B, S->T3, S->Trec, d, m->s)); SWAP();
+            CK(r4_rows_mode_launch(dt, R4_ROWS_RECOVER_BWD, m->W(m->t1), nullptr, gn, B, S->T3, S->Trec, d, m->s)); SWAP();
         }
         if (idx == S->reduce) {            // g = gradient of red = Linear(swish(conv3x3(h)))
             DenseW wp = S->Wred; wp.K = S->Kp;

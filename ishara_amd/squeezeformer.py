@@ -1,7 +1,7 @@
 """Host-side mirror of the reference's torch Squeezeformer encoder — `squeezeformer/encoder.py:26-166` (`SqueezeformerEncoder`)
 with its relative-position attention (`attention.py:25-139`), convolution module (`convolution.py:199-238`), conv2d subsampling
-(`:39-73`), time reduction (`:241-269`) and recovery (`modules.py:137-142`) — on the HIP library (csrc/squeezeformer_r4.hip,
-family ISHARA_FAMILY_TORCH_SQUEEZEFORMER).
+(`:39-73`), time reduction (`:241-269`) and recovery (`modules.py:137-142`) — on the HIP library (csrc/squeezeformer_r4.hip; its kernels:
+csrc/r4_subsample.hip, csrc/relattn_len.hip, csrc/relattn_mfma.hip; family ISHARA_FAMILY_TORCH_SQUEEZEFORMER).
 
 `SqueezeformerEncoder(input_dim, encoder_dim, num_layers, reduce_layer_index, recover_layer_index, num_attention_heads, ...)` has
 the reference's constructor; `enc(inputs, input_lengths) -> (outputs, output_lengths)` its forward contract; `state_dict()` /

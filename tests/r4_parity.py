@@ -26,7 +26,7 @@ import module_parity as MP
 from oracle import rng
 from oracle import squeezeformer_torch_oracle as S
 
-# (B, H, T, dh): the smallest shapes that reach each tiling edge of the relattn_* kernels (RA_QB = 64 rows per workgroup, RA_KT = 32 per chunk)
+# (B, H, T, dh): the smallest shapes that reach each tiling edge of the relattn_len_* kernels (RL_QB = 64 rows per workgroup, RL_KT = 32 per chunk)
 RELATTN_CASES = [(2, 2, 1, 8), (2, 3, 31, 16), (1, 2, 33, 8), (2, 2, 64, 32), (2, 2, 65, 64), (3, 4, 97, 32), (1, 2, 130, 16)]
 SUB_CASES = [(1, 7, 7, 8), (2, 30, 16, 16), (3, 33, 23, 24), (2, 131, 80, 256)]       # (B, T0, F, d)
 TRED_CASES = [(2, 7, 16), (2, 8, 24), (3, 37, 64), (2, 98, 512)]                      # (B, Tin, d)

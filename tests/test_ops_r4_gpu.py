@@ -1,7 +1,8 @@
-"""The torch Squeezeformer family's own kernels (squeezeformer_r4.hip) against fp64, operator by operator, through the ishara_op_relattn_* /
-ishara_op_r4_* entry points, which run the launch code of ishara_encoder_forward / _backward:
+"""The torch Squeezeformer family's own kernels (relattn_len.hip, r4_subsample.hip) against fp64, operator by operator, through the
+ishara_op_relattn_* / ishara_op_r4_* entry points, which run the launch code of ishara_encoder_forward / _backward:
 
-  relattn_fwd_kernel, relattn_bwd_dq / _dkv / _dpos and the two mixed-dtype pos_proj GEMMs (storage-dtype table, fp32 output / fp32 dy, M = 2T-1)
+  relattn_len_fwd_kernel, relattn_len_bwd_dq / _dkv / _dpos without lengths (a NULL key_len: every key) and the two mixed-dtype pos_proj GEMMs
+  (storage-dtype table, fp32 output / fp32 dy, M = 2T-1)
   r4_sub1_* / r4_sub2_* (DepthwiseConv2dSubsampling), r4_tred_fwd / _bwd_w / _bwd_x with the Linear over the padded K and its weight gradient
   through the [Kp, d] scratch and r4_axpy_f32, the five row maps r4_rows<MODE>.
 

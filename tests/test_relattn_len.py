@@ -184,8 +184,8 @@ def test_the_operator_pair_makes_the_parent_checks_then_its_own(lib, name):
 @pytest.mark.parametrize("T", [1, 99, 198, 199])
 def test_route_names(lib, dt, dh, T):
     name = lambda bwd, masked: lib.ishara_debug_relattn_kernel_name(dt, bwd, T, dh, masked).decode()
-    assert name(0, 0) == "relattn_fwd_kernel"                                      # the unmasked call: the kernels of squeezeformer_r4.hip
-    assert name(1, 0) == "relattn_bwd_dq_kernel+relattn_bwd_dkv_kernel+relattn_bwd_dpos_kernel"
+    assert name(0, 0) == "relattn_len_fwd_kernel"                                  # the call without lengths: the lane kernels, at every dtype and head dim
+    assert name(1, 0) == "relattn_len_bwd_dq_kernel+relattn_len_bwd_dkv_kernel+relattn_len_bwd_dpos_kernel"
     mfma = dt == BF16 and dh in (32, 64)      # the MFMA forward: bf16 at head dim 32 / 64, any T
     assert name(0, 1) == ("relattn_len_fwd_mfma_kernel" if mfma else "relattn_len_fwd_kernel")
     assert name(1, 1) == "relattn_len_bwd_dq_kernel+relattn_len_bwd_dkv_kernel+relattn_len_bwd_dpos_kernel"

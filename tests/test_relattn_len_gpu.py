@@ -2,7 +2,7 @@
 and SqueezeformerEncoder / Squeezeformer with mask_padding=True (ishara_encoder_forward_lengths / _backward_lengths).
 
 Operator level (cases, references and bounds of tests/relattn_len_parity.py; tests/test_relattn_len_mutants.py shows the bounds reject ordinary
-mistakes): every case against fp64 in f32 and bf16, dropout 0 and 0.2; full lengths through the lane route bit-equal to ishara_op_relattn_*; the
+mistakes): every case against fp64 in f32 and bf16, dropout 0 and 0.2; ishara_op_relattn_* (a NULL key_len) bit-equal to full lengths through the lane route; the
 K / V rows at keys >= n[b] redrawn change no bit of o, lse, dq and the valid dk / dv rows, and the dk / dv rows past n[b] are exact zeros; a dead
 clip is zeros.
 Encoder level: both encoder cases against the masked fp64 restatement, full lengths against the plain call, a NULL input_len bit-equal to the
@@ -92,7 +92,9 @@ def test_attention_with_lengths_matches_fp64(lib, case, dtype, rate):
 @pytest.mark.parametrize("rate", L.RATES, ids=lambda r: f"drop{r}")
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("shape", [(2, 2, 65, 64), (3, 4, 97, 32), (1, 2, 33, 8)], ids=lambda c: "B%d-H%d-T%d-dh%d" % c)
-def test_full_lengths_through_the_lane_route_are_the_parent_kernels_bit_for_bit(lib, shape, dtype, rate):
+def test_a_null_key_len_is_full_lengths_through_the_lane_route_bit_for_bit(lib, shape, dtype, rate):
+    """ishara_op_relattn_* (key_len NULL: every key) against key_len = T and key_len = T + 7 (clamped) with route 1: the same lane kernels, the same
+    bits; and against fp64"""
     seed = _seed(shape, rate)
     want = run_relattn(lib, shape, dtype, seed, rate)
     got = run_len(lib, shape, (shape[2],) * shape[0], dtype, seed, rate, route=1)

@@ -2,7 +2,8 @@
 """What the Squeezeformer family's attention with per-clip lengths costs (profiles/r12_relattn_lengths.json).
 
 Operator level, bf16, H 8, dh 64, B 8, at T 199 and T 99 (the attention shapes of a T0 = 800 clip), forward and backward timed apart:
-  parent       ishara_op_relattn_fwd / _bwd: the unmasked fp32 lane kernels
+  parent       ishara_op_relattn_fwd / _bwd: no lengths (a NULL key_len), the fp32 lane kernels of relattn_len.hip.  In r12_relattn_lengths.json
+               this variant ran the lane kernels' earlier copies without the key_len argument; r13_relattn_one_lane_set.json compares the two
   len_full     ishara_relattn_len_fwd / _bwd with key_len = T, the plan's route (MFMA forward, length-aware lane backward)
   len_ragged   the same with lengths drawn uniformly in [T/2, T]
   lane_full    the same as len_full with route = 1: the length-aware lane kernels, forward too

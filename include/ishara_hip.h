@@ -262,6 +262,64 @@ int ishara_edit_alignment(const int32_t* out_idx, const int32_t* out_len, int32_
                           int32_t fallback, int32_t* ops, int32_t* aligned, int32_t* inserted, int32_t* confusion /* may be NULL */,
                           void* workspace, ishara_stream s);
 
+/* ---- streaming sessions (no reference counterpart: this text is the specification) --------------------------------------------------
+ * S sessions, one signer each, recognised while the sign is being made.  The state is caller-owned device memory, described by a struct of
+ * device pointers that is passed by address (as ishara_gemm_tn_call is); ALL-ZERO MEMORY IS S EMPTY SESSIONS, no init kernel exists:
+ *   raw       f32   [S, window, 276]  stored raw frames (16-byte aligned)      hand      u8  [S, window]  1 = that row has a hand
+ *   counters  int32 [S, 8]            n (stored frames), active (stored frames with a hand), idle (trailing run of stored frames without
+ *                                     one), dropped, done, n_hist, committed_len, 0
+ *   hist      int32 [S, agree, T]     the last `agree` hypotheses, oldest first, slots 0..n_hist-1 used, each padded with -1
+ *   hist_len  int32 [S, agree]        their lengths                             committed int32 [S, T]  the first committed_len are valid
+ * 1 <= window <= 8192, 1 <= T <= 4096, 2 <= agree <= 4, 0 <= S <= 65535 (S == 0: every call is a no-op).
+ * "Hand present" is the frame filter's predicate of ishara_preprocess: the 3 x 42 hand columns summed in that kernel's order with NaN read
+ * as 0, present iff the sum != 0 (hand values that cancel to exactly 0 are "absent", as in the filter).
+ * One tick per session, given a chunk of k >= 0 new frames and a flag word:
+ *  1. start   RESET set, or done set by the tick before: counters, history and committed_len become 0 (a phrase that ended restarts by
+ *             itself; a final is reported once).
+ *  2. append  frame by frame: while active == 0 a frame without a hand is not stored, dropped += 1; a frame arriving at n == window is
+ *             not stored, dropped += 1; any other is stored at row n with its hand byte, n += 1, and with a hand active += 1, idle = 0,
+ *             without one idle += 1.  fresh = a frame was stored this tick; full = n == window afterwards.
+ *  3. recognise  the stored frames are one clip: ishara_preprocess_sessions, ishara_forward(training = 0), ishara_greedy_decode or the
+ *             beam's top-1 -> hyp = idx[s, :len[s]] (an empty session is the empty clip).
+ *  4. agree   endpoint = active >= min_active_frames && idle >= idle_frames; final = FINISH || full || endpoint.  If fresh, hyp is pushed
+ *             into the history (a tick that stored nothing pushes nothing: a waiting session must not agree with itself).  If the history
+ *             then holds `agree` entries and their longest common prefix l exceeds committed_len: committed[committed_len:l] =
+ *             hyp[committed_len:l], committed_len = l; a committed symbol is never retracted or rewritten.  final: text = hyp, stable_len =
+ *             text_len = len, done = 1 (the offline result).  Otherwise text = committed[:committed_len] ++ hyp[committed_len:len] (the
+ *             committed part alone when len <= committed_len), stable_len = committed_len, text_len = max(committed_len, len) <= T.
+ * record [S, 8] int32 = flag bits (FRESH | FINAL | FULL | ENDPOINT | STARTED, STARTED = active > 0), n, active, idle, dropped, stable_len,
+ * text_len, 0; text [S, T] int32 padded with -1.  All three calls are one kernel each, graph-capturable, no allocation, no memset, no host
+ * read, no atomics: bit-identical from run to run.  Each refuses, with a message and before any HIP call: a null state, S / window / T /
+ * agree out of range, null or misaligned buffers, idle_frames < 1, min_active_frames < 0. */
+#define ISHARA_STREAM_COUNTERS 8
+#define ISHARA_STREAM_RECORD 8
+#define ISHARA_STREAM_RESET 1             /* flag word of a tick */
+#define ISHARA_STREAM_FINISH 2
+#define ISHARA_STREAM_FRESH 1             /* record[0] */
+#define ISHARA_STREAM_FINAL 2
+#define ISHARA_STREAM_FULL 4
+#define ISHARA_STREAM_ENDPOINT 8
+#define ISHARA_STREAM_STARTED 16
+typedef struct ishara_stream_state {
+    float* raw; uint8_t* hand; int32_t* counters; int32_t* hist; int32_t* hist_len; int32_t* committed;
+    int32_t S, window, T, agree;
+} ishara_stream_state;
+/* Steps 1-2: frames [n_total, 276] (16-byte aligned) holds the sessions' chunks back to back, chunk s = rows [offsets[s], offsets[s+1]) of a
+ * device int64 table [S+1] (clamped to the buffer, the idiom of ishara_preprocess_batch; a chunk may be empty or longer than window), flags
+ * [S] device int32 -> rows, hand bytes and counters of the state, fresh [S] int32.  Rows at and past n are not touched. */
+int ishara_stream_append(const ishara_stream_state* st, const float* frames, int64_t n_total, const int64_t* offsets,
+                         const int32_t* flags, int32_t* fresh, ishara_stream s);
+/* ishara_preprocess_batch for fixed-stride buffers: session s is rows [0, n[s * n_stride]) of raw + s * window * 276 (n clamped to 0..window;
+ * n_stride >= 1 lets n point into the counters: n = counters, n_stride = 8) -> out [S, T, 276], each session bit-identical to
+ * ishara_preprocess on the same frames.  hand [S, window] (may be NULL): one byte per frame, != 0 = hand present, as ishara_stream_append
+ * writes it; the kept-frame list is then built from the bytes.  NULL: the predicate is evaluated from raw.  raw and out 16-byte aligned. */
+int ishara_preprocess_sessions(const float* raw, const int32_t* n, int32_t n_stride, const uint8_t* hand, int32_t S, int32_t window,
+                               const float* mean, const float* stdv, float* out, int32_t T, ishara_stream s);
+/* Step 4 from the decoder's idx [S, T] / len [S] (len clamped to 0..T), the tick's flags [S] and the fresh [S] of ishara_stream_append:
+ * updates history, committed text, done; writes record [S, 8] and text [S, T]. */
+int ishara_stream_agree(const ishara_stream_state* st, const int32_t* idx, const int32_t* len, const int32_t* flags, const int32_t* fresh,
+                        int32_t idle_frames, int32_t min_active_frames, int32_t* record, int32_t* text, ishara_stream s);
+
 /* CTC prefix beam search (Hannun et al. 2014) with optional character-bigram shallow fusion; the semantics of ishara_amd/ctc_beam.py.
  * logits [B,T,C] fp32 (log_softmax taken on the device), blank index, beam width W, nbest <= W; lm [C,C] natural-log probabilities
  * (row = previous class, row blank = start of phrase; column = next class, column blank = end of phrase) or NULL; ranking key

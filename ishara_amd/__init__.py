@@ -7,6 +7,7 @@ from ._lib import IsharaError  # noqa: F401
 from .conformer import ConformerEncoder  # noqa: F401  (torch family: conformer/conformer.py)
 from .squeezeformer import Squeezeformer, SqueezeformerEncoder  # noqa: F401  (torch family: squeezeformer/encoder.py, model.py)
 from .tflite_batch import BatchedTFLiteModel  # noqa: F401  (batched raw-clip inference + device test-set scoring)
+from .tflite_stream import StreamingTFLiteModel, StreamReference, StreamResult  # noqa: F401  (streaming sessions: stable prefix, endpointing)
 from .ctc_beam import CharBigramLM, prefix_beam_search  # noqa: F401  (CTC prefix beam search: host reference, bigram LM)
 from .ctc_lm import CharNGramLM, LMAutomaton  # noqa: F401  (character n-gram LMs as automata, for the beam search's lm=)
 from . import ctc_align  # noqa: F401  (forced alignment: the module, callable as ctc_align(logits, labels, lengths))

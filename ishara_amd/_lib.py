@@ -75,6 +75,14 @@ class GemmNtCall(C.Structure):
     ]
 
 
+class StreamState(C.Structure):
+    """ishara_stream_state: the device arrays of S streaming sessions (field order of the header); passed by address."""
+    _fields_ = [
+        ("raw", C.c_void_p), ("hand", C.c_void_p), ("counters", C.c_void_p), ("hist", C.c_void_p), ("hist_len", C.c_void_p), ("committed", C.c_void_p),
+        ("S", C.c_int32), ("window", C.c_int32), ("T", C.c_int32), ("agree", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/ishara_hip.h declares
 _P, _I32, _I64, _U32, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 SIGNATURES = {
@@ -119,6 +127,9 @@ SIGNATURES = {
     "ishara_greedy_decode_ex": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "ishara_preprocess": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _P]),
     "ishara_preprocess_batch": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _I32, _P]),
+    "ishara_stream_append": (C.c_int, [C.POINTER(StreamState), _P, _I64, _P, _P, _P, _P]),
+    "ishara_preprocess_sessions": (C.c_int, [_P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _I32, _P]),
+    "ishara_stream_agree": (C.c_int, [C.POINTER(StreamState), _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "ishara_edit_distance": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P]),
     "ishara_edit_alignment_workspace_bytes": (_I64, [_I32, _I32]),
     "ishara_edit_alignment": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),

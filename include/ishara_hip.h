@@ -390,6 +390,25 @@ enum { ISHARA_LAYOUT_FLAT = 0, ISHARA_LAYOUT_HANDS_LIPS_XY = 1 };
  * over all T*124 values in fp64.  1 <= T <= 4096.  One kernel, graph-capturable, bit-identical from run to run. */
 int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips, int32_t B, int32_t T, int32_t layout,
                       float* x, ishara_stream s);
+/* ishara_clip_batch with the two augmentations of the reference's CTC training script (asl-translation-nb4.ipynb
+ * spatial_random_affine, temporal_mask; drawn by ishara_amd/data.py draw_augmentation_ex) and the per-clip frame count.  The affine
+ * is applied to the raw clip before the four augmentations of `base`, row-vector convention [x' y'] = [x y] * M + shift_xy:
+ * x' = f32(f64(M00) x + f64(M10) y + f64(shift_xy)), y' = f32(f64(M01) x + f64(M11) y + f64(shift_xy)), z untouched; the temporal
+ * mask zeroes whole augmented frames after them.  A zero frame (padding, shifted out, masked) and a dropped finger landmark stay
+ * exactly 0 before the normalisation: the shift is not added to them.  M = identity, shift_xy = 0, m0 == m1 is ishara_clip_batch's
+ * batch.  96 bytes, no padding. */
+typedef struct ishara_clip_aug_ex {
+    ishara_clip_aug base;
+    float m[4];                     /* M00, M01, M10, M11 */
+    float shift_xy;                 /* one scalar added to x' and y' */
+    int32_t m0, m1;                 /* temporal mask [m0, m1) over the augmented frames (the index space of t0 / t1); m0 == m1: none */
+    int32_t reserved;               /* 0 */
+} ishara_clip_aug_ex;
+/* frame_len [B] int32 in device memory or NULL: frame_len[b] = min(L2, T), 0 for an empty clip (n == 0), written by the kernel; x has
+ * the same bits either way.  Arguments and refusals as for ishara_clip_batch; B == 0 launches nothing.  One kernel, no atomics,
+ * graph-capturable, bit-identical from run to run. */
+int ishara_clip_batch_ex(const float* raw, const ishara_clip_aug_ex* clips, int32_t B, int32_t T, int32_t layout,
+                         float* x, int32_t* frame_len, ishara_stream s);
 /* tf.nn.ctc_loss alone: logits [B,T,C] f32, labels [B,L] int64 padded with blank -> nll [B]; dlogits [B,T,C] = grad_scale * d nll / d logits
  * may be NULL; ws = ishara_ctc_workspace_bytes(B, T, L) bytes, 8-byte aligned, no initialisation needed.  B >= 0 (0: nothing is launched),
  * T >= 1 with 4*T + 256*ceil((2L+1)/64) bytes of LDS within what a launch grants (T <= 14844 at L = 255), 1 <= L <= 255, 2 <= C <= 64,

@@ -40,6 +40,13 @@ class ClipAug(C.Structure):
     ]
 
 
+class ClipAugEx(C.Structure):
+    """ishara_clip_aug_ex: ClipAug plus the spatial affine and the temporal mask for ishara_clip_batch_ex (96 bytes, field order of the header)."""
+    _fields_ = [
+        ("base", ClipAug), ("m", C.c_float * 4), ("shift_xy", C.c_float), ("m0", C.c_int32), ("m1", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 LAYOUT_FLAT, LAYOUT_HANDS_LIPS_XY = 0, 1
 
 
@@ -141,6 +148,7 @@ SIGNATURES = {
     "ishara_ctc_align": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "ishara_ctc_align_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ishara_clip_batch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    "ishara_clip_batch_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "ishara_ctc_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_ctc_loss": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P]),
     "ishara_ctc_loss_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P, _P, _U32, _P]),

@@ -235,6 +235,14 @@ extern "C" int ishara_clip_batch(const float* raw, const ishara_clip_aug* clips,
     if (((uintptr_t)raw | (uintptr_t)x) % 16) { ishara_set_error("ishara_clip_batch: raw and x must be 16-byte aligned"); return -1; }
     return launch_clip_batch(raw, clips, B, T, layout, x, (hipStream_t)s);
 }
+extern "C" int ishara_clip_batch_ex(const float* raw, const ishara_clip_aug_ex* clips, int32_t B, int32_t T, int32_t layout,
+                                    float* x, int32_t* frame_len, ishara_stream s) {
+    if (B < 0 || T < 1 || T > CLIP_MAX_T) { ishara_set_error("ishara_clip_batch_ex: B=%d T=%d unsupported (B >= 0, 1 <= T <= %d)", B, T, CLIP_MAX_T); return -1; }
+    if (layout != ISHARA_LAYOUT_FLAT && layout != ISHARA_LAYOUT_HANDS_LIPS_XY) { ishara_set_error("ishara_clip_batch_ex: unknown layout %d", layout); return -1; }
+    if (B > 0 && (!clips || !x)) { ishara_set_error("ishara_clip_batch_ex: null clips / x"); return -1; }
+    if (((uintptr_t)raw | (uintptr_t)x) % 16) { ishara_set_error("ishara_clip_batch_ex: raw and x must be 16-byte aligned"); return -1; }
+    return launch_clip_batch_ex(raw, clips, B, T, layout, x, frame_len, (hipStream_t)s);
+}
 
 // ---- operator tests: dense
 // every operator entry point checks its dtype first: ISHARA_F32 / BF16 / F16 known, F16 only where an fp16 kernel exists (forward /

@@ -394,6 +394,8 @@ int launch_ctc_align_len(const float* logits, const int64_t* labels, int B, int 
 // ---- training input batch (input_batch.hip): device store of raw clips + per-clip augmentation table -> x [B,T,F]
 #define CLIP_MAX_T 4096
 int launch_clip_batch(const float* raw, const ishara_clip_aug* clips, int B, int T, int layout, float* x, hipStream_t s);
+// the same with the spatial affine, the temporal mask and the per-clip frame count (input_batch_ex.hip); frame_len may be null
+int launch_clip_batch_ex(const float* raw, const ishara_clip_aug_ex* clips, int B, int T, int layout, float* x, int* frame_len, hipStream_t s);
 
 // ---- optimizer (optimizer.hip) -----------------------------------------------------------
 struct RAdamArgs { float lr, wd, beta1, beta2, eps, c1, c2, r_t; int rect; int sync; float slow_step; };

@@ -9,12 +9,13 @@ F = 124*3 (flattened) or 112*2 (hands + lips x,y only: the F=224 of BASELINE con
 padded with 59 (conv-hybrid-model.ipynb c4:21-23)."""
 from __future__ import annotations
 
+import math
 import random
 from typing import Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import ClipAug
+from ._lib import ClipAug, ClipAugEx
 
 MAX_PHRASE_LENGTH = 64   # c1:33
 PAD_TOKEN_IDX = 59       # c1:5
@@ -202,14 +203,137 @@ def fill_clip_table(table: np.ndarray, offsets: np.ndarray, draws: Sequence[Augm
     table["t0"], table["t1"], table["fingers"] = win[:, 0], win[:, 1], win[:, 2]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The two augmentations of the reference's CTC training script (Test Notebooks/asl-translation-nb4.ipynb: spatial_random_affine
+# with probability 0.75, temporal_mask with probability 0.5, chained by augment_fn), restated on the `random` draws of this module:
+# the affine on the raw clip, then apply_augmentations, then the mask over the augmented frames.  With both off, every function
+# below makes exactly the rng calls of its namesake above.  DESIGN §3 (spatial affine, temporal mask and frame counts).
+
+class AffineRanges(NamedTuple):
+    """Ranges of `spatial_random_affine` (the reference's defaults) and the probability `augment_fn` applies it with."""
+    scale: Tuple[float, float] = (0.8, 1.2)
+    shear: Tuple[float, float] = (-0.15, 0.15)
+    degree: Tuple[float, float] = (-30, 30)
+    shift: Tuple[float, float] = (-0.1, 0.1)
+    p: float = 0.75
+
+
+class MaskRanges(NamedTuple):
+    """Range of `temporal_mask`'s size (a fraction of the clip's frames) and the probability `augment_fn` applies it with."""
+    size: Tuple[float, float] = (0.2, 0.4)
+    p: float = 0.5
+
+
+class AugmentationDrawEx(NamedTuple):
+    """`AugmentationDraw` plus the affine (`M` = (M00, M01, M10, M11) and `shift`, float32 values) and the temporal mask `[m0, m1)`
+    over the augmented frames (`m0 == m1`: none)."""
+    draw: AugmentationDraw
+    M: Tuple[float, float, float, float]
+    shift: float
+    m0: int
+    m1: int
+
+
+_IDENTITY = (1.0, 0.0, 0.0, 1.0)
+
+
+def _ranges(option, default):
+    """None / False: off; True: the reference's defaults; a ranges tuple: those ranges."""
+    if option is None or option is False:
+        return None
+    return default() if option is True else default(*option)
+
+
+def affine_matrix(scale: float, shear_x: float, shear_y: float, degree: float) -> Tuple[float, float, float, float]:
+    """`M = scale * [[1, shear_x], [shear_y, 1]] @ [[cos, -sin], [sin, cos]]` in fp64, each entry rounded to float32: the scale, shear and
+    rotation of `spatial_random_affine` composed for the row-vector convention `[x' y'] = [x y] @ M`."""
+    a = float(degree) * math.pi / 180.0
+    c, s, k, hx, hy = math.cos(a), math.sin(a), float(scale), float(shear_x), float(shear_y)
+    M = (k * (c + hx * s), k * (hx * c - s), k * (hy * c + s), k * (c - hy * s))
+    return tuple(float(v) for v in np.array(M, np.float32))
+
+
+def _draw_affine(rng, r: AffineRanges):
+    """The affine block's draws: (M, shift) as float32 values, the identity when the gate fails."""
+    if not rng.random() < r.p:
+        return _IDENTITY, 0.0
+    scale, sh, coin = rng.uniform(*r.scale), rng.uniform(*r.shear), rng.random()
+    shear_x, shear_y = (0.0, sh) if coin < 0.5 else (sh, 0.0)           # the reference's coin
+    deg, shift = rng.uniform(*r.degree), rng.uniform(*r.shift)
+    return affine_matrix(scale, shear_x, shear_y, deg), float(np.float32(shift))
+
+
+def _draw_mask(rng, r: MaskRanges, L2: int) -> Tuple[int, int]:
+    """The mask block's draws over a clip of L2 augmented frames: [m0, m1), (0, 0) when the gate fails."""
+    if not rng.random() < r.p:
+        return 0, 0
+    size = int(L2 * rng.uniform(*r.size))
+    m0 = rng.randrange(L2 - size) if L2 > size else 0
+    return m0, m0 + size
+
+
+def affine_xy(landmarks: np.ndarray, M, shift: float) -> np.ndarray:
+    """`[x' y'] = [x y] @ M + shift` on a clip `[n,124,3]` of float32 values, z untouched: each product and the sum `(p + q) + shift` in
+    fp64, the result rounded to float32.  A product of two float32 values is exact in fp64, so the bits do not depend on FMA contraction."""
+    clip = np.array(landmarks, np.float32)
+    m00, m01, m10, m11 = (np.float64(np.float32(v)) for v in M)
+    s = np.float64(np.float32(shift))
+    x, y = clip[..., 0].astype(np.float64), clip[..., 1].astype(np.float64)
+    clip[..., 0] = ((m00 * x + m10 * y) + s).astype(np.float32)
+    clip[..., 1] = ((m01 * x + m11 * y) + s).astype(np.float32)
+    return clip
+
+
+def draw_augmentation_ex(n_frames: int, rng, augment: bool = True, spatial_affine=None, temporal_mask=None) -> AugmentationDrawEx:
+    """Draw what `apply_augmentations_ex` would apply to a clip of `n_frames` frames, making exactly its `rng` calls in its order: the
+    affine block (if on), `draw_augmentation` (if `augment`), the mask block (if on)."""
+    aff, msk = _ranges(spatial_affine, AffineRanges), _ranges(temporal_mask, MaskRanges)
+    M, shift = _draw_affine(rng, aff) if aff is not None else (_IDENTITY, 0.0)
+    d = draw_augmentation(n_frames, rng) if augment else no_augmentation(n_frames)
+    m0, m1 = _draw_mask(rng, msk, d.L2) if msk is not None else (0, 0)
+    return AugmentationDrawEx(d, M, shift, m0, m1)
+
+
+def apply_augmentations_ex(landmarks: np.ndarray, rng, augment: bool = True, spatial_affine=None, temporal_mask=None) -> np.ndarray:
+    """`spatial_random_affine` on the raw clip, then `apply_augmentations`, then `temporal_mask` (masked frames zeroed) over the augmented
+    frames, each only if its option is on.  Returns a new array; the input is not modified."""
+    aff, msk = _ranges(spatial_affine, AffineRanges), _ranges(temporal_mask, MaskRanges)
+    clip = np.array(landmarks)
+    if aff is not None:
+        M, shift = _draw_affine(rng, aff)
+        clip = affine_xy(clip, M, shift).astype(clip.dtype)
+    if augment:
+        clip = apply_augmentations(clip, rng)
+    if msk is not None:
+        m0, m1 = _draw_mask(rng, msk, clip.shape[0])
+        clip[m0:m1] = 0
+    return clip
+
+
+def no_augmentation_ex(n_frames: int) -> AugmentationDrawEx:
+    return AugmentationDrawEx(no_augmentation(n_frames), _IDENTITY, 0.0, 0, 0)
+
+
+def fill_clip_table_ex(table: np.ndarray, offsets: np.ndarray, draws: Sequence[AugmentationDrawEx]) -> None:
+    """Write one `ishara_clip_aug_ex` row per clip into `table` (a numpy view with the dtype of `_lib.ClipAugEx`)."""
+    fill_clip_table(table["base"], offsets, [d.draw for d in draws])
+    table["m"] = [d.M for d in draws]
+    table["shift_xy"] = [d.shift for d in draws]
+    table["m0"] = [d.m0 for d in draws]
+    table["m1"] = [d.m1 for d in draws]
+    table["reserved"] = 0
+
+
 class ClipDataset:
     """`ASLDataset.__getitem__` (data_loader.py:166-195) over in-memory raw clips: `(landmarks [n,124,3], phrase)` ->
     `(pad_resize_normalize([apply_augmentations](landmarks), max_frames), phrase)`.  The host path, for `BatchAdapter`.
-    `rng` defaults to the `random` module (the reference's global draws)."""
+    `rng` defaults to the `random` module (the reference's global draws).  `spatial_affine` / `temporal_mask` (True: the reference's
+    ranges, or an `AffineRanges` / `MaskRanges`) add the two augmentations of `apply_augmentations_ex`, with or without `augment`."""
 
-    def __init__(self, clips, max_frames: int = 384, augment: bool = False, rng=None):
+    def __init__(self, clips, max_frames: int = 384, augment: bool = False, rng=None, spatial_affine=None, temporal_mask=None):
         self.clips, self.max_frames, self.augment = clips, max_frames, augment
         self.rng = random if rng is None else rng
+        self.spatial_affine, self.temporal_mask = _ranges(spatial_affine, AffineRanges), _ranges(temporal_mask, MaskRanges)
 
     def __len__(self) -> int:
         return len(self.clips)
@@ -217,13 +341,17 @@ class ClipDataset:
     def __getitem__(self, i):
         lm, phrase = self.clips[i]
         lm = np.asarray(lm, np.float32)
-        if self.augment:
+        if self.spatial_affine is not None or self.temporal_mask is not None:
+            lm = apply_augmentations_ex(lm, self.rng, self.augment, self.spatial_affine, self.temporal_mask)
+        elif self.augment:
             lm = apply_augmentations(lm, self.rng)
         return pad_resize_normalize(lm, self.max_frames), phrase
 
 
 CLIP_AUG_DTYPE = np.dtype(ClipAug)                 # one ishara_clip_aug row
 C_CLIP_AUG_BYTES = CLIP_AUG_DTYPE.itemsize        # 64
+CLIP_AUG_EX_DTYPE = np.dtype(ClipAugEx)            # one ishara_clip_aug_ex row
+C_CLIP_AUG_EX_BYTES = CLIP_AUG_EX_DTYPE.itemsize  # 96
 _LAYOUT_IDS = {"flat": 0, "hands_lips_xy": 1}
 _LAYOUT_F = {"flat": 124 * 3, "hands_lips_xy": 224}
 
@@ -291,12 +419,17 @@ class DeviceBatchAdapter:
     same `np.random.default_rng(seed)` shuffle) and draws the augmentations per clip in batch order from `rng` (default
     `random.Random(seed)`; pass the `random` module for the reference's global draws).  The per-clip table is written to pinned
     memory, copied asynchronously and consumed by one kernel on the current stream; a pinned table is rewritten only after the
-    event of its previous copy has completed.  `shard=(rank, world)`: draw for the whole (global) batch, emit rank's slice."""
+    event of its previous copy has completed.  `shard=(rank, world)`: draw for the whole (global) batch, emit rank's slice.
+    `spatial_affine` / `temporal_mask` (True: the reference's ranges, or an `AffineRanges` / `MaskRanges`) add the two augmentations of
+    `apply_augmentations_ex`; `emit_lengths=True` yields `(x, y, frame_lengths)` with the clips' frame counts `min(L2, T)` as int32 `[b]`
+    on the device, the third element `Model.fit` / `evaluate` accept.  With any of the three on, the batch is built by
+    `ishara_clip_batch_ex` from 96-byte rows; with all off, by `ishara_clip_batch` exactly as before (same bits, same draws)."""
 
     _SLOTS = 3
 
     def __init__(self, store: DeviceClipStore, batch_size: int, T: int, layout: str = "hands_lips_xy", augment: bool = True,
-                 shuffle: bool = False, seed: int = 0, rng=None, drop_last: bool = False, shard: Optional[Tuple[int, int]] = None):
+                 shuffle: bool = False, seed: int = 0, rng=None, drop_last: bool = False, shard: Optional[Tuple[int, int]] = None,
+                 spatial_affine=None, temporal_mask=None, emit_lengths: bool = False):
         self._lib = _require_gpu()
         if layout not in _LAYOUT_IDS:
             raise ValueError(f"unknown layout {layout!r}")
@@ -304,6 +437,10 @@ class DeviceBatchAdapter:
             raise ValueError(f"T={T} unsupported (1..4096)")
         self.store, self.batch_size, self.T, self.layout, self.augment = store, batch_size, T, layout, augment
         self.shuffle, self.drop_last = shuffle, drop_last
+        self.spatial_affine, self.temporal_mask = _ranges(spatial_affine, AffineRanges), _ranges(temporal_mask, MaskRanges)
+        self.emit_lengths = bool(emit_lengths)
+        self._ex = self.spatial_affine is not None or self.temporal_mask is not None or self.emit_lengths
+        self._row_bytes = C_CLIP_AUG_EX_BYTES if self._ex else C_CLIP_AUG_BYTES
         self.rank, self.world = shard if shard is not None else (0, 1)
         if not 0 <= self.rank < self.world:
             raise ValueError(f"shard {shard} out of range")
@@ -329,7 +466,7 @@ class DeviceBatchAdapter:
     def _slot(self):
         """Next pinned table (+ its device copy) of the ring, once the copy of its previous use has completed."""
         import torch
-        nbytes = self.batch_size * (C_CLIP_AUG_BYTES + 8)
+        nbytes = self.batch_size * (self._row_bytes + 8)
         if len(self._slots) < self._SLOTS:
             host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
             dev = torch.empty(nbytes, dtype=torch.uint8, device=self.store.device)
@@ -340,26 +477,38 @@ class DeviceBatchAdapter:
             slot[2].synchronize()
         return slot
 
-    def batch(self, idx) -> Tuple["torch.Tensor", "torch.Tensor"]:
-        """One device batch of the store's clips `idx` (draws for all of them, emits this rank's slice)."""
+    def batch(self, idx):
+        """One device batch of the store's clips `idx` (draws for all of them, emits this rank's slice): `(x, y)`, or
+        `(x, y, frame_lengths)` with `emit_lengths`."""
         import torch
         from . import _lib
         idx = np.asarray(idx, np.int64)
         lengths = self.store.lengths[idx]
-        draws = [draw_augmentation(n, self.rng) if self.augment else no_augmentation(n) for n in lengths]
+        if self._ex:
+            draws = [draw_augmentation_ex(n, self.rng, self.augment, self.spatial_affine, self.temporal_mask) for n in lengths]
+        else:
+            draws = [draw_augmentation(n, self.rng) if self.augment else no_augmentation(n) for n in lengths]
         lo, hi = len(idx) * self.rank // self.world, len(idx) * (self.rank + 1) // self.world
         idx, draws = idx[lo:hi], draws[lo:hi]
-        b = len(idx)
+        b, row = len(idx), self._row_bytes
         host, dev, ev = self._slot()
         hn = host.numpy()
-        tab = hn[:b * C_CLIP_AUG_BYTES].view(CLIP_AUG_DTYPE)
-        fill_clip_table(tab, self.store.offsets[idx], draws)
-        hn[b * C_CLIP_AUG_BYTES:b * (C_CLIP_AUG_BYTES + 8)].view(np.int64)[:] = idx
-        used = b * (C_CLIP_AUG_BYTES + 8)
+        if self._ex:
+            fill_clip_table_ex(hn[:b * row].view(CLIP_AUG_EX_DTYPE), self.store.offsets[idx], draws)
+        else:
+            fill_clip_table(hn[:b * row].view(CLIP_AUG_DTYPE), self.store.offsets[idx], draws)
+        hn[b * row:b * (row + 8)].view(np.int64)[:] = idx
+        used = b * (row + 8)
         dev[:used].copy_(host[:used], non_blocking=True)
         ev.record()
         x = torch.empty((b, self.T, _LAYOUT_F[self.layout]), dtype=torch.float32, device=self.store.device)
-        _lib.check(self._lib.ishara_clip_batch(_lib.ptr(self.store.raw), _lib.ptr(dev), b, self.T, _LAYOUT_IDS[self.layout],
-                                               _lib.ptr(x), _lib.stream()), "ishara_clip_batch")
-        y = self.store.phrases.index_select(0, dev[b * C_CLIP_AUG_BYTES:used].view(torch.int64))
-        return x, y
+        y_idx = dev[b * row:used].view(torch.int64)
+        if not self._ex:
+            _lib.check(self._lib.ishara_clip_batch(_lib.ptr(self.store.raw), _lib.ptr(dev), b, self.T, _LAYOUT_IDS[self.layout],
+                                                   _lib.ptr(x), _lib.stream()), "ishara_clip_batch")
+            return x, self.store.phrases.index_select(0, y_idx)
+        flen = torch.empty(b, dtype=torch.int32, device=self.store.device) if self.emit_lengths else None
+        _lib.check(self._lib.ishara_clip_batch_ex(_lib.ptr(self.store.raw), _lib.ptr(dev), b, self.T, _LAYOUT_IDS[self.layout],
+                                                  _lib.ptr(x), _lib.ptr(flen), _lib.stream()), "ishara_clip_batch_ex")
+        y = self.store.phrases.index_select(0, y_idx)
+        return (x, y, flen) if self.emit_lengths else (x, y)

@@ -202,6 +202,32 @@ int ishara_gradient_accumulate(ishara_model* prof, float* acc, const float* g, i
 int ishara_optimizer_step_ex(ishara_model* m, float lr, float weight_decay, const float* grad, ishara_grad_stats* st, int32_t skip_nonfinite,
                              ishara_stream s);
 
+/* Exponential moving average of the weights (Keras `use_ema`, `ema_momentum`, `ema_overwrite_frequency`): one update of the caller's
+ * average `avg` [n] f32 from `theta` [n] f32 behind every applied optimizer step, over the trainable prefix of the parameter buffer
+ * (Keras averages trainable variables; the BatchNorm moving statistics stay live).  The caller initialises avg to theta when it
+ * switches averaging on (Keras: initial_value=var) and zeroes the 16-byte device record `rec` once.
+ *
+ *   n     = rec->updates, the updates applied so far
+ *   d     = (double)momentum; with warmup != 0: d = min(d, (1.0 + n) / (10.0 + n))  (tf.train.ExponentialMovingAverage's num_updates)
+ *   alpha = (float)(1.0 - d), evaluated in fp64
+ *   avg[i] = avg[i] + alpha * (theta[i] - avg[i]): three fp32 operations, each rounded to nearest, never contracted into an FMA
+ *   overwrite_every = N > 0 and (n + 1) % N == 0: the same launch also writes theta[i] = avg[i] (the optimizer slots are left alone)
+ *   then rec->updates = n + 1, rec->alpha = alpha, rec->overwrote = 1 if theta was overwritten, else 0
+ * With skip_nonfinite != 0 and st->nonfinite > 0 (the step ishara_optimizer_step_ex skipped) nothing is written to avg or theta,
+ * updates and alpha keep their values and overwrote = 0.  The record and `st` are read on the device: no host synchronise, and a
+ * captured graph replays correctly.  The record is advanced by a one-thread launch behind the update, never by the update kernel.
+ * After a launch that may have overwritten theta the caller runs ishara_sync_weights.
+ *
+ * ishara_weight_swap exchanges a [n] and b [n] bit for bit (as 32-bit words: NaN payloads included); ishara_sync_weights after it too.
+ *
+ * avg, theta, a, b: 16-byte aligned, the two ranges of a call disjoint; 1 <= n <= 2^31 - 1; rec 8-byte aligned; 0 <= momentum < 1;
+ * overwrite_every >= 0; skip_nonfinite != 0 needs st.  `prof` may be NULL: a handle only lends its profiler (keys weight_average,
+ * 12 n bytes, 16 n with overwrite_every > 0; weight_swap, 16 n bytes).  Anything else is refused with a message before any HIP call. */
+typedef struct ishara_ema_state { int64_t updates; float alpha; int32_t overwrote; } ishara_ema_state;
+int ishara_weight_average(ishara_model* prof, float* avg, float* theta, int64_t n, float momentum, int32_t warmup, int32_t overwrite_every,
+                          ishara_ema_state* rec, const ishara_grad_stats* st, int32_t skip_nonfinite, ishara_stream s);
+int ishara_weight_swap(ishara_model* prof, float* a, float* b, int64_t n, ishara_stream s);
+
 /* HIP-event profiler (no reference counterpart: the reference profiles with %%timeit / Keras
  * progress bars).  When enabled, every kernel launch of forward / loss_backward /
  * optimizer_step is bracketed by events on the launch stream; the report is text, one line per

@@ -55,6 +55,11 @@ class GradStats(C.Structure):
     _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("nonfinite", C.c_int32), ("skipped", C.c_int32)]
 
 
+class EmaState(C.Structure):
+    """ishara_ema_state: the 16-byte device record of ishara_weight_average (field order of the header)."""
+    _fields_ = [("updates", C.c_int64), ("alpha", C.c_float), ("overwrote", C.c_int32)]
+
+
 class GemmTnCall(C.Structure):
     """ishara_gemm_tn_call: one weight-gradient GEMM of ishara_op_gemm_tn / ishara_debug_gemm_tn_plan (field order of the header)."""
     _fields_ = [
@@ -128,6 +133,8 @@ SIGNATURES = {
     "ishara_gradient_stats": (C.c_int, [_P, _P, _I64, _F, _F, _P, _P, _P]),
     "ishara_gradient_accumulate": (C.c_int, [_P, _P, _P, _I64, _I32, _P]),
     "ishara_optimizer_step_ex": (C.c_int, [_P, _F, _F, _P, _P, _I32, _P]),
+    "ishara_weight_average": (C.c_int, [_P, _P, _P, _I64, _F, _I32, _I32, _P, _P, _I32, _P]),
+    "ishara_weight_swap": (C.c_int, [_P, _P, _P, _I64, _P]),
     "ishara_profile_enable": (C.c_int, [_P, _I32]),
     "ishara_profile_report": (C.c_int, [_P, C.c_char_p, _I32]),
     "ishara_greedy_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),

@@ -413,3 +413,11 @@ int launch_scale(float* x, int64_t n, float scale, hipStream_t s);
 int64_t grad_stats_workspace_bytes(int64_t n);
 int launch_grad_stats(const float* g, int64_t n, float grad_scale, float clip_norm, ishara_grad_stats* out, void* ws, hipStream_t s);
 int launch_grad_accumulate(float* acc, const float* g, int64_t n, int first, hipStream_t s);
+
+// ---- exponential moving average of the weights (weight_avg.hip) -----------------------------
+// avg, theta, a, b [n] f32 at 16-byte aligned addresses, disjoint, 1 <= n <= 2^31 - 1; rec 8-byte aligned, zeroed once by its owner.
+// weight_average: two launches, the update and, behind it, one thread that writes the record (see the file for why); st may be null
+// when skip == 0.  weight_swap exchanges the two buffers as 32-bit words.
+int launch_weight_average(float* avg, float* theta, int64_t n, float momentum, int warmup, int overwrite_every, ishara_ema_state* rec,
+                          const ishara_grad_stats* st, int skip, hipStream_t s);
+int launch_weight_swap(float* a, float* b, int64_t n, hipStream_t s);

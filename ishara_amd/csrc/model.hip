@@ -420,6 +420,39 @@ extern "C" int ishara_gradient_accumulate(ishara_model* prof, float* acc, const 
     CKP(prof, "grad_accumulate", 12.0 * n, 0, launch_grad_accumulate(acc, g, n, first != 0, s));
     return 0;
 }
+// ------------------------------------------------------------------ exponential moving average of the weights (weight_avg.hip)
+static bool ranges_overlap(const float* a, const float* b, int64_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+    return x < y + bytes && y < x + bytes;
+}
+extern "C" int ishara_weight_average(ishara_model* prof, float* avg, float* theta, int64_t n, float momentum, int32_t warmup, int32_t overwrite_every,
+                                     ishara_ema_state* rec, const ishara_grad_stats* stats, int32_t skip_nonfinite, ishara_stream st) {
+    const char* who = "ishara_weight_average";
+    if (!grad_vec_ok(who, {{"avg", avg}, {"theta", theta}}, n)) return -1;
+    if (!rec) { ishara_set_error("%s: null rec", who); return -1; }
+    if ((uintptr_t)rec % 8 != 0) { ishara_set_error("%s: misaligned rec: %p is not on an 8-byte boundary", who, (void*)rec); return -1; }
+    if (ranges_overlap(avg, theta, n)) { ishara_set_error("%s: avg and theta overlap", who); return -1; }
+    if (!(momentum >= 0.f && momentum < 1.f)) { ishara_set_error("%s: momentum %g is outside [0, 1)", who, (double)momentum); return -1; }
+    if (overwrite_every < 0) { ishara_set_error("%s: overwrite_every=%d is negative", who, (int)overwrite_every); return -1; }
+    if (skip_nonfinite && !stats) { ishara_set_error("%s: skip_nonfinite needs the record: null st", who); return -1; }
+    if ((uintptr_t)stats % 4 != 0) { ishara_set_error("%s: misaligned st: %p is not on a 4-byte boundary", who, (const void*)stats); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    if (!prof) return launch_weight_average(avg, theta, n, momentum, warmup != 0, overwrite_every, rec, stats, skip_nonfinite != 0, s);
+    prof->s = s;
+    CKP(prof, "weight_average", (overwrite_every > 0 ? 16.0 : 12.0) * n, 0,
+        launch_weight_average(avg, theta, n, momentum, warmup != 0, overwrite_every, rec, stats, skip_nonfinite != 0, s));
+    return 0;
+}
+extern "C" int ishara_weight_swap(ishara_model* prof, float* a, float* b, int64_t n, ishara_stream st) {
+    const char* who = "ishara_weight_swap";
+    if (!grad_vec_ok(who, {{"a", a}, {"b", b}}, n)) return -1;
+    if (ranges_overlap(a, b, n)) { ishara_set_error("%s: a and b overlap", who); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    if (!prof) return launch_weight_swap(a, b, n, s);
+    prof->s = s;
+    CKP(prof, "weight_swap", 16.0 * n, 0, launch_weight_swap(a, b, n, s));
+    return 0;
+}
 extern "C" int32_t ishara_optimizer_iterations(const ishara_model* m) { return m->opt_iter; }
 extern "C" int ishara_optimizer_set_iterations(ishara_model* m, int32_t it) { m->opt_iter = it; return 0; }
 

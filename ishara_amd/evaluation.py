@@ -268,8 +268,10 @@ class CallbackEval:
 
     def __init__(self, dataset: Iterable, num_to_char: Dict[int, str], n_show: int = 32,
                  weights_path: Optional[str] = "model.npz", printer: Callable[[str], None] = print,
-                 error_report: bool = False, n_confusions: int = 10):
-        """error_report: also align every decode with its label on the device (ishara_amd.score.edit_alignment_device, no fallback), print
+                 error_report: bool = False, n_confusions: int = 10, averaged: bool = False):
+        """averaged: run the epoch's evaluation on the moving average of the weights (Optimizer(use_ema=True)): the weights file, the
+        forward passes, the decodes and the report all happen inside `model.averaged_weights()`, which puts the training weights back
+        afterwards.  error_report: also align every decode with its label on the device (ishara_amd.score.edit_alignment_device, no fallback), print
         the merged ErrorReport's table (n_confusions pairs) after the transcript, keep it as `last_report` and log the operation totals."""
         self.dataset = dataset
         self.num_to_char = num_to_char
@@ -281,6 +283,7 @@ class CallbackEval:
         self.error_report = error_report
         self.n_confusions = n_confusions
         self.last_report: Optional[ErrorReport] = None
+        self.averaged = averaged
 
     def _align_batch(self, model, logits, y, confusion):
         """One validation batch decoded once on the device and aligned with its labels there: the decodes as decode_batch returns them, and
@@ -301,6 +304,12 @@ class CallbackEval:
         pass
 
     def on_epoch_end(self, epoch: int, logs=None):
+        if not self.averaged:
+            return self._evaluate_epoch(epoch, logs)
+        with self.model.averaged_weights():
+            return self._evaluate_epoch(epoch, logs)
+
+    def _evaluate_epoch(self, epoch: int, logs=None):
         model = self.model
         if self.weights_path:
             model.save_weights(self.weights_path)                                   # c9:10

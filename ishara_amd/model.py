@@ -12,6 +12,7 @@ built library and a GPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Tuple,  Dict, Iterable, List, Optional, Sequence
@@ -46,9 +47,16 @@ class Optimizer:
     is at most this value.  `skip_nonfinite` (what torch's GradScaler does for an overflowed step): a step whose gradient holds a NaN or Inf
     leaves parameters and optimizer slots untouched.  `accumulate_steps` = k: `train_on_batch` sums the gradients of k microbatches and
     applies their mean as one step.  All three act on the device (csrc/grad_ops.hip) without a host synchronise; at their defaults the
-    training step is the code path it was without them."""
+    training step is the code path it was without them.
 
-    def __init__(self, learning_rate=1e-3, weight_decay=0.0, global_clipnorm=None, skip_nonfinite=False, accumulate_steps=1):
+    `use_ema`, `ema_momentum`, `ema_overwrite_frequency` (Keras' arguments) and `ema_warmup`: an exponential moving average of the trainable
+    weights, updated on the device behind every applied step (csrc/weight_avg.hip): avg += (1 - momentum) * (theta - avg); with
+    `ema_warmup` the momentum of update n + 1 is min(momentum, (1 + n) / (10 + n)) (tf.train.ExponentialMovingAverage's num_updates);
+    every `ema_overwrite_frequency` updates the weights are overwritten with the average.  A skipped step leaves the average alone.  The
+    average is read through Model.ema_weights / averaged_weights / evaluate(averaged=True) / save_weights(averaged=True) / finalize_ema."""
+
+    def __init__(self, learning_rate=1e-3, weight_decay=0.0, global_clipnorm=None, skip_nonfinite=False, accumulate_steps=1,
+                 use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_warmup=False):
         self._lr = _Scalar(learning_rate)
         # The reference assigns `.weight_decay` on the Lookahead wrapper (c11:64), which is not
         # one of its hyper-parameters, so RectifiedAdam keeps weight_decay=0 (SURVEY §8a row 10).
@@ -59,6 +67,19 @@ class Optimizer:
         self.global_clipnorm = global_clipnorm
         self.skip_nonfinite = skip_nonfinite
         self.accumulate_steps = accumulate_steps
+        self.use_ema = use_ema
+        self.ema_momentum = ema_momentum
+        self.ema_overwrite_frequency = ema_overwrite_frequency
+        self.ema_warmup = ema_warmup
+
+    def ema_options(self):
+        """(use_ema, momentum, overwrite frequency or 0, warmup), checked"""
+        m, every = self.ema_momentum, self.ema_overwrite_frequency
+        if isinstance(m, bool) or not isinstance(m, (int, float, np.integer, np.floating)) or not 0.0 <= float(np.float32(m)) < 1.0:
+            raise ValueError(f"ema_momentum must be a number in [0, 1) (as float32), got {m!r}")
+        if every is not None and (isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not 1 <= every <= 2 ** 31 - 1):
+            raise ValueError(f"ema_overwrite_frequency must be None or an integer >= 1, got {every!r}")
+        return bool(self.use_ema), float(m), 0 if every is None else int(every), bool(self.ema_warmup)
 
     def train_options(self):
         """(accumulate_steps, clip norm or 0.0, skip_nonfinite), checked"""
@@ -152,6 +173,9 @@ class Model(Handle):
         self._gstats = None        # the 16-byte ishara_grad_stats record (4 x int32 storage) and the workspace of its kernel
         self._gstats_ws = None
         self._skipped_seen = 0
+        self._ema_avg = None       # [n_train] f32 moving average of params[:n_train], allocated by the first step with optimizer.use_ema
+        self._ema_rec = None       # the 16-byte ishara_ema_state record (2 x int64 storage)
+        self._ema_swapped = False  # inside averaged_weights(): params[:n_train] and _ema_avg have changed places
         if device is not None:
             self._to_device(device, seed)
 
@@ -188,14 +212,16 @@ class Model(Handle):
             self._lib.ishara_optimizer_set_iterations(self._h, 0)
         _lib.check(self._lib.ishara_sync_weights(self._h, _stream()), "ishara_sync_weights")
 
-    def save_weights(self, path: str):
+    def save_weights(self, path: str, averaged: bool = False):
         """model.save_weights (c9:10).  `*.h5` / `*.hdf5`: the Keras-2 save_weights HDF5 layout, written through the image's HDF5
-        library (keras_h5.py); anything else: .npz keyed by the library's Keras-style names."""
+        library (keras_h5.py); anything else: .npz keyed by the library's Keras-style names.  averaged: the file holds ema_weights()
+        (the moving average of the trainable weights, the live BatchNorm statistics) in place of get_weights()."""
+        weights = self.ema_weights() if averaged else self.get_weights()
         if path.endswith((".h5", ".hdf5")):
             from . import keras_h5
-            keras_h5.save_weights_h5(path, self.get_weights(), [(n, tuple(s)) for n, s, _, _ in self.entries])
+            keras_h5.save_weights_h5(path, weights, [(n, tuple(s)) for n, s, _, _ in self.entries])
             return
-        np.savez(path if path.endswith(".npz") else path + ".npz", **self.get_weights())
+        np.savez(path if path.endswith(".npz") else path + ".npz", **weights)
 
     def load_weights(self, path: str):
         """model.load_weights: a Keras-2 `.h5` weights file (matched by layer / weight order and shape, like by_name=False) or the .npz."""
@@ -306,6 +332,7 @@ class Model(Handle):
         """The optimizer step on `grads`.  With optimizer.global_clipnorm or .skip_nonfinite set: the statistics of `grads`, then the step
         that reads them (no all-reduce here: train_on_batch places it in front of the statistics).  Accumulation is train_on_batch's."""
         k, clip, skip = self.optimizer.train_options()
+        self._not_while_averaged("apply_gradients")
         if k > 1 or self._micro:
             raise ValueError("apply_gradients steps on one gradient; with accumulate_steps > 1 drive the cycle through train_on_batch")
         if clip > 0.0 or skip:
@@ -314,8 +341,11 @@ class Model(Handle):
             self._apply_gradients_ex(src, skip)
             return
         wd = float(self.optimizer.weight_decay) if self.optimizer.apply_weight_decay else 0.0
+        ema = self._ema_begin_step()
         _lib.check(self._lib.ishara_optimizer_step(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _stream()),
                    "ishara_optimizer_step")
+        if ema:
+            self._ema_update(ema, None, False)
         self.optimizer.iterations += 1
         self._steps += 1
 
@@ -335,6 +365,7 @@ class Model(Handle):
         `frame_lengths` [B]: per-clip frame counts of this (micro)batch, as in __call__; every path above takes them."""
         from . import parallel
         k, clip, skip = self.optimizer.train_options()
+        self._not_while_averaged("train_on_batch")
         if k > 1 or clip > 0.0 or skip or self._micro:
             return self._train_microbatch(x, y, seed, allreduce, k, clip, skip, frame_lengths)
         world = parallel.world_size()
@@ -399,11 +430,95 @@ class Model(Handle):
                                                    _lib.ptr(self._gstats), _lib.ptr(self._gstats_ws), _stream()), "ishara_gradient_stats")
 
     def _apply_gradients_ex(self, src: torch.Tensor, skip: bool):
+        self._not_while_averaged("the optimizer step")
         wd = float(self.optimizer.weight_decay) if self.optimizer.apply_weight_decay else 0.0
+        ema = self._ema_begin_step()
         _lib.check(self._lib.ishara_optimizer_step_ex(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _lib.ptr(src),
                                                       _lib.ptr(self._gstats), 1 if skip else 0, _stream()), "ishara_optimizer_step_ex")
+        if ema:
+            self._ema_update(ema, self._gstats, skip)
         self.optimizer.iterations += 1
         self._steps += 1
+
+    # ------------------------------------------------------------------ moving average of the weights (csrc/weight_avg.hip)
+    def _not_while_averaged(self, what: str):
+        if self._ema_swapped:
+            raise _lib.IsharaError(f"{what}: refused inside averaged_weights(): params hold the moving average, not the training weights")
+
+    def _ema_start(self, updates: int = 0):
+        """a fresh average at the present params[:n_train] (Keras: initial_value=var) and the record with `updates`; no host synchronise"""
+        self._ema_avg = self.params[:self.n_train].detach().clone()
+        self._ema_rec = torch.zeros(2, dtype=torch.int64, device=self.device)
+        if updates:
+            self._ema_rec[0] = int(updates)
+
+    def _ema_begin_step(self):
+        """In front of an optimizer step: the checked EMA options when optimizer.use_ema is on, else None (and then nothing of the
+        average is touched, allocated or launched).  The first such step creates the average at the weights the step starts from."""
+        opts = self.optimizer.ema_options()
+        if not opts[0]:
+            return None
+        if self._ema_avg is None:
+            self._ema_start()
+        return opts
+
+    def _ema_update(self, opts, gstats, skip: bool):
+        """ishara_weight_average behind the optimizer step on the same stream; with an overwrite frequency the 16-bit weight shadows are
+        refreshed behind it (the host cannot know whether this launch overwrote without reading the record)"""
+        _, momentum, every, warmup = opts
+        _lib.check(self._lib.ishara_weight_average(self._h, _lib.ptr(self._ema_avg), _lib.ptr(self.params), self.n_train, C.c_float(momentum),
+                                                   1 if warmup else 0, every, _lib.ptr(self._ema_rec), _lib.ptr(gstats), 1 if skip else 0,
+                                                   _stream()), "ishara_weight_average")
+        if every:
+            _lib.check(self._lib.ishara_sync_weights(self._h, _stream()), "ishara_sync_weights")
+
+    def _ema_required(self, what: str):
+        if self._ema_avg is None:
+            raise _lib.IsharaError(f"{what}: there is no moving average: no training step has run with optimizer.use_ema set")
+
+    def ema_weights(self) -> Dict[str, np.ndarray]:
+        """get_weights() of the averaged model: the trainable entries from the moving average, the others (the BatchNorm moving
+        statistics, which are not averaged) from `params`."""
+        self._ema_required("ema_weights")
+        flat = self.params.detach().cpu().numpy().copy()
+        if not self._ema_swapped:                              # inside averaged_weights() the average is what params hold
+            flat[:self.n_train] = self._ema_avg.cpu().numpy()
+        return {n: flat[o:o + int(np.prod(s))].reshape(s).copy() for n, s, o, _ in self.entries}
+
+    def ema_state(self) -> dict:
+        """{updates, alpha, overwrote} of the device record: the updates applied so far, the smoothing factor of the last one and whether
+        it overwrote the weights.  This read is the only host synchronise of the feature."""
+        self._ema_required("ema_state")
+        raw = self._ema_rec.cpu().numpy()
+        return dict(updates=int(raw[0]), alpha=float(raw[1:].view(np.float32)[0]), overwrote=int(raw[1:].view(np.int32)[1]))
+
+    def _ema_swap(self):
+        _lib.check(self._lib.ishara_weight_swap(self._h, _lib.ptr(self.params), _lib.ptr(self._ema_avg), self.n_train, _stream()), "ishara_weight_swap")
+        _lib.check(self._lib.ishara_sync_weights(self._h, _stream()), "ishara_sync_weights")
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """with model.averaged_weights(): ... runs the body on the moving average: params[:n_train] and the average change places on the
+        device (bit for bit, no copy through the host) and the weight shadows are refreshed; on exit, also through an exception, they change
+        back.  The BatchNorm moving statistics are not averaged and stay.  Training, nesting, and entering without an average are refused."""
+        self._ema_required("averaged_weights")
+        if self._ema_swapped:
+            raise _lib.IsharaError("averaged_weights: already inside averaged_weights() (nesting would swap the training weights back)")
+        self._ema_swap()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swap()
+            self._ema_swapped = False
+
+    def finalize_ema(self):
+        """Overwrites the trainable weights with their moving average (Keras' optimizer.finalize_variable_values, which `fit` calls after the
+        last epoch); the optimizer slots stay, the weight shadows are refreshed."""
+        self._ema_required("finalize_ema")
+        self._not_while_averaged("finalize_ema")
+        self.params[:self.n_train].copy_(self._ema_avg)
+        _lib.check(self._lib.ishara_sync_weights(self._h, _stream()), "ishara_sync_weights")
 
     def grad_stats(self) -> Dict[str, float]:
         """{norm, coef, nonfinite, skipped} of the last cycle that ran with clipping, skipping or accumulation: the global L2 norm of the
@@ -422,6 +537,7 @@ class Model(Handle):
         clipping / skipping / accumulation settings -> `path` (.npz).  Refused in the middle of an accumulation cycle: the accumulator
         is not part of the state."""
         from . import train_state as TS
+        self._not_while_averaged("save_state")
         if self._micro:
             raise ValueError(f"save_state: in the middle of an accumulation cycle ({self._micro} of {self.optimizer.accumulate_steps} microbatches); "
                              "save after the cycle's last train_on_batch")
@@ -430,12 +546,23 @@ class Model(Handle):
         st = TS.pack_state(self.entries, *(t.detach().cpu().numpy() for t in (self.params, self.opt_m, self.opt_v, self.opt_slow)),
                            iterations=o.iterations, steps=self._steps, step_seed=self._step_seed, learning_rate=float(o.learning_rate),
                            weight_decay=float(o.weight_decay), apply_weight_decay=o.apply_weight_decay, global_clipnorm=o.global_clipnorm,
-                           skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped)
+                           skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped, **self._ema_state_entries())
         return TS.save_state_file(path, st)
 
+    def _ema_state_entries(self) -> dict:
+        """what save_state adds for the moving average: nothing when there is none"""
+        if self._ema_avg is None:
+            return {}
+        use, momentum, every, warmup = self.optimizer.ema_options()
+        return dict(ema_avg=self._ema_avg.cpu().numpy(), ema_updates=self.ema_state()["updates"], use_ema=use, ema_momentum=momentum,
+                    ema_warmup=warmup, ema_overwrite_frequency=every or None)
+
     def load_state(self, path: str):
-        """Restores what save_state wrote into this model (same architecture: the entry list is checked)."""
+        """Restores what save_state wrote into this model (same architecture: the entry list is checked).  A file with a moving average
+        restores it, its update count and the four ema settings; a file without one leaves the settings alone and, with optimizer.use_ema
+        on, starts a fresh average at the loaded weights with 0 updates."""
         from . import train_state as TS
+        self._not_while_averaged("load_state")
         st = TS.load_state_file(path, self.entries)
         for t, k in ((self.params, "params"), (self.opt_m, "opt_m"), (self.opt_v, "opt_v"), (self.opt_slow, "opt_slow")):
             t.copy_(torch.from_numpy(st[k]))
@@ -448,6 +575,13 @@ class Model(Handle):
             self._gstats_ws = torch.empty(int(self._lib.ishara_grad_stats_workspace_bytes(self.n_train)), dtype=torch.uint8, device=self.device)
         self._gstats[3] = st["skipped"]
         self._skipped_seen = st["skipped"]
+        self._ema_avg = self._ema_rec = None
+        if "ema_avg" in st:
+            o.use_ema, o.ema_momentum, o.ema_warmup, o.ema_overwrite_frequency = st["use_ema"], st["ema_momentum"], st["ema_warmup"], st["ema_overwrite_frequency"]
+            self._ema_start(st["ema_updates"])
+            self._ema_avg.copy_(torch.from_numpy(st["ema_avg"]))
+        elif o.ema_options()[0]:
+            self._ema_start()
         _lib.check(self._lib.ishara_optimizer_set_iterations(self._h, st["iterations"]), "ishara_optimizer_set_iterations")
         _lib.check(self._lib.ishara_sync_weights(self._h, _stream()), "ishara_sync_weights")
 
@@ -474,6 +608,8 @@ class Model(Handle):
         Datasets are re-iterable objects yielding (x [B,T,F] float32, y [B,64] int64) or (x, y, frame_lengths [B]).  `initial_epoch` (Keras): the epoch to start
         from when a run is resumed (after load_state); epochs initial_epoch .. epochs - 1 run.  With optimizer.global_clipnorm or
         .skip_nonfinite the epoch logs gain `grad_norm` (the last cycle's) and `skipped_steps` (in this epoch): one device read per epoch.
+        With optimizer.use_ema they gain `ema_updates` (one more read), and after the last epoch, before on_train_end, finalize_ema()
+        overwrites the weights with their moving average, as Keras' fit does.
         With accumulate_steps = k every batch is a microbatch; an epoch whose batch count is no multiple of k leaves its last cycle open."""
         hist = History()
         for cb in callbacks:
@@ -500,6 +636,8 @@ class Model(Handle):
                 logs["grad_norm"] = gs["norm"]
                 logs["skipped_steps"] = gs["skipped"] - self._skipped_seen
                 self._skipped_seen = gs["skipped"]
+            if self.optimizer.use_ema and self._ema_avg is not None:
+                logs["ema_updates"] = self.ema_state()["updates"]
             if validation_data is not None:
                 logs["val_loss"] = self.evaluate(validation_data)
             for cb in callbacks: cb.on_epoch_end(epoch, logs)
@@ -509,6 +647,8 @@ class Model(Handle):
                 print(f"Epoch {epoch + 1}/{epochs} - " + " - ".join(f"{k}: {v:.4g}" for k, v in logs.items()))
             if self.stop_training:
                 break
+        if self.optimizer.use_ema and self._ema_avg is not None:
+            self.finalize_ema()
         for cb in callbacks: getattr(cb, "on_train_end", lambda logs=None: None)()
         return hist
 
@@ -608,9 +748,12 @@ class Model(Handle):
                                              C.c_float(1.0), _lib.ptr(ws), _stream()), "ishara_ctc_loss")
         return nll
 
-    def evaluate(self, dataset: Iterable) -> float:
+    def evaluate(self, dataset: Iterable, averaged: bool = False) -> float:
         """Mean CTC loss over a dataset of (x, y) or (x, y, frame_lengths) batches; the lengths mask the model as in __call__, the loss
-        keeps logit_length = T like the training loss."""
+        keeps logit_length = T like the training loss.  averaged: of the moving average of the weights (inside averaged_weights())."""
+        if averaged:
+            with self.averaged_weights():
+                return self.evaluate(dataset)
         tot, n = 0.0, 0
         for batch in dataset:
             x, y, fl = split_batch(batch)

@@ -95,7 +95,47 @@ def clipped_step_reference(theta: np.ndarray, grad: np.ndarray, state: dict, lr:
     return theta
 
 
+# ---------------------------------------------------------------------------------- the moving average of the weights (csrc/weight_avg.hip)
+def ema_alpha(n: int, momentum: float, warmup: bool = False) -> np.float32:
+    """The smoothing factor of update number n + 1 (n updates applied so far): alpha = (float)(1 - d), d = (double)(float)momentum, under
+    warm-up min(d, (1 + n) / (10 + n)) (tf.train.ExponentialMovingAverage's num_updates rule); evaluated in fp64 like the kernel."""
+    d = float(np.float32(momentum))
+    if warmup:
+        d = min(d, (1.0 + float(n)) / (10.0 + float(n)))
+    return np.float32(1.0 - d)
+
+
+def ema_state_init() -> dict:
+    """the zeroed ishara_ema_state record"""
+    return dict(updates=0, alpha=np.float32(0.0), overwrote=0)
+
+
+def ema_reference(avg: np.ndarray, theta: np.ndarray, state: dict, momentum: float, warmup: bool = False, overwrite_every: int = 0,
+                  nonfinite: int = 0, skip_nonfinite: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """One ishara_weight_average in numpy fp32 -> (avg, theta); `state` ({updates, alpha, overwrote}, ema_state_init) is updated in
+    place.  avg + alpha * (theta - avg): numpy rounds each of the three operations to fp32 and fuses nothing, as the kernel.  With
+    skip_nonfinite and nonfinite > 0 the inputs come back as they are, updates and alpha stay, overwrote = 0.  With overwrite_every = N > 0
+    and the new update count a multiple of N, theta comes back as a copy of the new average."""
+    if skip_nonfinite and nonfinite > 0:
+        state["overwrote"] = 0
+        return avg, theta
+    avg = np.asarray(avg, dtype=np.float32)
+    theta = np.asarray(theta, dtype=np.float32)
+    alpha = ema_alpha(state["updates"], momentum, warmup)
+    with np.errstate(over="ignore", invalid="ignore"):
+        avg = avg + alpha * (theta - avg)
+    state["updates"] += 1
+    state["alpha"] = alpha
+    state["overwrote"] = 1 if overwrite_every > 0 and state["updates"] % overwrite_every == 0 else 0
+    if state["overwrote"]:
+        theta = avg.copy()
+    return avg, theta
+
+
 # ---------------------------------------------------------------------------------- the state file
+EMA_KEYS = ("ema_avg", "ema_updates", "ema_momentum", "ema_warmup", "ema_overwrite_frequency", "use_ema")
+
+
 class TrainStateError(ValueError):
     pass
 
@@ -112,16 +152,24 @@ def _entry_arrays(entries: Iterable[Tuple[str, tuple, int, bool]]) -> Dict[str, 
 
 def pack_state(entries, params: np.ndarray, opt_m: np.ndarray, opt_v: np.ndarray, opt_slow: np.ndarray, *, iterations: int, steps: int,
                step_seed: int, learning_rate: float, weight_decay: float, apply_weight_decay: bool = False,
-               global_clipnorm: Optional[float] = None, skip_nonfinite: bool = False, accumulate_steps: int = 1, skipped: int = 0
-               ) -> Dict[str, np.ndarray]:
+               global_clipnorm: Optional[float] = None, skip_nonfinite: bool = False, accumulate_steps: int = 1, skipped: int = 0,
+               ema_avg: Optional[np.ndarray] = None, ema_updates: int = 0, use_ema: bool = True, ema_momentum: float = 0.99,
+               ema_warmup: bool = False, ema_overwrite_frequency: Optional[int] = None) -> Dict[str, np.ndarray]:
     """The arrays of one state file (np.savez(path, **pack_state(...))): the flat fp32 `params` (BatchNorm moving statistics included), the
-    three optimizer slots, the counters, the hyper-parameters, the format version and the entry list the buffers were laid out by."""
+    three optimizer slots, the counters, the hyper-parameters, the format version and the entry list the buffers were laid out by.  With
+    `ema_avg` (the moving average of the trainable prefix, when one exists) the file also holds EMA_KEYS: the average, its update count
+    and the four settings; without it the key set is what it was before the average existed."""
     out = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in zip(ARRAYS, (params, opt_m, opt_v, opt_slow))}
     out.update(_entry_arrays(entries))
     out.update(format_version=np.int64(FORMAT_VERSION), iterations=np.int64(iterations), steps=np.int64(steps), step_seed=np.int64(step_seed),
                learning_rate=np.float64(learning_rate), weight_decay=np.float64(weight_decay), apply_weight_decay=np.bool_(apply_weight_decay),
                global_clipnorm=np.float64(0.0 if global_clipnorm is None else global_clipnorm), skip_nonfinite=np.bool_(skip_nonfinite),
                accumulate_steps=np.int64(accumulate_steps), skipped=np.int64(skipped))
+    if ema_avg is not None:
+        a = np.asarray(ema_avg)
+        out.update(ema_avg=np.ascontiguousarray(a).reshape(-1) if a.dtype == np.float32 else a, ema_updates=np.int64(ema_updates),
+                   use_ema=np.bool_(use_ema), ema_momentum=np.float64(ema_momentum), ema_warmup=np.bool_(ema_warmup),
+                   ema_overwrite_frequency=np.int64(0 if ema_overwrite_frequency is None else ema_overwrite_frequency))
     validate_state(out, entries)
     return out
 
@@ -159,10 +207,22 @@ def validate_state(z, entries) -> None:
             raise TrainStateError(f"train state: wrong shape of '{k}': {a.dtype}{tuple(a.shape)}, expected float32({n},)")
     if int(z["accumulate_steps"]) < 1 or int(z["iterations"]) < 0 or int(z["steps"]) < 0:
         raise TrainStateError("train state: a counter is out of range")
+    if "ema_avg" in keys:               # the moving average is optional: a file without it is a complete version-1 state
+        for k in EMA_KEYS:
+            if k not in keys:
+                raise TrainStateError(f"train state: missing entry '{k}' (the file holds 'ema_avg')")
+        a = z["ema_avg"]
+        if a.dtype != np.float32 or a.shape != (n_train,):
+            raise TrainStateError(f"train state: wrong shape of 'ema_avg': {a.dtype}{tuple(a.shape)}, expected float32({n_train},)")
+        m = float(z["ema_momentum"])
+        if int(z["ema_updates"]) < 0 or int(z["ema_overwrite_frequency"]) < 0 or not 0.0 <= m < 1.0:
+            raise TrainStateError("train state: an entry of the moving average (ema_updates, ema_overwrite_frequency, ema_momentum) is out of range")
 
 
 def unpack_state(z, entries) -> dict:
-    """validate_state, then plain Python values: the four arrays (float32, flat) and the scalars; global_clipnorm is None when off"""
+    """validate_state, then plain Python values: the four arrays (float32, flat) and the scalars; global_clipnorm is None when off.  A file
+    with the moving average adds ema_avg (float32), ema_updates, use_ema, ema_momentum, ema_warmup and ema_overwrite_frequency (None when
+    off); a file without it adds none of them."""
     validate_state(z, entries)
     out = {k: np.array(z[k], dtype=np.float32) for k in ARRAYS}
     for k in ("iterations", "steps", "step_seed", "accumulate_steps", "skipped"):
@@ -173,6 +233,11 @@ def unpack_state(z, entries) -> dict:
         out[k] = bool(z[k])
     clip = float(z["global_clipnorm"])
     out["global_clipnorm"] = clip if clip > 0 else None
+    keys = set(z.files) if hasattr(z, "files") else set(z)
+    if "ema_avg" in keys:
+        every = int(z["ema_overwrite_frequency"])
+        out.update(ema_avg=np.array(z["ema_avg"], dtype=np.float32), ema_updates=int(z["ema_updates"]), use_ema=bool(z["use_ema"]),
+                   ema_momentum=float(z["ema_momentum"]), ema_warmup=bool(z["ema_warmup"]), ema_overwrite_frequency=every if every > 0 else None)
     return out
 
 

@@ -228,6 +228,41 @@ int ishara_weight_average(ishara_model* prof, float* avg, float* theta, int64_t 
                           ishara_ema_state* rec, const ishara_grad_stats* st, int32_t skip_nonfinite, ishara_stream s);
 int ishara_weight_swap(ishara_model* prof, float* a, float* b, int64_t n, ishara_stream s);
 
+/* Adversarial weight perturbation (AWP; Wu, Xia, Wang, NeurIPS 2020, in the per-tensor form of the Keras fingerspelling recipes): every
+ * weight tensor moves a step up its own gradient, the caller runs forward and backward again at the moved weights, puts the weights back
+ * and steps the optimizer on the second gradient.  ishara_awp_perturb moves the weights and keeps a copy; ishara_awp_restore copies it back.
+ *
+ * The first n elements of w and g (the trainable prefix of the flat buffers) are cut into S segments, one per parameter entry, by
+ * seg_off: a DEVICE array int64 [S + 1] with seg_off[0] = 0, strictly increasing, seg_off[S] = n.  The offsets need no alignment.  The
+ * host cannot validate the values without a device read, so they are the caller's contract (the kernels clamp every index they derive
+ * from the table to [0, n), nothing more).  For every segment s, over its elements i:
+ *   ss_g = sum (double)g[i]^2 and, with relative != 0, ss_w = sum (double)w[i]^2: fp64 sums in a fixed order, no float atomics, so the
+ *     results are bit-identical from run to run
+ *   ss_g not finite (a NaN or Inf in the segment's gradient, or an overflowed sum), or relative != 0 and ss_w not finite:
+ *     scale[s] = 0, w keeps every bit over the segment, rec->zeroed counts the segment
+ *   else rec->perturbed counts it and, evaluated in fp64 and rounded once,
+ *     scale[s] = (float)((double)delta / (sqrt(ss_g) + (double)eps)), with relative != 0
+ *     scale[s] = (float)((double)delta * sqrt(ss_w) / (sqrt(ss_g) + (double)eps));
+ *     w[i] = w[i] + scale[s] * g[i]: the product rounded to fp32, then the sum rounded to fp32, never contracted into an FMA.
+ *     An all-zero gradient gives a finite scale (eps > 0) and a step of 0
+ *   backup[i] = w[i] as it was, a copy of the 32-bit word, for every segment, the zeroed ones too; g is only read
+ *   rec->grad_norm = (float)sqrt(sum_s ss_g), rec->delta_norm = (float)sqrt(sum_s (double)scale[s]^2 * ss_g), both sums over the
+ *     segments that were not zeroed, in segment order
+ * scale (device, [S]) and rec are written by the device only: no host synchronise, no allocation, no memset, and a captured graph
+ * replays the call.  ws: ishara_awp_workspace_bytes of (n, S) bytes of device memory, every word of which the call writes before it reads it.
+ * ishara_awp_restore copies backup [n] over w [n] as 32-bit words (NaN payloads included).  The caller runs ishara_sync_weights behind
+ * each of the two when the weights are a model's.
+ *
+ * Refused with a message before any HIP call: a null w, backup, g, seg_off, scale, rec or ws; w or backup not 16-byte aligned, g or scale
+ * not 4-byte, seg_off or ws not 8-byte, rec not 4-byte aligned; w and backup overlapping; n outside 1 .. 2^31 - 1; S outside 1 .. n; delta
+ * or eps not a finite value > 0.  `prof` may be NULL: a handle only lends its profiler (keys awp_norms, 4 n bytes, 8 n with relative;
+ * awp_perturb, 16 n bytes; awp_restore, 8 n bytes). */
+typedef struct ishara_awp_stats { float grad_norm; float delta_norm; int32_t perturbed; int32_t zeroed; } ishara_awp_stats;
+int64_t ishara_awp_workspace_bytes(int64_t n, int32_t S);
+int ishara_awp_perturb(ishara_model* prof, float* w, float* backup, const float* g, const int64_t* seg_off, int32_t S, int64_t n,
+                       float delta, float eps, int32_t relative, float* scale, ishara_awp_stats* rec, void* ws, ishara_stream s);
+int ishara_awp_restore(ishara_model* prof, float* w, const float* backup, int64_t n, ishara_stream s);
+
 /* HIP-event profiler (no reference counterpart: the reference profiles with %%timeit / Keras
  * progress bars).  When enabled, every kernel launch of forward / loss_backward /
  * optimizer_step is bracketed by events on the launch stream; the report is text, one line per

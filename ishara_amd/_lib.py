@@ -60,6 +60,11 @@ class EmaState(C.Structure):
     _fields_ = [("updates", C.c_int64), ("alpha", C.c_float), ("overwrote", C.c_int32)]
 
 
+class AwpStats(C.Structure):
+    """ishara_awp_stats: the 16-byte device record of ishara_awp_perturb (field order of the header)."""
+    _fields_ = [("grad_norm", C.c_float), ("delta_norm", C.c_float), ("perturbed", C.c_int32), ("zeroed", C.c_int32)]
+
+
 class GemmTnCall(C.Structure):
     """ishara_gemm_tn_call: one weight-gradient GEMM of ishara_op_gemm_tn / ishara_debug_gemm_tn_plan (field order of the header)."""
     _fields_ = [
@@ -135,6 +140,9 @@ SIGNATURES = {
     "ishara_optimizer_step_ex": (C.c_int, [_P, _F, _F, _P, _P, _I32, _P]),
     "ishara_weight_average": (C.c_int, [_P, _P, _P, _I64, _F, _I32, _I32, _P, _P, _I32, _P]),
     "ishara_weight_swap": (C.c_int, [_P, _P, _P, _I64, _P]),
+    "ishara_awp_workspace_bytes": (_I64, [_I64, _I32]),
+    "ishara_awp_perturb": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _F, _F, _I32, _P, _P, _P, _P]),
+    "ishara_awp_restore": (C.c_int, [_P, _P, _P, _I64, _P]),
     "ishara_profile_enable": (C.c_int, [_P, _I32]),
     "ishara_profile_report": (C.c_int, [_P, C.c_char_p, _I32]),
     "ishara_greedy_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),

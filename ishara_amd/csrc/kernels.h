@@ -421,3 +421,14 @@ int launch_grad_accumulate(float* acc, const float* g, int64_t n, int first, hip
 int launch_weight_average(float* avg, float* theta, int64_t n, float momentum, int warmup, int overwrite_every, ishara_ema_state* rec,
                           const ishara_grad_stats* st, int skip, hipStream_t s);
 int launch_weight_swap(float* a, float* b, int64_t n, hipStream_t s);
+
+// ---- adversarial weight perturbation (awp.hip) ------------------------------------------------
+// w, backup [n] f32 at 16-byte aligned addresses, disjoint; g [n] f32 (16-byte accesses when its address allows them); seg_off device int64
+// [S + 1], 0 = seg_off[0] < ... < seg_off[S] = n (the caller's contract: the host cannot read it); scale device [S]; ws of
+// awp_workspace_bytes(n, S) bytes at an 8-byte aligned address.  awp_norms: four launches (chunk table, chunk sums, per-segment scale,
+// the record); awp_apply behind it on the same stream with the same ws / seg_off / S / n: backup = w, w += scale[s] * g.
+int64_t awp_workspace_bytes(int64_t n, int32_t S);
+int launch_awp_norms(const float* w, const float* g, const int64_t* seg_off, int32_t S, int64_t n, float delta, float eps, int relative, float* scale,
+                     ishara_awp_stats* rec, void* ws, hipStream_t s);
+int launch_awp_apply(float* w, float* backup, const float* g, const int64_t* seg_off, int32_t S, int64_t n, const float* scale, void* ws, hipStream_t s);
+int launch_awp_restore(float* w, const float* backup, int64_t n, hipStream_t s);

@@ -453,6 +453,53 @@ extern "C" int ishara_weight_swap(ishara_model* prof, float* a, float* b, int64_
     CKP(prof, "weight_swap", 16.0 * n, 0, launch_weight_swap(a, b, n, s));
     return 0;
 }
+// ------------------------------------------------------------------ adversarial weight perturbation (awp.hip)
+static bool awp_count_ok(const char* who, int64_t n) {
+    if (n < 1 || n > 2147483647LL) { ishara_set_error("%s: n=%lld is outside 1..2147483647", who, (long long)n); return false; }
+    return true;
+}
+static bool awp_ptr_ok(const char* who, const char* name, const void* p, int align) {
+    if (!p) { ishara_set_error("%s: null %s", who, name); return false; }
+    if ((uintptr_t)p % align != 0) { ishara_set_error("%s: misaligned %s: %p is not on a %d-byte boundary", who, name, p, align); return false; }
+    return true;
+}
+extern "C" int64_t ishara_awp_workspace_bytes(int64_t n, int32_t S) {
+    const char* who = "ishara_awp_workspace_bytes";
+    if (!awp_count_ok(who, n)) return -1;
+    if (S < 1 || S > n) { ishara_set_error("%s: S=%d is outside 1..n=%lld", who, (int)S, (long long)n); return -1; }
+    return awp_workspace_bytes(n, S);
+}
+extern "C" int ishara_awp_perturb(ishara_model* prof, float* w, float* backup, const float* g, const int64_t* seg_off, int32_t S, int64_t n,
+                                  float delta, float eps, int32_t relative, float* scale, ishara_awp_stats* rec, void* ws, ishara_stream st) {
+    const char* who = "ishara_awp_perturb";
+    if (!awp_ptr_ok(who, "w", w, 16) || !awp_ptr_ok(who, "backup", backup, 16) || !awp_ptr_ok(who, "g", g, 4) || !awp_ptr_ok(who, "seg_off", seg_off, 8) ||
+        !awp_ptr_ok(who, "scale", scale, 4) || !awp_ptr_ok(who, "rec", rec, 4) || !awp_ptr_ok(who, "ws", ws, 8)) return -1;
+    if (!awp_count_ok(who, n)) return -1;
+    if (S < 1 || S > n) { ishara_set_error("%s: S=%d is outside 1..n=%lld", who, (int)S, (long long)n); return -1; }
+    if (ranges_overlap(w, backup, n)) { ishara_set_error("%s: w and backup overlap", who); return -1; }
+    if (!(delta > 0.f) || std::isinf(delta)) { ishara_set_error("%s: delta %g is not a finite value > 0", who, (double)delta); return -1; }
+    if (!(eps > 0.f) || std::isinf(eps)) { ishara_set_error("%s: eps %g is not a finite value > 0", who, (double)eps); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    if (!prof) {
+        CK(launch_awp_norms(w, g, seg_off, S, n, delta, eps, relative != 0, scale, rec, ws, s));
+        return launch_awp_apply(w, backup, g, seg_off, S, n, scale, ws, s);
+    }
+    prof->s = s;
+    CKP(prof, "awp_norms", (relative ? 8.0 : 4.0) * n, 0, launch_awp_norms(w, g, seg_off, S, n, delta, eps, relative != 0, scale, rec, ws, s));
+    CKP(prof, "awp_perturb", 16.0 * n, 0, launch_awp_apply(w, backup, g, seg_off, S, n, scale, ws, s));
+    return 0;
+}
+extern "C" int ishara_awp_restore(ishara_model* prof, float* w, const float* backup, int64_t n, ishara_stream st) {
+    const char* who = "ishara_awp_restore";
+    if (!awp_ptr_ok(who, "w", w, 16) || !awp_ptr_ok(who, "backup", backup, 16)) return -1;
+    if (!awp_count_ok(who, n)) return -1;
+    if (ranges_overlap(w, backup, n)) { ishara_set_error("%s: w and backup overlap", who); return -1; }
+    hipStream_t s = (hipStream_t)st;
+    if (!prof) return launch_awp_restore(w, backup, n, s);
+    prof->s = s;
+    CKP(prof, "awp_restore", 8.0 * n, 0, launch_awp_restore(w, backup, n, s));
+    return 0;
+}
 extern "C" int32_t ishara_optimizer_iterations(const ishara_model* m) { return m->opt_iter; }
 extern "C" int ishara_optimizer_set_iterations(ishara_model* m, int32_t it) { m->opt_iter = it; return 0; }
 

@@ -53,10 +53,19 @@ class Optimizer:
     weights, updated on the device behind every applied step (csrc/weight_avg.hip): avg += (1 - momentum) * (theta - avg); with
     `ema_warmup` the momentum of update n + 1 is min(momentum, (1 + n) / (10 + n)) (tf.train.ExponentialMovingAverage's num_updates);
     every `ema_overwrite_frequency` updates the weights are overwritten with the average.  A skipped step leaves the average alone.  The
-    average is read through Model.ema_weights / averaged_weights / evaluate(averaged=True) / save_weights(averaged=True) / finalize_ema."""
+    average is read through Model.ema_weights / averaged_weights / evaluate(averaged=True) / save_weights(averaged=True) / finalize_ema.
+
+    `awp_delta`, `awp_eps`, `awp_start_step`, `awp_relative`: adversarial weight perturbation in `train_on_batch` (csrc/awp.hip).  With
+    `awp_delta` set, a step whose number `iterations` has reached `awp_start_step` takes the gradient, moves every weight tensor W by
+    awp_delta * g_W / (||g_W|| + awp_eps) (with `awp_relative` by awp_delta * ||W|| * g_W / (||g_W|| + awp_eps)), runs forward and backward
+    again at the moved weights with the same dropout masks, puts the weights back bit for bit and steps on the second gradient.  The
+    recipes' "AWP from epoch E" is awp_start_step = E * steps_per_epoch.  Both training-mode forwards update the BatchNorm moving
+    statistics, as a Keras model called twice does.  The step is read through Model.awp_stats / awp_scales; None (the default) is the
+    step without any of it."""
 
     def __init__(self, learning_rate=1e-3, weight_decay=0.0, global_clipnorm=None, skip_nonfinite=False, accumulate_steps=1,
-                 use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_warmup=False):
+                 use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_warmup=False,
+                 awp_delta=None, awp_eps=1e-4, awp_start_step=0, awp_relative=False):
         self._lr = _Scalar(learning_rate)
         # The reference assigns `.weight_decay` on the Lookahead wrapper (c11:64), which is not
         # one of its hyper-parameters, so RectifiedAdam keeps weight_decay=0 (SURVEY §8a row 10).
@@ -71,6 +80,28 @@ class Optimizer:
         self.ema_momentum = ema_momentum
         self.ema_overwrite_frequency = ema_overwrite_frequency
         self.ema_warmup = ema_warmup
+        self.awp_delta = awp_delta
+        self.awp_eps = awp_eps
+        self.awp_start_step = awp_start_step
+        self.awp_relative = awp_relative
+
+    def awp_options(self):
+        """(delta or None, eps, start step, relative), checked"""
+        d, e, start = self.awp_delta, self.awp_eps, self.awp_start_step
+
+        def positive_f32(v):       # what the kernel is handed: 1e39 is inf and 1e-50 is 0 as float32
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                return False
+            with np.errstate(over="ignore", under="ignore"):
+                f = float(np.float32(v))
+            return math.isfinite(f) and f > 0
+        if d is not None and not positive_f32(d):
+            raise ValueError(f"awp_delta must be None or a finite number > 0 (as float32), got {d!r}")
+        if not positive_f32(e):
+            raise ValueError(f"awp_eps must be a finite number > 0 (as float32), got {e!r}")
+        if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or start < 0:
+            raise ValueError(f"awp_start_step must be an integer >= 0, got {start!r}")
+        return None if d is None else float(d), float(e), int(start), bool(self.awp_relative)
 
     def ema_options(self):
         """(use_ema, momentum, overwrite frequency or 0, warmup), checked"""
@@ -176,6 +207,8 @@ class Model(Handle):
         self._ema_avg = None       # [n_train] f32 moving average of params[:n_train], allocated by the first step with optimizer.use_ema
         self._ema_rec = None       # the 16-byte ishara_ema_state record (2 x int64 storage)
         self._ema_swapped = False  # inside averaged_weights(): params[:n_train] and _ema_avg have changed places
+        self._awp_backup = None    # [n_train] f32 copy of params[:n_train] while they are perturbed, allocated by the first step AWP is active in
+        self._awp = None           # with it: the segment table, the scale array, the record, the workspace and the two loss tensors
         if device is not None:
             self._to_device(device, seed)
 
@@ -362,7 +395,11 @@ class Model(Handle):
         (parallel.overlap_enabled) applies only when accumulate_steps == 1; otherwise the accumulator is reduced in one piece.  Still no
         host sync: `grad_stats()` reads the record when asked.
 
-        `frame_lengths` [B]: per-clip frame counts of this (micro)batch, as in __call__; every path above takes them."""
+        `frame_lengths` [B]: per-clip frame counts of this (micro)batch, as in __call__; every path above takes them.
+
+        With `optimizer.awp_delta` set and `optimizer.iterations` >= `awp_start_step`, the gradient of every (micro)batch on every path
+        above is the adversarial one (_loss_and_gradients_step: two passes around ishara_awp_perturb / ishara_awp_restore); the loss
+        returned is the first pass's, the all-reduce stays where it is, behind the second pass."""
         from . import parallel
         k, clip, skip = self.optimizer.train_options()
         self._not_while_averaged("train_on_batch")
@@ -370,7 +407,7 @@ class Model(Handle):
             return self._train_microbatch(x, y, seed, allreduce, k, clip, skip, frame_lengths)
         world = parallel.world_size()
         if not allreduce:
-            loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world, **_fl_kw(frame_lengths))
+            loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths)
             self.apply_gradients()
             return loss
         overlap = world > 1 and parallel.overlap_enabled()
@@ -380,7 +417,7 @@ class Model(Handle):
             # replicas share the weight-initialisation seed but draw independent dropout / drop-path masks for their shards,
             # like the reference's replicas (tf.distribute / nn.DataParallel keep per-replica RNG streams)
             seed = ((self._step_seed + 0x9E3779B1 * self._steps) ^ (parallel.rank() * 0x85EBCA6B)) & 0xFFFFFFFF
-        loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world, **_fl_kw(frame_lengths))
+        loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths)
         if overlap:
             parallel.allreduce_buckets_(self)          # ranges of the gradient reduced on a side stream as the backward pass finishes them
         elif world > 1:
@@ -401,7 +438,7 @@ class Model(Handle):
             seed = (self._step_seed + 0x9E3779B1 * (self._steps * k + self._micro)) & 0xFFFFFFFF
             if world > 1:
                 seed = (seed ^ (parallel.rank() * 0x85EBCA6B)) & 0xFFFFFFFF
-        loss, _ = self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0 / world, **_fl_kw(frame_lengths))
+        loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths, ends_cycle=self._micro + 1 >= k)
         src = self.grads[:self.n_train]
         if k > 1:
             if self._grad_acc is None:
@@ -439,6 +476,78 @@ class Model(Handle):
             self._ema_update(ema, self._gstats, skip)
         self.optimizer.iterations += 1
         self._steps += 1
+
+    # ------------------------------------------------------------------ adversarial weight perturbation (csrc/awp.hip)
+    def _awp_begin_step(self):
+        """In front of a (micro)batch of train_on_batch: the checked AWP options when the perturbation is configured and the step number has
+        reached awp_start_step, else None (and then nothing of it is touched, allocated or launched).  The first active step allocates
+        the backup of the trainable prefix, the segment table (one segment per trainable entry), the scale array, the 16-byte record, the
+        workspace and the two loss tensors; nothing of it needs initialising."""
+        opts = self.optimizer.awp_options()
+        if opts[0] is None or self.optimizer.iterations < opts[2]:
+            return None
+        if self._awp_backup is None:
+            from . import train_state as TS
+            seg = TS.awp_segments(self.entries, self.n_train)
+            S = len(seg) - 1
+            ws_bytes = int(self._lib.ishara_awp_workspace_bytes(self.n_train, S))
+            if ws_bytes < 0:
+                _lib.check(-1, "ishara_awp_workspace_bytes")
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self._awp = dict(seg=torch.from_numpy(seg).to(self.device), S=S, scale=torch.zeros(S, **f32),
+                             rec=torch.zeros(4, dtype=torch.int32, device=self.device), ws=torch.empty(ws_bytes, dtype=torch.uint8, device=self.device),
+                             clean=torch.zeros(1, **f32), adv=torch.zeros(1, **f32), ran=False)
+            self._awp_backup = torch.empty(self.n_train, **f32)
+        return opts
+
+    def _loss_and_gradients_step(self, x, y, seed, loss_scale: float, frame_lengths, ends_cycle: bool = True) -> torch.Tensor:
+        """The gradient of one (micro)batch of train_on_batch -> its loss tensor.  Without AWP: loss_and_gradients, as ever.  With it:
+        pass 1 at loss scale 1 (the perturbation does not depend on the world size; no collective), ishara_awp_perturb on the trainable
+        prefix by that gradient, pass 2 at the perturbed weights with the same seed (the dropout and drop-path masks the adversary was
+        computed for) and the caller's loss scale, ishara_awp_restore.  `grads` then hold the second gradient; the loss returned is the
+        first pass's, in a tensor of the helper's own, comparable with a run without AWP.  The weight shadows are refreshed behind the
+        perturbation, and behind the restore by the optimizer step that follows, or here when the microbatch does not end its cycle
+        (ends_cycle False).  No host synchronise."""
+        awp = self._awp_begin_step()
+        if awp is None:
+            return self.loss_and_gradients(x, y, seed=seed, loss_scale=loss_scale, **_fl_kw(frame_lengths))[0]
+        delta, eps, _, relative = awp
+        a = self._awp
+        if seed is None:                # both passes draw the masks __call__ would have drawn for this step
+            seed = (self._step_seed + 0x9E3779B1 * self._steps) & 0xFFFFFFFF
+        self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0, **_fl_kw(frame_lengths))
+        a["clean"].copy_(self._loss_buf)
+        _lib.check(self._lib.ishara_awp_perturb(self._h, _lib.ptr(self.params), _lib.ptr(self._awp_backup), _lib.ptr(self.grads), _lib.ptr(a["seg"]),
+                                                a["S"], self.n_train, C.c_float(delta), C.c_float(eps), 1 if relative else 0, _lib.ptr(a["scale"]),
+                                                _lib.ptr(a["rec"]), _lib.ptr(a["ws"]), _stream()), "ishara_awp_perturb")
+        _lib.check(self._lib.ishara_sync_weights(self._h, _stream()), "ishara_sync_weights")
+        self.loss_and_gradients(x, y, seed=seed, loss_scale=loss_scale, **_fl_kw(frame_lengths))
+        a["adv"].copy_(self._loss_buf)
+        _lib.check(self._lib.ishara_awp_restore(self._h, _lib.ptr(self.params), _lib.ptr(self._awp_backup), self.n_train, _stream()), "ishara_awp_restore")
+        if not ends_cycle:
+            _lib.check(self._lib.ishara_sync_weights(self._h, _stream()), "ishara_sync_weights")
+        a["ran"] = True
+        return a["clean"]
+
+    def _awp_required(self, what: str):
+        if self._awp is None or not self._awp["ran"]:
+            raise _lib.IsharaError(f"{what}: no step has run with adversarial weight perturbation (optimizer.awp_delta set and awp_start_step reached)")
+
+    def awp_stats(self) -> Dict[str, float]:
+        """{grad_norm, delta_norm, perturbed, zeroed, clean_loss, adv_loss} of the last perturbed (micro)batch: the norm of its first
+        gradient and of the perturbation over the tensors that were perturbed, how many tensors were perturbed and how many were left alone
+        (a NaN or Inf in their gradient), the loss at the weights and at the perturbed weights.  This read is the only host synchronise of
+        the feature."""
+        self._awp_required("awp_stats")
+        raw = self._awp["rec"].cpu().numpy()
+        return dict(grad_norm=float(raw[:2].view(np.float32)[0]), delta_norm=float(raw[:2].view(np.float32)[1]), perturbed=int(raw[2]), zeroed=int(raw[3]),
+                    clean_loss=float(self._awp["clean"].item()), adv_loss=float(self._awp["adv"].item()))
+
+    def awp_scales(self) -> Dict[str, float]:
+        """{entry name: the factor its gradient was multiplied by} of the last perturbed (micro)batch, 0.0 for a tensor left alone"""
+        self._awp_required("awp_scales")
+        names = [n for _, n in sorted((o, n) for n, _, o, t in self.entries if t)]
+        return dict(zip(names, (float(v) for v in self._awp["scale"].cpu().numpy())))
 
     # ------------------------------------------------------------------ moving average of the weights (csrc/weight_avg.hip)
     def _not_while_averaged(self, what: str):
@@ -546,7 +655,7 @@ class Model(Handle):
         st = TS.pack_state(self.entries, *(t.detach().cpu().numpy() for t in (self.params, self.opt_m, self.opt_v, self.opt_slow)),
                            iterations=o.iterations, steps=self._steps, step_seed=self._step_seed, learning_rate=float(o.learning_rate),
                            weight_decay=float(o.weight_decay), apply_weight_decay=o.apply_weight_decay, global_clipnorm=o.global_clipnorm,
-                           skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped, **self._ema_state_entries())
+                           skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped, **self._ema_state_entries(), **self._awp_state_entries())
         return TS.save_state_file(path, st)
 
     def _ema_state_entries(self) -> dict:
@@ -557,10 +666,19 @@ class Model(Handle):
         return dict(ema_avg=self._ema_avg.cpu().numpy(), ema_updates=self.ema_state()["updates"], use_ema=use, ema_momentum=momentum,
                     ema_warmup=warmup, ema_overwrite_frequency=every or None)
 
+    def _awp_state_entries(self) -> dict:
+        """what save_state adds for adversarial weight perturbation: its four options when it is configured (it has no device state
+        beyond them), nothing otherwise"""
+        delta, eps, start, relative = self.optimizer.awp_options()
+        if delta is None:
+            return {}
+        return dict(awp_delta=delta, awp_eps=eps, awp_start_step=start, awp_relative=relative)
+
     def load_state(self, path: str):
         """Restores what save_state wrote into this model (same architecture: the entry list is checked).  A file with a moving average
         restores it, its update count and the four ema settings; a file without one leaves the settings alone and, with optimizer.use_ema
-        on, starts a fresh average at the loaded weights with 0 updates."""
+        on, starts a fresh average at the loaded weights with 0 updates.  A file with the options of adversarial weight perturbation sets
+        them; a file without them leaves them alone."""
         from . import train_state as TS
         self._not_while_averaged("load_state")
         st = TS.load_state_file(path, self.entries)
@@ -575,6 +693,8 @@ class Model(Handle):
             self._gstats_ws = torch.empty(int(self._lib.ishara_grad_stats_workspace_bytes(self.n_train)), dtype=torch.uint8, device=self.device)
         self._gstats[3] = st["skipped"]
         self._skipped_seen = st["skipped"]
+        if "awp_delta" in st:
+            o.awp_delta, o.awp_eps, o.awp_start_step, o.awp_relative = st["awp_delta"], st["awp_eps"], st["awp_start_step"], st["awp_relative"]
         self._ema_avg = self._ema_rec = None
         if "ema_avg" in st:
             o.use_ema, o.ema_momentum, o.ema_warmup, o.ema_overwrite_frequency = st["use_ema"], st["ema_momentum"], st["ema_warmup"], st["ema_overwrite_frequency"]

@@ -132,8 +132,74 @@ def ema_reference(avg: np.ndarray, theta: np.ndarray, state: dict, momentum: flo
     return avg, theta
 
 
+# ---------------------------------------------------------------------------------- adversarial weight perturbation (csrc/awp.hip)
+AWP_CHUNK = 4096          # elements of one chunk of a segment (csrc/awp.hip): a segment longer than this is summed in pieces
+
+
+def awp_segments(entries: Iterable[Tuple[str, tuple, int, bool]], n_train: int) -> np.ndarray:
+    """seg_off of ishara_awp_perturb, int64 [S + 1]: the offsets of the trainable entries in offset order, then n_train.  The trainable
+    entries must tile [0, n_train) exactly (they do: the parameter layout puts them in front of the BatchNorm moving statistics)."""
+    segs = sorted((int(o), int(np.prod(s))) for _, s, o, t in entries if t)
+    pos = 0
+    for o, size in segs:
+        if o != pos or size < 1:
+            raise ValueError(f"awp_segments: the trainable entries do not tile [0, {n_train}): an entry of {size} elements at offset {o}, expected offset {pos}")
+        pos += size
+    if pos != int(n_train) or not segs:
+        raise ValueError(f"awp_segments: the trainable entries cover [0, {pos}), not [0, {n_train})")
+    return np.array([o for o, _ in segs] + [pos], dtype=np.int64)
+
+
+def _awp_sumsq(x: np.ndarray) -> float:
+    """sum of (double)x[i]^2, exactly rounded (each square of an fp32 value is exact in fp64); inf / nan when the data holds one"""
+    d = np.asarray(x, dtype=np.float32).astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        sq = d * d
+    if not np.isfinite(sq).all():
+        return float("nan") if np.isnan(sq).any() else float("inf")
+    try:
+        return math.fsum(sq.tolist())
+    except OverflowError:
+        return float("inf")
+
+
+def awp_reference(w: np.ndarray, g: np.ndarray, seg_off: Sequence[int], delta: float, eps: float, relative: bool = False
+                  ) -> Tuple[np.ndarray, np.ndarray, dict]:
+    """One ishara_awp_perturb in numpy -> (w_adv float32 [n], scale float32 [S], {grad_norm, delta_norm, perturbed, zeroed}).  Per
+    segment s = [seg_off[s], seg_off[s + 1]): ss_g = sum g^2 (and ss_w = sum w^2 with `relative`) in fp64 through math.fsum; a sum that is
+    not finite zeroes the segment (scale 0, the weights keep their bits); else scale = fp32(delta / (sqrt(ss_g) + eps)), with `relative`
+    fp32(delta * sqrt(ss_w) / (sqrt(ss_g) + eps)), delta and eps taken as fp32 values like the kernel's arguments, and
+    w_adv = fp32(w + fp32(scale * g)): numpy rounds each operation to fp32 and fuses nothing.  The two norms sum over the segments that
+    were not zeroed, in segment order."""
+    w = np.asarray(w, dtype=np.float32).reshape(-1)
+    g = np.asarray(g, dtype=np.float32).reshape(-1)
+    seg_off = [int(o) for o in seg_off]
+    d64, e64 = float(np.float32(delta)), float(np.float32(eps))
+    out = w.copy()
+    scale = np.zeros(len(seg_off) - 1, dtype=np.float32)
+    tot_g = tot_d = 0.0
+    zeroed = 0
+    for s, (lo, hi) in enumerate(zip(seg_off[:-1], seg_off[1:])):
+        ss_g = _awp_sumsq(g[lo:hi])
+        ss_w = _awp_sumsq(w[lo:hi]) if relative else 0.0
+        if not math.isfinite(ss_g) or not math.isfinite(ss_w):
+            zeroed += 1
+            continue
+        num = d64 * math.sqrt(ss_w) if relative else d64
+        scale[s] = np.float32(num / (math.sqrt(ss_g) + e64))
+        with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+            step = scale[s] * g[lo:hi]
+            out[lo:hi] = w[lo:hi] + step
+        tot_g += ss_g
+        tot_d += float(scale[s]) ** 2 * ss_g
+    stats = dict(grad_norm=float(np.float32(math.sqrt(tot_g))), delta_norm=float(np.float32(math.sqrt(tot_d))),
+                 perturbed=len(scale) - zeroed, zeroed=zeroed)
+    return out, scale, stats
+
+
 # ---------------------------------------------------------------------------------- the state file
 EMA_KEYS = ("ema_avg", "ema_updates", "ema_momentum", "ema_warmup", "ema_overwrite_frequency", "use_ema")
+AWP_KEYS = ("awp_delta", "awp_eps", "awp_start_step", "awp_relative")
 
 
 class TrainStateError(ValueError):
@@ -154,11 +220,13 @@ def pack_state(entries, params: np.ndarray, opt_m: np.ndarray, opt_v: np.ndarray
                step_seed: int, learning_rate: float, weight_decay: float, apply_weight_decay: bool = False,
                global_clipnorm: Optional[float] = None, skip_nonfinite: bool = False, accumulate_steps: int = 1, skipped: int = 0,
                ema_avg: Optional[np.ndarray] = None, ema_updates: int = 0, use_ema: bool = True, ema_momentum: float = 0.99,
-               ema_warmup: bool = False, ema_overwrite_frequency: Optional[int] = None) -> Dict[str, np.ndarray]:
+               ema_warmup: bool = False, ema_overwrite_frequency: Optional[int] = None, awp_delta: Optional[float] = None,
+               awp_eps: float = 1e-4, awp_start_step: int = 0, awp_relative: bool = False) -> Dict[str, np.ndarray]:
     """The arrays of one state file (np.savez(path, **pack_state(...))): the flat fp32 `params` (BatchNorm moving statistics included), the
     three optimizer slots, the counters, the hyper-parameters, the format version and the entry list the buffers were laid out by.  With
     `ema_avg` (the moving average of the trainable prefix, when one exists) the file also holds EMA_KEYS: the average, its update count
-    and the four settings; without it the key set is what it was before the average existed."""
+    and the four settings; without it the key set is what it was before the average existed.  With `awp_delta` (adversarial weight
+    perturbation is configured) it holds AWP_KEYS, the four options; AWP has no other state."""
     out = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in zip(ARRAYS, (params, opt_m, opt_v, opt_slow))}
     out.update(_entry_arrays(entries))
     out.update(format_version=np.int64(FORMAT_VERSION), iterations=np.int64(iterations), steps=np.int64(steps), step_seed=np.int64(step_seed),
@@ -170,6 +238,8 @@ def pack_state(entries, params: np.ndarray, opt_m: np.ndarray, opt_v: np.ndarray
         out.update(ema_avg=np.ascontiguousarray(a).reshape(-1) if a.dtype == np.float32 else a, ema_updates=np.int64(ema_updates),
                    use_ema=np.bool_(use_ema), ema_momentum=np.float64(ema_momentum), ema_warmup=np.bool_(ema_warmup),
                    ema_overwrite_frequency=np.int64(0 if ema_overwrite_frequency is None else ema_overwrite_frequency))
+    if awp_delta is not None:
+        out.update(awp_delta=np.float64(awp_delta), awp_eps=np.float64(awp_eps), awp_start_step=np.int64(awp_start_step), awp_relative=np.bool_(awp_relative))
     validate_state(out, entries)
     return out
 
@@ -217,12 +287,20 @@ def validate_state(z, entries) -> None:
         m = float(z["ema_momentum"])
         if int(z["ema_updates"]) < 0 or int(z["ema_overwrite_frequency"]) < 0 or not 0.0 <= m < 1.0:
             raise TrainStateError("train state: an entry of the moving average (ema_updates, ema_overwrite_frequency, ema_momentum) is out of range")
+    if "awp_delta" in keys:             # so are the options of adversarial weight perturbation
+        for k in AWP_KEYS:
+            if k not in keys:
+                raise TrainStateError(f"train state: missing entry '{k}' (the file holds 'awp_delta')")
+        d, e = float(np.float32(z["awp_delta"])), float(np.float32(z["awp_eps"]))
+        if not (math.isfinite(d) and d > 0 and math.isfinite(e) and e > 0 and int(z["awp_start_step"]) >= 0):
+            raise TrainStateError("train state: an option of the weight perturbation (awp_delta, awp_eps, awp_start_step) is out of range")
 
 
 def unpack_state(z, entries) -> dict:
     """validate_state, then plain Python values: the four arrays (float32, flat) and the scalars; global_clipnorm is None when off.  A file
     with the moving average adds ema_avg (float32), ema_updates, use_ema, ema_momentum, ema_warmup and ema_overwrite_frequency (None when
-    off); a file without it adds none of them."""
+    off); a file without it adds none of them.  A file with the options of the weight perturbation adds awp_delta, awp_eps, awp_start_step
+    and awp_relative."""
     validate_state(z, entries)
     out = {k: np.array(z[k], dtype=np.float32) for k in ARRAYS}
     for k in ("iterations", "steps", "step_seed", "accumulate_steps", "skipped"):
@@ -238,6 +316,8 @@ def unpack_state(z, entries) -> dict:
         every = int(z["ema_overwrite_frequency"])
         out.update(ema_avg=np.array(z["ema_avg"], dtype=np.float32), ema_updates=int(z["ema_updates"]), use_ema=bool(z["use_ema"]),
                    ema_momentum=float(z["ema_momentum"]), ema_warmup=bool(z["ema_warmup"]), ema_overwrite_frequency=every if every > 0 else None)
+    if "awp_delta" in keys:
+        out.update(awp_delta=float(z["awp_delta"]), awp_eps=float(z["awp_eps"]), awp_start_step=int(z["awp_start_step"]), awp_relative=bool(z["awp_relative"]))
     return out
 
 

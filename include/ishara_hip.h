@@ -430,6 +430,26 @@ int ishara_ctc_align_ex(const float* logits, const int64_t* labels, int32_t B, i
                         void* ws, int32_t* frame_pos, int32_t* start, int32_t* end, float* conf, float* score,
                         const int32_t* frame_len, ishara_stream s);
 
+/* Model ensembling before the CTC decode: the frame posteriors of M models fused into one normalised log-distribution per frame.
+ * logits: a HOST array of M device pointers, each [B,T,C] fp32; the launcher copies them into the kernel's arguments by value (no device
+ * pointer table, no allocation, no memset; a captured graph replays the call).  weights: device fp32 [M]; inv_temp: device fp32 [M]
+ * (1 / temperature) or NULL for all 1; both are read on the device at every launch, so a caller may rewrite them between replays of a
+ * graph without capturing again.  out [B,T,C] fp32.  prof may be NULL; a handle only lends its profiler (key logits_combine,
+ * (M + 1) * B*T*C*4 bytes: the weights cannot be read on the host, every model counts as read).
+ * Per row (b, t), every step in fp32, for the models with weights[m] > 0 in ascending m:
+ *     z = logits_m[row, c] * inv_temp[m]  (one multiply; none with NULL),   lp_m[c] = (z[c] - max_c z) - log(sum_c exp(z[c] - max_c z))
+ *   mode 0 (log-linear, product of experts):  s[c] = sum_m weights[m] * lp_m[c]
+ *   mode 1 (linear, mixture):                 s[c] = a[c] + log(sum_m exp(log(weights[m]) + lp_m[c] - a[c])),  a[c] = max_m (log(weights[m]) + lp_m[c])
+ *   out[row, c] = s[c] - logsumexp_c s[c]:  a normalised log-distribution in both modes, whatever the weights sum to.
+ * A model whose weight is not > 0 is not read at all (its buffer may hold NaN); no weight > 0: every row is the uniform -log C.  frame_len:
+ * device int32 [B] or NULL (the convention of ishara_greedy_decode_ex): clip b has Tb = frame_len[b] frames, a value outside [1, T] means no
+ * frames; rows t >= Tb are not read from any model and are written +0.0.  Inputs are assumed finite; no index is derived from data.
+ * One kernel, no atomics, fixed-order class reductions: bit-identical from run to run.  Refused with a message before any HIP call: a null
+ * logits, logits[m], weights or out; M outside 1..8; C outside 2..64; T outside 1..4096; B < 0 (B == 0: nothing is launched); mode not 0 or
+ * 1; a pointer that is not 4-byte aligned; out overlapping any input range (B*T*C*4 bytes each). */
+int ishara_logits_combine(ishara_model* prof, const float* const* logits, int32_t M, int32_t B, int32_t T, int32_t C,
+                          const float* weights, const float* inv_temp, int32_t mode, const int32_t* frame_len, float* out, ishara_stream s);
+
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */
 typedef struct ishara_clip_aug {

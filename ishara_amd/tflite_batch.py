@@ -212,11 +212,24 @@ class BatchedTFLiteModel:
 
     # ---- device work of one batch
     def _launch(self, slot: int, scoring: bool, breakdown: bool = False):
+        self._launch_logits(slot)
+        self._launch_tail(slot, scoring, breakdown)
+
+    def _launch_preprocess(self, slot: int):
+        d = self._d_in[slot]
+        _lib.check(self.model._lib.ishara_preprocess_batch(_lib.ptr(self._raw(d)), self._cap, _lib.ptr(self._off(d)), self.batch_size, self.max_frames,
+                                                           _lib.ptr(self._mean), _lib.ptr(self._std), _lib.ptr(self._x), self.T, _stream()),
+                   "ishara_preprocess_batch")
+
+    def _launch_logits(self, slot: int):
+        """device slot `slot` -> self._logits, the buffer the decoders read (EnsembleTFLiteModel: every model's forward pass and the fusion)"""
+        self._launch_preprocess(slot)
+        _lib.check(self.model._lib.ishara_forward(self.model._h, _lib.ptr(self._x), self.batch_size, _lib.ptr(self._logits), 0, C.c_uint32(0), _stream()),
+                   "ishara_forward")
+
+    def _launch_tail(self, slot: int, scoring: bool, breakdown: bool = False):
         lib, m, d, bs = self.model._lib, self.model, self._d_in[slot], self.batch_size
         st = _stream()
-        _lib.check(lib.ishara_preprocess_batch(_lib.ptr(self._raw(d)), self._cap, _lib.ptr(self._off(d)), bs, self.max_frames,
-                                               _lib.ptr(self._mean), _lib.ptr(self._std), _lib.ptr(self._x), self.T, st), "ishara_preprocess_batch")
-        _lib.check(lib.ishara_forward(m._h, _lib.ptr(self._x), bs, _lib.ptr(self._logits), 0, C.c_uint32(0), st), "ishara_forward")
         if self._beam is None:
             _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), bs, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), st),
                        "ishara_greedy_decode")
@@ -236,18 +249,21 @@ class BatchedTFLiteModel:
                                                          _lib.ptr(k["conf"]), k["ws"], _stream()), "ishara_edit_alignment")
 
     def _graph(self, slot: int, scoring: bool, breakdown: bool = False):
-        key = (slot, scoring, breakdown)
+        return self._captured((slot, scoring, breakdown), lambda: self._launch(slot, scoring, breakdown), breakdown)
+
+    def _captured(self, key, launch, breakdown: bool = False):
+        """The graph of `launch()` under `key`, captured on first use."""
         if key not in self._graphs:              # as TFLiteModel._capture: warm-up outside the capture, then capture once
             conf = self._breakdown_buffers()["conf"].clone() if breakdown else None      # the warm-up launch adds to the matrix: put it back
             side = torch.cuda.Stream(device=self.model.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._launch(slot, scoring, breakdown)
+                launch()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._launch(slot, scoring, breakdown)
+                launch()
             if breakdown:
                 self._brk["conf"].copy_(conf)
             self._graphs[key] = g
@@ -289,33 +305,41 @@ class BatchedTFLiteModel:
                 part = clips[b0:b0 + bs]
                 yield (lambda raw, out_off, part=part: pack_clips(part, raw, out_off)), len(part)
 
+    def _stage(self, i: int, fill, n: int, targets=None) -> int:
+        """Pack batch i (n clips, with its rows of `targets` when scoring) into its pinned slot and copy it to the device slot on the copy
+        stream; the current stream waits for the copy.  Returns the slot."""
+        s, bs = i & 1, self.batch_size
+        h, d = self._h_in[s], self._d_in[s]
+        # the pinned slot is free: the batch that used it two steps ago was collected (its `done` waited on its copy)
+        rows = fill(self._raw(h).numpy(), self._off(h).numpy())
+        if targets is not None:
+            t = self._tgt(h).numpy()
+            t[:n] = targets[i * bs:i * bs + n]
+            t[n:] = PAD_TOKEN_IDX
+        nbytes = self._raw_at + rows * _ROW_BYTES
+        with torch.cuda.stream(self._copy_stream):
+            if self._consumed[s] is not None:    # the replay that last read this device slot
+                self._copy_stream.wait_event(self._consumed[s])
+            d[:nbytes].copy_(h[:nbytes], non_blocking=True)
+            self._copied[s].record(self._copy_stream)
+        torch.cuda.current_stream().wait_event(self._copied[s])
+        return s
+
+    def _mark_consumed(self, s: int):
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        self._consumed[s] = ev
+
     def _process(self, clips, targets=None, breakdown: bool = False):
         """Run every batch; returns the host results per batch: (indices [n, T], lengths, dist, tlen), with breakdown followed by
         (ops [n, 4], aligned [n, L], inserted [n, L + 1])."""
         scoring = targets is not None
-        bs = self.batch_size
         cur = torch.cuda.current_stream()
         out, pending = [], None
         for i, (fill, n) in enumerate(self._batches(clips)):
-            s = i & 1
-            h, d = self._h_in[s], self._d_in[s]
-            # the pinned slot is free: the batch that used it two steps ago was collected (its `done` waited on its copy)
-            rows = fill(self._raw(h).numpy(), self._off(h).numpy())
-            if scoring:
-                t = self._tgt(h).numpy()
-                t[:n] = targets[i * bs:i * bs + n]
-                t[n:] = PAD_TOKEN_IDX
-            nbytes = self._raw_at + rows * _ROW_BYTES
-            with torch.cuda.stream(self._copy_stream):
-                if self._consumed[s] is not None:    # the replay that last read this device slot
-                    self._copy_stream.wait_event(self._consumed[s])
-                d[:nbytes].copy_(h[:nbytes], non_blocking=True)
-                self._copied[s].record(self._copy_stream)
-            cur.wait_event(self._copied[s])
+            s = self._stage(i, fill, n, targets)
             self._run(s, scoring, breakdown, n)
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            self._consumed[s] = ev
+            self._mark_consumed(s)
             self._h_res[s].copy_(self._d_res, non_blocking=True)
             if breakdown:
                 self._brk["h"][s].copy_(self._brk["d"], non_blocking=True)

@@ -450,6 +450,37 @@ int ishara_ctc_align_ex(const float* logits, const int64_t* labels, int32_t B, i
 int ishara_logits_combine(ishara_model* prof, const float* const* logits, int32_t M, int32_t B, int32_t T, int32_t C,
                           const float* weights, const float* inv_temp, int32_t mode, const int32_t* frame_len, float* out, ishara_stream s);
 
+/* Minimum-Bayes-risk selection over an n-best list; the semantics of ishara_amd/mbr.py (mbr_reference).  Per clip, among the live
+ * hypotheses, the one whose expected edit distance to the others is smallest, copied into the greedy layout.
+ *   hyp_idx [B,N,T] int32 as ishara_ctc_beam_decode writes it (only the first min(len, T) symbols of a live row are read); hyp_len [B,N]:
+ *   a slot is live iff hyp_len >= 0, the length is clamped to T; dead slots are neither candidates nor voters.  hyp_score [B,N]
+ *   natural-log scores (ignored, and may be NULL, when weights != NULL); weights [B,N] or NULL: explicit votes; inv_temp: ONE float on the
+ *   device or NULL for 1.0, read at every launch (a captured graph follows a caller that rewrites it, as it follows rewritten weights).
+ * Distance: d[i][j] = the unit-cost Levenshtein distance of the live hypotheses i and j, an integer, symmetric, d[i][i] = 0.
+ * Vote of slot j: with weights, w_j = weights[j] where that is finite and > 0, else +0.  Without, x_j = (s_j - s_max) * inv_temp (one fp32
+ *   subtraction, one fp32 multiplication), s_max the largest finite score of the live slots, w_j = expf(x_j); a live slot whose score is
+ *   not finite (-inf, NaN, +inf) votes +0 and does not enter s_max.  The votes are not normalised.
+ * Risk: risk_i = sum_j w_j * c_ij over the live j in ascending slot order from +0; mode 0: c_ij = (float)d_ij; mode 1: c_ij =
+ *   (float)d_ij / (float)max(len_j, 1) (the c18 metric, normalised by the voter's length as by a target's).  The division, the
+ *   multiplication and every addition are single round-to-nearest fp32 operations without FMA contraction: given w_out, float32 arithmetic
+ *   in that order reproduces risk bit for bit.
+ * Selection: slots in ascending order, a later slot wins only with a strictly smaller risk (ties go to the lowest slot, the higher score
+ *   of a ranked n-best; a NaN never wins).
+ * -> out_idx [B,T] (the selected hypothesis, -1 past its end; every element is written), out_len [B], best [B] (the selected slot), and,
+ *   each NULL or: risk [B,N] fp32 (NaN in dead slots), w_out [B,N] fp32 (the votes used, +0 in dead slots), dist [B,N,N] int32 (-1 in dead
+ *   rows and columns), status [B] int32.
+ * Status, for a clip the kernel does not rank: bit 0 a live hypothesis is longer than 64 symbols (MAX_PHRASE_LENGTH, the limit of
+ *   ishara_edit_distance's targets); bit 1 a live symbol lies outside [0, C) (among the first 64 of each hypothesis; never used as an
+ *   index); bit 2 no live slot.  With bit 0 or 1: best = the lowest live slot, risk of the whole clip NaN, dist of the clip -1, w_out as
+ *   above.  With bit 2: best = -1, out_len = 0, out_idx all -1.
+ * 1 <= N <= 64, 1 <= T <= 4096, 2 <= C <= 64, mode 0 or 1, B >= 0 (0: nothing is launched), 4-byte alignment of every buffer, out_idx
+ * not overlapping hyp_idx, hyp_idx / hyp_len / out_idx / out_len / best non-NULL and hyp_score non-NULL when weights is NULL; anything
+ * else is refused with a message before any HIP call.  One kernel (one workgroup per clip, bit-vector edit distances, no workspace), no
+ * atomics, graph-capturable, bit-identical from run to run. */
+int ishara_mbr_select(const int32_t* hyp_idx, const int32_t* hyp_len, const float* hyp_score, const float* weights, const float* inv_temp,
+                      int32_t B, int32_t N, int32_t T, int32_t C, int32_t mode, int32_t* out_idx, int32_t* out_len, int32_t* best,
+                      float* risk, float* w_out, int32_t* dist, int32_t* status, ishara_stream s);
+
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */
 typedef struct ishara_clip_aug {

@@ -182,6 +182,28 @@ def ctc_beam_decode(logits, lengths=None, beam_width: int = 16, nbest: int = 1, 
     return [[(idx[b, n, :ln[b, n]].astype(np.int64), float(sc[b, n])) for n in range(nbest) if ln[b, n] >= 0] for b in range(B)]
 
 
+def ctc_beam_nbest_device(logits, lengths=None, beam_width: int = 16, nbest: int = 8, lm=None, alpha: float = 0.0, beta: float = 0.0,
+                          workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The same search left on the device: (indices int32 [B, nbest, T] padded with -1, lengths int32 [B, nbest] with -1 in a slot without
+    a hypothesis, scores fp32 [B, nbest] with -inf there), ranked best first: what `mbr.mbr_select` and `mbr.pool_nbest` read.  Launched on
+    the current stream; nothing waits."""
+    from . import ctc_beam
+    x, fl = _ragged(logits, lengths)
+    B, T, Cc = x.shape
+    ctc_beam.check_device_args(Cc, T, beam_width, nbest)
+    lm_dev = ctc_beam.lm_to_device(lm, Cc, x.device)
+    lib = _lib.load()
+    nbytes = max(ctc_beam.workspace_bytes(lib, B, T, Cc, beam_width), 4)
+    ws = workspace if workspace is not None and workspace.numel() >= nbytes else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    idx = torch.empty((B, nbest, T), dtype=torch.int32, device=x.device)
+    ln = torch.empty((B, nbest), dtype=torch.int32, device=x.device)
+    sc = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        ctc_beam.launch(lib, x, B, T, Cc, beam_width, nbest, lm_dev, alpha, beta, ws, idx, ln, sc, _lib.stream(), frame_len=fl, ex=True)
+    del ws        # the caching allocator hands the block out again in stream order: the kernel has read it by then
+    return idx, ln, sc
+
+
 def ctc_align(logits, labels, lengths=None, blank: Optional[int] = None, workspace: Optional[torch.Tensor] = None) -> list:
     """CTC forced alignment (ishara_amd/ctc_align.py semantics) of every clip's first `lengths[b]` frames to labels [B, L] padded with
     blank (default C - 1) -> per clip an Alignment, what `Model.align` returns; frame_pos keeps the buffer's T entries, -1 past the clip."""

@@ -932,6 +932,25 @@ class Model(Handle):
         idx, ln, sc = idx.cpu().numpy(), ln.cpu().numpy(), sc.cpu().numpy()
         return [[(idx[b, n, :ln[b, n]].astype(np.int64), float(sc[b, n])) for n in range(nbest) if ln[b, n] >= 0] for b in range(B)]
 
+    def mbr_decode(self, logits, beam_width: int = 16, nbest: int = 8, temperature: float = 1.0, normalise: bool = True, lm=None,
+                   alpha: float = 0.0, beta: float = 0.0, frame_lengths=None) -> List[Tuple[np.ndarray, int, float]]:
+        """Minimum-Bayes-risk decode (ishara_amd/mbr.py): the beam search's n-best list (beam_decode's arguments), then, on the device,
+        the hypothesis with the smallest expected edit distance to the others under the votes exp((score - max) / temperature);
+        normalise: the distance to a voter is divided by that voter's length, as the score of c18 divides by the target's.
+        -> per clip (indices int64, the selected slot of the n-best, its risk); a clip the selection did not rank (mbr.py: a hypothesis
+        longer than 64 symbols) gets the beam's top-1 and a NaN risk."""
+        from . import ctc, mbr
+        logits = torch.as_tensor(logits).to(self.device, torch.float32).contiguous()
+        if logits.ndim != 3:
+            raise ValueError(f"logits must be [B, T, C], got {tuple(logits.shape)}")
+        it = mbr.inverse_temperature(temperature)
+        mbr.check_device_args(nbest, logits.shape[1], logits.shape[2], 1 if normalise else 0)
+        hyp = ctc.ctc_beam_nbest_device(logits, frame_lengths, beam_width, nbest, lm, alpha, beta)
+        idx, ln, best, det = mbr.mbr_select(*hyp, inv_temp=it, mode=1 if normalise else 0, C=logits.shape[2], return_details=True)
+        idx, ln, best, risk = idx.cpu().numpy(), ln.cpu().numpy(), best.cpu().numpy(), det["risk"].cpu().numpy()
+        return [(idx[b, :ln[b]].astype(np.int64), int(best[b]), float(risk[b, best[b]]) if best[b] >= 0 else float("nan"))
+                for b in range(idx.shape[0])]
+
     def align(self, logits, y, frame_lengths=None) -> list:
         """CTC forced alignment (ishara_amd/ctc_align.py semantics, blank = C - 1) of logits [B, T, C] to the labels y [B, L] (padded with
         C - 1) on the device -> per clip an Alignment: the label index every frame emits, the log-probability of the best path and one

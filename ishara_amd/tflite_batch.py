@@ -30,7 +30,7 @@ from . import _lib
 from ._lib import stream as _stream
 from .evaluation import ErrorReport
 from .model import Model
-from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS, _beam_launch, _beam_setup, refuse_frame_lengths
+from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS, _beam_launch, _beam_setup, _mbr_launch, _mbr_setup, _set_mbr_temperature, refuse_frame_lengths
 
 PAD_TOKEN_IDX = 59           # c1:5: the targets' padding; never a decoded index (the blank is C - 1 = 59)
 MAX_SCORE_LABEL_LEN = 64     # one wavefront lane per target symbol (ishara_edit_distance)
@@ -139,9 +139,12 @@ def normalized_scores(dist: np.ndarray, tlen: np.ndarray) -> Tuple[float, np.nda
 # ---------------------------------------------------------------------------------------------------- device runner
 class BatchedTFLiteModel:
     def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, batch_size: int = 64, max_frames: int = 1024,
-                 use_graph: bool = True, beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0):
+                 use_graph: bool = True, beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0, mbr_nbest: int = 0,
+                 mbr_temperature: float = 1.0, mbr_normalise: bool = True):
         """beam_width / lm / lm_alpha / lm_beta as for TFLiteModel: 0 keeps the greedy decode; > 0 captures the beam decoder (top-1) in
-        its place, and predict_indices / __call__ / score() work on the beam's top-1."""
+        its place, and predict_indices / __call__ / score() work on the beam's top-1.  mbr_nbest / mbr_temperature / mbr_normalise as for
+        TFLiteModel: with mbr_nbest >= 2 the beam search keeps that many hypotheses, ishara_mbr_select follows it in the graph and writes
+        the indices and lengths the tail reads, so everything downstream works on the minimum-Bayes-risk choice."""
         if model.F != N_COLS:
             raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
         if batch_size < 1 or batch_size > model.max_batch:
@@ -177,6 +180,7 @@ class BatchedTFLiteModel:
         self._x = torch.zeros((bs, T, N_COLS), dtype=torch.float32, device=dev)
         self._logits = torch.zeros((bs, T, model.C), dtype=torch.float32, device=dev)
         self._beam = _beam_setup(model, bs, beam_width, lm, lm_alpha, lm_beta)
+        self._mbr = _mbr_setup(model, bs, self._beam, mbr_nbest, mbr_temperature, mbr_normalise)
         self._copy_stream = torch.cuda.Stream(device=dev)
         self._copied = [torch.cuda.Event() for _ in range(2)]
         self._consumed = [None, None]            # event after the replay that last read a device slot
@@ -233,6 +237,8 @@ class BatchedTFLiteModel:
         if self._beam is None:
             _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), bs, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), st),
                        "ishara_greedy_decode")
+        elif self._mbr is not None:
+            _mbr_launch(m, self._beam, self._mbr, self._logits, bs, self._idx, self._len, st)
         else:
             _beam_launch(m, self._beam, self._logits, bs, self._idx, self._len, st)
         if scoring:
@@ -364,6 +370,10 @@ class BatchedTFLiteModel:
         return idx, ln, dist, tlen
 
     # ---- public surface
+    def set_mbr_temperature(self, temperature: float) -> None:
+        """1 / temperature written into the device float every replay reads (on the current stream; no new capture)."""
+        _set_mbr_temperature(self._mbr, temperature)
+
     def predict_indices(self, clips, frame_lengths=None) -> List[np.ndarray]:
         """The decode per clip (greedy, or the beam's top-1; before the len < 3 fallback): equal to `TFLiteModel.predict_indices` clip by clip."""
         refuse_frame_lengths(frame_lengths, "BatchedTFLiteModel")

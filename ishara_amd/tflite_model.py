@@ -84,12 +84,57 @@ def _beam_launch(model: Model, cfg: _BeamConfig, logits, batch: int, idx, ln, st
     ctc_beam.launch(model._lib, logits, batch, model.T, model.C, cfg.width, 1, cfg.lm, cfg.alpha, cfg.beta, cfg.ws, idx, ln, cfg.score, stream)
 
 
+class _MbrConfig:
+    """Device state of a wrapper's minimum-Bayes-risk selection (ishara_amd/mbr.py): the n-best buffers the beam search fills and the
+    selection reads, the selected slots, and 1 / temperature as the device float every launch reads."""
+    def __init__(self, nbest, mode, inv_temp, hyp_idx, hyp_len, hyp_score, best):
+        self.nbest, self.mode, self.inv_temp, self.hyp_idx, self.hyp_len, self.hyp_score, self.best = nbest, mode, inv_temp, hyp_idx, hyp_len, hyp_score, best
+
+
+def _mbr_setup(model: Model, batch: int, beam: Optional[_BeamConfig], mbr_nbest: int, temperature: float, normalise: bool) -> Optional[_MbrConfig]:
+    """None for mbr_nbest == 0 (nothing is allocated); else 2 <= mbr_nbest <= beam_width and the buffers on the model's device."""
+    from . import ctc_beam, mbr
+    if mbr_nbest == 0:
+        return None
+    if mbr_nbest < 2:
+        raise ValueError(f"mbr_nbest {mbr_nbest}: 0 (off) or at least 2 hypotheses to choose among")
+    if beam is None or beam.width < mbr_nbest:
+        raise ValueError(f"mbr_nbest {mbr_nbest} needs beam_width >= mbr_nbest, got beam_width {0 if beam is None else beam.width}")
+    ctc_beam.check_device_args(model.C, model.T, beam.width, mbr_nbest)
+    mode = mbr.check_device_args(mbr_nbest, model.T, model.C, 1 if normalise else 0)
+    dev = model.device
+    inv_temp = torch.full((1,), mbr.inverse_temperature(temperature), dtype=torch.float32, device=dev)
+    return _MbrConfig(int(mbr_nbest), mode, inv_temp, torch.full((batch, mbr_nbest, model.T), -1, dtype=torch.int32, device=dev),
+                      torch.full((batch, mbr_nbest), -1, dtype=torch.int32, device=dev), torch.zeros((batch, mbr_nbest), dtype=torch.float32, device=dev),
+                      torch.zeros(batch, dtype=torch.int32, device=dev))
+
+
+def _mbr_launch(model: Model, beam: _BeamConfig, cfg: _MbrConfig, logits, batch: int, idx, ln, stream) -> None:
+    """ishara_ctc_beam_decode with nbest = cfg.nbest into cfg's buffers, then ishara_mbr_select into idx [batch, T] / ln [batch], the layout
+    ishara_greedy_decode writes."""
+    from . import ctc_beam, mbr
+    ctc_beam.launch(model._lib, logits, batch, model.T, model.C, beam.width, cfg.nbest, beam.lm, beam.alpha, beam.beta, beam.ws, cfg.hyp_idx,
+                    cfg.hyp_len, cfg.hyp_score, stream)
+    mbr.launch(model._lib, cfg.hyp_idx, cfg.hyp_len, cfg.hyp_score, None, cfg.inv_temp, batch, cfg.nbest, model.T, model.C, cfg.mode, idx, ln, cfg.best,
+               None, None, None, None, stream)
+
+
+def _set_mbr_temperature(cfg: Optional[_MbrConfig], temperature: float) -> None:
+    from . import mbr
+    if cfg is None:
+        raise ValueError("set_mbr_temperature: the wrapper was built without mbr_nbest")
+    cfg.inv_temp.fill_(mbr.inverse_temperature(temperature))
+
+
 class TFLiteModel:
     def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, max_frames: int = 1024, use_graph: bool = True,
-                 beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0):
+                 beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0, mbr_nbest: int = 0, mbr_temperature: float = 1.0,
+                 mbr_normalise: bool = True):
         """beam_width = 0: the reference's greedy decode (c8:4-12).  beam_width > 0: the CTC prefix beam search of ishara_amd/ctc_beam.py
         (top-1, optional LM weighted by lm_alpha, lm_beta per character: a table lm [C, C], or a CharNGramLM / LMAutomaton of ctc_lm.py,
-        whose device tables are built here once) replaces it inside the same graph."""
+        whose device tables are built here once) replaces it inside the same graph.  mbr_nbest >= 2 (needs beam_width >= mbr_nbest): the
+        beam search keeps mbr_nbest hypotheses and ishara_mbr_select (ishara_amd/mbr.py) picks the one of smallest expected edit distance
+        under the votes exp((score - max) / mbr_temperature), normalised by the voter's length with mbr_normalise; 0 changes nothing."""
         if model.F != N_COLS:
             raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
         self.model, self.max_frames, self.T = model, max_frames, model.T
@@ -105,6 +150,7 @@ class TFLiteModel:
         self._idx = torch.zeros((1, self.T), dtype=torch.int32, device=dev)
         self._len = torch.zeros(1, dtype=torch.int32, device=dev)
         self._beam = _beam_setup(model, 1, beam_width, lm, lm_alpha, lm_beta)
+        self._mbr = _mbr_setup(model, 1, self._beam, mbr_nbest, mbr_temperature, mbr_normalise)
         self._graph = None
         if use_graph:
             self._capture()
@@ -117,8 +163,14 @@ class TFLiteModel:
         if self._beam is None:
             _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), 1, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), _stream()),
                        "ishara_greedy_decode")
+        elif self._mbr is not None:
+            _mbr_launch(m, self._beam, self._mbr, self._logits, 1, self._idx, self._len, _stream())
         else:
             _beam_launch(m, self._beam, self._logits, 1, self._idx, self._len, _stream())
+
+    def set_mbr_temperature(self, temperature: float) -> None:
+        """1 / temperature written into the device float every replay reads (on the current stream; no new capture)."""
+        _set_mbr_temperature(self._mbr, temperature)
 
     def _capture(self):
         side = torch.cuda.Stream(device=self.model.device)

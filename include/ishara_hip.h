@@ -263,6 +263,50 @@ int ishara_awp_perturb(ishara_model* prof, float* w, float* backup, const float*
                        float delta, float eps, int32_t relative, float* scale, ishara_awp_stats* rec, void* ws, ishara_stream s);
 int ishara_awp_restore(ishara_model* prof, float* w, const float* backup, int64_t n, ishara_stream s);
 
+/* Optimizer parameter groups: frozen tensors, per-tensor learning-rate and weight-decay scales (Keras `layer.trainable = False`, torch
+ * `requires_grad_(False)` and optimizer param_groups; the weight-decay exclusion of biases and norm scales of the AdamW recipes).
+ *
+ * The trainable prefix [0, n) is cut into S segments by seg_off, the DEVICE table of ishara_awp_perturb (int64 [S + 1], seg_off[0] = 0,
+ * strictly increasing, seg_off[S] = n, no alignment of the offsets; the values are the caller's contract, indices derived from them are
+ * clamped to [0, n)).  `groups` is a DEVICE array of S rows of 16 bytes, row s for segment s.  ishara_optimizer_step_groups is
+ * ishara_optimizer_step_ex (iteration counter, weight shadows also behind a skipped step, grad NULL: the bound gradient, st, the skip
+ * switch) whose update, over the elements of segment s with row r, is
+ *   r.frozen != 0: nothing is written to params or the three slots over the segment (every 32-bit word stays, NaN payloads included) and
+ *     the segment's gradient is not read
+ *   else the update of ishara_optimizer_step_ex, the same device function, with lr * r.lr_scale and weight_decay * r.wd_scale, each
+ *     one fp32 multiply rounded to nearest; a product of 0 is a step without decay (no 0 * theta term: an infinite weight stays
+ *     infinite); lr_scale = 0 is not frozen: the slots move and the weights change by -0 * update
+ *   with st: grad[i] * st->coef; with skip_nonfinite != 0 and st->nonfinite > 0 nothing at all is written and st->skipped rises by 1
+ * So rows that are all (1, 1, 0) give every bit of ishara_optimizer_step_ex, and a segment with row (a, b, 0) gets the bits a plain step
+ * with lr' = fp32(lr * a), wd' = fp32(wd * b) gives it.
+ * ishara_gradient_mask_groups writes g[i] = +0.0f (the word 0) over the frozen segments and touches no other word: a frozen tensor then
+ * counts neither in ishara_gradient_stats (norm, the non-finite guard) nor in the norms of ishara_awp_perturb.
+ *
+ * The device does all reading of the rows: no host synchronise, no allocation, no memset, no atomics; a captured graph replays the
+ * calls, and rows changed on the device between replays take effect without a new capture.  ws: ishara_param_groups_workspace_bytes of
+ * (n, S) bytes of device memory; every call writes each word of it before reading it.  Work is cut into chunks of 4096 elements that never
+ * cross a segment (the scheme of ishara_awp_perturb); 16-byte accesses over the aligned body of a chunk.
+ *
+ * ishara_optimizer_op_step is the update of ishara_optimizer_step[_ex] (the same launches) on caller's buffers, for step number
+ * `iteration` (1-based); ishara_optimizer_op_step_groups the grouped update likewise.  No handle, no weight shadows.
+ *
+ * Refused with a message before any HIP call: a null handle, theta, grad (of the op entry points and the mask), m, v, slow, seg_off,
+ * groups or ws; theta, grad / g, m, v or slow not 16-byte aligned, seg_off or ws not 8-byte, groups or st not 4-byte aligned; n outside
+ * 1 .. 2^31 - 1; S outside 1 .. n; iteration < 1; skip_nonfinite != 0 with a null st.  `prof` may be NULL: a handle only lends its
+ * profiler.  Profiler keys: radam_lookahead_groups (28 n bytes), grad_mask_groups (4 n bytes). */
+typedef struct ishara_param_group { float lr_scale; float wd_scale; int32_t frozen; int32_t reserved; } ishara_param_group;   /* 16 bytes */
+int64_t ishara_param_groups_workspace_bytes(int64_t n, int32_t S);
+int ishara_optimizer_step_groups(ishara_model* m, float lr, float weight_decay, const float* grad, ishara_grad_stats* st, int32_t skip_nonfinite,
+                                 const int64_t* seg_off, const ishara_param_group* groups, int32_t S, void* ws, ishara_stream s);
+int ishara_gradient_mask_groups(ishara_model* prof, float* g, int64_t n, const int64_t* seg_off, const ishara_param_group* groups, int32_t S,
+                                void* ws, ishara_stream s);
+/* model-free operator entry points, for the parity tests */
+int ishara_optimizer_op_step(float* theta, const float* grad, float* m, float* v, float* slow, int64_t n, int32_t iteration,
+                             float lr, float weight_decay, ishara_grad_stats* st, int32_t skip_nonfinite, ishara_stream s);
+int ishara_optimizer_op_step_groups(float* theta, const float* grad, float* m, float* v, float* slow, int64_t n, int32_t iteration,
+                                    float lr, float weight_decay, ishara_grad_stats* st, int32_t skip_nonfinite,
+                                    const int64_t* seg_off, const ishara_param_group* groups, int32_t S, void* ws, ishara_stream s);
+
 /* HIP-event profiler (no reference counterpart: the reference profiles with %%timeit / Keras
  * progress bars).  When enabled, every kernel launch of forward / loss_backward /
  * optimizer_step is bracketed by events on the launch stream; the report is text, one line per

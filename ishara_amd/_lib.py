@@ -65,6 +65,11 @@ class AwpStats(C.Structure):
     _fields_ = [("grad_norm", C.c_float), ("delta_norm", C.c_float), ("perturbed", C.c_int32), ("zeroed", C.c_int32)]
 
 
+class ParamGroup(C.Structure):
+    """ishara_param_group: one 16-byte device row of ishara_optimizer_step_groups, per segment (field order of the header)."""
+    _fields_ = [("lr_scale", C.c_float), ("wd_scale", C.c_float), ("frozen", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GemmTnCall(C.Structure):
     """ishara_gemm_tn_call: one weight-gradient GEMM of ishara_op_gemm_tn / ishara_debug_gemm_tn_plan (field order of the header)."""
     _fields_ = [
@@ -143,6 +148,11 @@ SIGNATURES = {
     "ishara_awp_workspace_bytes": (_I64, [_I64, _I32]),
     "ishara_awp_perturb": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _F, _F, _I32, _P, _P, _P, _P]),
     "ishara_awp_restore": (C.c_int, [_P, _P, _P, _I64, _P]),
+    "ishara_param_groups_workspace_bytes": (_I64, [_I64, _I32]),
+    "ishara_optimizer_step_groups": (C.c_int, [_P, _F, _F, _P, _P, _I32, _P, _P, _I32, _P, _P]),
+    "ishara_gradient_mask_groups": (C.c_int, [_P, _P, _I64, _P, _P, _I32, _P, _P]),
+    "ishara_optimizer_op_step": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _F, _F, _P, _I32, _P]),
+    "ishara_optimizer_op_step_groups": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _F, _F, _P, _I32, _P, _P, _I32, _P, _P]),
     "ishara_profile_enable": (C.c_int, [_P, _I32]),
     "ishara_profile_report": (C.c_int, [_P, C.c_char_p, _I32]),
     "ishara_greedy_decode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),

@@ -12,16 +12,17 @@
 //   awp_record_kernel   one workgroup: the 16-byte record from seg_ss / scale / seg_zero
 //   awp_apply_kernel    the same chunks: backup = w (words), w = w + scale[s] * g unless the segment was zeroed
 // A workgroup finds the segment of a chunk by bisection of first[] (wave-uniform loads of a table that stays in L2).
-#include "kernels.h"
+#include "seg_chunks.h"
 
-static constexpr int AWP_THREADS = 256;                        // threads of a workgroup
-static constexpr int AWP_VEC = 4;                              // floats of one 16-byte access
+// the chunk scheme lives in seg_chunks.h (the optimizer's parameter groups walk the same table); these are its constants under AWP's names
+static constexpr int AWP_THREADS = SEG_THREADS;                // threads of a workgroup
+static constexpr int AWP_VEC = SEG_VEC;                        // floats of one 16-byte access
 static constexpr int AWP_CHUNK = 4096;                         // elements of a chunk (train_state.AWP_CHUNK): 4 x 16 bytes per thread
 static constexpr int AWP_GRID_CAP = 2048;                      // most workgroups of a launch (train_state.GRAD_GRID_CAP)
+static_assert(AWP_CHUNK == SEG_CHUNK && AWP_GRID_CAP == SEG_GRID_CAP, "awp.hip and seg_chunks.h disagree about the chunk scheme");
 
 struct AwpWs { int64_t* first; double* seg_ss; int32_t* seg_zero; double* part_g; double* part_w; };
 
-static inline int64_t awp_chunk_bound(int64_t n, int64_t S) { return (n + AWP_CHUNK - 1) / AWP_CHUNK + S; }
 static inline int64_t awp_rup8(int64_t v) { return (v + 7) / 8 * 8; }
 // first int64 [S + 1] | seg_ss double [S] | seg_zero int32 [S] (padded to 8 bytes) | part_g double [bound] | part_w double [bound]
 int64_t awp_workspace_bytes(int64_t n, int32_t S) {
@@ -37,56 +38,6 @@ static inline AwpWs awp_carve(void* ws, int64_t n, int32_t S) {
     a.part_g = (double*)p;      p += 8 * awp_chunk_bound(n, S);
     a.part_w = (double*)p;
     return a;
-}
-static inline int awp_grid(int64_t work) { return (int)(work < AWP_GRID_CAP ? (work < 1 ? 1 : work) : AWP_GRID_CAP); }
-
-__device__ __forceinline__ int64_t awp_chunks_of(int64_t len) { return (len + AWP_CHUNK - 1) / AWP_CHUNK; }
-
-// exclusive prefix of the chunk counts: thread t takes a contiguous run of segments, thread 0 scans the 256 run totals
-__global__ __launch_bounds__(AWP_THREADS) void awp_setup_kernel(const int64_t* __restrict__ seg_off, int S, int64_t* __restrict__ first) {
-    __shared__ int64_t s_run[AWP_THREADS];
-    const int per = (S + AWP_THREADS - 1) / AWP_THREADS;
-    const int lo = min((int64_t)threadIdx.x * per, (int64_t)S), hi = min((int64_t)lo + per, (int64_t)S);
-    int64_t tot = 0;
-    for (int s = lo; s < hi; ++s) tot += awp_chunks_of(seg_off[s + 1] - seg_off[s]);
-    s_run[threadIdx.x] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t acc = 0;
-        for (int t = 0; t < AWP_THREADS; ++t) { const int64_t r = s_run[t]; s_run[t] = acc; acc += r; }
-        first[S] = acc;
-    }
-    __syncthreads();
-    int64_t acc = s_run[threadIdx.x];
-    for (int s = lo; s < hi; ++s) { first[s] = acc; acc += awp_chunks_of(seg_off[s + 1] - seg_off[s]); }
-}
-
-// the segment that owns chunk c: the largest s with first[s] <= c (first is strictly increasing: every segment has a chunk)
-__device__ __forceinline__ int awp_segment_of(const int64_t* __restrict__ first, int S, int64_t c) {
-    int lo = 0, hi = S;                 // first[lo] <= c < first[hi]
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (first[mid] <= c) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// The elements [e0, e1) of chunk c, cut where 16-byte accesses begin and end: [e0, a0) head, [a0, a1) whole float4s, [a1, e1) tail.
-// The buffers' base addresses are 16-byte aligned, so element i is on a 16-byte boundary when i % 4 == 0.
-struct AwpSpan { int64_t e0, a0, a1, e1; int seg; };
-__device__ __forceinline__ AwpSpan awp_span(const int64_t* __restrict__ seg_off, const int64_t* __restrict__ first, int S, int64_t n, int64_t c) {
-    AwpSpan p;
-    p.seg = awp_segment_of(first, S, c);
-    const int64_t end = seg_off[p.seg + 1] < n ? seg_off[p.seg + 1] : n;      // a table that keeps its contract never needs the clamps: they
-    p.e0 = seg_off[p.seg] + (c - first[p.seg]) * AWP_CHUNK;                     // keep one that does not inside [0, n)
-    if (p.e0 < 0) p.e0 = 0;
-    p.e1 = p.e0 + AWP_CHUNK < end ? p.e0 + AWP_CHUNK : end;
-    if (p.e1 < p.e0) p.e1 = p.e0;
-    p.a0 = (p.e0 + AWP_VEC - 1) / AWP_VEC * AWP_VEC;
-    if (p.a0 > p.e1) p.a0 = p.e1;
-    p.a1 = p.e1 / AWP_VEC * AWP_VEC;
-    if (p.a1 < p.a0) p.a1 = p.a0;
-    return p;
 }
 
 __device__ __forceinline__ void awp_sq(float x, double& ss) { const double d = (double)x; ss += d * d; }      // squared in fp64: (3e19)^2 is past fp32

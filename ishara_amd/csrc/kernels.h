@@ -406,6 +406,16 @@ int launch_radam_lookahead(float* theta, const float* grad, float* m, float* v, 
 int launch_radam_lookahead_ex(float* theta, const float* grad, float* m, float* v, float* slow, int64_t n,
                               RAdamArgs a, ishara_grad_stats* st, int skip, hipStream_t s);
 int launch_scale(float* x, int64_t n, float scale, hipStream_t s);
+// the host-side scalars of step `iteration` (1-based): bias corrections, rectification, the Lookahead sync flag
+RAdamArgs radam_args(int32_t iteration, float lr, float wd);
+// Parameter groups: the same update over the segment table of awp.hip (seg_off device int64 [S + 1]) with one device row per segment:
+// a frozen segment is neither read nor written, another steps with lr * lr_scale and wd * wd_scale.  theta, grad, m, v, slow at 16-byte
+// aligned addresses; st may be null (then skip must be 0); ws of param_groups_workspace_bytes(n, S) bytes, 8-byte aligned, written by
+// every call before it is read.  Two launches each: the chunk table, then the pass.  grad_mask_groups: g = +0.0f over the frozen segments.
+int64_t param_groups_workspace_bytes(int64_t n, int32_t S);
+int launch_radam_lookahead_groups(float* theta, const float* grad, float* m, float* v, float* slow, int64_t n, RAdamArgs a, ishara_grad_stats* st,
+                                  int skip, const int64_t* seg_off, const ishara_param_group* groups, int32_t S, void* ws, hipStream_t s);
+int launch_grad_mask_groups(float* g, int64_t n, const int64_t* seg_off, const ishara_param_group* groups, int32_t S, void* ws, hipStream_t s);
 
 // ---- gradient statistics and accumulation (grad_ops.hip) ------------------------------------
 // g, acc [n] f32 at 16-byte aligned addresses, 1 <= n <= 2^31 - 1; ws: grad_stats_workspace_bytes(n) bytes, 8-byte aligned, needs no

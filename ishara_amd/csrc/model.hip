@@ -349,24 +349,17 @@ extern "C" int ishara_grad_buckets_enable(ishara_model* m) {
 }
 
 // ------------------------------------------------------------------ optimizer
-static int optimizer_step(ishara_model* m, const char* who, float lr, float weight_decay, const float* grad, ishara_grad_stats* rec, int skip, ishara_stream st) {
+// groups != nullptr: the grouped update (parameter groups) in place of the plain one; everything around it is the same
+static int optimizer_step(ishara_model* m, const char* who, float lr, float weight_decay, const float* grad, ishara_grad_stats* rec, int skip, ishara_stream st,
+                          const int64_t* seg_off = nullptr, const ishara_param_group* groups = nullptr, int32_t S = 0, void* ws = nullptr) {
     if (!m->om || !m->ov || !m->oslow || !m->grads) { ishara_set_error("%s: optimizer slots are not bound", who); return -1; }
     hipStream_t s = (hipStream_t)st;
     m->opt_iter += 1;
-    const double t = (double)m->opt_iter, b1 = 0.9, b2 = 0.999;
-    const double b1p = pow(b1, t), b2p = pow(b2, t);
-    const double sma_inf = 2.0 / (1.0 - b2) - 1.0;
-    const double sma_t = sma_inf - 2.0 * t * b2p / (1.0 - b2p);
-    RAdamArgs a;
-    a.lr = lr; a.wd = weight_decay; a.beta1 = (float)b1; a.beta2 = (float)b2; a.eps = 1e-7f;
-    a.c1 = (float)(1.0 / (1.0 - b1p)); a.c2 = (float)(1.0 / (1.0 - b2p));
-    a.rect = sma_t >= 4.0 ? 1 : 0;       // sma_threshold = 4 (c7:68)
-    a.r_t = a.rect ? (float)sqrt(fmax((sma_t - 4.0) / (sma_inf - 4.0) * (sma_t - 2.0) / (sma_inf - 2.0) * sma_inf / sma_t, 0.0)) : 0.f;
-    a.sync = (m->opt_iter % 5 == 0) ? 1 : 0;   // Lookahead(sync_period=5, slow_step_size=0.5) (c7:69)
-    a.slow_step = 0.5f;
+    const RAdamArgs a = radam_args(m->opt_iter, lr, weight_decay);
     m->s = s;
     if (!grad) grad = m->grads;
-    if (rec) CKP(m, "radam_lookahead", 28.0 * m->n_train, 0, launch_radam_lookahead_ex(m->params, grad, m->om, m->ov, m->oslow, m->n_train, a, rec, skip, s));
+    if (groups) CKP(m, "radam_lookahead_groups", 28.0 * m->n_train, 0, launch_radam_lookahead_groups(m->params, grad, m->om, m->ov, m->oslow, m->n_train, a, rec, skip, seg_off, groups, S, ws, s));
+    else if (rec) CKP(m, "radam_lookahead", 28.0 * m->n_train, 0, launch_radam_lookahead_ex(m->params, grad, m->om, m->ov, m->oslow, m->n_train, a, rec, skip, s));
     else CKP(m, "radam_lookahead", 28.0 * m->n_train, 0, launch_radam_lookahead(m->params, grad, m->om, m->ov, m->oslow, m->n_train, a, s));
     CKP(m, "weight_shadows", 0, 0, ishara_sync_weights(m, st));      // also after a skipped step: the host cannot know it was one
     return 0;
@@ -499,6 +492,68 @@ extern "C" int ishara_awp_restore(ishara_model* prof, float* w, const float* bac
     prof->s = s;
     CKP(prof, "awp_restore", 8.0 * n, 0, launch_awp_restore(w, backup, n, s));
     return 0;
+}
+// ------------------------------------------------------------------ optimizer parameter groups (optimizer.hip)
+static bool groups_table_ok(const char* who, const int64_t* seg_off, const ishara_param_group* groups, int32_t S, int64_t n, const void* ws) {
+    if (!awp_ptr_ok(who, "seg_off", seg_off, 8) || !awp_ptr_ok(who, "groups", groups, 4) || !awp_ptr_ok(who, "ws", ws, 8)) return false;
+    if (S < 1 || S > n) { ishara_set_error("%s: S=%d is outside 1..n=%lld", who, (int)S, (long long)n); return false; }
+    return true;
+}
+static bool step_record_ok(const char* who, const ishara_grad_stats* rec, int32_t skip_nonfinite) {
+    if ((uintptr_t)rec % 4 != 0) { ishara_set_error("%s: misaligned st: %p is not on a 4-byte boundary", who, (const void*)rec); return false; }
+    if (skip_nonfinite && !rec) { ishara_set_error("%s: skip_nonfinite needs the record: null st", who); return false; }
+    return true;
+}
+static bool op_step_ok(const char* who, float* theta, const float* grad, float* m, float* v, float* slow, int64_t n, int32_t iteration,
+                       const ishara_grad_stats* rec, int32_t skip_nonfinite) {
+    if (!awp_ptr_ok(who, "theta", theta, 16) || !awp_ptr_ok(who, "grad", grad, 16) || !awp_ptr_ok(who, "m", m, 16) || !awp_ptr_ok(who, "v", v, 16) ||
+        !awp_ptr_ok(who, "slow", slow, 16)) return false;
+    if (!awp_count_ok(who, n)) return false;
+    if (iteration < 1) { ishara_set_error("%s: iteration=%d is not >= 1", who, (int)iteration); return false; }
+    return step_record_ok(who, rec, skip_nonfinite);
+}
+extern "C" int64_t ishara_param_groups_workspace_bytes(int64_t n, int32_t S) {
+    const char* who = "ishara_param_groups_workspace_bytes";
+    if (!awp_count_ok(who, n)) return -1;
+    if (S < 1 || S > n) { ishara_set_error("%s: S=%d is outside 1..n=%lld", who, (int)S, (long long)n); return -1; }
+    return param_groups_workspace_bytes(n, S);
+}
+extern "C" int ishara_optimizer_step_groups(ishara_model* m, float lr, float weight_decay, const float* grad, ishara_grad_stats* rec, int32_t skip_nonfinite,
+                                            const int64_t* seg_off, const ishara_param_group* groups, int32_t S, void* ws, ishara_stream st) {
+    const char* who = "ishara_optimizer_step_groups";
+    if (!m) { ishara_set_error("%s: null handle", who); return -1; }
+    if ((uintptr_t)grad % 16 != 0) { ishara_set_error("%s: misaligned grad: %p is not on a 16-byte boundary", who, (const void*)grad); return -1; }
+    if (!step_record_ok(who, rec, skip_nonfinite)) return -1;
+    if (!awp_ptr_ok(who, "seg_off", seg_off, 8) || !awp_ptr_ok(who, "groups", groups, 4) || !awp_ptr_ok(who, "ws", ws, 8)) return -1;      // before the handle is read
+    if (!awp_count_ok(who, m->n_train) || !groups_table_ok(who, seg_off, groups, S, m->n_train, ws)) return -1;
+    return optimizer_step(m, who, lr, weight_decay, grad, rec, skip_nonfinite != 0, st, seg_off, groups, S, ws);
+}
+extern "C" int ishara_gradient_mask_groups(ishara_model* prof, float* g, int64_t n, const int64_t* seg_off, const ishara_param_group* groups, int32_t S,
+                                           void* ws, ishara_stream st) {
+    const char* who = "ishara_gradient_mask_groups";
+    if (!awp_ptr_ok(who, "g", g, 16)) return -1;
+    if (!awp_count_ok(who, n) || !groups_table_ok(who, seg_off, groups, S, n, ws)) return -1;
+    hipStream_t s = (hipStream_t)st;
+    if (!prof) return launch_grad_mask_groups(g, n, seg_off, groups, S, ws, s);
+    prof->s = s;
+    CKP(prof, "grad_mask_groups", 4.0 * n, 0, launch_grad_mask_groups(g, n, seg_off, groups, S, ws, s));
+    return 0;
+}
+extern "C" int ishara_optimizer_op_step(float* theta, const float* grad, float* m, float* v, float* slow, int64_t n, int32_t iteration,
+                                        float lr, float weight_decay, ishara_grad_stats* rec, int32_t skip_nonfinite, ishara_stream st) {
+    const char* who = "ishara_optimizer_op_step";
+    if (!op_step_ok(who, theta, grad, m, v, slow, n, iteration, rec, skip_nonfinite)) return -1;
+    const RAdamArgs a = radam_args(iteration, lr, weight_decay);
+    if (rec) return launch_radam_lookahead_ex(theta, grad, m, v, slow, n, a, rec, skip_nonfinite != 0, (hipStream_t)st);
+    return launch_radam_lookahead(theta, grad, m, v, slow, n, a, (hipStream_t)st);
+}
+extern "C" int ishara_optimizer_op_step_groups(float* theta, const float* grad, float* m, float* v, float* slow, int64_t n, int32_t iteration,
+                                               float lr, float weight_decay, ishara_grad_stats* rec, int32_t skip_nonfinite,
+                                               const int64_t* seg_off, const ishara_param_group* groups, int32_t S, void* ws, ishara_stream st) {
+    const char* who = "ishara_optimizer_op_step_groups";
+    if (!op_step_ok(who, theta, grad, m, v, slow, n, iteration, rec, skip_nonfinite) || !groups_table_ok(who, seg_off, groups, S, n, ws)) return -1;
+    return launch_radam_lookahead_groups(theta, grad, m, v, slow, n, radam_args(iteration, lr, weight_decay), rec, skip_nonfinite != 0, seg_off, groups, S, ws,
+                                         (hipStream_t)st);
 }
 extern "C" int32_t ishara_optimizer_iterations(const ishara_model* m) { return m->opt_iter; }
 extern "C" int ishara_optimizer_set_iterations(ishara_model* m, int32_t it) { m->opt_iter = it; return 0; }

@@ -13,6 +13,7 @@ built library and a GPU.
 from __future__ import annotations
 
 import contextlib
+import copy
 import ctypes as C
 import math
 from typing import Tuple,  Dict, Iterable, List, Optional, Sequence
@@ -61,11 +62,22 @@ class Optimizer:
     again at the moved weights with the same dropout masks, puts the weights back bit for bit and steps on the second gradient.  The
     recipes' "AWP from epoch E" is awp_start_step = E * steps_per_epoch.  Both training-mode forwards update the BatchNorm moving
     statistics, as a Keras model called twice does.  The step is read through Model.awp_stats / awp_scales; None (the default) is the
-    step without any of it."""
+    step without any of it.
+
+    `param_groups`: a list of {"match": pattern or [patterns], "lr_scale": 1.0, "weight_decay_scale": 1.0, "trainable": True}.  The
+    patterns are fnmatch.fnmatchcase patterns over the names of the trainable entries (Keras-style: ".../kernel", "/bias", "/gamma",
+    "/beta"); the first matching group wins, an unmatched entry keeps the defaults, a pattern that matches no trainable entry raises.  A
+    tensor steps with learning_rate * lr_scale and weight_decay * weight_decay_scale (one fp32 product each); with trainable False it
+    is frozen: the step writes nothing to it or its slots, and its gradient counts neither in the global norm, nor in the non-finite
+    guard, nor in AWP's norms (csrc/optimizer.hip; train_state.no_decay_groups builds the usual no-decay group).  Model.param_groups()
+    shows the resolution.  None (the default) is the step without any of it.  Limits: the backward pass still computes a frozen tensor's
+    gradient (skipping those GEMMs is a later change); the BatchNorm moving statistics of a frozen block keep updating in training mode,
+    unlike Keras' trainable = False; equality with a TensorFlow run is unpinned, and no accuracy effect is measured (there is neither a
+    dataset nor trained weights)."""
 
     def __init__(self, learning_rate=1e-3, weight_decay=0.0, global_clipnorm=None, skip_nonfinite=False, accumulate_steps=1,
                  use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_warmup=False,
-                 awp_delta=None, awp_eps=1e-4, awp_start_step=0, awp_relative=False):
+                 awp_delta=None, awp_eps=1e-4, awp_start_step=0, awp_relative=False, param_groups=None):
         self._lr = _Scalar(learning_rate)
         # The reference assigns `.weight_decay` on the Lookahead wrapper (c11:64), which is not
         # one of its hyper-parameters, so RectifiedAdam keeps weight_decay=0 (SURVEY §8a row 10).
@@ -84,6 +96,12 @@ class Optimizer:
         self.awp_eps = awp_eps
         self.awp_start_step = awp_start_step
         self.awp_relative = awp_relative
+        self.param_groups = param_groups
+
+    def group_options(self):
+        """None, or the checked parameter groups: [{"match": [patterns], "lr_scale", "weight_decay_scale", "trainable"}]"""
+        from . import train_state as TS
+        return TS.check_param_groups(self.param_groups)
 
     def awp_options(self):
         """(delta or None, eps, start step, relative), checked"""
@@ -209,6 +227,9 @@ class Model(Handle):
         self._ema_swapped = False  # inside averaged_weights(): params[:n_train] and _ema_avg have changed places
         self._awp_backup = None    # [n_train] f32 copy of params[:n_train] while they are perturbed, allocated by the first step AWP is active in
         self._awp = None           # with it: the segment table, the scale array, the record, the workspace and the two loss tensors
+        self._pg = None            # parameter groups: the segment table, the device rows, the workspace, allocated by the first step with optimizer.param_groups
+        self._pg_key = None        # the canonical text of the groups the rows were resolved from (None: the option is off)
+        self._pg_seen = None       # a deep copy of optimizer.param_groups as it was then: an equal value needs no second look
         if device is not None:
             self._to_device(device, seed)
 
@@ -375,8 +396,12 @@ class Model(Handle):
             return
         wd = float(self.optimizer.weight_decay) if self.optimizer.apply_weight_decay else 0.0
         ema = self._ema_begin_step()
-        _lib.check(self._lib.ishara_optimizer_step(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _stream()),
-                   "ishara_optimizer_step")
+        pg = self._pg_begin_step()
+        if pg is None:
+            _lib.check(self._lib.ishara_optimizer_step(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _stream()),
+                       "ishara_optimizer_step")
+        else:
+            self._step_groups(pg, wd, None, None, False)
         if ema:
             self._ema_update(ema, None, False)
         self.optimizer.iterations += 1
@@ -463,6 +488,7 @@ class Model(Handle):
         if self._gstats is None:
             self._gstats = torch.zeros(4, dtype=torch.int32, device=self.device)
             self._gstats_ws = torch.empty(int(self._lib.ishara_grad_stats_workspace_bytes(self.n_train)), dtype=torch.uint8, device=self.device)
+        self._mask_frozen(src)         # a frozen tensor's gradient counts neither in the norm nor in the non-finite guard
         _lib.check(self._lib.ishara_gradient_stats(self._h, _lib.ptr(src), src.numel(), C.c_float(grad_scale), C.c_float(clip),
                                                    _lib.ptr(self._gstats), _lib.ptr(self._gstats_ws), _stream()), "ishara_gradient_stats")
 
@@ -470,12 +496,67 @@ class Model(Handle):
         self._not_while_averaged("the optimizer step")
         wd = float(self.optimizer.weight_decay) if self.optimizer.apply_weight_decay else 0.0
         ema = self._ema_begin_step()
-        _lib.check(self._lib.ishara_optimizer_step_ex(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _lib.ptr(src),
-                                                      _lib.ptr(self._gstats), 1 if skip else 0, _stream()), "ishara_optimizer_step_ex")
+        pg = self._pg_begin_step()
+        if pg is None:
+            _lib.check(self._lib.ishara_optimizer_step_ex(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _lib.ptr(src),
+                                                          _lib.ptr(self._gstats), 1 if skip else 0, _stream()), "ishara_optimizer_step_ex")
+        else:
+            self._step_groups(pg, wd, src, self._gstats, skip)
         if ema:
             self._ema_update(ema, self._gstats, skip)
         self.optimizer.iterations += 1
         self._steps += 1
+
+    # ------------------------------------------------------------------ optimizer parameter groups (csrc/optimizer.hip)
+    def _pg_begin_step(self):
+        """In front of a (micro)batch and of an optimizer step: None when optimizer.param_groups is None (and then nothing of the feature is
+        touched, allocated or launched), else the device tables.  The groups are resolved against the entry names and the 16-byte rows
+        uploaded only when the option changed by value since the last look; a change in the middle of an accumulation cycle, or inside
+        averaged_weights(), is refused."""
+        raw = self.optimizer.param_groups
+        if raw is None and self._pg_key is None:
+            return None
+        if self._pg_key is not None and type(raw) is type(self._pg_seen) and raw == self._pg_seen:      # unchanged by value: no check, no JSON
+            return self._pg
+        from . import train_state as TS
+        groups = self.optimizer.group_options()
+        key = None if groups is None else TS.param_groups_json(groups)
+        if key != self._pg_key:
+            self._not_while_averaged("a change of optimizer.param_groups")
+            if self._micro:
+                raise ValueError(f"optimizer.param_groups changed in the middle of an accumulation cycle ({self._micro} microbatches summed)")
+            if key is not None:
+                seg, rows = TS.param_group_rows(self.entries, self.n_train, groups)
+                S = len(rows)
+                if self._pg is None:
+                    ws_bytes = int(self._lib.ishara_param_groups_workspace_bytes(self.n_train, S))
+                    if ws_bytes < 0:
+                        _lib.check(-1, "ishara_param_groups_workspace_bytes")
+                    self._pg = dict(seg=torch.from_numpy(seg).to(self.device), S=S, rows=torch.empty(4 * S, dtype=torch.int32, device=self.device),
+                                    ws=torch.empty(ws_bytes, dtype=torch.uint8, device=self.device), frozen=False)
+                self._pg["rows"].copy_(torch.from_numpy(rows.view(np.int32).copy()))
+                self._pg["frozen"] = bool((rows["frozen"] != 0).any())
+            self._pg_key = key
+        self._pg_seen = copy.deepcopy(raw)
+        return None if key is None else self._pg
+
+    def _step_groups(self, pg, wd: float, src, gstats, skip: bool):
+        _lib.check(self._lib.ishara_optimizer_step_groups(self._h, C.c_float(float(self.optimizer.learning_rate)), C.c_float(wd), _lib.ptr(src),
+                                                          _lib.ptr(gstats), 1 if skip else 0, _lib.ptr(pg["seg"]), _lib.ptr(pg["rows"]), pg["S"],
+                                                          _lib.ptr(pg["ws"]), _stream()), "ishara_optimizer_step_groups")
+
+    def _mask_frozen(self, g: torch.Tensor):
+        """g = +0.0 over the frozen tensors: one launch, only when the groups freeze something"""
+        pg = self._pg_begin_step()
+        if pg is None or not pg["frozen"]:
+            return
+        _lib.check(self._lib.ishara_gradient_mask_groups(self._h, _lib.ptr(g), self.n_train, _lib.ptr(pg["seg"]), _lib.ptr(pg["rows"]), pg["S"],
+                                                         _lib.ptr(pg["ws"]), _stream()), "ishara_gradient_mask_groups")
+
+    def param_groups(self) -> Dict[str, dict]:
+        """{trainable entry name: {lr_scale, weight_decay_scale, trainable}} as optimizer.param_groups resolves (all defaults when it is None)"""
+        from . import train_state as TS
+        return TS.resolve_param_groups(self.entries, self.optimizer.group_options())
 
     # ------------------------------------------------------------------ adversarial weight perturbation (csrc/awp.hip)
     def _awp_begin_step(self):
@@ -508,6 +589,7 @@ class Model(Handle):
         first pass's, in a tensor of the helper's own, comparable with a run without AWP.  The weight shadows are refreshed behind the
         perturbation, and behind the restore by the optimizer step that follows, or here when the microbatch does not end its cycle
         (ends_cycle False).  No host synchronise."""
+        self._pg_begin_step()          # a change of the groups in the middle of a cycle is refused before any work
         awp = self._awp_begin_step()
         if awp is None:
             return self.loss_and_gradients(x, y, seed=seed, loss_scale=loss_scale, **_fl_kw(frame_lengths))[0]
@@ -517,6 +599,7 @@ class Model(Handle):
             seed = (self._step_seed + 0x9E3779B1 * self._steps) & 0xFFFFFFFF
         self.loss_and_gradients(x, y, seed=seed, loss_scale=1.0, **_fl_kw(frame_lengths))
         a["clean"].copy_(self._loss_buf)
+        self._mask_frozen(self.grads[:self.n_train])       # a frozen tensor is not perturbed (a zero gradient: a step of 0) and is not in the norms
         _lib.check(self._lib.ishara_awp_perturb(self._h, _lib.ptr(self.params), _lib.ptr(self._awp_backup), _lib.ptr(self.grads), _lib.ptr(a["seg"]),
                                                 a["S"], self.n_train, C.c_float(delta), C.c_float(eps), 1 if relative else 0, _lib.ptr(a["scale"]),
                                                 _lib.ptr(a["rec"]), _lib.ptr(a["ws"]), _stream()), "ishara_awp_perturb")
@@ -655,7 +738,8 @@ class Model(Handle):
         st = TS.pack_state(self.entries, *(t.detach().cpu().numpy() for t in (self.params, self.opt_m, self.opt_v, self.opt_slow)),
                            iterations=o.iterations, steps=self._steps, step_seed=self._step_seed, learning_rate=float(o.learning_rate),
                            weight_decay=float(o.weight_decay), apply_weight_decay=o.apply_weight_decay, global_clipnorm=o.global_clipnorm,
-                           skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped, **self._ema_state_entries(), **self._awp_state_entries())
+                           skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped, **self._ema_state_entries(), **self._awp_state_entries(),
+                           param_groups=o.group_options())
         return TS.save_state_file(path, st)
 
     def _ema_state_entries(self) -> dict:
@@ -678,7 +762,7 @@ class Model(Handle):
         """Restores what save_state wrote into this model (same architecture: the entry list is checked).  A file with a moving average
         restores it, its update count and the four ema settings; a file without one leaves the settings alone and, with optimizer.use_ema
         on, starts a fresh average at the loaded weights with 0 updates.  A file with the options of adversarial weight perturbation sets
-        them; a file without them leaves them alone."""
+        them; a file without them leaves them alone, and so with the optimizer's parameter groups."""
         from . import train_state as TS
         self._not_while_averaged("load_state")
         st = TS.load_state_file(path, self.entries)
@@ -693,6 +777,8 @@ class Model(Handle):
             self._gstats_ws = torch.empty(int(self._lib.ishara_grad_stats_workspace_bytes(self.n_train)), dtype=torch.uint8, device=self.device)
         self._gstats[3] = st["skipped"]
         self._skipped_seen = st["skipped"]
+        if "param_groups" in st:
+            o.param_groups = st["param_groups"]
         if "awp_delta" in st:
             o.awp_delta, o.awp_eps, o.awp_start_step, o.awp_relative = st["awp_delta"], st["awp_eps"], st["awp_start_step"], st["awp_relative"]
         self._ema_avg = self._ema_rec = None

@@ -11,6 +11,8 @@ Semantics (include/ishara_hip.h, DESIGN.md):
 """
 from __future__ import annotations
 
+import fnmatch
+import json
 import math
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
@@ -197,9 +199,139 @@ def awp_reference(w: np.ndarray, g: np.ndarray, seg_off: Sequence[int], delta: f
     return out, scale, stats
 
 
+# ---------------------------------------------------------------------------------- optimizer parameter groups (csrc/optimizer.hip)
+PARAM_GROUP_DTYPE = np.dtype([("lr_scale", "<f4"), ("wd_scale", "<f4"), ("frozen", "<i4"), ("reserved", "<i4")])      # ishara_param_group
+PARAM_GROUP_FIELDS = ("match", "lr_scale", "weight_decay_scale", "trainable")
+
+
+def _scale_f32(v, what: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"param_groups: {what} must be a number, got {v!r}")
+    with np.errstate(over="ignore", under="ignore"):
+        f = float(np.float32(v))
+    if not (math.isfinite(f) and f >= 0):
+        raise ValueError(f"param_groups: {what} must be finite and >= 0 (as float32), got {v!r}")
+    return float(v)
+
+
+def check_param_groups(groups) -> Optional[List[dict]]:
+    """The checked form of Optimizer.param_groups: None, or a list of {"match": [pattern, ...], "lr_scale", "weight_decay_scale",
+    "trainable"} with the defaults (1.0, 1.0, True) filled in.  Anything else raises ValueError."""
+    if groups is None:
+        return None
+    if not isinstance(groups, (list, tuple)):
+        raise ValueError(f"param_groups must be None or a list of dicts, got {type(groups).__name__}")
+    out = []
+    for i, g in enumerate(groups):
+        if not isinstance(g, dict):
+            raise ValueError(f"param_groups[{i}] must be a dict, got {type(g).__name__}")
+        unknown = sorted(set(g) - set(PARAM_GROUP_FIELDS))
+        if unknown:
+            raise ValueError(f"param_groups[{i}]: unknown key(s) {unknown}; the keys are {list(PARAM_GROUP_FIELDS)}")
+        if "match" not in g:
+            raise ValueError(f"param_groups[{i}] has no 'match'")
+        pats = [g["match"]] if isinstance(g["match"], str) else g["match"]
+        if not isinstance(pats, (list, tuple)) or not pats or not all(isinstance(p, str) and p for p in pats):
+            raise ValueError(f"param_groups[{i}]: 'match' must be a pattern or a non-empty list of patterns, got {g['match']!r}")
+        trainable = g.get("trainable", True)
+        if not isinstance(trainable, (bool, np.bool_)):
+            raise ValueError(f"param_groups[{i}]: 'trainable' must be a bool, got {trainable!r}")
+        out.append(dict(match=list(pats), lr_scale=_scale_f32(g.get("lr_scale", 1.0), f"lr_scale of group {i}"),
+                        weight_decay_scale=_scale_f32(g.get("weight_decay_scale", 1.0), f"weight_decay_scale of group {i}"), trainable=bool(trainable)))
+    return out
+
+
+def param_groups_json(groups) -> str:
+    """the canonical text of checked groups: the state-file entry, and the key the model compares to see a change by value"""
+    return json.dumps(check_param_groups(groups), sort_keys=True)
+
+
+def _trainable_names(entries) -> List[str]:
+    return [n for _, n in sorted((int(o), n) for n, _, o, t in entries if t)]
+
+
+def resolve_param_groups(entries, groups) -> Dict[str, dict]:
+    """{trainable entry name, in offset order: {lr_scale, weight_decay_scale, trainable}}: fnmatch.fnmatchcase of every pattern over the
+    names of the trainable entries, the first matching group wins, an unmatched entry gets (1.0, 1.0, True).  A pattern that matches no
+    trainable entry (a typo, or one that only hits the BatchNorm moving statistics) raises and names the pattern."""
+    groups = check_param_groups(groups) or []
+    names = _trainable_names(entries)
+    for i, g in enumerate(groups):
+        for p in g["match"]:
+            if not any(fnmatch.fnmatchcase(n, p) for n in names):
+                raise ValueError(f"param_groups[{i}]: the pattern {p!r} matches no trainable entry")
+    out = {}
+    for n in names:
+        hit = next((g for g in groups if any(fnmatch.fnmatchcase(n, p) for p in g["match"])), None)
+        out[n] = dict(lr_scale=hit["lr_scale"] if hit else 1.0, weight_decay_scale=hit["weight_decay_scale"] if hit else 1.0,
+                      trainable=hit["trainable"] if hit else True)
+    return out
+
+
+def param_group_rows(entries, n_train: int, groups) -> Tuple[np.ndarray, np.ndarray]:
+    """(seg_off, rows) of ishara_optimizer_step_groups: awp_segments of the entries and one PARAM_GROUP_DTYPE row per segment."""
+    seg_off = awp_segments(entries, n_train)
+    res = resolve_param_groups(entries, groups)
+    rows = np.zeros(len(seg_off) - 1, dtype=PARAM_GROUP_DTYPE)
+    for s, r in enumerate(res.values()):
+        rows[s] = (np.float32(r["lr_scale"]), np.float32(r["weight_decay_scale"]), 0 if r["trainable"] else 1, 0)
+    return seg_off, rows
+
+
+def no_decay_groups(entries) -> List[dict]:
+    """one group with weight_decay_scale = 0 naming every trainable entry of at most one dimension (biases, gamma, beta): the
+    weight-decay exclusion of the AdamW recipes, for Optimizer(param_groups=...) with apply_weight_decay"""
+    return [dict(match=[n for n, s, _, t in entries if t and len(tuple(s)) <= 1], weight_decay_scale=0.0)]
+
+
+def param_groups_reference(theta: np.ndarray, grad: np.ndarray, state: dict, seg_off: Sequence[int], rows: np.ndarray, lr: float, coef: float = 1.0,
+                           nonfinite: int = 0, skip_nonfinite: bool = False, weight_decay: float = 0.0, **kw) -> np.ndarray:
+    """One ishara_optimizer_step_groups in numpy -> the new theta; `state` (step_state_init) is updated in place.  clipped_step_reference
+    runs once per distinct unfrozen row on copies, with lr' = fp32(lr) * fp32(lr_scale) and wd' = fp32(wd) * fp32(wd_scale) (one fp32
+    product each; wd' = 0 is a step without decay), and the segments are stitched from the run of their row; a frozen segment keeps
+    theta and the three slots as they came.  A skipped step advances the step number and `skipped` once."""
+    rows = np.asarray(rows, dtype=PARAM_GROUP_DTYPE)
+    seg_off = [int(o) for o in seg_off]
+    if skip_nonfinite and nonfinite > 0:
+        state["step"] += 1
+        state["skipped"] += 1
+        return theta
+    out = {k: np.array(state[k], dtype=np.float32) for k in ("m", "v", "slow")}
+    new_theta = np.array(theta, dtype=np.float32)
+    runs = {}
+    for s, r in enumerate(rows):
+        if r["frozen"] != 0:
+            continue
+        key = (r["lr_scale"].tobytes(), r["wd_scale"].tobytes())
+        if key not in runs:
+            st = dict(m=state["m"].copy(), v=state["v"].copy(), slow=state["slow"].copy(), step=state["step"], skipped=state["skipped"])
+            with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+                lr_s, wd_s = np.float32(lr) * r["lr_scale"], np.float32(weight_decay) * r["wd_scale"]
+                th = clipped_step_reference(np.array(theta, dtype=np.float32), grad, st, float(lr_s), coef=coef, weight_decay=float(wd_s), **kw)
+            runs[key] = (th, st)
+        th, st = runs[key]
+        lo, hi = seg_off[s], seg_off[s + 1]
+        new_theta[lo:hi] = th[lo:hi]
+        for k in out:
+            out[k][lo:hi] = st[k][lo:hi]
+    state.update(out)
+    state["step"] += 1
+    return new_theta
+
+
+def mask_reference(g: np.ndarray, seg_off: Sequence[int], rows: np.ndarray) -> np.ndarray:
+    """ishara_gradient_mask_groups in numpy: a copy of g with +0.0 over the frozen segments, every other word untouched"""
+    out = np.array(g, dtype=np.float32)
+    for s, r in enumerate(np.asarray(rows, dtype=PARAM_GROUP_DTYPE)):
+        if r["frozen"] != 0:
+            out[int(seg_off[s]):int(seg_off[s + 1])] = np.float32(0.0)
+    return out
+
+
 # ---------------------------------------------------------------------------------- the state file
 EMA_KEYS = ("ema_avg", "ema_updates", "ema_momentum", "ema_warmup", "ema_overwrite_frequency", "use_ema")
 AWP_KEYS = ("awp_delta", "awp_eps", "awp_start_step", "awp_relative")
+PARAM_GROUP_KEYS = ("param_groups",)
 
 
 class TrainStateError(ValueError):
@@ -221,12 +353,13 @@ def pack_state(entries, params: np.ndarray, opt_m: np.ndarray, opt_v: np.ndarray
                global_clipnorm: Optional[float] = None, skip_nonfinite: bool = False, accumulate_steps: int = 1, skipped: int = 0,
                ema_avg: Optional[np.ndarray] = None, ema_updates: int = 0, use_ema: bool = True, ema_momentum: float = 0.99,
                ema_warmup: bool = False, ema_overwrite_frequency: Optional[int] = None, awp_delta: Optional[float] = None,
-               awp_eps: float = 1e-4, awp_start_step: int = 0, awp_relative: bool = False) -> Dict[str, np.ndarray]:
+               awp_eps: float = 1e-4, awp_start_step: int = 0, awp_relative: bool = False, param_groups=None) -> Dict[str, np.ndarray]:
     """The arrays of one state file (np.savez(path, **pack_state(...))): the flat fp32 `params` (BatchNorm moving statistics included), the
     three optimizer slots, the counters, the hyper-parameters, the format version and the entry list the buffers were laid out by.  With
     `ema_avg` (the moving average of the trainable prefix, when one exists) the file also holds EMA_KEYS: the average, its update count
     and the four settings; without it the key set is what it was before the average existed.  With `awp_delta` (adversarial weight
-    perturbation is configured) it holds AWP_KEYS, the four options; AWP has no other state."""
+    perturbation is configured) it holds AWP_KEYS, the four options; AWP has no other state.  With `param_groups` (the optimizer's
+    parameter groups are set) it holds PARAM_GROUP_KEYS: the JSON text of the checked list."""
     out = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in zip(ARRAYS, (params, opt_m, opt_v, opt_slow))}
     out.update(_entry_arrays(entries))
     out.update(format_version=np.int64(FORMAT_VERSION), iterations=np.int64(iterations), steps=np.int64(steps), step_seed=np.int64(step_seed),
@@ -240,6 +373,8 @@ def pack_state(entries, params: np.ndarray, opt_m: np.ndarray, opt_v: np.ndarray
                    ema_overwrite_frequency=np.int64(0 if ema_overwrite_frequency is None else ema_overwrite_frequency))
     if awp_delta is not None:
         out.update(awp_delta=np.float64(awp_delta), awp_eps=np.float64(awp_eps), awp_start_step=np.int64(awp_start_step), awp_relative=np.bool_(awp_relative))
+    if param_groups is not None:
+        out.update(param_groups=np.array(param_groups_json(param_groups), dtype=np.str_))
     validate_state(out, entries)
     return out
 
@@ -294,13 +429,18 @@ def validate_state(z, entries) -> None:
         d, e = float(np.float32(z["awp_delta"])), float(np.float32(z["awp_eps"]))
         if not (math.isfinite(d) and d > 0 and math.isfinite(e) and e > 0 and int(z["awp_start_step"]) >= 0):
             raise TrainStateError("train state: an option of the weight perturbation (awp_delta, awp_eps, awp_start_step) is out of range")
+    if "param_groups" in keys:          # and the optimizer's parameter groups
+        try:
+            resolve_param_groups(entries, json.loads(str(z["param_groups"])))
+        except ValueError as e:
+            raise TrainStateError(f"train state: the entry 'param_groups' does not fit the model: {e}")
 
 
 def unpack_state(z, entries) -> dict:
     """validate_state, then plain Python values: the four arrays (float32, flat) and the scalars; global_clipnorm is None when off.  A file
     with the moving average adds ema_avg (float32), ema_updates, use_ema, ema_momentum, ema_warmup and ema_overwrite_frequency (None when
     off); a file without it adds none of them.  A file with the options of the weight perturbation adds awp_delta, awp_eps, awp_start_step
-    and awp_relative."""
+    and awp_relative; a file with the optimizer's parameter groups adds param_groups (the checked list)."""
     validate_state(z, entries)
     out = {k: np.array(z[k], dtype=np.float32) for k in ARRAYS}
     for k in ("iterations", "steps", "step_seed", "accumulate_steps", "skipped"):
@@ -318,6 +458,8 @@ def unpack_state(z, entries) -> dict:
                    ema_momentum=float(z["ema_momentum"]), ema_warmup=bool(z["ema_warmup"]), ema_overwrite_frequency=every if every > 0 else None)
     if "awp_delta" in keys:
         out.update(awp_delta=float(z["awp_delta"]), awp_eps=float(z["awp_eps"]), awp_start_step=int(z["awp_start_step"]), awp_relative=bool(z["awp_relative"]))
+    if "param_groups" in keys:
+        out.update(param_groups=check_param_groups(json.loads(str(z["param_groups"]))))
     return out
 
 

@@ -720,6 +720,40 @@ int ishara_op_gemm_nt(const ishara_gemm_nt_call* call, ishara_stream s);
  * "NT_REG"; "NT_REFUSED" for every call the entry refuses, with the reason in ishara_last_error) and the profiler key of the kernel
  * (gemm_nt_kernel_name; "" for a refused call).  Pointers are only tested for NULL and alignment.  Host only, launches nothing; the strings are static. */
 int ishara_debug_gemm_nt_route(const ishara_gemm_nt_call* call, const char** route, const char** kernel);
+/* One forward / dgrad GEMM on the A-stationary kernels (gemm_as.hip; fp16 operands: gemm_as_f16.hip): the call of ishara_op_gemm_nt plus the
+ * fields only this family reads.  16-bit operands of one type (dtA == dtM, op 0), K in {256, 512} (bf16 operands with bf16 C also 128 and 1024),
+ * N a multiple of 32 up to 1024, C in the operand type or f32.  Bt is the CALLER-BUILT weight shadow [bt_rows][ldb]: bt_rows >= N, ldb >= K and a multiple of 64;
+ * rows n >= N and columns k >= K are never read.
+ * ln_gamma / ln_beta [K] f32 (with ln_eps): the operand rows are LayerNorm-ed over K in registers, A' = (A - mean) * rstd * gamma + beta;
+ *   ln_mean / ln_rstd [M] f32 (both or neither) receive the row statistics.  pa_P / pa_Q [ceil(M / T), K] f32: A' = A * P[m / T] + Q[m / T], T a
+ *   multiple of the rows per workgroup (ishara_debug_gemm_as_plan).  At most one of the two; each with C in the operand type, K >= 256 and one of
+ *   the epilogues it is compiled with (LayerNorm: none, act + pre_out, act + pre_out + dropout, QKV; affine: resid, resid + rowscale).
+ *   pro_out [M, K] (operand type, may be NULL) receives A'.
+ * ldc (0: N): elements between rows of C and pre_out, at least the columns a row stores, whole 16-byte pieces.  n_valid (0: all): only the columns below it are stored, bias
+ *   is read below it only; a multiple of the 16-byte store group (8 for 16-bit C, 4 for f32).  Neither with resid, aux or a QKV split.
+ * as_flags: bit 0 paired half-line stores, bit 1 non-temporal side outputs, bits 4 / 5 the chunked kernel at K = 256 / 512, bits 6 / 7 the
+ *   C-stationary kernel's switches (a call that they send there is refused here); -1: the library default. */
+typedef struct ishara_gemm_as_ext {
+    const float* ln_gamma; const float* ln_beta; float* ln_mean; float* ln_rstd;
+    const float* pa_P; const float* pa_Q; void* pro_out;
+    float ln_eps;
+    int32_t ldc, n_valid, as_flags;
+} ishara_gemm_as_ext;
+/* runs the call on stream s: exactly one kernel launch, nothing else.  Before any HIP call it refuses, with a message that names the field,
+ * what ishara_op_gemm_nt refuses and: a NULL ext, a prologue without an instantiation for its epilogue, pa_P with T off the rows per workgroup,
+ * ldc / n_valid with resid, aux or QKV or off their multiples, a misaligned C, pre_out, aux, resid, q, k, pro_out, addtab (16 bytes), a shadow
+ * smaller than the contract above, and a call that lands on another kernel than the A-stationary ones (by the route's name). */
+int ishara_op_gemm_as(const ishara_gemm_nt_call* call, const ishara_gemm_as_ext* ext, ishara_stream s);
+/* what the A-stationary launcher does with the call, read from the function it launches from (gemm_nt_as_plan): route ("NT_AS", "NT_AS_F16";
+ * "NT_REFUSED" for every call ishara_op_gemm_as refuses, the reason in ishara_last_error, everything else zero), the profiler key, rows per
+ * workgroup, the grid (gx, gy), 32-column steps per workgroup, ring depth, column steps per stage, waves, the sequential row passes of a
+ * workgroup and their rows, whether the chunked kernel runs, whether paired stores are active, the compiled epilogue mask (255: all features
+ * behind run-time flags) and the prologue (0 none, 1 LayerNorm, 2 affine).  Host only, launches nothing; the strings are static. */
+typedef struct ishara_gemm_as_plan {
+    const char* route; const char* kernel;
+    int32_t rows, gx, gy, nsteps, ring, cs, waves, passes, pass_rows[2], chunked, hold, inst_mask, prologue;
+} ishara_gemm_as_plan;
+int ishara_debug_gemm_as_plan(const ishara_gemm_nt_call* call, const ishara_gemm_as_ext* ext, ishara_gemm_as_plan* plan);
 /* QKV projection of the attention module at inference: LayerNorm of x [B*T, H*dh] (gamma, beta f32; gamma NULL: none; H*dh <= 512 with it),
  * x @ W + b (W [H*dh, 3*H*dh] f32, bias [3*H*dh] or NULL) scattered to q, k [B,H,T,dh] and vt [B,H,dh,T] (dt) — head_major 1: W's columns
  * are [q|k|v] per head, 0: [q of all heads | k | v].  T, dh multiples of 8.  The LayerNorm runs inside the GEMM or as a kernel of its own

@@ -97,6 +97,24 @@ class GemmNtCall(C.Structure):
     ]
 
 
+class GemmAsExt(C.Structure):
+    """ishara_gemm_as_ext: the A-stationary-only fields of ishara_op_gemm_as / ishara_debug_gemm_as_plan (field order of the header)."""
+    _fields_ = [
+        ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_mean", C.c_void_p), ("ln_rstd", C.c_void_p),
+        ("pa_P", C.c_void_p), ("pa_Q", C.c_void_p), ("pro_out", C.c_void_p),
+        ("ln_eps", C.c_float), ("ldc", C.c_int32), ("n_valid", C.c_int32), ("as_flags", C.c_int32),
+    ]
+
+
+class GemmAsPlan(C.Structure):
+    """ishara_gemm_as_plan: what ishara_debug_gemm_as_plan reports (field order of the header)."""
+    _fields_ = [
+        ("route", C.c_char_p), ("kernel", C.c_char_p),
+        ("rows", C.c_int32), ("gx", C.c_int32), ("gy", C.c_int32), ("nsteps", C.c_int32), ("ring", C.c_int32), ("cs", C.c_int32), ("waves", C.c_int32),
+        ("passes", C.c_int32), ("pass_rows", C.c_int32 * 2), ("chunked", C.c_int32), ("hold", C.c_int32), ("inst_mask", C.c_int32), ("prologue", C.c_int32),
+    ]
+
+
 class StreamState(C.Structure):
     """ishara_stream_state: the device arrays of S streaming sessions (field order of the header); passed by address."""
     _fields_ = [
@@ -204,6 +222,8 @@ SIGNATURES = {
     "ishara_debug_gemm_tn_plan": (C.c_int, [C.POINTER(GemmTnCall), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_I32), C.POINTER(_I32)]),
     "ishara_op_gemm_nt": (C.c_int, [C.POINTER(GemmNtCall), _P]),
     "ishara_debug_gemm_nt_route": (C.c_int, [C.POINTER(GemmNtCall), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
+    "ishara_op_gemm_as": (C.c_int, [C.POINTER(GemmNtCall), C.POINTER(GemmAsExt), _P]),
+    "ishara_debug_gemm_as_plan": (C.c_int, [C.POINTER(GemmNtCall), C.POINTER(GemmAsExt), C.POINTER(GemmAsPlan)]),
     "ishara_op_qkv_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "ishara_op_qkv_fwd": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "ishara_op_classifier_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),

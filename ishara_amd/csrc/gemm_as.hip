@@ -588,17 +588,6 @@ static int as_mask_of(const EpiArgs& ea) {
            (ea.rowscale ? AS_ROWSCALE : 0) | (ea.pre_out ? AS_PREOUT : 0) | (ea.mode == EPI_QKV ? AS_QKV : 0) | (ea.addtab ? AS_ADDTAB : 0);
 }
 
-// the instantiation run_as picks for a feature mask (bf16 C: the listed combinations, else AS_ALL; f32 C: 0 or AS_ALL)
-static int as_inst_mask(bool c_bf16, int mask, int K = 256) {
-    if (!c_bf16) return mask == 0 ? 0 : AS_ALL;
-    if (K == 128) return (mask == AS_DACT || mask == (AS_DACT | AS_DROP)) ? mask : AS_ALL;      // K = 128: the classifier's dgrad only
-    switch (mask) {
-        case 0: case AS_RESID: case AS_RESID | AS_ROWSCALE: case AS_ROWSCALE: case AS_RESID | AS_DROP: case AS_ACT | AS_PREOUT: case AS_ACT | AS_PREOUT | AS_DROP:
-        case AS_ACT | AS_DROP: case AS_ACT: case AS_DACT: case AS_DACT | AS_DROP: case AS_QKV: case AS_ADDTAB: return mask;
-        default: return AS_ALL;
-    }
-}
-
 #define AS_LAUNCH_PLAIN(MASK, PRO) hipLaunchKernelGGL((gemm_nt_as_kernel<TC, KT, MASK, 0, PRO>), grid, block, 0, s, (const as_t*)A, (const as_t*)Bt, (TC*)C, M, N, ldb, ea)
 #ifdef AS_F16
 #define AS_LAUNCH2(MASK, PRO) AS_LAUNCH_PLAIN(MASK, PRO)
@@ -626,28 +615,21 @@ static int as_default_flags() {
     static const int v = getenv("ISHARA_AS_FLAGS") ? atoi(getenv("ISHARA_AS_FLAGS")) : 51;     // 1 paired stores | 2 nt side outputs | 16 chunked K = 256 | 32 chunked K = 512
     return g_as_flags_override >= 0 ? g_as_flags_override : v;
 }
-static bool as_chunk_applies(int flags, int M, int N, int K, const EpiArgs& ea) {      // (bf16 C checked by the caller); bit 4: K = 256, bit 5: K = 512
-    const int cs = K == 256 ? 4 : 2;
-    // PSA prologue: a workgroup's rows (both passes at K = 512: 256 + 128) must lie inside one sample
-    return (K == 256 ? (flags & 16) : (K == 512 && (flags & 32))) && M >= 128 * AS_CHUNK_ROWS && (N / AS_NS) % cs == 0 && N >= 128 && !ea.n_valid && !ea.dbg &&
-           (!ea.pa_P || (ea.T > 0 && ea.T % AS_CHUNK_ROWS == 0));
-}
 template <typename TC, int KT>
 static int run_as(const void* A, const void* Bt, void* C, int M, int N, int ldb, const EpiArgs& ea_in, hipStream_t s) {
     EpiArgs ea = ea_in;
     if (ea.as_flags < 0) ea.as_flags = as_default_flags();
-    const int BR = KT <= 8 ? (M <= AS_SMALL_M ? 64 : 128) : (KT <= 16 ? (M <= AS_MID_M_K512 ? 64 : 192) : 128);     // rows per workgroup
-    // few rows (config #4 at small batches: M / 192 = 171 workgroups for 512 slots): split the columns 2- or 4-way; every
-    // workgroup then loads its A rows again, which is cheap exactly when M is small
-    const int gx = (M + BR - 1) / BR, slots = KT <= 8 ? 768 : (KT <= 16 ? 512 : 256);
-    int gy = 1;
-    // (a clip's worth of rows: up to 8 splits of at least 64 columns — what counts there is the number of sequential column steps of one workgroup)
-    const int max_gy = M <= AS_SMALL_M ? 16 : 4, min_cols = M <= AS_SMALL_M ? 32 : 128;
-    while (gy < max_gy && gx * gy * 2 <= slots && (N / AS_NS) % (gy * 2) == 0 && N / (gy * 2) >= min_cols) gy *= 2;
-    const dim3 grid(gx, gy), block(KT <= 16 ? 256 : 512);
+    // rows per workgroup, the column split, the chunked form and the instantiation: gemm_nt_as_plan, which the prologue check, the profiler key
+    // and ishara_debug_gemm_as_plan read too
+    AsPlan p;
+    if (!gemm_nt_as_plan(AS_DT, std::is_same<TC, float>::value ? DT_F32 : AS_DT, M, N, KT * 32, ea, &p)) {      // (an f32 C or K = 128 would otherwise run without the prologue)
+        ishara_set_error("gemm_nt_as: %s prologue with epilogue mask %d, %s C and K=%d is not compiled", ea.ln_gamma ? "LayerNorm" : "affine", as_mask_of(ea),
+                         std::is_same<TC, float>::value ? "f32" : "16-bit", KT * 32);
+        return -1;
+    }
+    const dim3 grid(p.plain_gx, p.gy), block(KT <= 16 ? 256 : 512);
     const int mask = as_mask_of(ea);
-    // chunked form (K = 256): whole 128-column stages, rows enough to give every CU a 384-row workgroup, no column split, no narrow output
-    const bool chunked = (KT == 8 || KT == 16) && as_chunk_applies(ea.as_flags, M, N, KT * 32, ea) && gy == 1;
+    const bool chunked = p.chunked != 0;
     (void)chunked;
     if constexpr (is_16b_t<TC>::value && KT >= 8) {
 #define AS_PRO(MASK, PRO) AS_LAUNCH2(MASK, PRO)
@@ -672,11 +654,11 @@ static int run_as(const void* A, const void* Bt, void* C, int M, int N, int ldb,
 #undef AS_PRO
     }
     if constexpr (KT == 4) {
-        if (mask == AS_DACT) AS_LAUNCH(AS_DACT); else if (mask == (AS_DACT | AS_DROP)) AS_LAUNCH(AS_DACT | AS_DROP); else AS_LAUNCH(AS_ALL);
+        if (p.inst == AS_DACT) AS_LAUNCH(AS_DACT); else if (p.inst == (AS_DACT | AS_DROP)) AS_LAUNCH(AS_DACT | AS_DROP); else AS_LAUNCH(AS_ALL);
     }
 #ifdef AS_F16
     else if constexpr (is_16b_t<TC>::value) {      // fp16 = inference: the forward passes' combinations, everything else through AS_ALL
-        switch (mask) {
+        switch (p.inst) {          // (a mask that is not listed: AS_ALL)
             case 0: AS_LAUNCH(0); break;
             case AS_RESID: AS_LAUNCH(AS_RESID); break;
             case AS_ACT | AS_PREOUT: AS_LAUNCH(AS_ACT | AS_PREOUT); break;
@@ -689,7 +671,7 @@ static int run_as(const void* A, const void* Bt, void* C, int M, int N, int ldb,
 #else
     else if constexpr (is_16b_t<TC>::value) {
         // the feature combinations the encoder's forward / backward passes use (model.hip), compiled without the others
-        switch (mask) {
+        switch (p.inst) {          // (a mask that is not listed: AS_ALL)
             case 0:
                 if (ea.dbg) hipLaunchKernelGGL((gemm_nt_as_kernel<TC, KT, 0, 1>), grid, block, 0, s, (const as_t*)A, (const as_t*)Bt, (TC*)C, M, N, ldb, ea);
                 else AS_LAUNCH(0);
@@ -711,22 +693,82 @@ static int run_as(const void* A, const void* Bt, void* C, int M, int N, int ldb,
     }
 #endif
     else {
-        if (mask == 0) AS_LAUNCH(0); else AS_LAUNCH(AS_ALL);
+        if (p.inst == 0) AS_LAUNCH(0); else AS_LAUNCH(AS_ALL);
     }
     return launch_rc();
 }
 #undef AS_LAUNCH
 
 #ifndef AS_F16
+// the instantiation of a feature mask, -1 when there is none.  A prologue: the listed masks only, 16-bit C of the operand type, K >= 256.
+// Without one: 16-bit C the listed combinations (bf16 operands: what the encoder's forward / backward passes use, K = 128 the classifier's dgrad
+// only; fp16 operands: the forward passes'), every other mask AS_ALL; f32 C 0 or AS_ALL.  run_as switches over the same lists.
+static int as_inst_mask(int dtM, int dtC, int mask, int K, int pro) {
+    if (pro) {
+        if (dtC != dtM || K < 256) return -1;
+        if (pro == 1) return (mask == 0 || mask == (AS_ACT | AS_PREOUT) || mask == (AS_ACT | AS_PREOUT | AS_DROP) || mask == AS_QKV) ? mask : -1;
+        return (mask == AS_RESID || mask == (AS_RESID | AS_ROWSCALE)) ? mask : -1;
+    }
+    if (!dt_is16(dtC)) return mask == 0 ? 0 : AS_ALL;
+    if (K == 128) return (mask == AS_DACT || mask == (AS_DACT | AS_DROP)) ? mask : AS_ALL;
+    if (dtM == DT_F16) {
+        switch (mask) {
+            case 0: case AS_RESID: case AS_ACT | AS_PREOUT: case AS_ACT: case AS_QKV: case AS_ADDTAB: return mask;
+            default: return AS_ALL;
+        }
+    }
+    switch (mask) {
+        case 0: case AS_RESID: case AS_RESID | AS_ROWSCALE: case AS_ROWSCALE: case AS_RESID | AS_DROP: case AS_ACT | AS_PREOUT: case AS_ACT | AS_PREOUT | AS_DROP:
+        case AS_ACT | AS_DROP: case AS_ACT: case AS_DACT: case AS_DACT | AS_DROP: case AS_QKV: case AS_ADDTAB: return mask;
+        default: return AS_ALL;
+    }
+}
+
+int gemm_nt_as_mask(const EpiArgs& ea) { return as_mask_of(ea); }
+
+// What run_as does with a call, decided here and nowhere else (kernels.h: AsPlan).  dtM: the operand type (DT_BF16 / DT_F16), K in {128, 256, 512,
+// 1024}, N a multiple of 32 (gemm_nt_as_applicable).  false: the call's prologue has no instantiation (p->inst = -1; the geometry is filled in).
+bool gemm_nt_as_plan(int dtM, int dtC, int M, int N, int K, const EpiArgs& ea, AsPlan* p) {
+    const int flags = ea.as_flags < 0 ? as_default_flags() : ea.as_flags, KT = K / 32;
+    const int mask = as_mask_of(ea);
+    p->pro = ea.ln_gamma ? 1 : (ea.pa_P ? 2 : 0);
+    p->inst = as_inst_mask(dtM, dtC, mask, K, p->pro);
+    const int BR = KT <= 8 ? (M <= AS_SMALL_M ? 64 : 128) : (KT <= 16 ? (M <= AS_MID_M_K512 ? 64 : 192) : 128);     // rows per workgroup
+    // few rows (config #4 at small batches: M / 192 = 171 workgroups for 512 slots): split the columns 2- or 4-way; every
+    // workgroup then loads its A rows again, which is cheap exactly when M is small
+    const int gx = (M + BR - 1) / BR, slots = KT <= 8 ? 768 : (KT <= 16 ? 512 : 256);
+    int gy = 1;
+    // (a clip's worth of rows: up to 8 splits of at least 64 columns — what counts there is the number of sequential column steps of one workgroup)
+    const int max_gy = M <= AS_SMALL_M ? 16 : 4, min_cols = M <= AS_SMALL_M ? 32 : 128;
+    while (gy < max_gy && gx * gy * 2 <= slots && (N / AS_NS) % (gy * 2) == 0 && N / (gy * 2) >= min_cols) gy *= 2;
+    p->plain_rows = BR; p->plain_gx = gx; p->gy = gy;
+    // chunked form (as_flags bit 4: K = 256, bit 5: K = 512): bf16 operands and C, a compiled mask, whole stages of cs column steps, rows enough to give
+    // every CU a 384-row workgroup, no column split, no narrow output; per-sample affine prologue: a workgroup's rows (both passes at K = 512:
+    // 256 + 128) must lie inside one sample
+    const int cs = K == 256 ? 4 : 2;
+    p->chunked = dtM == DT_BF16 && dtC == DT_BF16 && p->inst >= 0 && p->inst != AS_ALL && (K == 256 ? (flags & 16) != 0 : (K == 512 && (flags & 32))) &&
+                 M >= 128 * AS_CHUNK_ROWS && (N / AS_NS) % cs == 0 && N >= 128 && !ea.n_valid && !ea.dbg && (!ea.pa_P || (ea.T > 0 && ea.T % AS_CHUNK_ROWS == 0)) && gy == 1;
+    if (p->chunked) {
+        p->rows = AS_CHUNK_ROWS; p->gx = (M + AS_CHUNK_ROWS - 1) / AS_CHUNK_ROWS; p->ring = 2; p->cs = cs; p->waves = K == 256 ? 12 : 8;
+        p->passes = K == 256 ? 1 : 2; p->pass_rows[0] = K == 256 ? 384 : 256; p->pass_rows[1] = K == 256 ? 0 : 128;
+    } else {
+        p->rows = BR; p->gx = gx; p->ring = KT <= 8 ? 3 : 2; p->cs = 1; p->waves = KT <= 16 ? 4 : 8;
+        p->passes = BR == 192 ? 2 : 1; p->pass_rows[0] = BR == 192 ? 128 : BR; p->pass_rows[1] = BR == 192 ? 64 : 0;
+    }
+    p->nsteps = N / AS_NS / gy;
+    // paired stores (as_pass: HOLDABLE and as_flags bit 0, never with a narrow output)
+    p->hold = dt_is16(dtC) && dtC == dtM && p->inst >= 0 && p->inst != AS_ALL && (p->inst & AS_QKV) == 0 && (flags & 1) && !ea.n_valid;
+    return p->inst >= 0;
+}
+
 bool gemm_nt_as_prologue_ok(int dtA, int dtM, int dtC, int M, int N, int K, int ldb, const EpiArgs& ea) {
     if (!dt_is16(dtA) || dtM != dtA || dtC != dtA || (K != 256 && K != 512 && !(K == 1024 && dtA == DT_BF16)) || !gemm_nt_as_applicable(dtC, M, N, K, ldb, ea)) return false;
     if (ldb % 64 != 0 || g_force_regstage) return false;
-    const int BR = K == 256 ? (M <= AS_SMALL_M ? 64 : 128) : (K == 512 ? (M <= AS_MID_M_K512 ? 64 : 192) : 128), gx = (M + BR - 1) / BR, slots = K == 256 ? 768 : (K == 512 ? 512 : 256);
     // (when the launcher splits the columns every split redoes the prologue on its rows and the blockIdx.y == 0 split writes the side outputs)
-    (void)gx; (void)slots;
-    const int mask = as_mask_of(ea);
-    if (ea.ln_gamma) return mask == 0 || mask == (AS_ACT | AS_PREOUT) || mask == (AS_ACT | AS_PREOUT | AS_DROP) || mask == AS_QKV;
-    if (ea.pa_P) return ea.T > 0 && ea.T % BR == 0 && (mask == AS_RESID || mask == (AS_RESID | AS_ROWSCALE));   // a workgroup's rows inside one sample
+    AsPlan p;
+    if (!gemm_nt_as_plan(dtA, dtC, M, N, K, ea, &p)) return false;          // an epilogue mask the prologue is not compiled with
+    if (ea.ln_gamma) return true;
+    if (ea.pa_P) return ea.T > 0 && ea.T % p.rows == 0;   // a workgroup's rows inside one sample
     return false;
 }
 
@@ -740,9 +782,10 @@ bool gemm_nt_as_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs&
 // profiler key = the rocprof kernel name of the instantiation launch_gemm_nt_as runs
 const char* gemm_nt_as_name(int dtC, int K, const EpiArgs& ea, int M, int N) {
     static std::map<int, std::string> names;
-    const int inst = as_inst_mask(dtC == DT_BF16, as_mask_of(ea), K);
-    const int pro = ea.ln_gamma ? 1 : (ea.pa_P ? 2 : 0);
-    const bool chunk = dtC == DT_BF16 && inst != AS_ALL && as_chunk_applies(ea.as_flags < 0 ? as_default_flags() : ea.as_flags, M, N, K, ea);
+    AsPlan p;
+    gemm_nt_as_plan(DT_BF16, dtC, M, N, K, ea, &p);
+    const int inst = p.inst < 0 ? as_mask_of(ea) : p.inst, pro = p.pro;
+    const bool chunk = p.chunked != 0;
     const int id = (dtC == DT_BF16 ? 0 : 1 << 20) | (pro << 22) | (chunk ? 1 << 24 : 0) | (K << 8) | inst;
     auto it = names.find(id);
     if (it == names.end()) {

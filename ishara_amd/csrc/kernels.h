@@ -73,6 +73,14 @@ bool gemm_nt_as_applicable(int dtC, int M, int N, int K, int ldb, const EpiArgs&
 // the kernel also takes ea's prologue (ln_* / pa_*): bf16 output, K in {256, 512}, whole 16-row tiles inside one sample for pa_*
 bool gemm_nt_as_prologue_ok(int dtA, int dtM, int dtC, int M, int N, int K, int ldb, const EpiArgs& ea);   // gemm_as.hip: the A-stationary kernel takes this shape
 const char* gemm_nt_as_name(int dtC, int K, const EpiArgs& ea, int M, int N);
+// what the A-stationary launcher does with a call (gemm_as.hip: the one place that decides; run_as launches from it, gemm_nt_as_prologue_ok,
+// gemm_nt_as_name and ishara_debug_gemm_as_plan read it).  rows / gx: rows per workgroup and workgroups along M of the kernel that runs (the chunked
+// one: 384); plain_rows / plain_gx: the same for the per-step kernel; gy: column splits; nsteps: 32-column steps per workgroup; ring: weight stages
+// in LDS; cs: column steps per stage; passes / pass_rows: the sequential row passes of a workgroup; hold: paired stores; inst: the compiled
+// epilogue mask (255: every feature behind its run-time flag; -1: none for this prologue); pro: 0 none, 1 LayerNorm, 2 per-sample affine.  Host only
+struct AsPlan { int rows, gx, plain_rows, plain_gx, gy, nsteps, ring, cs, waves, passes, pass_rows[2], chunked, hold, inst, pro; };
+bool gemm_nt_as_plan(int dtM, int dtC, int M, int N, int K, const EpiArgs& ea, AsPlan* p);
+int gemm_nt_as_mask(const EpiArgs& ea);      // the epilogue feature mask of a call (bits: gemm_as.hip AS_RESID ..)
 int launch_gemm_nt_as(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);
 int launch_gemm_nt_as_f16(int dtC, const void* A, const void* Bt, void* C, int M, int N, int K, int ldb, const EpiArgs& ea, hipStream_t s);   // gemm_as_f16.hip
 // the C-stationary kernel of the K = 512 -> N = 256 projections and the K = 768 -> N = 256 plain dgrad at training-size M (gemm_cs.hip; as_flags bit 6 turns

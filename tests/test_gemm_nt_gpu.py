@@ -84,7 +84,9 @@ def test_reported_shape_five_times_through_the_dense_operator(lib):
     Observed on the MI355X (the open item): this test passed when the file ran alone and failed once in a whole-suite run, at
     launch 0 of the 5 — 16 wrong elements of 26 738 688, rows 576.. of column 636 only, tile (4, 4), id 36, workgroup 36, round 0 (that
     workgroup's FIRST tile), got - want = -2, -1, +6, -8, -4, +7, ...: one accumulator register (acc[3][0][0] of wave (1, 1)) in one quarter of the
-    lanes.  Launches 1 .. 4 of that run and all launches on the caller-built shadow were exact.  The cause is not found; the test keeps asserting."""
+    lanes.  Launches 1 .. 4 of that run and all launches on the caller-built shadow were exact.  A later whole-suite run saw the same register wrong in
+    test_case_exact[t_reported], the first launch of the shape in the process, on the caller-built shadow (tile (20, 0), workgroup 100, round 0, rows 2624 ..
+    of column 124): the shadow rebuild is not needed for it.  The cause is not found; the test keeps asserting."""
     import torch
     c = G.BY_NAME[G.REPORTED]
     op = G.inputs(c.name, False)

@@ -34,6 +34,7 @@ def _ops():
         "ishara_op_classifier_fwd": lambda L, dt: L.ishara_op_classifier_fwd(dt, N, N, N, N, 64, 256, 60, 0, N, N),
         "ishara_op_gemm_tn": lambda L, dt: _gemm_tn(L, dict(dtA=dt, dtB=dt, dtM=dt)),
         "ishara_op_gemm_nt": lambda L, dt: _gemm_nt(L, dtA=dt, dtM=dt, dtC=dt),
+        "ishara_op_gemm_as": lambda L, dt: _gemm_as(L, dtA=dt, dtM=dt, dtC=dt),
         **{n: (lambda L, dt, n=n: _r4_call(L, n, dt=dt)) for n in R4_DEFAULTS},
     }
 
@@ -624,5 +625,121 @@ def test_gemm_nt_null_arguments_and_accepted_calls(lib):
         assert _gemm_nt_route(lib)[1] == b"NT_REG"
         lib.ishara_debug_force_regstage(8192)
         assert _gemm_nt_route(lib, M=34816, N=768, K=640, bt_rows=768, ldb=640)[1] == b"NT_TILE_T"
+    finally:
+        lib.ishara_debug_force_regstage(0)
+
+
+# ---- ishara_op_gemm_as / ishara_debug_gemm_as_plan: what ishara_op_gemm_nt refuses, plus the fields only the A-stationary family reads; a call
+# that lands on another kernel is refused by the route's name.  The plan entry answers "NT_REFUSED", everything else zero, with the same message
+AS_EXT = ("ln_gamma", "ln_beta", "ln_mean", "ln_rstd", "pa_P", "pa_Q", "pro_out", "ln_eps", "ldc", "n_valid", "as_flags")
+
+
+def _gemm_as_call(**kw):
+    """(call, ext): a plain bf16 call of the per-step kernel (K = 256, bias + residual, 64-row workgroups) with made-up aligned addresses, `kw`
+    replacing single fields of either struct"""
+    v = dict(M=200, N=96, K=256, bt_rows=96, ldb=256)
+    v.update({n: x for n, x in kw.items() if n not in AS_EXT})
+    k, x = _gemm_nt_call(**v), _lib.GemmAsExt()
+    for n, val in dict(dict(as_flags=51, ln_eps=1e-5), **{n: x for n, x in kw.items() if n in AS_EXT}).items():
+        setattr(x, n, val)
+    return k, x
+
+
+def _gemm_as(L, **kw):
+    k, x = _gemm_as_call(**kw)
+    return L.ishara_op_gemm_as(C.byref(k), C.byref(x), N)
+
+
+def _gemm_as_plan(L, **kw):
+    k, x = _gemm_as_call(**kw)
+    p = _lib.GemmAsPlan()
+    rc = L.ishara_debug_gemm_as_plan(C.byref(k), C.byref(x), C.byref(p))
+    return rc, p
+
+
+LN_FIELDS = dict(ln_gamma=40960, ln_beta=45056, resid=0)
+PA_FIELDS = dict(pa_P=40960, pa_Q=45056, T=64)
+AS_QKV = dict(mode=1, q=24576, k=28672, vt=32768, C=0, resid=0, T=40, H=1, dh=32, M=160)
+GEMM_AS_REFUSALS = [
+    # what the tile entry refuses too
+    (dict(dtA=5), ("unknown dtype", "dtA=5")), (dict(op=5), ("unknown op=5",)), (dict(act=3), ("unknown act=3",)), (dict(dact=3), ("unknown dact=3",)),
+    (dict(mode=2), ("unknown mode=2",)), (dict(head_major=2), ("head_major=2",)), (dict(rowscale_bias=2), ("rowscale_bias=2",)), (dict(drop_rate=1.0), ("drop_rate",)),
+    (dict(A=0), ("null A",)), (dict(Bt=0), ("null Bt",)), (dict(C=0), ("null C",)), (dict(Bt=8200), ("misaligned Bt",)), (dict(A=4104), ("gemm_nt: A rows must be 16-byte aligned",)),
+    (dict(addtab=40960, tab_period=0), ("tab_period=0",)), (dict(rowscale=40960, T=0), ("rowscale", "T=0")), (dict(dact=2), ("dact=2 without aux",)),
+    (dict(AS_QKV, q=0), ("QKV", "q, k, vt")), (dict(AS_QKV, M=170), ("QKV", "M=170")), (dict(AS_QKV, N=64, bt_rows=64), ("QKV", "N=64")),
+    (dict(AS_QKV, T=20), ("gemm_nt: QKV split needs T, dh multiples of 8",)), (dict(M=0), ("gemm_nt: bad shape",)),
+    # the weight shadow of this family
+    (dict(bt_rows=95), ("bt_rows=95", "N=96")), (dict(bt_rows=0), ("bt_rows=0",)), (dict(ldb=192), ("ldb=192", "K=256")), (dict(ldb=288), ("ldb=288", "multiple of 64")),
+    # outputs and side operands: 16 bytes
+    (dict(C=12296), ("misaligned C", "16-byte")), (dict(resid=20488), ("misaligned resid", "16-byte")), (dict(pre_out=40968), ("misaligned pre_out",)),
+    (dict(dact=2, aux=40968, resid=0), ("misaligned aux",)), (dict(addtab=40964, resid=0), ("misaligned addtab", "16-byte")), (dict(AS_QKV, q=24584), ("misaligned q",)),
+    (dict(AS_QKV, k=28680), ("misaligned k",)), (dict(AS_QKV, vt=32769), ("misaligned vt",)), (dict(LN_FIELDS, pro_out=49160), ("misaligned pro_out", "16-byte")),
+    (dict(bias=16386), ("misaligned bias", "4-byte")), (dict(LN_FIELDS, ln_gamma=40962), ("misaligned ln_gamma",)), (dict(LN_FIELDS, ln_mean=49154, ln_rstd=53248), ("misaligned ln_mean",)),
+    (dict(PA_FIELDS, pa_Q=45058), ("misaligned pa_Q",)),
+    # the ext's own fields
+    (dict(as_flags=-2), ("as_flags=-2",)), (dict(as_flags=512), ("as_flags=512",)),
+    (dict(LN_FIELDS, pa_P=49152, pa_Q=53248), ("ln_gamma and pa_P",)), (dict(ln_gamma=40960, resid=0), ("ln_gamma and ln_beta",)), (dict(pa_Q=45056), ("pa_P and pa_Q",)),
+    (dict(LN_FIELDS, ln_mean=49152), ("ln_mean and ln_rstd",)), (dict(ln_mean=49152, ln_rstd=53248), ("ln_mean / ln_rstd without ln_gamma",)),
+    (dict(pro_out=49152), ("pro_out without a prologue",)), (dict(LN_FIELDS, ln_eps=-1.0), ("ln_eps",)), (dict(LN_FIELDS, ln_eps=float("nan")), ("ln_eps",)),
+    # a prologue run_as has no instantiation for: the epilogue mask, the C type, K
+    (dict(LN_FIELDS, resid=20480), ("ln_gamma", "LayerNorm", "mask 1", "no instantiation")), (dict(LN_FIELDS, act=2), ("ln_gamma", "mask 4")),
+    (dict(PA_FIELDS, resid=0), ("pa_P", "affine", "mask 0", "no instantiation")), (dict(PA_FIELDS, act=2), ("pa_P", "mask 5")),
+    (dict(LN_FIELDS, dtC=F32), ("ln_gamma", "dtC=0", "no instantiation")), (dict(LN_FIELDS, dtA=F16, dtM=F16, dtC=F32), ("ln_gamma", "dtC=0")),
+    (dict(LN_FIELDS, dtA=F16, dtM=F16, dtC=F16, resid=20480), ("ln_gamma", "mask 1")), (dict(LN_FIELDS, K=128, ldb=128), ("ln_gamma", "K=128")),
+    # pa_P: a workgroup's rows inside one sample
+    (dict(PA_FIELDS, T=0), ("pa_P", "T=0")), (dict(PA_FIELDS, T=96), ("pa_P", "T=96", "64 rows per workgroup")), (dict(PA_FIELDS, T=64, M=1600), ("pa_P", "T=64", "128 rows per workgroup")),
+    (dict(PA_FIELDS, T=128, M=33000, K=512, ldb=512), ("pa_P", "T=128", "192 rows per workgroup")), (dict(PA_FIELDS, dtA=F16, dtM=F16, dtC=F16, T=96), ("pa_P", "T=96")),
+    # the narrow output
+    (dict(ldc=-8), ("ldc=-8",)), (dict(ldc=88, resid=0), ("ldc=88", "columns a row stores")), (dict(ldc=100, resid=0), ("ldc=100", "16-byte")), (dict(dtC=F32, ldc=98, resid=0), ("ldc=98", "16-byte")),
+    (dict(n_valid=-8), ("n_valid=-8",)), (dict(n_valid=104, resid=0), ("n_valid=104", "N=96")), (dict(n_valid=60, resid=0), ("n_valid=60", "store group", "8 columns")),
+    (dict(dtC=F32, n_valid=62, resid=0), ("n_valid=62", "4 columns")), (dict(n_valid=56, ldc=48, resid=0), ("ldc=48",)),
+    (dict(n_valid=88), ("n_valid=88", "resid")), (dict(ldc=104), ("ldc=104", "resid")), (dict(ldc=104, resid=0, dact=2, aux=40960), ("ldc=104", "aux")),
+    (dict(AS_QKV, n_valid=88), ("n_valid=88", "QKV")),
+    # calls that land on another kernel: by the route's name
+    (dict(K=64, ldb=64), ("route NT_TILE_T", "only the A-stationary kernels")), (dict(N=98, bt_rows=98), ("route NT_GLDS", "only the A-stationary kernels")),
+    (dict(N=1056, bt_rows=1056, resid=0), ("route NT_TILE_T",)), (dict(M=49536, N=256, K=512, bt_rows=256, ldb=512, as_flags=115), ("route NT_CS", "bits 6 / 7")),
+    (dict(M=32768, N=512, K=512, bt_rows=512, ldb=512), ("route NT_BIG",)), (dict(dtA=F32, dtM=F32, dtC=F32), ("route NT_TILE_T",)),
+    (dict(dtA=F16, dtM=F16, dtC=F16, K=128, ldb=128), ("route NT_REG",)), (dict(op=1), ("route NT_REG",)), (dict(dtA=F32), ("route NT_REG",)),
+]
+
+
+@pytest.mark.parametrize("kw,words", GEMM_AS_REFUSALS)
+def test_gemm_as_refuses_fields_prologues_and_other_routes(lib, kw, words):
+    _refused(lib, _gemm_as(lib, **kw), "ishara_op_gemm_as", *words)
+    rc, p = _gemm_as_plan(lib, **kw)
+    assert (rc, p.route, p.kernel) == (0, b"NT_REFUSED", b"")
+    assert (p.rows, p.gx, p.gy, p.nsteps, p.ring, p.cs, p.waves, p.passes, tuple(p.pass_rows), p.chunked, p.hold, p.inst_mask, p.prologue) == (0,) * 8 + ((0, 0),) + (0,) * 4
+    _refused(lib, -1, "ishara_debug_gemm_as_plan", *words)
+
+
+def test_gemm_as_null_arguments_and_accepted_calls(lib):
+    k, x = _gemm_as_call()
+    p = _lib.GemmAsPlan()
+    _refused(lib, lib.ishara_op_gemm_as(None, C.byref(x), N), "ishara_op_gemm_as", "null call")
+    _refused(lib, lib.ishara_op_gemm_as(C.byref(k), None, N), "ishara_op_gemm_as", "null ext")
+    for args in ((None, C.byref(x), C.byref(p)), (C.byref(k), None, C.byref(p)), (C.byref(k), C.byref(x), None)):
+        _refused(lib, lib.ishara_debug_gemm_as_plan(*args), "ishara_debug_gemm_as_plan", "null")
+
+    def plan(**kw):
+        rc, p = _gemm_as_plan(lib, **kw)
+        assert rc == 0, lib.ishara_last_error()
+        return p.route, p.kernel, p.rows, p.gx, p.gy, p.nsteps, p.inst_mask, p.prologue
+
+    # what the refusal rows vary, unvaried, is taken: each row is refused for its own field
+    assert plan() == (b"NT_AS", b"gemm_nt_as_kernel<bf16,8,1,0>", 64, 4, 1, 3, 1, 0)
+    assert plan(**LN_FIELDS) == (b"NT_AS", b"gemm_nt_as_kernel<bf16,8,0,0,1>", 64, 4, 1, 3, 0, 1)
+    assert plan(**LN_FIELDS, ln_mean=49152, ln_rstd=53248, pro_out=57344)[0] == b"NT_AS"
+    assert plan(**PA_FIELDS) == (b"NT_AS", b"gemm_nt_as_kernel<bf16,8,1,0,2>", 64, 4, 1, 3, 1, 2)
+    assert plan(**PA_FIELDS, dtA=F16, dtM=F16, dtC=F16) == (b"NT_AS_F16", b"gemm_nt_kernel<f16>", 64, 4, 1, 3, 1, 2)
+    assert plan(**AS_QKV)[:2] == (b"NT_AS", b"gemm_nt_as_kernel<bf16,8,64,0>")
+    assert plan(**dict(AS_QKV, vt=32770))[0] == b"NT_AS"                                 # vt takes single elements
+    assert plan(dtC=F32, n_valid=60, ldc=60, resid=0, N=64, bt_rows=64)[:2] == (b"NT_AS", b"gemm_nt_as_kernel<f32,8,0,0>")      # the classifier's call
+    assert plan(n_valid=56, ldc=72, resid=0, N=64, bt_rows=64)[0] == b"NT_AS"
+    assert plan(ldb=320)[0] == b"NT_AS" and plan(bt_rows=4096)[0] == b"NT_AS"
+    assert plan(as_flags=-1)[0] == b"NT_AS"
+    assert plan(M=49536, N=256, K=512, bt_rows=256, ldb=512)[:3] == (b"NT_AS", b"gemm_nt_as_chunk_kernel<bf16,16,1,0>", 384)      # without bits 6 / 7
+    try:      # a forced tile kernel takes the call away from the family, as it does in the launcher
+        lib.ishara_debug_force_regstage(8192)
+        _refused(lib, _gemm_as(lib), "ishara_op_gemm_as", "route NT_TILE_T")
     finally:
         lib.ishara_debug_force_regstage(0)

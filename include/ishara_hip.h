@@ -525,6 +525,65 @@ int ishara_mbr_select(const int32_t* hyp_idx, const int32_t* hyp_len, const floa
                       int32_t B, int32_t N, int32_t T, int32_t C, int32_t mode, int32_t* out_idx, int32_t* out_len, int32_t* best,
                       float* risk, float* w_out, int32_t* dist, int32_t* status, ishara_stream s);
 
+/* Second-pass n-best rescoring, part 1: the exact CTC log-likelihood of every hypothesis of every clip under one model; the semantics of
+ * ishara_amd/rescore.py (ctc_logp_reference).  out_score of the beam search sums only the alignments that survived the beam; this is the
+ * whole sum, logp[b,n] = log sum_alignments prod_t softmax(logits[b,t])[path_t], with tf.nn.ctc_loss semantics as in ishara_ctc_loss.
+ *   logits [B,T,C] fp32; hyp_idx [B,N,Th] int32 / hyp_len [B,N] int32 as the beam search and mbr.pool_nbest write them (padded with -1, a slot
+ *   is live iff hyp_len >= 0; only the first hyp_len symbols of a live row are read).  Th is the width of the hypothesis rows and need not
+ *   equal this model's T (a pooled list is padded to the longest).  frame_len [B] int32 or NULL: the convention of ishara_greedy_decode_ex
+ *   (clip b has Tb = frame_len[b] frames, a value outside [1, T] means no frames, rows t >= Tb are never read and may hold NaN).
+ * -> logp [B,N] fp32 and status [B,N] int32 (may be NULL).  The empty hypothesis (len 0, the all-blank path) is a hypothesis like any
+ *   other and gets its score.  logp is -inf, with exactly one status bit, the first that applies, for:
+ *     bit 0 (1)  a dead slot;
+ *     bit 3 (8)  hyp_len > Th or hyp_len > 255 (the loss kernel's label limit); the row is not read;
+ *     bit 2 (4)  a symbol outside [0, C) or equal to blank among the first hyp_len; it is never used as an index;
+ *     bit 1 (2)  no alignment: Tb < len + repeats (repeats = the positions whose symbol equals its predecessor), or the clip has no frames.
+ *   Every other slot has status 0 and its logp is bit-identical to a launch without the offending slots.
+ * Numerics: the alpha recursion of the loss kernel and nothing else (lse[t] as that kernel computes it, emissions raw - lse, fp64 state with
+ *   fp32 exp / log, the final log-sum over the last two lattice states): for every slot with status 0, logp[b,n] == (float)(-nll), bit for
+ *   bit, nll being ishara_ctc_loss_ex's on that clip with that hypothesis, padded with blank, as its label row and the same frame_len.
+ * One kernel: a workgroup per (clip, group of slots) computes the clip's lse[t] once into LDS, then each wave runs the chains of its slots
+ *   with the lattice states in registers.  No lattice in memory, no workspace, no atomics; graph-capturable, bit-identical from run to
+ *   run.  Refused with a message before any HIP call: C outside 2..64, T or Th outside 1..4096, N outside 1..64, blank outside [0, C),
+ *   B < 0 or B > 65535 (B == 0: nothing is launched), a null logits, hyp_idx, hyp_len or logp, a pointer that is not 4-byte aligned. */
+int ishara_ctc_score_nbest(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank,
+                           const int32_t* hyp_idx, const int32_t* hyp_len, int32_t N, int32_t Th,
+                           const int32_t* frame_len /* may be NULL */, float* logp, int32_t* status /* may be NULL */, ishara_stream s);
+/* tests / tools: the slots one wave of that kernel scores one after the other (1..16; a workgroup of four waves takes four times as many
+ * slots of one clip and computes its lse once); 0 = the library default.  The results do not depend on it. */
+int ishara_debug_set_score_group(int32_t hyps_per_wave);
+/* Second-pass n-best rescoring, part 2: combine, dedupe, rerank; the semantics of ishara_amd/rescore.py (rescore_reference).
+ *   hyp_idx [B,N,Th] / hyp_len [B,N] as above (the length is clamped to Th).  logp: a HOST array of M device pointers, each [B,N] fp32 (the
+ *   logp of ishara_ctc_score_nbest under model m); the launcher copies them into the kernel's arguments by value (no pointer table, no
+ *   allocation).  weights: device fp32 [M], read at every launch.  lm_logp [S,C] fp32 / lm_next [S,C] int32 / S / start_state: an LM
+ *   automaton with the contract of ishara_ctc_beam_decode_lm (an lm_next value outside [0, S) reads as state 0), or both tables NULL for no
+ *   LM (S, start_state, C and blank are then not looked at).  alpha (LM weight) and beta (bonus per symbol) by value, finite.  inv_temp:
+ *   ONE float on the device (1 / temperature) or NULL for 1.0, read at every launch.
+ * Duplicates: a live slot j dies when a live slot i < j holds the same string (same length, same symbols); the earlier slot stays.
+ * Score of a live slot, every step a single round-to-nearest fp32 operation without FMA contraction, in this order: s = +0; for m ascending
+ *   with weights[m] > 0: s = s + weights[m] * logp_m[b,n] (a model whose weight is not > 0 is not read: its array may hold NaN).  With an
+ *   LM: l = +0, state = start_state; for each symbol c in order l = l + lm_logp[state][c], state = lm_next[state][c]; then
+ *   l = l + lm_logp[state][blank]; then s = s + alpha * l (a symbol outside [0, C) is never an index: the slot's score is -inf).  Finally
+ *   s = s + beta * (float)len.  A -inf from a participating model gives -inf: the slot stays live and ranks after every finite score.
+ * Order: live slots whose score is a number by descending score, ties to the lower input slot; then live slots whose score is NaN, in
+ *   input order (a NaN never outranks a number); then the dead slots (dead on input or merged), in input order.
+ * Posterior over the live slots with a finite score: x = (s - s_max) * inv_temp (one subtraction, one multiplication), e = expf(x),
+ *   p = e / sum e, the sum taken in ascending output order from +0; p = +0 for every other slot, and everywhere when no score is finite.
+ * -> out_idx [B,N,Th], out_len [B,N], out_score [B,N]: the beam search's layout in the new order (a dead slot has len -1, score -inf and a
+ *   row of -1; every element is written), so ishara_mbr_select, ishara_edit_distance and ishara_edit_alignment take the result as it is;
+ *   posterior [B,N] fp32 or NULL (by output slot: usable as ishara_mbr_select's weights); perm [B,N] int32 or NULL: the input slot of each
+ *   output slot.
+ * One kernel (one workgroup per clip), no workspace, no atomics, graph-capturable, bit-identical from run to run.  Refused with a message
+ *   before any HIP call: N outside 1..64, Th outside 1..4096, M outside 1..8, B < 0 (B == 0: nothing is launched), alpha or beta not
+ *   finite; with an LM C outside 2..64, blank outside [0, C), S outside 1..2^22, start_state outside [0, S), one table without the other, a
+ *   table that is not 16-byte aligned; a null hyp_idx, hyp_len, logp, logp[m], weights, out_idx, out_len or out_score; a pointer that is
+ *   not 4-byte aligned; an output that overlaps hyp_idx, hyp_len or a logp[m]. */
+int ishara_nbest_rescore(const int32_t* hyp_idx, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Th,
+                         const float* const* logp, int32_t M, const float* weights,
+                         const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state, int32_t C, int32_t blank,
+                         float alpha, float beta, const float* inv_temp,
+                         int32_t* out_idx, int32_t* out_len, float* out_score, float* posterior, int32_t* perm, ishara_stream s);
+
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */
 typedef struct ishara_clip_aug {

@@ -15,3 +15,5 @@ from .ctc import ctc_beam_decode, ctc_greedy_decode, ctc_loss  # noqa: F401  (CT
 from .score import edit_alignment_device  # noqa: F401  (edit-operation alignment of device decodes: ops, positions, confusion matrix)
 from .ensemble import EnsembleTFLiteModel, combine_logits, combine_reference, normalise_weights  # noqa: F401  (model ensembling: device logit fusion)
 from .mbr import mbr_reference, mbr_select, pool_nbest  # noqa: F401  (minimum-Bayes-risk decoding over the beam's n-best)
+from .rescore import (ctc_logp_reference, ctc_score_nbest, rescore_models, rescore_nbest,  # noqa: F401  (second-pass n-best rescoring:
+                      rescore_reference)                                                   # exact CTC scores, LM, rerank)

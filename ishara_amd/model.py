@@ -1037,6 +1037,40 @@ class Model(Handle):
         return [(idx[b, :ln[b]].astype(np.int64), int(best[b]), float(risk[b, best[b]]) if best[b] >= 0 else float("nan"))
                 for b in range(idx.shape[0])]
 
+    def rescore_decode(self, logits, beam_width: int = 16, nbest: int = 8, lm=None, alpha: float = 0.0, beta: float = 0.0, search_lm=None,
+                       frame_lengths=None, mbr: bool = False, temperature: float = 1.0) -> List[Tuple[np.ndarray, float, float]]:
+        """Two-pass decode (ishara_amd/rescore.py): the beam search with `search_lm` (or no LM; its alpha / beta are this call's), then, on
+        the device, the exact CTC log-likelihood of every hypothesis of the n-best and the rescoring logp + alpha * lm + beta * len with
+        `lm` (a CharNGramLM, an LMAutomaton or a [C, C] table).  -> per clip (indices int64, score, posterior): the top hypothesis of the
+        rescored list, or with mbr=True the minimum-Bayes-risk choice voted with the posterior.  A clip without a hypothesis gives
+        (empty, -inf, 0)."""
+        from . import ctc, rescore
+        from . import mbr as mbr_mod
+        logits = torch.as_tensor(logits).to(self.device, torch.float32).contiguous()
+        if logits.ndim != 3:
+            raise ValueError(f"logits must be [B, T, C], got {tuple(logits.shape)}")
+        mbr_mod.inverse_temperature(temperature)
+        lm = rescore.lm_to_device(lm, self.device)
+        if lm is not None and int(lm.logp.shape[1]) != logits.shape[2]:
+            raise ValueError(f"the lm has {int(lm.logp.shape[1])} classes, the logits {logits.shape[2]}")
+        idx, ln, _ = ctc.ctc_beam_nbest_device(logits, frame_lengths, beam_width, nbest, search_lm, alpha if search_lm is not None else 0.0, beta)
+        logp = rescore.ctc_score_nbest(logits, idx, ln, frame_lengths)
+        idx, ln, sc, det = rescore.rescore_nbest(idx, ln, logp, None, lm, alpha, beta, temperature, return_details=True)
+        post = det["posterior"]
+        if mbr:
+            best = mbr_mod.mbr_select(idx, ln, weights=post, mode=1, C=logits.shape[2])[2]
+        else:
+            best = torch.zeros(idx.shape[0], dtype=torch.int32, device=idx.device)
+        idx, ln, sc, post, best = idx.cpu().numpy(), ln.cpu().numpy(), sc.cpu().numpy(), post.cpu().numpy(), best.cpu().numpy()
+        out = []
+        for b in range(idx.shape[0]):
+            k = int(best[b])
+            if k < 0 or ln[b, k] < 0:
+                out.append((np.zeros(0, np.int64), float("-inf"), 0.0))
+            else:
+                out.append((idx[b, k, :ln[b, k]].astype(np.int64), float(sc[b, k]), float(post[b, k])))
+        return out
+
     def align(self, logits, y, frame_lengths=None) -> list:
         """CTC forced alignment (ishara_amd/ctc_align.py semantics, blank = C - 1) of logits [B, T, C] to the labels y [B, L] (padded with
         C - 1) on the device -> per clip an Alignment: the label index every frame emits, the log-probability of the best path and one

@@ -583,6 +583,45 @@ int ishara_nbest_rescore(const int32_t* hyp_idx, const int32_t* hyp_len, int32_t
                          const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state, int32_t C, int32_t blank,
                          float alpha, float beta, const float* inv_temp,
                          int32_t* out_idx, int32_t* out_len, float* out_score, float* posterior, int32_t* perm, ishara_stream s);
+/* The same with the rescoring parameters on the device: params fp32 [M + 2] = (w_0 .. w_{M-1}, alpha, beta), 4-byte aligned, read at every
+ * launch, so a captured graph follows a caller that rewrites them.  Every other argument, every output, every refusal (a null params in
+ * place of a null weights) and every bit of the arithmetic is ishara_nbest_rescore's: it is the same kernel, and fed the same numbers the
+ * two entries write identical bytes.  A non-finite alpha or beta cannot be refused here: the arithmetic proceeds as IEEE 754 says and a
+ * NaN score ranks where the order above puts NaN. */
+int ishara_nbest_rescore_p(const int32_t* hyp_idx, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Th,
+                           const float* const* logp, int32_t M, const float* params,
+                           const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state, int32_t C, int32_t blank,
+                           const float* inv_temp,
+                           int32_t* out_idx, int32_t* out_len, float* out_score, float* posterior, int32_t* perm, ishara_stream s);
+/* The weight sweep of the second pass; the semantics of ishara_amd/rescore.py (rescore_sweep_reference).  Row g of best and dist equals
+ * perm[:, 0] (-1 where out_len[:, 0] < 0) of ishara_nbest_rescore_p(params = grid[g]) on the same inputs, and ishara_edit_distance of its
+ * top row, integer for integer; one launch instead of 2 G.
+ *   hyp_idx, hyp_len, B, N, Th, logp (a HOST array of M device pointers), M, lm_logp, lm_next, S, start_state, C, blank: as
+ *   ishara_nbest_rescore, same limits and layouts.  targets [B,L] int32 padded with 59, 1 <= L <= 64: ishara_edit_distance's (the target
+ *   is the symbols before the first 59).  grid [G, M + 2] fp32 on the device, 1 <= G <= 65536, each row a params vector, read at every launch.
+ *   fallback 1: the wrapper's rule as in ishara_edit_distance: a hypothesis shorter than 3 symbols, and a clip without a live slot, is
+ *   scored as the constant phrase.  fallback 0: the hypothesis as it is; a clip without a live slot as the empty string (dist = tlen).
+ * Duplicates merge into their first slot and a merged slot never wins.  The float32 score of a live slot is ishara_nbest_rescore's, in its
+ *   order, without FMA contraction; a model whose weight is not > 0 takes no part (its array may hold NaN).  The top slot holds the largest
+ *   number, ties to the lower slot; -inf is a number and ranks last among them; when no live slot holds a number the top is the first live
+ *   (NaN) slot; when no slot is live it is -1.  Symbols are compared as integers, as ishara_edit_distance compares them.
+ * -> best [G,B] int32: the INPUT slot; dist [G,B] int32; tlen [B] int32; optional (NULL: not wanted) hyp_dist [B,N] int32: what dist would
+ *   hold if the slot won (after the fallback rule), -1 in dead or merged slots; lm_score [B,N] fp32: the LM walk's l (-inf for a slot with a
+ *   symbol outside [0, C)), +0 without an LM and in slots that are not live.  Every element of every output is written.
+ * One kernel: a workgroup per (clip, 256 grid rows) computes the clip's part once (merge, LM walks, lengths, the M scores, every slot's
+ *   distance by one 64-bit Myers word with the target as the pattern), then one wave per row.  ws: ishara_rescore_sweep_workspace_bytes
+ *   bytes (0 today: ws is not looked at; < 0: B, N or G unsupported).  No atomics, no host read, no allocation, graph-capturable,
+ *   bit-identical from run to run; B == 0 launches nothing.  Refused with a message before any HIP call: everything ishara_nbest_rescore
+ *   refuses about these arguments, G or L out of range, fallback not 0 or 1, a null targets, grid, best, dist or tlen, a pointer that is not
+ *   4-byte aligned, an output that overlaps hyp_idx, hyp_len, a logp[m], targets or grid. */
+int64_t ishara_rescore_sweep_workspace_bytes(int32_t B, int32_t N, int32_t G);
+int ishara_rescore_sweep(const int32_t* hyp_idx, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Th,
+                         const float* const* logp, int32_t M,
+                         const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state, int32_t C, int32_t blank,
+                         const int32_t* targets, int32_t L, int32_t fallback,
+                         const float* grid, int32_t G,
+                         int32_t* best, int32_t* dist, int32_t* tlen, int32_t* hyp_dist, float* lm_score,
+                         void* ws, ishara_stream s);
 
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */

@@ -195,6 +195,10 @@ SIGNATURES = {
     "ishara_ctc_score_nbest": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "ishara_debug_set_score_group": (C.c_int, [_I32]),
     "ishara_nbest_rescore": (C.c_int, [_P, _P, _I32, _I32, _I32, C.POINTER(_P), _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "ishara_nbest_rescore_p": (C.c_int, [_P, _P, _I32, _I32, _I32, C.POINTER(_P), _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "ishara_rescore_sweep_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "ishara_rescore_sweep": (C.c_int, [_P, _P, _I32, _I32, _I32, C.POINTER(_P), _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P,
+                                       _P, _P, _P]),
     "ishara_clip_batch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "ishara_clip_batch_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "ishara_ctc_workspace_bytes": (_I64, [_I32, _I32, _I32]),

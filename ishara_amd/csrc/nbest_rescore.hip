@@ -14,20 +14,12 @@
 //               sum walked in ascending output order by every lane alike, one division.
 //   6. copy     all threads copy the rows in the new order; every element of every output is written.
 // The M model pointers travel in the kernel's arguments (logits_combine.hip's idiom); weights and inv_temp are read on the device at every
-// launch, so a captured graph follows a caller that rewrites them.
-#include "kernels.h"
+// launch, so a captured graph follows a caller that rewrites them.  ishara_nbest_rescore_p is the same kernel with alpha and beta read from
+// the device as well: params = (w_0 .. w_{M-1}, alpha, beta); the kernel's `weights` then points at params and `ab` behind the weights.
+#include "rescore_common.h"
 
 static constexpr int NR_WAVES = 4;
-static constexpr int NR_MAXN = 64;
-static constexpr int NR_MAX_M = 8;
 
-struct NrPtrs { const float* p[NR_MAX_M]; };
-
-DEVI float nr_madd(float s, float w, float v) {
-#pragma clang fp contract(off)
-    const float p = w * v;
-    return s + p;
-}
 DEVI float nr_x(float s, float smax, float it) {
 #pragma clang fp contract(off)
     const float d = s - smax;
@@ -38,7 +30,7 @@ __global__ __launch_bounds__(NR_WAVES * 64) void nbest_rescore_kernel(const int*
                                                                       NrPtrs logp, int M, const float* __restrict__ weights,
                                                                       const float* __restrict__ lm_logp, const int* __restrict__ lm_next, int S,
                                                                       int start_state, int C, int blank, float alpha, float beta,
-                                                                      const float* __restrict__ inv_temp, int* __restrict__ out_idx,
+                                                                      const float* __restrict__ ab, const float* __restrict__ inv_temp, int* __restrict__ out_idx,
                                                                       int* __restrict__ out_len, float* __restrict__ out_score,
                                                                       float* __restrict__ posterior, int* __restrict__ perm_out) {
     __shared__ int s_len[NR_MAXN];                      // clamped to Th; -1: dead (on input, or a duplicate after step 2)
@@ -47,6 +39,7 @@ __global__ __launch_bounds__(NR_WAVES * 64) void nbest_rescore_kernel(const int*
     __shared__ int s_olen[NR_MAXN];                     // the output slots' lengths
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int* __restrict__ hyp = hyp_idx + (size_t)b * N * Th;
+    if (ab) { alpha = ab[0]; beta = ab[1]; }            // the _p entry: the two numbers of this launch, read like the weights
 
     // ---- 1. lengths
     if (tid < NR_MAXN) {
@@ -141,21 +134,16 @@ __global__ __launch_bounds__(NR_WAVES * 64) void nbest_rescore_kernel(const int*
     }
 }
 
-static bool nr_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
-extern "C" int ishara_nbest_rescore(const int32_t* hyp_idx, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Th, const float* const* logp,
-                                    int32_t M, const float* weights, const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state,
-                                    int32_t C, int32_t blank, float alpha, float beta, const float* inv_temp, int32_t* out_idx, int32_t* out_len,
-                                    float* out_score, float* posterior, int32_t* perm, ishara_stream st) {
-    const char* me = "ishara_nbest_rescore";
+// both entries: `params` NULL is the by-value entry (weights, alpha, beta), otherwise weights / alpha / beta are not looked at
+static int nr_run(const char* me, const int32_t* hyp_idx, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Th, const float* const* logp, int32_t M,
+                  const float* weights, const float* params, const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state, int32_t C,
+                  int32_t blank, float alpha, float beta, const float* inv_temp, int32_t* out_idx, int32_t* out_len, float* out_score, float* posterior,
+                  int32_t* perm, ishara_stream st, bool by_value) {
     if (N < 1 || N > NR_MAXN) { ishara_set_error("%s: N=%d outside 1..%d (one lane per hypothesis)", me, N, NR_MAXN); return -1; }
     if (Th < 1 || Th > 4096) { ishara_set_error("%s: Th=%d outside 1..4096", me, Th); return -1; }
     if (M < 1 || M > NR_MAX_M) { ishara_set_error("%s: M=%d outside 1..%d (the models' pointers travel in the kernel's arguments)", me, M, NR_MAX_M); return -1; }
     if (B < 0) { ishara_set_error("%s: B=%d < 0", me, B); return -1; }
-    if (!(alpha == alpha && beta == beta) || alpha - alpha != 0.0f || beta - beta != 0.0f) { ishara_set_error("%s: alpha and beta must be finite", me); return -1; }
+    if (by_value && (!(alpha == alpha && beta == beta) || alpha - alpha != 0.0f || beta - beta != 0.0f)) { ishara_set_error("%s: alpha and beta must be finite", me); return -1; }
     const bool with_lm = lm_logp || lm_next;
     if (with_lm) {
         if (C < 2 || C > 64) { ishara_set_error("%s: C=%d outside 2..64", me, C); return -1; }
@@ -170,7 +158,9 @@ extern "C" int ishara_nbest_rescore(const int32_t* hyp_idx, const int32_t* hyp_l
     if (!logp) { ishara_set_error("%s: null logp", me); return -1; }
     for (int m = 0; m < M; ++m)
         if (!logp[m]) { ishara_set_error("%s: null logp[%d]", me, m); return -1; }
-    if (!weights) { ishara_set_error("%s: null weights", me); return -1; }
+    if (by_value && !weights) { ishara_set_error("%s: null weights", me); return -1; }
+    if (!by_value && !params) { ishara_set_error("%s: null params", me); return -1; }
+    if (!by_value) weights = params;
     if (!out_idx || !out_len || !out_score) { ishara_set_error("%s: null out_idx / out_len / out_score (posterior and perm may be NULL)", me); return -1; }
     uintptr_t bits = (uintptr_t)hyp_idx | (uintptr_t)hyp_len | (uintptr_t)weights | (uintptr_t)inv_temp | (uintptr_t)out_idx | (uintptr_t)out_len |
                      (uintptr_t)out_score | (uintptr_t)posterior | (uintptr_t)perm;
@@ -189,6 +179,23 @@ extern "C" int ishara_nbest_rescore(const int32_t* hyp_idx, const int32_t* hyp_l
     NrPtrs in;
     for (int m = 0; m < NR_MAX_M; ++m) in.p[m] = m < M ? logp[m] : nullptr;
     hipLaunchKernelGGL(nbest_rescore_kernel, dim3((unsigned)B), dim3(NR_WAVES * 64), 0, (hipStream_t)st, hyp_idx, hyp_len, N, Th, in, M, weights,
-                       lm_logp, lm_next, S, start_state, C, blank, alpha, beta, inv_temp, out_idx, out_len, out_score, posterior, perm);
+                       lm_logp, lm_next, S, start_state, C, blank, alpha, beta, by_value ? (const float*)nullptr : params + M, inv_temp, out_idx, out_len, out_score,
+                       posterior, perm);
     return launch_rc();
+}
+
+extern "C" int ishara_nbest_rescore(const int32_t* hyp_idx, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Th, const float* const* logp,
+                                    int32_t M, const float* weights, const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state,
+                                    int32_t C, int32_t blank, float alpha, float beta, const float* inv_temp, int32_t* out_idx, int32_t* out_len,
+                                    float* out_score, float* posterior, int32_t* perm, ishara_stream st) {
+    return nr_run("ishara_nbest_rescore", hyp_idx, hyp_len, B, N, Th, logp, M, weights, nullptr, lm_logp, lm_next, S, start_state, C, blank, alpha, beta,
+                  inv_temp, out_idx, out_len, out_score, posterior, perm, st, true);
+}
+
+extern "C" int ishara_nbest_rescore_p(const int32_t* hyp_idx, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Th, const float* const* logp,
+                                      int32_t M, const float* params, const float* lm_logp, const int32_t* lm_next, int32_t S, int32_t start_state,
+                                      int32_t C, int32_t blank, const float* inv_temp, int32_t* out_idx, int32_t* out_len, float* out_score,
+                                      float* posterior, int32_t* perm, ishara_stream st) {
+    return nr_run("ishara_nbest_rescore_p", hyp_idx, hyp_len, B, N, Th, logp, M, nullptr, params, lm_logp, lm_next, S, start_state, C, blank, 0.f, 0.f,
+                  inv_temp, out_idx, out_len, out_score, posterior, perm, st, false);
 }

@@ -169,7 +169,10 @@ class EnsembleTFLiteModel(BatchedTFLiteModel):
 
     def __init__(self, models, weights=None, mode: str = "log_linear", temperatures=None, stats: Optional[Dict[str, tuple]] = None,
                  batch_size: int = 64, max_frames: int = 1024, use_graph: bool = True, beam_width: int = 0, lm=None, lm_alpha: float = 0.0,
-                 lm_beta: float = 0.0, mbr_nbest: int = 0, mbr_temperature: float = 1.0, mbr_normalise: bool = True):
+                 lm_beta: float = 0.0, mbr_nbest: int = 0, mbr_temperature: float = 1.0, mbr_normalise: bool = True, rescore_nbest: int = 0,
+                 rescore_lm=None, rescore_alpha: float = 0.0, rescore_beta: float = 0.0, rescore_temperature: float = 1.0):
+        """rescore_*: BatchedTFLiteModel's second pass, here on the FUSED rows: the exact scores are taken under the combined logits, one
+        "model" (M = 1); scoring every hypothesis under every member (rescore.rescore_models) is not wired into a wrapper."""
         models = list(models)
         M = len(models)
         if M < 1 or M > MAX_MODELS:
@@ -189,7 +192,9 @@ class EnsembleTFLiteModel(BatchedTFLiteModel):
         if len({m.device for m in models}) != 1:
             raise ValueError(f"the models of an ensemble must be on one device, got {[str(m.device) for m in models]}")
         super().__init__(models[0], stats=stats, batch_size=batch_size, max_frames=max_frames, use_graph=use_graph, beam_width=beam_width, lm=lm,
-                         lm_alpha=lm_alpha, lm_beta=lm_beta, mbr_nbest=mbr_nbest, mbr_temperature=mbr_temperature, mbr_normalise=mbr_normalise)
+                         lm_alpha=lm_alpha, lm_beta=lm_beta, mbr_nbest=mbr_nbest, mbr_temperature=mbr_temperature, mbr_normalise=mbr_normalise,
+                         rescore_nbest=rescore_nbest, rescore_lm=rescore_lm, rescore_alpha=rescore_alpha, rescore_beta=rescore_beta,
+                         rescore_temperature=rescore_temperature)
         self.models, self.mode = models, mode
         dev = self.model.device
         self._per_model = torch.zeros((M, batch_size, self.T, self.model.C), dtype=torch.float32, device=dev)

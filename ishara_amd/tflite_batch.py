@@ -31,6 +31,7 @@ from ._lib import stream as _stream
 from .evaluation import ErrorReport
 from .model import Model
 from .tflite_model import FALLBACK_PHRASE, N_COLS, PARTS, _beam_launch, _beam_setup, _mbr_launch, _mbr_setup, _set_mbr_temperature, refuse_frame_lengths
+from .tflite_model import _rescore_launch, _rescore_search, _rescore_setup, _set_rescore
 
 PAD_TOKEN_IDX = 59           # c1:5: the targets' padding; never a decoded index (the blank is C - 1 = 59)
 MAX_SCORE_LABEL_LEN = 64     # one wavefront lane per target symbol (ishara_edit_distance)
@@ -140,11 +141,15 @@ def normalized_scores(dist: np.ndarray, tlen: np.ndarray) -> Tuple[float, np.nda
 class BatchedTFLiteModel:
     def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, batch_size: int = 64, max_frames: int = 1024,
                  use_graph: bool = True, beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0, mbr_nbest: int = 0,
-                 mbr_temperature: float = 1.0, mbr_normalise: bool = True):
+                 mbr_temperature: float = 1.0, mbr_normalise: bool = True, rescore_nbest: int = 0, rescore_lm=None, rescore_alpha: float = 0.0,
+                 rescore_beta: float = 0.0, rescore_temperature: float = 1.0):
         """beam_width / lm / lm_alpha / lm_beta as for TFLiteModel: 0 keeps the greedy decode; > 0 captures the beam decoder (top-1) in
         its place, and predict_indices / __call__ / score() work on the beam's top-1.  mbr_nbest / mbr_temperature / mbr_normalise as for
         TFLiteModel: with mbr_nbest >= 2 the beam search keeps that many hypotheses, ishara_mbr_select follows it in the graph and writes
-        the indices and lengths the tail reads, so everything downstream works on the minimum-Bayes-risk choice."""
+        the indices and lengths the tail reads, so everything downstream works on the minimum-Bayes-risk choice.  rescore_nbest /
+        rescore_lm / rescore_alpha / rescore_beta / rescore_temperature as for TFLiteModel: with rescore_nbest >= 2 the exact scores and
+        ishara_nbest_rescore_p follow the beam search in the graph, and predict_indices / __call__ / score() / score(breakdown=True) work
+        on the rescored choice; set_rescore rewrites the parameters on the device and score_rescore_grid sweeps them in one launch."""
         if model.F != N_COLS:
             raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
         if batch_size < 1 or batch_size > model.max_batch:
@@ -181,6 +186,8 @@ class BatchedTFLiteModel:
         self._logits = torch.zeros((bs, T, model.C), dtype=torch.float32, device=dev)
         self._beam = _beam_setup(model, bs, beam_width, lm, lm_alpha, lm_beta)
         self._mbr = _mbr_setup(model, bs, self._beam, mbr_nbest, mbr_temperature, mbr_normalise)
+        self._rescore = _rescore_setup(model, bs, self._beam, self._mbr, rescore_nbest, rescore_lm, rescore_alpha, rescore_beta, rescore_temperature)
+        self._sweep = {}                         # score_rescore_grid's buffers by grid size, made on first use
         self._copy_stream = torch.cuda.Stream(device=dev)
         self._copied = [torch.cuda.Event() for _ in range(2)]
         self._consumed = [None, None]            # event after the replay that last read a device slot
@@ -237,6 +244,8 @@ class BatchedTFLiteModel:
         if self._beam is None:
             _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), bs, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), st),
                        "ishara_greedy_decode")
+        elif self._rescore is not None:
+            _rescore_launch(m, self._beam, self._rescore, self._mbr, self._logits, bs, self._idx, self._len, st)
         elif self._mbr is not None:
             _mbr_launch(m, self._beam, self._mbr, self._logits, bs, self._idx, self._len, st)
         else:
@@ -373,6 +382,73 @@ class BatchedTFLiteModel:
     def set_mbr_temperature(self, temperature: float) -> None:
         """1 / temperature written into the device float every replay reads (on the current stream; no new capture)."""
         _set_mbr_temperature(self._mbr, temperature)
+
+    def set_rescore(self, weight=None, alpha=None, beta=None, temperature=None) -> None:
+        """The second pass's parameters (the weight on the exact score, alpha, beta, the posterior's temperature; None: as it is) written
+        into the device floats every replay reads (on the current stream; no new capture)."""
+        _set_rescore(self._rescore, weight, alpha, beta, temperature)
+
+    def _sweep_buffers(self, G: int):
+        """grid fp32 [G, 3] on the device and best [G, bs] | dist [G, bs] | tlen [bs] as one int32 result buffer with its pinned copy"""
+        if G not in self._sweep:
+            bs, dev = self.batch_size, self.model.device
+            d = torch.zeros(2 * G * bs + bs, dtype=torch.int32, device=dev)
+            need = int(self.model._lib.ishara_rescore_sweep_workspace_bytes(bs, self._rescore.nbest, G))
+            if need < 0:
+                raise ValueError(f"ishara_rescore_sweep takes no batch_size={bs}, N={self._rescore.nbest}, G={G}")
+            ws_owner, ws = _lib.aligned(need, dev) if need else (None, None)
+            self._sweep[G] = dict(grid=torch.zeros((G, 3), dtype=torch.float32, device=dev), d=d, h=torch.empty(2 * G * bs + bs, dtype=torch.int32, pin_memory=True),
+                                  best=d[:G * bs].view(G, bs), dist=d[G * bs:2 * G * bs].view(G, bs), tlen=d[2 * G * bs:], ws_owner=ws_owner, ws=ws)
+        return self._sweep[G]
+
+    def _launch_sweep(self, slot: int, G: int):
+        """device slot `slot` -> logits -> the n-best and its exact scores -> one ishara_rescore_sweep over the object's grid buffer"""
+        from . import rescore
+        k, cfg, m, bs = self._sweep_buffers(G), self._rescore, self.model, self.batch_size
+        self._launch_logits(slot)
+        _rescore_search(m, self._beam, cfg, self._logits, bs, _stream())
+        _lib.check(m._lib.ishara_rescore_sweep(_lib.ptr(cfg.hyp_idx), _lib.ptr(cfg.hyp_len), bs, cfg.nbest, self.T, cfg.ptrs, 1,
+                                               _lib.ptr(cfg.lm.logp) if cfg.lm is not None else None, _lib.ptr(cfg.lm.next) if cfg.lm is not None else None,
+                                               cfg.lm.S if cfg.lm is not None else 0, cfg.lm.start if cfg.lm is not None else 0, m.C if cfg.lm is not None else 0,
+                                               cfg.eos, _lib.ptr(self._tgt(self._d_in[slot])), self.L, 1, _lib.ptr(k["grid"]), G, _lib.ptr(k["best"]),
+                                               _lib.ptr(k["dist"]), _lib.ptr(k["tlen"]), None, None, k["ws"], _stream()), "ishara_rescore_sweep")
+
+    def score_rescore_grid(self, clips, targets, grid, char_to_num: Optional[Dict[str, int]] = None) -> Dict[str, np.ndarray]:
+        """`score` under every row (weight, alpha, beta) of `grid` [G, 3] (rescore.sweep_grid([weights], alphas, betas)) with everything
+        run once: per batch ONE graph of preprocessing, forward, beam search, exact scores and one ishara_rescore_sweep, then one D2H copy.
+        Returns mean_scores [G], distances [G, n] and best [G, n] (the slot of the beam's n-best that tops the rescored list).  Row g equals
+        `set_rescore(*grid[g]); score(clips, targets)`; the object's own parameters are left as they were (they are not touched).  The
+        sweep covers the top-1 choice only: with mbr_nbest set, score() reports the minimum-Bayes-risk vote, which this does not follow."""
+        if self._rescore is None:
+            raise ValueError("score_rescore_grid: the wrapper was built without rescore_nbest")
+        grid = np.ascontiguousarray(grid, dtype=np.float32)
+        if grid.ndim != 2 or grid.shape[1] != 3 or not 1 <= grid.shape[0] <= 65536:
+            raise ValueError(f"grid must be [G, 3] rows of (weight, alpha, beta) with 1 <= G <= 65536, got {grid.shape}")
+        G = grid.shape[0]
+        enc = np.stack([encode_phrase(t, char_to_num, self.L) for t in targets]) if len(targets) else np.zeros((0, self.L), np.int32)
+        n_clips = (np.asarray(clips[1]).shape[0] - 1) if (isinstance(clips, tuple) and len(clips) == 2 and np.ndim(clips[1]) == 1) else len(clips)
+        if enc.shape[0] != n_clips:
+            raise ValueError(f"{enc.shape[0]} targets for {n_clips} clips")
+        k, bs = self._sweep_buffers(G), self.batch_size
+        k["grid"].copy_(torch.from_numpy(grid))
+        best, dist, tlen = [], [], []
+        for i, (fill, n) in enumerate(self._batches(clips)):
+            s = self._stage(i, fill, n, enc)
+            if self.use_graph:
+                self._captured(("sweep", s, G), lambda s=s: self._launch_sweep(s, G)).replay()
+            else:
+                self._launch_sweep(s, G)
+            self._mark_consumed(s)
+            k["h"].copy_(k["d"], non_blocking=True)
+            torch.cuda.current_stream().synchronize()          # the one host wait of a batch
+            r = k["h"].numpy()
+            best.append(r[:G * bs].reshape(G, bs)[:, :n].copy())
+            dist.append(r[G * bs:2 * G * bs].reshape(G, bs)[:, :n].copy())
+            tlen.append(r[2 * G * bs:2 * G * bs + n].copy())
+        d = np.concatenate(dist, axis=1).astype(np.int64) if dist else np.zeros((G, 0), np.int64)
+        bst = np.concatenate(best, axis=1).astype(np.int64) if best else np.zeros((G, 0), np.int64)
+        tl = np.concatenate(tlen) if tlen else np.zeros(0, np.int32)
+        return dict(mean_scores=np.array([normalized_scores(d[g], tl)[0] for g in range(G)], dtype=np.float64), distances=d, best=bst)
 
     def predict_indices(self, clips, frame_lengths=None) -> List[np.ndarray]:
         """The decode per clip (greedy, or the beam's top-1; before the len < 3 fallback): equal to `TFLiteModel.predict_indices` clip by clip."""

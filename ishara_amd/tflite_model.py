@@ -126,15 +126,112 @@ def _set_mbr_temperature(cfg: Optional[_MbrConfig], temperature: float) -> None:
     cfg.inv_temp.fill_(mbr.inverse_temperature(temperature))
 
 
+class _RescoreConfig:
+    """Device state of a wrapper's second pass (ishara_amd/rescore.py): the n-best buffers the beam search fills, the exact scores, the
+    rescored list, and params = (weight, alpha, beta) / 1 / temperature as the device floats every launch reads."""
+    def __init__(self, nbest, lm_dev, eos, values, params, inv_temp, batch, T, dev):
+        self.nbest, self.lm, self.eos, self.params, self.inv_temp = nbest, lm_dev, eos, params, inv_temp
+        self.hyp_idx = torch.full((batch, nbest, T), -1, dtype=torch.int32, device=dev)
+        self.hyp_len = torch.full((batch, nbest), -1, dtype=torch.int32, device=dev)
+        self.hyp_score = torch.zeros((batch, nbest), dtype=torch.float32, device=dev)
+        self.logp = torch.zeros((batch, nbest), dtype=torch.float32, device=dev)
+        self.out_idx = torch.full((batch, nbest, T), -1, dtype=torch.int32, device=dev)
+        self.out_len = torch.full((batch, nbest), -1, dtype=torch.int32, device=dev)
+        self.out_score = torch.zeros((batch, nbest), dtype=torch.float32, device=dev)
+        self.posterior = torch.zeros((batch, nbest), dtype=torch.float32, device=dev)
+        self.best = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.values = [float(v) for v in values]             # the host's copy of (weight, alpha, beta)
+        from . import rescore
+        self.ptrs = rescore.pointer_array([self.logp])
+
+
+def _rescore_setup(model: Model, batch: int, beam: Optional[_BeamConfig], mbr: Optional[_MbrConfig], rescore_nbest: int, lm, alpha: float, beta: float,
+                   temperature: float) -> Optional[_RescoreConfig]:
+    """None for rescore_nbest == 0 (nothing is allocated); else 2 <= rescore_nbest <= beam_width, equal to mbr_nbest when that is set, and
+    the buffers on the model's device."""
+    import math
+    from . import ctc_beam, rescore
+    from . import mbr as mbr_mod
+    if rescore_nbest == 0:
+        if lm is not None or float(alpha) != 0.0 or float(beta) != 0.0:
+            raise ValueError("rescore_lm / rescore_alpha / rescore_beta need rescore_nbest >= 2")
+        return None
+    if rescore_nbest < 2:
+        raise ValueError(f"rescore_nbest {rescore_nbest}: 0 (off) or at least 2 hypotheses to rerank")
+    if beam is None or beam.width < rescore_nbest:
+        raise ValueError(f"rescore_nbest {rescore_nbest} needs beam_width >= rescore_nbest, got beam_width {0 if beam is None else beam.width}")
+    if mbr is not None and mbr.nbest != rescore_nbest:
+        raise ValueError(f"mbr_nbest {mbr.nbest} must equal rescore_nbest {rescore_nbest}: the vote runs over the rescored list")
+    if rescore_nbest > rescore.MAX_NBEST:
+        raise ValueError(f"rescore_nbest {rescore_nbest} outside 2..{rescore.MAX_NBEST}")
+    if not (math.isfinite(float(alpha)) and math.isfinite(float(beta))):
+        raise ValueError("rescore_alpha and rescore_beta must be finite")
+    ctc_beam.check_device_args(model.C, model.T, beam.width, rescore_nbest)
+    dev = model.device
+    lm_dev = rescore.lm_to_device(lm, dev)
+    if lm_dev is not None and int(lm_dev.logp.shape[1]) != model.C:
+        raise ValueError(f"rescore_lm has {int(lm_dev.logp.shape[1])} classes, the model {model.C}")
+    values = [1.0, float(alpha), float(beta)]
+    params = torch.tensor(values, dtype=torch.float32, device=dev)
+    inv_temp = torch.full((1,), mbr_mod.inverse_temperature(temperature), dtype=torch.float32, device=dev)
+    return _RescoreConfig(int(rescore_nbest), lm_dev, model.C - 1, values, params, inv_temp, batch, model.T, dev)
+
+
+def _rescore_search(model: Model, beam: _BeamConfig, cfg: _RescoreConfig, logits, batch: int, stream) -> None:
+    """the n-best of the beam search into cfg's buffers and their exact CTC scores under `logits` into cfg.logp"""
+    from . import ctc_beam
+    ctc_beam.launch(model._lib, logits, batch, model.T, model.C, beam.width, cfg.nbest, beam.lm, beam.alpha, beam.beta, beam.ws, cfg.hyp_idx,
+                    cfg.hyp_len, cfg.hyp_score, stream)
+    _lib.check(model._lib.ishara_ctc_score_nbest(_lib.ptr(logits), batch, model.T, model.C, model.C - 1, _lib.ptr(cfg.hyp_idx), _lib.ptr(cfg.hyp_len),
+                                                 cfg.nbest, model.T, None, _lib.ptr(cfg.logp), None, stream), "ishara_ctc_score_nbest")
+
+
+def _rescore_launch(model: Model, beam: _BeamConfig, cfg: _RescoreConfig, mbr: Optional[_MbrConfig], logits, batch: int, idx, ln, stream) -> None:
+    """beam search (nbest = cfg.nbest), ishara_ctc_score_nbest on `logits`, ishara_nbest_rescore_p, then the top row (or, with mbr, the
+    ishara_mbr_select choice voted with the posterior) into idx [batch, T] / ln [batch], the layout ishara_greedy_decode writes."""
+    from . import mbr as mbr_mod
+    from . import rescore
+    _rescore_search(model, beam, cfg, logits, batch, stream)
+    rescore.launch_p(model._lib, cfg.hyp_idx, cfg.hyp_len, batch, cfg.nbest, model.T, cfg.ptrs, 1, cfg.params, cfg.lm, cfg.eos, cfg.inv_temp, cfg.out_idx,
+                     cfg.out_len, cfg.out_score, cfg.posterior, None, stream)
+    if mbr is not None:
+        mbr_mod.launch(model._lib, cfg.out_idx, cfg.out_len, None, cfg.posterior, None, batch, cfg.nbest, model.T, model.C, mbr.mode, idx, ln, cfg.best,
+                       None, None, None, None, stream)
+    else:                                        # the top row; a clip always has a live hypothesis (the empty one at least), the clamp is for the layout
+        idx.copy_(cfg.out_idx[:, 0])
+        torch.clamp(cfg.out_len[:, 0], min=0, out=ln)
+
+
+def _set_rescore(cfg: Optional[_RescoreConfig], weight, alpha, beta, temperature) -> None:
+    import math
+    from . import mbr
+    if cfg is None:
+        raise ValueError("set_rescore: the wrapper was built without rescore_nbest")
+    vals = [cfg.values[k] if v is None else float(v) for k, v in enumerate((weight, alpha, beta))]
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError("set_rescore: weight, alpha and beta must be finite")
+    it = None if temperature is None else mbr.inverse_temperature(temperature)
+    cfg.params.copy_(torch.tensor(vals, dtype=torch.float32))
+    cfg.values = vals
+    if it is not None:
+        cfg.inv_temp.fill_(it)
+
+
 class TFLiteModel:
     def __init__(self, model: Model, stats: Optional[Dict[str, tuple]] = None, max_frames: int = 1024, use_graph: bool = True,
                  beam_width: int = 0, lm=None, lm_alpha: float = 0.0, lm_beta: float = 0.0, mbr_nbest: int = 0, mbr_temperature: float = 1.0,
-                 mbr_normalise: bool = True):
+                 mbr_normalise: bool = True, rescore_nbest: int = 0, rescore_lm=None, rescore_alpha: float = 0.0, rescore_beta: float = 0.0,
+                 rescore_temperature: float = 1.0):
         """beam_width = 0: the reference's greedy decode (c8:4-12).  beam_width > 0: the CTC prefix beam search of ishara_amd/ctc_beam.py
         (top-1, optional LM weighted by lm_alpha, lm_beta per character: a table lm [C, C], or a CharNGramLM / LMAutomaton of ctc_lm.py,
         whose device tables are built here once) replaces it inside the same graph.  mbr_nbest >= 2 (needs beam_width >= mbr_nbest): the
         beam search keeps mbr_nbest hypotheses and ishara_mbr_select (ishara_amd/mbr.py) picks the one of smallest expected edit distance
-        under the votes exp((score - max) / mbr_temperature), normalised by the voter's length with mbr_normalise; 0 changes nothing."""
+        under the votes exp((score - max) / mbr_temperature), normalised by the voter's length with mbr_normalise; 0 changes nothing.
+        rescore_nbest >= 2 (needs beam_width >= rescore_nbest): the second pass of ishara_amd/rescore.py inside the same graph: the beam
+        search (with its own lm / lm_alpha / lm_beta) keeps rescore_nbest hypotheses, ishara_ctc_score_nbest scores them exactly on the
+        wrapper's logits, ishara_nbest_rescore_p reranks by logp + rescore_alpha * rescore_lm + rescore_beta * len, and the top row is
+        what everything downstream reads; with mbr_nbest == rescore_nbest the ishara_mbr_select vote, weighted by the posterior at
+        rescore_temperature, follows instead (Model.rescore_decode(mbr=True)).  0 allocates, launches and captures nothing new."""
         if model.F != N_COLS:
             raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
         self.model, self.max_frames, self.T = model, max_frames, model.T
@@ -151,6 +248,7 @@ class TFLiteModel:
         self._len = torch.zeros(1, dtype=torch.int32, device=dev)
         self._beam = _beam_setup(model, 1, beam_width, lm, lm_alpha, lm_beta)
         self._mbr = _mbr_setup(model, 1, self._beam, mbr_nbest, mbr_temperature, mbr_normalise)
+        self._rescore = _rescore_setup(model, 1, self._beam, self._mbr, rescore_nbest, rescore_lm, rescore_alpha, rescore_beta, rescore_temperature)
         self._graph = None
         if use_graph:
             self._capture()
@@ -163,6 +261,8 @@ class TFLiteModel:
         if self._beam is None:
             _lib.check(lib.ishara_greedy_decode(_lib.ptr(self._logits), 1, self.T, m.C, m.C - 1, _lib.ptr(self._idx), _lib.ptr(self._len), _stream()),
                        "ishara_greedy_decode")
+        elif self._rescore is not None:
+            _rescore_launch(m, self._beam, self._rescore, self._mbr, self._logits, 1, self._idx, self._len, _stream())
         elif self._mbr is not None:
             _mbr_launch(m, self._beam, self._mbr, self._logits, 1, self._idx, self._len, _stream())
         else:
@@ -171,6 +271,11 @@ class TFLiteModel:
     def set_mbr_temperature(self, temperature: float) -> None:
         """1 / temperature written into the device float every replay reads (on the current stream; no new capture)."""
         _set_mbr_temperature(self._mbr, temperature)
+
+    def set_rescore(self, weight=None, alpha=None, beta=None, temperature=None) -> None:
+        """The second pass's parameters written into the device floats every replay reads (on the current stream; no new capture): the
+        weight on the exact score (1 at construction), alpha, beta, the posterior's temperature; None leaves a value as it is."""
+        _set_rescore(self._rescore, weight, alpha, beta, temperature)
 
     def _capture(self):
         side = torch.cuda.Stream(device=self.model.device)

@@ -235,13 +235,16 @@ def pack_push(frames, finish, reset, sessions: int, max_push: int, offsets: np.n
 class StreamingTFLiteModel:
     def __init__(self, model, stats: Optional[Dict[str, tuple]] = None, sessions: int = 16, window: int = 1024, max_push: int = 64,
                  agree: int = 2, idle_frames: int = 15, min_active_frames: int = 8, use_graph: bool = True, beam_width: int = 0, lm=None,
-                 lm_alpha: float = 0.0, lm_beta: float = 0.0, mbr_nbest: int = 0):
+                 lm_alpha: float = 0.0, lm_beta: float = 0.0, mbr_nbest: int = 0, rescore_nbest: int = 0):
         """sessions: concurrent signers (one batch slot each); window: most frames of one phrase (a phrase that fills it is finalised);
         max_push: most new frames per session and tick; agree / idle_frames / min_active_frames: see the module text (untuned defaults);
-        beam_width / lm / lm_alpha / lm_beta as for BatchedTFLiteModel; mbr_nbest is refused (see below)."""
+        beam_width / lm / lm_alpha / lm_beta as for BatchedTFLiteModel; mbr_nbest and rescore_nbest are refused (see below)."""
         if mbr_nbest:
             raise ValueError("StreamingTFLiteModel: mbr_nbest is refused: the stable prefix is what successive decodes of ONE decoder agree on, and the "
                              "minimum-Bayes-risk choice may jump between hypotheses from tick to tick; use BatchedTFLiteModel(mbr_nbest=) on whole clips")
+        if rescore_nbest:
+            raise ValueError("StreamingTFLiteModel: rescore_nbest is refused: the stable prefix is what successive decodes of ONE decoder agree on, and the "
+                             "rescored top of an n-best list may jump between hypotheses from tick to tick; use BatchedTFLiteModel(rescore_nbest=) on whole clips")
         if model.F != N_COLS:
             raise ValueError(f"the TFLite wrapper feeds {N_COLS} columns (92 landmarks x 3); model has F={model.F}")
         if sessions < 1 or sessions > model.max_batch:

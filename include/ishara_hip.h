@@ -118,6 +118,16 @@ int ishara_forward_ex(ishara_model* m, const float* x, int32_t B, float* logits,
                       ishara_stream s);
 int ishara_loss_backward_ex(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale,
                             const int32_t* frame_len, ishara_stream s);
+/* The same backward pass with a second loss term, minimum-risk training over an n-best list: between the CTC kernel and the head one stage,
+ * ishara_ctc_nbest_grad's kernels on the model's own dlogits with accumulate = 1, grad_scale = risk_scale / B, frame_len = NULL (the risk
+ * term keeps logit_length = T as the CTC loss does) and the model's padded 16-bit copy as dlb, so the gradients are those of
+ * loss_scale * mean_b nll_b + risk_scale / B * sum_b sum_n coef[b,n] * nll(hyp[b,n]).  hyp_idx [B,N,Th], hyp_len [B,N], max_len, coef [B,N]
+ * and workspace as ishara_ctc_nbest_grad (T and C are the model's, blank = C - 1), with its refusals; frame_len as ishara_loss_backward_ex
+ * (NULL: the unmasked pass).  loss and nll keep their meaning: the CTC loss of the reference label.  Every other launch is
+ * ishara_loss_backward_ex's, with the same arguments. */
+int ishara_loss_backward_nbest(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale,
+                               const int32_t* frame_len /* may be NULL */, const int32_t* hyp_idx, const int32_t* hyp_len, int32_t N, int32_t Th,
+                               int32_t max_len, const float* coef, float risk_scale, void* workspace, ishara_stream s);
 /* frame lengths of a zero-padded batch x [B,T,F] f32 (device): out_len[b] (device int32 [B]) = 1 + the index of the last frame of clip b that
  * has any non-zero feature, 0 if there is none.  The prefix reading of Masking(0.0): an all-zero frame INSIDE a clip stays valid, where Keras
  * masks that frame too.  One workgroup per clip; B, T, F > 0. */
@@ -622,6 +632,62 @@ int ishara_rescore_sweep(const int32_t* hyp_idx, const int32_t* hyp_len, int32_t
                          const float* grid, int32_t G,
                          int32_t* best, int32_t* dist, int32_t* tlen, int32_t* hyp_dist, float* lm_score,
                          void* ws, ishara_stream s);
+/* Minimum-risk (MWER) training, part 1: the gradient of a weighted sum of n-best scores; the semantics of ishara_amd/mwer.py
+ * (mwer_reference).  For every clip b, frame t < Tb and class k
+ *     G[b,t,k] = grad_scale * acc,  acc = +0, then for n ascending over the participating slots
+ *                                   acc = acc + coef[b,n] * (softmax(logits[b,t])[k] - post_n[b,t,k]),
+ * post_n being the CTC class posterior of hypothesis n (exp(alpha + bsum - logp) summed over the lattice states that carry class k), so G is
+ * the gradient of grad_scale * sum_n coef[b,n] * nll_n with respect to the logits.  Every multiplication and addition is a single
+ * round-to-nearest fp32 operation without FMA contraction, in that order.
+ *   logits, hyp_idx [B,N,Th], hyp_len [B,N], frame_len (may be NULL): as ishara_ctc_score_nbest.  max_len, 1..255: the longest hypothesis
+ *   that takes part; it sizes the workspace, not Th (the beam search's rows have Th = T).  coef [B,N] fp32 on the device (the coef of
+ *   ishara_mwer_weights), grad_scale by value.
+ * Participation: a slot takes part iff ishara_ctc_score_nbest would give it status 0 and its length is <= max_len; a longer slot gets
+ *   status bit 3 (8); every other slot the same bits by the same first-that-applies rule.  A slot whose coef is +0 or -0 is skipped: it
+ *   contributes neither its posterior nor its softmax term, and when neither logp nor status is wanted its row is not read.  A clip without
+ *   a participating slot contributes acc = +0.
+ * -> dlogits [B,T,C] fp32: accumulate 0 writes G, and +0 in the rows t >= Tb; accumulate 1 writes dlogits + G by one fp32 addition and leaves
+ *   the rows t >= Tb as they are.  dlb (may be NULL): the bf16 copy of the FINAL dlogits rows, zero padded to 128 classes, [B*T, 64] packed
+ *   pairs: the layout the loss kernel writes for the classifier's MFMA operand.  logp [B,N] fp32 (may be NULL): ishara_ctc_score_nbest's
+ *   bits (-inf in a slot longer than max_len); status [B,N] int32 (may be NULL).
+ * Numerics: the recursions of the loss kernel (lse[t], emissions raw - lse, fp64 state with fp32 exp / log, the alpha wave, the beta wave
+ *   that stores bsum, the per-frame LDS scatter-add of the state posteriors).  With N = 1, coef = 1, accumulate = 0, dlogits and dlb equal
+ *   those of ishara_op_ctc_loss (ishara_ctc_loss_ex with frame_len) bit for bit, run on that hypothesis, padded with blank, as its label
+ *   row with the same grad_scale.
+ * Two kernels: grid (N, B) runs the two recursion waves of one slot and writes its fp64 alpha / bsum rows into the workspace (only the
+ *   ceil((2 len + 1) / 64) occupied registers, rows of 64 * ceil((2 max_len + 1) / 64) doubles); grid (ceil(T / 16), B) loops n ascending per
+ *   frame and writes dlogits / dlb.  No atomics on global memory, no dependence of a slot on its neighbours, bit-identical from run to run,
+ *   graph-capturable (no allocation, no memset node, no host read).  workspace: ishara_ctc_nbest_grad_workspace_bytes(B, T, N, max_len)
+ *   bytes (-1: an argument out of range), 16-byte aligned, needs no initialisation.
+ * Refused with a message before any HIP call: C outside 2..64, T or Th outside 1..4096, N outside 1..64, max_len outside 1..255, blank
+ *   outside [0, C), B < 0 or B > 65535 (B == 0: nothing is launched), accumulate not 0 or 1, a null logits, hyp_idx, hyp_len, coef, dlogits
+ *   or workspace, a pointer that is not 4-byte aligned (the workspace: 16), dlogits overlapping logits. */
+int64_t ishara_ctc_nbest_grad_workspace_bytes(int32_t B, int32_t T, int32_t N, int32_t max_len);
+int ishara_ctc_nbest_grad(const float* logits, int32_t B, int32_t T, int32_t C, int32_t blank,
+                          const int32_t* hyp_idx, const int32_t* hyp_len, int32_t N, int32_t Th, int32_t max_len,
+                          const int32_t* frame_len /* may be NULL */, const float* coef, float grad_scale,
+                          float* dlogits, int32_t accumulate, void* dlb /* may be NULL */, float* logp /* may be NULL */,
+                          int32_t* status /* may be NULL */, void* workspace, ishara_stream s);
+/* Minimum-risk training, part 2: the weights.  hyp_idx [B,N,Th] / hyp_len [B,N] as above (the length is clamped to Th); logp [B,N] fp32: the
+ * exact scores of ishara_ctc_score_nbest; status [B,N] int32 or NULL; targets [B,L] int32 padded with 59, 1 <= L <= 64
+ * (ishara_edit_distance's: the target is the symbols before the first 59); inv_temp: ONE float on the device or NULL for 1.0; mode 0: the
+ * plain distance, 1: divided by max(tlen, 1) (the normalisation of the reported metric).
+ * A slot is live iff hyp_len >= 0, its status is 0 (when given) and its logp is finite.  Duplicate strings are NOT merged: the prefix beam
+ *   search emits distinct prefixes; a pooled list goes through ishara_nbest_rescore first.
+ * -> every element of every output is written:
+ *   dist [B,N] int32  unit-cost Levenshtein distance to the target (one 64-bit Myers word, the target as the pattern, no fallback phrase),
+ *                     -1 in slots that are not live;
+ *   post [B,N] fp32   over the live slots x = (logp - max) * inv_temp, e = expf(x), p = e / sum e, the sum ascending from +0; +0 elsewhere;
+ *   risk [B] fp32     sum_n p_n * W_n ascending from +0, W_n = (float)dist (mode 1: / (float)max(tlen, 1)); NaN for a clip with no live slot;
+ *   coef [B,N] fp32   -inv_temp * (p_n * (W_n - risk)): the derivative of the risk with respect to nll_n; +0 in slots that are not live;
+ *   tlen [B] int32.
+ *   All arithmetic is fp32, one rounding per operation, no FMA contraction, in the stated order.
+ * One kernel, one wave per clip, no workspace, no atomics, graph-capturable, bit-identical from run to run.  Refused with a message before
+ *   any HIP call: N outside 1..64, Th outside 1..4096, L outside 1..64, mode not 0 or 1, B < 0 (B == 0: nothing is launched), a null
+ *   hyp_idx, hyp_len, logp, targets or output, a pointer that is not 4-byte aligned. */
+int ishara_mwer_weights(const int32_t* hyp_idx, const int32_t* hyp_len, const float* logp, const int32_t* status /* may be NULL */,
+                        int32_t B, int32_t N, int32_t Th, const int32_t* targets, int32_t L, const float* inv_temp /* may be NULL */,
+                        int32_t mode, int32_t* dist, float* post, float* risk, float* coef, int32_t* tlen, ishara_stream s);
 
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */

@@ -18,3 +18,4 @@ from .mbr import mbr_reference, mbr_select, pool_nbest  # noqa: F401  (minimum-B
 from .rescore import (ctc_logp_reference, ctc_score_nbest, rescore_models, rescore_nbest,  # noqa: F401  (second-pass n-best rescoring:
                       rescore_reference)                                                   # exact CTC scores, LM, rerank)
 from .rescore import rescore_sweep, rescore_sweep_reference, sweep_grid, sweep_scores  # noqa: F401  (its weight sweep on the device)
+from .mwer import ctc_nbest_grad, mwer_loss, mwer_reference, mwer_weights  # noqa: F401  (minimum-risk training over the beam's n-best)

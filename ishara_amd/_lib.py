@@ -199,6 +199,10 @@ SIGNATURES = {
     "ishara_rescore_sweep_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "ishara_rescore_sweep": (C.c_int, [_P, _P, _I32, _I32, _I32, C.POINTER(_P), _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P,
                                        _P, _P, _P]),
+    "ishara_ctc_nbest_grad_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "ishara_ctc_nbest_grad": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _F, _P, _I32, _P, _P, _P, _P, _P]),
+    "ishara_mwer_weights": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "ishara_loss_backward_nbest": (C.c_int, [_P, _P, _P, _I32, _P, _P, _F, _P, _P, _P, _I32, _I32, _I32, _P, _F, _P, _P]),
     "ishara_clip_batch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "ishara_clip_batch_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "ishara_ctc_workspace_bytes": (_I64, [_I32, _I32, _I32]),

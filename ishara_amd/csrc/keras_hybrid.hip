@@ -331,7 +331,11 @@ bool frame_len_agrees(const char* fn, bool fwd_had, const int32_t* frame_len) {
     ishara_set_error("%s: the training forward was %s frame lengths, this call is %s", fn, fwd_had ? "given" : "not given", frame_len ? "given some" : "given none");
     return false;
 }
-static int keras_loss_backward(const char* fn, ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, const int32_t* frame_len, ishara_stream st) {
+// A second loss term between the CTC kernel and the head: the gradient of risk_scale / B * sum_n coef[b, n] * nll_n over an n-best list, added
+// into m->dlogits (and m->dlb rewritten from the sum) by ishara_ctc_nbest_grad's kernels.  nullptr: no stage, the launches of before.
+struct NbestStage { const int32_t* hyp_idx; const int32_t* hyp_len; int32_t N, Th, max_len; const float* coef; float risk_scale; void* ws; };
+static int keras_loss_backward(const char* fn, ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, const int32_t* frame_len, ishara_stream st,
+                               const NbestStage* nb = nullptr) {
     if (!frame_len_ok(m, fn, frame_len)) return -1;
     if (!m->ws || !m->grads) { ishara_set_error("%s: model is not bound (grads required)", fn); return -1; }
     if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("%s: this handle is an encoder-only family; use ishara_encoder_backward", fn); return -1; }
@@ -347,6 +351,9 @@ static int keras_loss_backward(const char* fn, ishara_model* m, const float* log
     CK(launch_fill_u32(m->grads, (size_t)m->n_train, 0u, m->s));      // a kernel, not a memset node: the whole step stays capturable (hipGraph note)
     CKP(m, "ctc", 2.0 * r.M * m->C * 4, 0, launch_ctc(logits, labels, B, T, m->C, m->L, m->C - 1, nl, m->Wf(m->dlogits), loss_scale / (float)B, m->Wf(m->ctcws), m->s, m->cls_pad ? m->W(m->dlb) : nullptr));
     if (loss) CKP(m, "mean", 0, 0, launch_mean(nl, loss, B, 1.f / (float)B, m->s));
+    if (nb)     // the risk term keeps logit_length = T, as the CTC loss above
+        CKP(m, "ctc_nbest_grad", 2.0 * r.M * m->C * 4, 0, launch_ctc_nbest_grad(logits, B, T, m->C, m->C - 1, nb->hyp_idx, nb->hyp_len, nb->N, nb->Th, nb->max_len, nullptr, nb->coef,
+                                                                                  nb->risk_scale / (float)B, m->Wf(m->dlogits), 1, m->cls_pad ? m->W(m->dlb) : nullptr, nullptr, nullptr, nb->ws, m->s));
     // ---- head
     // input of the head = output of the last layer
     const void* hin = m->layers.empty() ? m->W(m->stem_out) : layer_out(m, m->layers.back());
@@ -387,5 +394,18 @@ extern "C" int ishara_loss_backward(ishara_model* m, const float* logits, const 
 extern "C" int ishara_loss_backward_ex(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, const int32_t* frame_len,
                                        ishara_stream st) {
     return keras_loss_backward("ishara_loss_backward_ex", m, logits, labels, B, loss, nll, loss_scale, frame_len, st);
+}
+extern "C" int ishara_loss_backward_nbest(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale,
+                                          const int32_t* frame_len, const int32_t* hyp_idx, const int32_t* hyp_len, int32_t N, int32_t Th, int32_t max_len,
+                                          const float* coef, float risk_scale, void* workspace, ishara_stream st) {
+    const char* fn = "ishara_loss_backward_nbest";
+    if (!m) { ishara_set_error("%s: null model", fn); return -1; }
+    if (B < 1) { ishara_set_error("%s: B=%d < 1", fn, B); return -1; }
+    // the stage's own refusals before anything is launched; dlogits is the model's buffer
+    const int rc = ctc_nbest_grad_check(fn, logits, B, m->T, m->C, m->C - 1, hyp_idx, hyp_len, N, Th, max_len, nullptr, coef, m->ws ? m->Wf(m->dlogits) : nullptr, nullptr,
+                                        nullptr, nullptr, workspace);
+    if (rc != 0) return rc;
+    const NbestStage nb{hyp_idx, hyp_len, N, Th, max_len, coef, risk_scale, workspace};
+    return keras_loss_backward(fn, m, logits, labels, B, loss, nll, loss_scale, frame_len, st, &nb);
 }
 

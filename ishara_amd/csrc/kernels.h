@@ -364,6 +364,17 @@ int launch_ctc(const float* logits, const int64_t* labels, int B, int T, int C, 
 // grad_scale (sample_scale [B] f32 or NULL) and zero_inf: an infeasible sample's gradient is +0.  T stays the stride (contract: ishara_hip.h)
 int launch_ctc_len(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, float* nll, float* dlogits,
                    float grad_scale, float* ws, const int* frame_len, const float* sample_scale, int zero_inf, hipStream_t s);
+// ---- gradient of the n-best scores (ctc_nbest_grad.hip) and the MWER weights (mwer_weights.hip): contracts in ishara_hip.h.  The launchers
+// check nothing: ctc_nbest_grad_check holds the refusals of ishara_ctc_nbest_grad (0: go ahead; B == 0 passes and launches nothing)
+int64_t ctc_nbest_grad_workspace_bytes(int B, int T, int N, int max_len);
+int ctc_nbest_grad_check(const char* fn, const float* logits, int B, int T, int C, int blank, const int* hyp_idx, const int* hyp_len, int N, int Th,
+                         int max_len, const int* frame_len, const float* coef, const float* dlogits, const void* dlb, const float* logp,
+                         const int* status, const void* ws);
+int launch_ctc_nbest_grad(const float* logits, int B, int T, int C, int blank, const int* hyp_idx, const int* hyp_len, int N, int Th, int max_len,
+                          const int* frame_len, const float* coef, float grad_scale, float* dlogits, int accumulate, void* dlb, float* logp,
+                          int* status, void* ws, hipStream_t s);
+int launch_mwer_weights(const int* hyp_idx, const int* hyp_len, const float* logp, const int* status, int B, int N, int Th, const int* targets, int L,
+                        const float* inv_temp, int mode, int* dist, float* post, float* risk, float* coef, int* tlen, hipStream_t s);
 int launch_fill_u32(void* p, size_t n_words, uint32_t v, hipStream_t s);   // model.hip
 int launch_mean(const float* v, float* out, int n, float scale, hipStream_t s);
 int launch_greedy_decode(const float* logits, int B, int T, int C, int blank, int* out_idx, int* out_len, hipStream_t s);

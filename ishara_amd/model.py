@@ -73,11 +73,22 @@ class Optimizer:
     shows the resolution.  None (the default) is the step without any of it.  Limits: the backward pass still computes a frozen tensor's
     gradient (skipping those GEMMs is a later change); the BatchNorm moving statistics of a frozen block keep updating in training mode,
     unlike Keras' trainable = False; equality with a TensorFlow run is unpinned, and no accuracy effect is measured (there is neither a
-    dataset nor trained weights)."""
+    dataset nor trained weights).
+
+    `mwer_nbest`, `mwer_beam_width`, `mwer_weight`, `mwer_ctc_weight`, `mwer_temperature`, `mwer_normalise`, `mwer_start_step`:
+    minimum-risk (MWER) training over the beam's n-best list (ishara_amd/mwer.py).  With `mwer_nbest` > 0, a step whose number
+    `iterations` has reached `mwer_start_step` runs, inside Model.loss_and_gradients, the prefix beam search (width `mwer_beam_width`, no
+    LM) on the step's logits, the exact CTC score of every hypothesis, the posterior of the list at `mwer_temperature` and the expected
+    edit distance to the label (divided by the label's length with `mwer_normalise`), and takes the gradient of
+    mwer_ctc_weight * CTC + mwer_weight * mean_b risk_b; the loss returned stays the CTC loss of the label.  A hypothesis longer than
+    max_label_len leaves the list.  AWP's two passes, accumulation, clipping, skipped steps, EMA and parameter groups compose unchanged.
+    Model.mwer_stats() reads the last step's mean risk.  0 (the default) is the step without any of it.  No accuracy effect is measured."""
 
     def __init__(self, learning_rate=1e-3, weight_decay=0.0, global_clipnorm=None, skip_nonfinite=False, accumulate_steps=1,
                  use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_warmup=False,
-                 awp_delta=None, awp_eps=1e-4, awp_start_step=0, awp_relative=False, param_groups=None):
+                 awp_delta=None, awp_eps=1e-4, awp_start_step=0, awp_relative=False, param_groups=None,
+                 mwer_nbest=0, mwer_beam_width=8, mwer_weight=1.0, mwer_ctc_weight=0.01, mwer_temperature=1.0, mwer_normalise=True,
+                 mwer_start_step=0):
         self._lr = _Scalar(learning_rate)
         # The reference assigns `.weight_decay` on the Lookahead wrapper (c11:64), which is not
         # one of its hyper-parameters, so RectifiedAdam keeps weight_decay=0 (SURVEY §8a row 10).
@@ -97,6 +108,18 @@ class Optimizer:
         self.awp_start_step = awp_start_step
         self.awp_relative = awp_relative
         self.param_groups = param_groups
+        self.mwer_nbest = mwer_nbest
+        self.mwer_beam_width = mwer_beam_width
+        self.mwer_weight = mwer_weight
+        self.mwer_ctc_weight = mwer_ctc_weight
+        self.mwer_temperature = mwer_temperature
+        self.mwer_normalise = mwer_normalise
+        self.mwer_start_step = mwer_start_step
+
+    def mwer_options(self) -> dict:
+        """the seven mwer_* options as a checked dict (ishara_amd/mwer.py check_options)"""
+        from . import mwer
+        return mwer.check_options(**{k: getattr(self, k) for k in mwer.OPTION_NAMES})
 
     def group_options(self):
         """None, or the checked parameter groups: [{"match": [patterns], "lr_scale", "weight_decay_scale", "trainable"}]"""
@@ -226,6 +249,7 @@ class Model(Handle):
         self._ema_rec = None       # the 16-byte ishara_ema_state record (2 x int64 storage)
         self._ema_swapped = False  # inside averaged_weights(): params[:n_train] and _ema_avg have changed places
         self._awp_backup = None    # [n_train] f32 copy of params[:n_train] while they are perturbed, allocated by the first step AWP is active in
+        self._mwer = None          # the buffers of minimum-risk training, allocated by the first step it is active in
         self._awp = None           # with it: the segment table, the scale array, the record, the workspace and the two loss tensors
         self._pg = None            # parameter groups: the segment table, the device rows, the workspace, allocated by the first step with optimizer.param_groups
         self._pg_key = None        # the canonical text of the groups the rows were resolved from (None: the option is off)
@@ -374,7 +398,10 @@ class Model(Handle):
         B = logits.shape[0]
         if y.shape != (B, self._cfg.max_label_len):
             raise ValueError(f"labels must be [B,{self._cfg.max_label_len}] padded with {self.C - 1}")
-        if fl is None:
+        mw = self._mwer_begin_step(B)
+        if mw is not None:
+            self._mwer_loss_backward(mw, logits, y, B, loss_scale, fl)
+        elif fl is None:
             _lib.check(self._lib.ishara_loss_backward(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf),
                                                       _lib.ptr(self._nll_buf), C.c_float(loss_scale), _stream()), "ishara_loss_backward")
         else:
@@ -558,6 +585,70 @@ class Model(Handle):
         from . import train_state as TS
         return TS.resolve_param_groups(self.entries, self.optimizer.group_options())
 
+    # ------------------------------------------------------------------ minimum-risk training over the beam's n-best (ishara_amd/mwer.py)
+    def _mwer_begin_step(self, B: int):
+        """The checked mwer_* options when this step adds the risk term (optimizer.mwer_nbest > 0 and optimizer.iterations has reached
+        mwer_start_step), else None (and then nothing of it is touched, allocated or launched).  The first such step allocates the
+        buffers: the n-best list, its scores, the weights, the beam search's and the gradient stage's workspaces, for max_batch clips."""
+        o = self.optimizer
+        if not o.mwer_nbest:
+            return None
+        opts = o.mwer_options()
+        if opts["mwer_nbest"] == 0 or o.iterations < opts["mwer_start_step"]:
+            return None
+        from . import ctc_beam, mbr, mwer
+        N, W, L = opts["mwer_nbest"], opts["mwer_beam_width"], self._cfg.max_label_len
+        if L > mwer.MAX_TARGET_LEN:
+            raise ValueError(f"minimum-risk training takes targets of at most {mwer.MAX_TARGET_LEN} symbols, max_label_len is {L}")
+        key = (N, W)
+        if self._mwer is None or self._mwer["key"] != key:
+            ctc_beam.check_device_args(self.C, self.T, W, N)
+            Bm, T, dev = self.max_batch, self.T, self.device
+            i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+            max_len = min(mwer.MAX_HYP_LEN, L)        # a hypothesis longer than every label leaves the list: it sizes the lattice workspace
+            self._mwer = dict(key=key, max_len=max_len, idx=torch.empty((Bm, N, T), **i32), len=torch.empty((Bm, N), **i32), score=torch.empty((Bm, N), **f32),
+                              logp=torch.empty((Bm, N), **f32), status=torch.empty((Bm, N), **i32), tgt=torch.empty((Bm, L), **i32),
+                              dist=torch.empty((Bm, N), **i32), post=torch.empty((Bm, N), **f32), risk=torch.empty((Bm,), **f32),
+                              coef=torch.empty((Bm, N), **f32), tlen=torch.empty((Bm,), **i32), it=torch.empty((1,), **f32),
+                              beam_ws=torch.empty(max(ctc_beam.workspace_bytes(self._lib, Bm, T, self.C, W), 4), dtype=torch.uint8, device=dev),
+                              grad_ws=torch.empty(mwer.workspace_bytes(self._lib, Bm, T, N, max_len), dtype=torch.uint8, device=dev), B=0)
+        self._mwer["it"].fill_(mbr.inverse_temperature(opts["mwer_temperature"]))
+        return opts
+
+    def _mwer_loss_backward(self, opts: dict, logits, y, B: int, loss_scale: float, fl) -> None:
+        """search (no LM) -> exact scores -> weights -> ishara_loss_backward_nbest, all on the current stream; nothing waits"""
+        from . import ctc_beam, mwer
+        m, lib, st = self._mwer, self._lib, _stream()
+        N, W = m["key"]
+        T, Cn, L = self.T, self.C, self._cfg.max_label_len
+        ctc_beam.launch(lib, logits, B, T, Cn, W, N, None, 0.0, 0.0, m["beam_ws"], m["idx"], m["len"], m["score"], st, ex=True)
+        _lib.check(lib.ishara_ctc_score_nbest(_lib.ptr(logits), B, T, Cn, Cn - 1, _lib.ptr(m["idx"]), _lib.ptr(m["len"]), N, T, None, _lib.ptr(m["logp"]),
+                                              _lib.ptr(m["status"]), st), "ishara_ctc_score_nbest")
+        # a slot the gradient stage will not take (longer than max_len) is not live for the weights either; the labels' padding (the blank
+        # C - 1) becomes the targets' 59
+        m["status"][:B] = torch.where(m["len"][:B] > m["max_len"], torch.full_like(m["status"][:B], mwer.STATUS_LONG), m["status"][:B])
+        m["tgt"][:B] = torch.where(y == Cn - 1, torch.full_like(y, PAD_TOKEN_IDX), y).to(torch.int32)
+        mwer.launch_weights(lib, m["idx"], m["len"], m["logp"], m["status"], B, N, T, m["tgt"], L, m["it"], 1 if opts["mwer_normalise"] else 0,
+                            m["dist"], m["post"], m["risk"], m["coef"], m["tlen"], st)
+        _lib.check(lib.ishara_loss_backward_nbest(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf), _lib.ptr(self._nll_buf),
+                                                  C.c_float(loss_scale * opts["mwer_ctc_weight"]), _lib.ptr(fl), _lib.ptr(m["idx"]), _lib.ptr(m["len"]), N, T,
+                                                  m["max_len"], _lib.ptr(m["coef"]), C.c_float(loss_scale * opts["mwer_weight"]), _lib.ptr(m["grad_ws"]), st),
+                   "ishara_loss_backward_nbest")
+        m["B"] = B
+
+    def mwer_stats(self) -> Dict[str, float]:
+        """The last step that added the risk term, read on request (one device-to-host copy): risk, the mean expected distance of the
+        batch's clips that have a live hypothesis; top_distance, the mean plain edit distance of the first slot over the clips where it
+        is live; live_slots, how many slots of the batch are live; clips, how many clips have one."""
+        if self._mwer is None or not self._mwer["B"]:
+            raise _lib.IsharaError("mwer_stats: no step has run with minimum-risk training (optimizer.mwer_nbest > 0 and mwer_start_step reached)")
+        m = self._mwer
+        B = m["B"]
+        risk, dist = m["risk"][:B].cpu().numpy().astype(np.float64), m["dist"][:B].cpu().numpy()
+        has, top = np.isfinite(risk), dist[:, 0] >= 0
+        return dict(risk=float(risk[has].mean()) if has.any() else float("nan"), top_distance=float(dist[top, 0].mean()) if top.any() else float("nan"),
+                    live_slots=int((dist >= 0).sum()), clips=int(has.sum()))
+
     # ------------------------------------------------------------------ adversarial weight perturbation (csrc/awp.hip)
     def _awp_begin_step(self):
         """In front of a (micro)batch of train_on_batch: the checked AWP options when the perturbation is configured and the step number has
@@ -739,7 +830,7 @@ class Model(Handle):
                            iterations=o.iterations, steps=self._steps, step_seed=self._step_seed, learning_rate=float(o.learning_rate),
                            weight_decay=float(o.weight_decay), apply_weight_decay=o.apply_weight_decay, global_clipnorm=o.global_clipnorm,
                            skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped, **self._ema_state_entries(), **self._awp_state_entries(),
-                           param_groups=o.group_options())
+                           param_groups=o.group_options(), **self._mwer_state_entries())
         return TS.save_state_file(path, st)
 
     def _ema_state_entries(self) -> dict:
@@ -749,6 +840,11 @@ class Model(Handle):
         use, momentum, every, warmup = self.optimizer.ema_options()
         return dict(ema_avg=self._ema_avg.cpu().numpy(), ema_updates=self.ema_state()["updates"], use_ema=use, ema_momentum=momentum,
                     ema_warmup=warmup, ema_overwrite_frequency=every or None)
+
+    def _mwer_state_entries(self) -> dict:
+        """what save_state adds for minimum-risk training: its seven options as one key when it is configured, nothing otherwise"""
+        opts = self.optimizer.mwer_options()
+        return dict(mwer=opts) if opts["mwer_nbest"] > 0 else {}
 
     def _awp_state_entries(self) -> dict:
         """what save_state adds for adversarial weight perturbation: its four options when it is configured (it has no device state
@@ -762,7 +858,8 @@ class Model(Handle):
         """Restores what save_state wrote into this model (same architecture: the entry list is checked).  A file with a moving average
         restores it, its update count and the four ema settings; a file without one leaves the settings alone and, with optimizer.use_ema
         on, starts a fresh average at the loaded weights with 0 updates.  A file with the options of adversarial weight perturbation sets
-        them; a file without them leaves them alone, and so with the optimizer's parameter groups."""
+        them; a file without them leaves them alone, and so with the optimizer's parameter groups and the options of minimum-risk
+        training."""
         from . import train_state as TS
         self._not_while_averaged("load_state")
         st = TS.load_state_file(path, self.entries)
@@ -779,6 +876,9 @@ class Model(Handle):
         self._skipped_seen = st["skipped"]
         if "param_groups" in st:
             o.param_groups = st["param_groups"]
+        if "mwer" in st:
+            for k, v in st["mwer"].items():
+                setattr(o, k, v)
         if "awp_delta" in st:
             o.awp_delta, o.awp_eps, o.awp_start_step, o.awp_relative = st["awp_delta"], st["awp_eps"], st["awp_start_step"], st["awp_relative"]
         self._ema_avg = self._ema_rec = None

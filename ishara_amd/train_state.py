@@ -332,10 +332,26 @@ def mask_reference(g: np.ndarray, seg_off: Sequence[int], rows: np.ndarray) -> n
 EMA_KEYS = ("ema_avg", "ema_updates", "ema_momentum", "ema_warmup", "ema_overwrite_frequency", "use_ema")
 AWP_KEYS = ("awp_delta", "awp_eps", "awp_start_step", "awp_relative")
 PARAM_GROUP_KEYS = ("param_groups",)
+MWER_KEYS = ("mwer",)          # the seven Optimizer(mwer_*) options as one JSON text (ishara_amd/mwer.py check_options)
 
 
 class TrainStateError(ValueError):
     pass
+
+
+def mwer_json(options: dict) -> str:
+    """the canonical text of the seven mwer_* options in a state file"""
+    from .mwer import check_options
+    return json.dumps(check_options(**options), sort_keys=True)
+
+
+def mwer_options(text: str) -> dict:
+    """the checked options of that text; a key that is not one of the seven is refused (TypeError)"""
+    from .mwer import check_options
+    d = json.loads(text)
+    if not isinstance(d, dict):
+        raise ValueError(f"expected a JSON object, got {type(d).__name__}")
+    return check_options(**d)
 
 
 def _entry_arrays(entries: Iterable[Tuple[str, tuple, int, bool]]) -> Dict[str, np.ndarray]:
@@ -353,13 +369,15 @@ def pack_state(entries, params: np.ndarray, opt_m: np.ndarray, opt_v: np.ndarray
                global_clipnorm: Optional[float] = None, skip_nonfinite: bool = False, accumulate_steps: int = 1, skipped: int = 0,
                ema_avg: Optional[np.ndarray] = None, ema_updates: int = 0, use_ema: bool = True, ema_momentum: float = 0.99,
                ema_warmup: bool = False, ema_overwrite_frequency: Optional[int] = None, awp_delta: Optional[float] = None,
-               awp_eps: float = 1e-4, awp_start_step: int = 0, awp_relative: bool = False, param_groups=None) -> Dict[str, np.ndarray]:
+               awp_eps: float = 1e-4, awp_start_step: int = 0, awp_relative: bool = False, param_groups=None, mwer: Optional[dict] = None
+               ) -> Dict[str, np.ndarray]:
     """The arrays of one state file (np.savez(path, **pack_state(...))): the flat fp32 `params` (BatchNorm moving statistics included), the
     three optimizer slots, the counters, the hyper-parameters, the format version and the entry list the buffers were laid out by.  With
     `ema_avg` (the moving average of the trainable prefix, when one exists) the file also holds EMA_KEYS: the average, its update count
     and the four settings; without it the key set is what it was before the average existed.  With `awp_delta` (adversarial weight
     perturbation is configured) it holds AWP_KEYS, the four options; AWP has no other state.  With `param_groups` (the optimizer's
-    parameter groups are set) it holds PARAM_GROUP_KEYS: the JSON text of the checked list."""
+    parameter groups are set) it holds PARAM_GROUP_KEYS: the JSON text of the checked list.  With `mwer` (minimum-risk training is
+    configured: the dict of the seven mwer_* options) it holds MWER_KEYS: their JSON text; it has no other state."""
     out = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in zip(ARRAYS, (params, opt_m, opt_v, opt_slow))}
     out.update(_entry_arrays(entries))
     out.update(format_version=np.int64(FORMAT_VERSION), iterations=np.int64(iterations), steps=np.int64(steps), step_seed=np.int64(step_seed),
@@ -375,6 +393,8 @@ def pack_state(entries, params: np.ndarray, opt_m: np.ndarray, opt_v: np.ndarray
         out.update(awp_delta=np.float64(awp_delta), awp_eps=np.float64(awp_eps), awp_start_step=np.int64(awp_start_step), awp_relative=np.bool_(awp_relative))
     if param_groups is not None:
         out.update(param_groups=np.array(param_groups_json(param_groups), dtype=np.str_))
+    if mwer is not None:
+        out.update(mwer=np.array(mwer_json(mwer), dtype=np.str_))
     validate_state(out, entries)
     return out
 
@@ -434,13 +454,19 @@ def validate_state(z, entries) -> None:
             resolve_param_groups(entries, json.loads(str(z["param_groups"])))
         except ValueError as e:
             raise TrainStateError(f"train state: the entry 'param_groups' does not fit the model: {e}")
+    if "mwer" in keys:                  # and the options of minimum-risk training
+        try:
+            mwer_options(str(z["mwer"]))
+        except (ValueError, TypeError) as e:
+            raise TrainStateError(f"train state: the entry 'mwer' is not the seven mwer_* options: {e}")
 
 
 def unpack_state(z, entries) -> dict:
     """validate_state, then plain Python values: the four arrays (float32, flat) and the scalars; global_clipnorm is None when off.  A file
     with the moving average adds ema_avg (float32), ema_updates, use_ema, ema_momentum, ema_warmup and ema_overwrite_frequency (None when
     off); a file without it adds none of them.  A file with the options of the weight perturbation adds awp_delta, awp_eps, awp_start_step
-    and awp_relative; a file with the optimizer's parameter groups adds param_groups (the checked list)."""
+    and awp_relative; a file with the optimizer's parameter groups adds param_groups (the checked list); a file with the options of
+    minimum-risk training adds mwer (the checked dict of the seven mwer_* options)."""
     validate_state(z, entries)
     out = {k: np.array(z[k], dtype=np.float32) for k in ARRAYS}
     for k in ("iterations", "steps", "step_seed", "accumulate_steps", "skipped"):
@@ -460,6 +486,8 @@ def unpack_state(z, entries) -> dict:
         out.update(awp_delta=float(z["awp_delta"]), awp_eps=float(z["awp_eps"]), awp_start_step=int(z["awp_start_step"]), awp_relative=bool(z["awp_relative"]))
     if "param_groups" in keys:
         out.update(param_groups=check_param_groups(json.loads(str(z["param_groups"]))))
+    if "mwer" in keys:
+        out.update(mwer=mwer_options(str(z["mwer"])))
     return out
 
 

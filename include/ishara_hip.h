@@ -128,6 +128,38 @@ int ishara_loss_backward_ex(ishara_model* m, const float* logits, const int64_t*
 int ishara_loss_backward_nbest(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale,
                                const int32_t* frame_len /* may be NULL */, const int32_t* hyp_idx, const int32_t* hyp_len, int32_t N, int32_t Th,
                                int32_t max_len, const float* coef, float risk_scale, void* workspace, ishara_stream s);
+/* The same backward pass with knowledge distillation as a further loss term, and the risk term beside it when wanted.  The order between the
+ * CTC kernel and the head is fixed: the CTC kernel, then the n-best stage when `nbest` is given (exactly ishara_loss_backward_nbest's), then
+ * the distillation stage when `kd` is given: ishara_kd_grad's kernels on the model's own dlogits with accumulate = 1,
+ * grad_scale = kd_scale / B, frame_len = NULL (the term keeps logit_length = T as the CTC loss and the risk term do) and the model's padded
+ * 16-bit copy as dlb; whichever stage runs last leaves that copy.  The gradients are those of
+ *     loss_scale * mean_b nll_b  +  risk_scale / B * sum_b sum_n coef[b,n] * nll(hyp[b,n])  +  kd_scale / B * tau * sum_b w_b * sum_t KL_t,
+ * tau = 1 / inv_temp: the usual lambda * tau^2 * KL per clip, averaged over the batch, is kd_scale = lambda * tau.
+ *   ishara_kd_stage     teacher [B,T,C] fp32 on the device (logits or log-probabilities; it may be the `logits` argument itself), inv_temp,
+ *                       mode, kl_frame [B,T] and kl_clip [B] (both may be NULL) as ishara_kd_grad; kd_scale by value.
+ *   ishara_nbest_stage  the arguments of ishara_loss_backward_nbest from hyp_idx to workspace, under their names.
+ * Either pointer may be NULL: with both NULL the call is ishara_loss_backward_ex, with `kd` NULL it is ishara_loss_backward_nbest, launch for
+ * launch.  The refusals of both stages (ishara_ctc_nbest_grad's and ishara_kd_grad's, T and C being the model's) come before anything is
+ * launched.  loss and nll keep their meaning: the CTC loss of the reference label. */
+typedef struct ishara_kd_stage {
+    const float* teacher;
+    float inv_temp;
+    int32_t mode;
+    float kd_scale;
+    float* kl_frame;                /* may be NULL */
+    float* kl_clip;                 /* may be NULL; needs kl_frame */
+} ishara_kd_stage;
+typedef struct ishara_nbest_stage {
+    const int32_t* hyp_idx;
+    const int32_t* hyp_len;
+    int32_t N, Th, max_len;
+    const float* coef;
+    float risk_scale;
+    void* workspace;
+} ishara_nbest_stage;
+int ishara_loss_backward_kd(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale,
+                            const int32_t* frame_len /* may be NULL */, const ishara_kd_stage* kd /* may be NULL */,
+                            const ishara_nbest_stage* nbest /* may be NULL */, ishara_stream s);
 /* frame lengths of a zero-padded batch x [B,T,F] f32 (device): out_len[b] (device int32 [B]) = 1 + the index of the last frame of clip b that
  * has any non-zero feature, 0 if there is none.  The prefix reading of Masking(0.0): an all-zero frame INSIDE a clip stays valid, where Keras
  * masks that frame too.  One workgroup per clip; B, T, F > 0. */
@@ -688,6 +720,36 @@ int ishara_ctc_nbest_grad(const float* logits, int32_t B, int32_t T, int32_t C, 
 int ishara_mwer_weights(const int32_t* hyp_idx, const int32_t* hyp_len, const float* logp, const int32_t* status /* may be NULL */,
                         int32_t B, int32_t N, int32_t Th, const int32_t* targets, int32_t L, const float* inv_temp /* may be NULL */,
                         int32_t mode, int32_t* dist, float* post, float* risk, float* coef, int32_t* tlen, ishara_stream s);
+/* Knowledge distillation, frame level: the gradient of a temperature-softened KL(teacher || student) with respect to the student's logits;
+ * the semantics of ishara_amd/kd.py (kd_reference).  logits and teacher [B,T,C] fp32; the teacher's rows may be raw logits or normalised
+ * log-probabilities (ishara_logits_combine's output): the kernel normalises them itself.  frame_len (may be NULL: T each) as
+ * ishara_greedy_decode_ex: a value outside [1, T] means the clip has no frames.  Inputs are assumed finite; no index is derived from data.
+ * For every clip b and frame t < Tb, lane = class, everything in fp32:
+ *     a[c] = logits[c] * inv_temp,  ma = max a,  ea = expf(a - ma),  sa = sum ea,  lps = (a - ma) - logf(sa),  ps = ea / sa;
+ *     the teacher's row through the same steps: lpt, pt;
+ *     KL_t = sum_c pt[c] * (lpt[c] - lps[c]);
+ *     G[b,t,c] = grad_scale * (w_b * (ps[c] - pt[c])),  w_b absent in mode 0 (the clip's sum over frames), 1 / (float)Tb in mode 1 (its mean),
+ * so G is the gradient of grad_scale * tau * w_b * sum_t KL_t, tau = 1 / inv_temp: the usual lambda * tau^2 * KL per clip, averaged over the
+ * batch, is grad_scale = lambda * tau / B.
+ * Arithmetic: max and both sums over the classes are the xor butterfly over the 64 lanes, offsets 32, 16, 8, 4, 2, 1 (x = op(x, x of lane ^
+ *   offset)), lanes >= C holding -inf for the max and +0 for a sum: one fixed order, every lane ends with the same bits.  Every
+ *   multiplication, subtraction, division and the accumulate addition is a single round-to-nearest fp32 operation without FMA contraction.
+ *   Both rows go through the same instructions, so teacher == logits (the same pointer or a copy) gives G = 0 and KL_t = 0 exactly.
+ * -> dlogits [B,T,C] fp32: accumulate 0 writes G, and +0 in the rows t >= Tb; accumulate 1 writes dlogits + G by one fp32 addition and leaves
+ *   the rows t >= Tb as they are.  dlb (may be NULL): the bf16 copy of the FINAL dlogits rows, zero padded to 128 classes, [B*T, 64] packed
+ *   pairs: the layout the loss kernel and ishara_ctc_nbest_grad write.  kl_frame [B,T] (may be NULL): KL_t, +0 past the clip's end.
+ *   kl_clip [B] (may be NULL; needs kl_frame): the sum of kl_frame over t ascending from +0, in mode 1 then multiplied by 1 / (float)Tb; +0
+ *   for a clip without frames.  Rows past a clip's end are read from neither input.
+ * One kernel, grid (ceil(T / 16), B), four waves, a frame per wave at a time and four in flight; with kl_clip a second one, a wave per clip.
+ *   No atomics on global memory, no workspace, no allocation, no memset node, no host read: graph-capturable and bit-identical from run to
+ *   run.  teacher may alias logits; dlogits must overlap neither.  prof (may be NULL) lends its profiler only.
+ * Refused with a message that names the argument, before any HIP call: C outside 2..64, T outside 1..4096, B < 0 or B > 65535 (B == 0:
+ *   nothing is launched), mode or accumulate not 0 or 1, inv_temp not finite or <= 0, grad_scale not finite, kl_clip without kl_frame, a
+ *   null logits, teacher or dlogits, a pointer that is not 4-byte aligned, an output that overlaps an input or another output. */
+int ishara_kd_grad(ishara_model* prof /* may be NULL */, const float* logits, const float* teacher, int32_t B, int32_t T, int32_t C,
+                   float inv_temp, int32_t mode, const int32_t* frame_len /* may be NULL */, float grad_scale,
+                   float* dlogits, int32_t accumulate, void* dlb /* may be NULL */,
+                   float* kl_frame /* may be NULL */, float* kl_clip /* may be NULL; needs kl_frame */, ishara_stream s);
 
 /* Training-side input batch: the per-clip augmentation parameters of ASLDataset._apply_augmentations (data_loader.py:124-166), drawn
  * on the host in the reference's `random` call order (ishara_amd/data.py draw_augmentation).  64 bytes, no padding. */

@@ -19,3 +19,4 @@ from .rescore import (ctc_logp_reference, ctc_score_nbest, rescore_models, resco
                       rescore_reference)                                                   # exact CTC scores, LM, rerank)
 from .rescore import rescore_sweep, rescore_sweep_reference, sweep_grid, sweep_scores  # noqa: F401  (its weight sweep on the device)
 from .mwer import ctc_nbest_grad, mwer_loss, mwer_reference, mwer_weights  # noqa: F401  (minimum-risk training over the beam's n-best)
+from .kd import kd_grad, kd_loss, kd_reference  # noqa: F401  (knowledge distillation from a teacher's frame posteriors)

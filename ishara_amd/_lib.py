@@ -70,6 +70,18 @@ class ParamGroup(C.Structure):
     _fields_ = [("lr_scale", C.c_float), ("wd_scale", C.c_float), ("frozen", C.c_int32), ("reserved", C.c_int32)]
 
 
+class KdStage(C.Structure):
+    """ishara_kd_stage: the distillation stage of ishara_loss_backward_kd (field order of the header)."""
+    _fields_ = [("teacher", C.c_void_p), ("inv_temp", C.c_float), ("mode", C.c_int32), ("kd_scale", C.c_float), ("kl_frame", C.c_void_p),
+                ("kl_clip", C.c_void_p)]
+
+
+class NbestStage(C.Structure):
+    """ishara_nbest_stage: the n-best stage of ishara_loss_backward_kd, the arguments of ishara_loss_backward_nbest (field order of the header)."""
+    _fields_ = [("hyp_idx", C.c_void_p), ("hyp_len", C.c_void_p), ("N", C.c_int32), ("Th", C.c_int32), ("max_len", C.c_int32), ("coef", C.c_void_p),
+                ("risk_scale", C.c_float), ("workspace", C.c_void_p)]
+
+
 class GemmTnCall(C.Structure):
     """ishara_gemm_tn_call: one weight-gradient GEMM of ishara_op_gemm_tn / ishara_debug_gemm_tn_plan (field order of the header)."""
     _fields_ = [
@@ -203,6 +215,8 @@ SIGNATURES = {
     "ishara_ctc_nbest_grad": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _F, _P, _I32, _P, _P, _P, _P, _P]),
     "ishara_mwer_weights": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "ishara_loss_backward_nbest": (C.c_int, [_P, _P, _P, _I32, _P, _P, _F, _P, _P, _P, _I32, _I32, _I32, _P, _F, _P, _P]),
+    "ishara_kd_grad": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _F, _I32, _P, _F, _P, _I32, _P, _P, _P, _P]),
+    "ishara_loss_backward_kd": (C.c_int, [_P, _P, _P, _I32, _P, _P, _F, _P, C.POINTER(KdStage), C.POINTER(NbestStage), _P]),
     "ishara_clip_batch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "ishara_clip_batch_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "ishara_ctc_workspace_bytes": (_I64, [_I32, _I32, _I32]),

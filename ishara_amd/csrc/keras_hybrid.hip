@@ -333,9 +333,11 @@ bool frame_len_agrees(const char* fn, bool fwd_had, const int32_t* frame_len) {
 }
 // A second loss term between the CTC kernel and the head: the gradient of risk_scale / B * sum_n coef[b, n] * nll_n over an n-best list, added
 // into m->dlogits (and m->dlb rewritten from the sum) by ishara_ctc_nbest_grad's kernels.  nullptr: no stage, the launches of before.
+// A third term behind it, of the same shape: kd (the public ishara_kd_stage), the distillation gradient kd_scale / B * (w_b * (ps - pt)) by
+// ishara_kd_grad's kernels.  nullptr: no stage.
 struct NbestStage { const int32_t* hyp_idx; const int32_t* hyp_len; int32_t N, Th, max_len; const float* coef; float risk_scale; void* ws; };
 static int keras_loss_backward(const char* fn, ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale, const int32_t* frame_len, ishara_stream st,
-                               const NbestStage* nb = nullptr) {
+                               const NbestStage* nb = nullptr, const ishara_kd_stage* kd = nullptr) {
     if (!frame_len_ok(m, fn, frame_len)) return -1;
     if (!m->ws || !m->grads) { ishara_set_error("%s: model is not bound (grads required)", fn); return -1; }
     if (m->family != ISHARA_FAMILY_KERAS_HYBRID) { ishara_set_error("%s: this handle is an encoder-only family; use ishara_encoder_backward", fn); return -1; }
@@ -354,6 +356,9 @@ static int keras_loss_backward(const char* fn, ishara_model* m, const float* log
     if (nb)     // the risk term keeps logit_length = T, as the CTC loss above
         CKP(m, "ctc_nbest_grad", 2.0 * r.M * m->C * 4, 0, launch_ctc_nbest_grad(logits, B, T, m->C, m->C - 1, nb->hyp_idx, nb->hyp_len, nb->N, nb->Th, nb->max_len, nullptr, nb->coef,
                                                                                   nb->risk_scale / (float)B, m->Wf(m->dlogits), 1, m->cls_pad ? m->W(m->dlb) : nullptr, nullptr, nullptr, nb->ws, m->s));
+    if (kd)     // the distillation term behind it, with logit_length = T as well; the stage that runs last leaves m->dlb
+        CKP(m, "kd_grad", 4.0 * r.M * m->C * 4, 0, launch_kd_grad(logits, kd->teacher, B, T, m->C, kd->inv_temp, kd->mode, nullptr, kd->kd_scale / (float)B, m->Wf(m->dlogits), 1,
+                                                                  m->cls_pad ? m->W(m->dlb) : nullptr, kd->kl_frame, kd->kl_clip, m->s));
     // ---- head
     // input of the head = output of the last layer
     const void* hin = m->layers.empty() ? m->W(m->stem_out) : layer_out(m, m->layers.back());
@@ -408,4 +413,24 @@ extern "C" int ishara_loss_backward_nbest(ishara_model* m, const float* logits, 
     const NbestStage nb{hyp_idx, hyp_len, N, Th, max_len, coef, risk_scale, workspace};
     return keras_loss_backward(fn, m, logits, labels, B, loss, nll, loss_scale, frame_len, st, &nb);
 }
-
+extern "C" int ishara_loss_backward_kd(ishara_model* m, const float* logits, const int64_t* labels, int32_t B, float* loss, float* nll, float loss_scale,
+                                       const int32_t* frame_len, const ishara_kd_stage* kd, const ishara_nbest_stage* nbest, ishara_stream st) {
+    const char* fn = "ishara_loss_backward_kd";
+    if (!m) { ishara_set_error("%s: null model", fn); return -1; }
+    if (B < 1) { ishara_set_error("%s: B=%d < 1", fn, B); return -1; }
+    // both stages' own refusals before anything is launched; dlogits and dlb are the model's buffers
+    const float* dl = m->ws ? m->Wf(m->dlogits) : nullptr;
+    NbestStage nb{};
+    if (nbest) {
+        const int rc = ctc_nbest_grad_check(fn, logits, B, m->T, m->C, m->C - 1, nbest->hyp_idx, nbest->hyp_len, nbest->N, nbest->Th, nbest->max_len, nullptr, nbest->coef, dl,
+                                            nullptr, nullptr, nullptr, nbest->workspace);
+        if (rc != 0) return rc;
+        nb = NbestStage{nbest->hyp_idx, nbest->hyp_len, nbest->N, nbest->Th, nbest->max_len, nbest->coef, nbest->risk_scale, nbest->workspace};
+    }
+    if (kd) {
+        if (!std::isfinite(kd->kd_scale)) { ishara_set_error("%s: kd_scale=%g is not finite", fn, (double)kd->kd_scale); return -1; }
+        const int rc = kd_grad_check(fn, logits, kd->teacher, B, m->T, m->C, kd->inv_temp, kd->mode, nullptr, kd->kd_scale / (float)B, dl, 1, nullptr, kd->kl_frame, kd->kl_clip);
+        if (rc != 0) return rc;
+    }
+    return keras_loss_backward(fn, m, logits, labels, B, loss, nll, loss_scale, frame_len, st, nbest ? &nb : nullptr, kd);
+}

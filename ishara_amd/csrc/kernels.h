@@ -375,6 +375,12 @@ int launch_ctc_nbest_grad(const float* logits, int B, int T, int C, int blank, c
                           int* status, void* ws, hipStream_t s);
 int launch_mwer_weights(const int* hyp_idx, const int* hyp_len, const float* logp, const int* status, int B, int N, int Th, const int* targets, int L,
                         const float* inv_temp, int mode, int* dist, float* post, float* risk, float* coef, int* tlen, hipStream_t s);
+// ---- gradient of the distillation term (kd_grad.hip): contract in ishara_hip.h.  The launcher checks nothing: kd_grad_check holds the
+// refusals of ishara_kd_grad (0: go ahead; B == 0 passes and launches nothing)
+int kd_grad_check(const char* fn, const float* logits, const float* teacher, int B, int T, int C, float inv_temp, int mode, const int* frame_len,
+                  float grad_scale, const float* dlogits, int accumulate, const void* dlb, const float* kl_frame, const float* kl_clip);
+int launch_kd_grad(const float* logits, const float* teacher, int B, int T, int C, float inv_temp, int mode, const int* frame_len, float grad_scale,
+                   float* dlogits, int accumulate, void* dlb, float* kl_frame, float* kl_clip, hipStream_t s);
 int launch_fill_u32(void* p, size_t n_words, uint32_t v, hipStream_t s);   // model.hip
 int launch_mean(const float* v, float* out, int n, float scale, hipStream_t s);
 int launch_greedy_decode(const float* logits, int B, int T, int C, int blank, int* out_idx, int* out_len, hipStream_t s);

@@ -82,13 +82,23 @@ class Optimizer:
     edit distance to the label (divided by the label's length with `mwer_normalise`), and takes the gradient of
     mwer_ctc_weight * CTC + mwer_weight * mean_b risk_b; the loss returned stays the CTC loss of the label.  A hypothesis longer than
     max_label_len leaves the list.  AWP's two passes, accumulation, clipping, skipped steps, EMA and parameter groups compose unchanged.
-    Model.mwer_stats() reads the last step's mean risk.  0 (the default) is the step without any of it.  No accuracy effect is measured."""
+    Model.mwer_stats() reads the last step's mean risk.  0 (the default) is the step without any of it.  No accuracy effect is measured.
+
+    `kd_weight`, `kd_temperature`, `kd_ctc_weight`, `kd_normalise`, `kd_start_step`: knowledge distillation from a teacher
+    (ishara_amd/kd.py; Model.set_teacher attaches one, train_on_batch(teacher_logits=) takes precomputed rows).  With `kd_weight` > 0, a
+    step whose number `iterations` has reached `kd_start_step` runs the teacher in inference mode on the step's input and takes, inside
+    Model.loss_and_gradients, the gradient of kd_ctc_weight * CTC + kd_weight * tau^2 * mean_b KL_b, KL_b the KL divergence of the
+    student's from the teacher's class posteriors at temperature tau = `kd_temperature`, summed over the clip's T frames (with
+    `kd_normalise` their mean); the loss returned stays the CTC loss of the label.  With `mwer_nbest` > 0 as well, both terms ride in one
+    backward call and the CTC term carries kd_ctc_weight * mwer_ctc_weight.  AWP's two passes (the teacher runs once), accumulation,
+    clipping, skipped steps, EMA and parameter groups compose unchanged.  Model.kd_stats() reads the last step's mean KL.  0 (the default)
+    is the step without any of it.  No accuracy effect is measured."""
 
     def __init__(self, learning_rate=1e-3, weight_decay=0.0, global_clipnorm=None, skip_nonfinite=False, accumulate_steps=1,
                  use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_warmup=False,
                  awp_delta=None, awp_eps=1e-4, awp_start_step=0, awp_relative=False, param_groups=None,
                  mwer_nbest=0, mwer_beam_width=8, mwer_weight=1.0, mwer_ctc_weight=0.01, mwer_temperature=1.0, mwer_normalise=True,
-                 mwer_start_step=0):
+                 mwer_start_step=0, kd_weight=0.0, kd_temperature=2.0, kd_ctc_weight=1.0, kd_normalise=True, kd_start_step=0):
         self._lr = _Scalar(learning_rate)
         # The reference assigns `.weight_decay` on the Lookahead wrapper (c11:64), which is not
         # one of its hyper-parameters, so RectifiedAdam keeps weight_decay=0 (SURVEY §8a row 10).
@@ -115,6 +125,16 @@ class Optimizer:
         self.mwer_temperature = mwer_temperature
         self.mwer_normalise = mwer_normalise
         self.mwer_start_step = mwer_start_step
+        self.kd_weight = kd_weight
+        self.kd_temperature = kd_temperature
+        self.kd_ctc_weight = kd_ctc_weight
+        self.kd_normalise = kd_normalise
+        self.kd_start_step = kd_start_step
+
+    def kd_options(self) -> dict:
+        """the five kd_* options as a checked dict (ishara_amd/kd.py check_options)"""
+        from . import kd
+        return kd.check_options(**{k: getattr(self, k) for k in kd.OPTION_NAMES})
 
     def mwer_options(self) -> dict:
         """the seven mwer_* options as a checked dict (ishara_amd/mwer.py check_options)"""
@@ -250,6 +270,9 @@ class Model(Handle):
         self._ema_swapped = False  # inside averaged_weights(): params[:n_train] and _ema_avg have changed places
         self._awp_backup = None    # [n_train] f32 copy of params[:n_train] while they are perturbed, allocated by the first step AWP is active in
         self._mwer = None          # the buffers of minimum-risk training, allocated by the first step it is active in
+        self._kd = None            # the buffers of distillation (kl_frame, kl_clip), allocated by the first step it is active in
+        self._teacher = None       # what set_teacher attached: ("models", [Model], weights, mode) or ("callable", fn); never saved
+        self._kd_rows = None       # the teacher's rows of the (micro)batch in flight: AWP's second pass reuses them
         self._awp = None           # with it: the segment table, the scale array, the record, the workspace and the two loss tensors
         self._pg = None            # parameter groups: the segment table, the device rows, the workspace, allocated by the first step with optimizer.param_groups
         self._pg_key = None        # the canonical text of the groups the rows were resolved from (None: the option is off)
@@ -389,9 +412,15 @@ class Model(Handle):
         return self
 
     # ------------------------------------------------------------------ training
-    def loss_and_gradients(self, x, y, seed: Optional[int] = None, loss_scale: float = 1.0, frame_lengths=None):
+    def loss_and_gradients(self, x, y, seed: Optional[int] = None, loss_scale: float = 1.0, frame_lengths=None, teacher_logits=None):
         """forward(training=True) + CTCLoss + backward.  Returns (loss tensor[1], logits).  frame_lengths: as in __call__, for both passes;
-        the CTC loss keeps logit_length = T (c6:3) — a per-clip loss is ctc_loss(..., frame_lengths=)."""
+        the CTC loss keeps logit_length = T (c6:3) — a per-clip loss is ctc_loss(..., frame_lengths=).  teacher_logits: with distillation
+        active (optimizer.kd_weight > 0 and kd_start_step reached), fp32 [B,T,C] rows on the device that stand in for the attached
+        teacher; otherwise not looked at."""
+        kd = self._kd_begin_step()
+        rows = None
+        if kd is not None:      # the teacher runs in front of the student's training forward, once per (micro)batch
+            rows = self._kd_rows if self._kd_rows is not None else self._teacher_rows(x, frame_lengths, teacher_logits)
         logits = self(x, training=True, seed=seed, **_fl_kw(frame_lengths))
         fl = self._last_fl
         y = torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(self.device, torch.int64).contiguous()
@@ -399,7 +428,9 @@ class Model(Handle):
         if y.shape != (B, self._cfg.max_label_len):
             raise ValueError(f"labels must be [B,{self._cfg.max_label_len}] padded with {self.C - 1}")
         mw = self._mwer_begin_step(B)
-        if mw is not None:
+        if kd is not None:
+            self._kd_loss_backward(kd, mw, rows, logits, y, B, loss_scale, fl)
+        elif mw is not None:
             self._mwer_loss_backward(mw, logits, y, B, loss_scale, fl)
         elif fl is None:
             _lib.check(self._lib.ishara_loss_backward(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf),
@@ -434,7 +465,7 @@ class Model(Handle):
         self.optimizer.iterations += 1
         self._steps += 1
 
-    def train_on_batch(self, x, y, seed: Optional[int] = None, allreduce: bool = True, frame_lengths=None) -> torch.Tensor:
+    def train_on_batch(self, x, y, seed: Optional[int] = None, allreduce: bool = True, frame_lengths=None, teacher_logits=None) -> torch.Tensor:
         """One Keras train_step (c12): forward, CTC, backward, [RCCL grad all-reduce], update.
         Returns the device loss tensor (no host sync).  `allreduce=False` skips the gradient exchange (bench.py's diagnostic
         of the exposed all-reduce time; replicas diverge — never for training).
@@ -451,15 +482,20 @@ class Model(Handle):
 
         With `optimizer.awp_delta` set and `optimizer.iterations` >= `awp_start_step`, the gradient of every (micro)batch on every path
         above is the adversarial one (_loss_and_gradients_step: two passes around ishara_awp_perturb / ishara_awp_restore); the loss
-        returned is the first pass's, the all-reduce stays where it is, behind the second pass."""
+        returned is the first pass's, the all-reduce stays where it is, behind the second pass.
+
+        With `optimizer.kd_weight` > 0 and `optimizer.iterations` >= `kd_start_step`, the gradient of every (micro)batch on every path above
+        carries the distillation term (ishara_amd/kd.py).  The teacher of set_teacher runs once per call, in inference mode on the step's
+        stream, in front of the student's forward; AWP's second pass reuses its rows.  `teacher_logits` (fp32 [B,T,C] on the device: an
+        offline-cached teacher) stands in for it."""
         from . import parallel
         k, clip, skip = self.optimizer.train_options()
         self._not_while_averaged("train_on_batch")
         if k > 1 or clip > 0.0 or skip or self._micro:
-            return self._train_microbatch(x, y, seed, allreduce, k, clip, skip, frame_lengths)
+            return self._train_microbatch(x, y, seed, allreduce, k, clip, skip, frame_lengths, teacher_logits)
         world = parallel.world_size()
         if not allreduce:
-            loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths)
+            loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths, teacher_logits=teacher_logits)
             self.apply_gradients()
             return loss
         overlap = world > 1 and parallel.overlap_enabled()
@@ -469,7 +505,7 @@ class Model(Handle):
             # replicas share the weight-initialisation seed but draw independent dropout / drop-path masks for their shards,
             # like the reference's replicas (tf.distribute / nn.DataParallel keep per-replica RNG streams)
             seed = ((self._step_seed + 0x9E3779B1 * self._steps) ^ (parallel.rank() * 0x85EBCA6B)) & 0xFFFFFFFF
-        loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths)
+        loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths, teacher_logits=teacher_logits)
         if overlap:
             parallel.allreduce_buckets_(self)          # ranges of the gradient reduced on a side stream as the backward pass finishes them
         elif world > 1:
@@ -477,7 +513,7 @@ class Model(Handle):
         self.apply_gradients()
         return loss
 
-    def _train_microbatch(self, x, y, seed, allreduce, k, clip, skip, frame_lengths=None) -> torch.Tensor:
+    def _train_microbatch(self, x, y, seed, allreduce, k, clip, skip, frame_lengths=None, teacher_logits=None) -> torch.Tensor:
         """microbatch `_micro` of a cycle of k; the k-th one ends the cycle with all-reduce, statistics and the step"""
         from . import parallel
         world = parallel.world_size()
@@ -490,7 +526,7 @@ class Model(Handle):
             seed = (self._step_seed + 0x9E3779B1 * (self._steps * k + self._micro)) & 0xFFFFFFFF
             if world > 1:
                 seed = (seed ^ (parallel.rank() * 0x85EBCA6B)) & 0xFFFFFFFF
-        loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths, ends_cycle=self._micro + 1 >= k)
+        loss = self._loss_and_gradients_step(x, y, seed, 1.0 / world, frame_lengths, ends_cycle=self._micro + 1 >= k, teacher_logits=teacher_logits)
         src = self.grads[:self.n_train]
         if k > 1:
             if self._grad_acc is None:
@@ -617,6 +653,17 @@ class Model(Handle):
 
     def _mwer_loss_backward(self, opts: dict, logits, y, B: int, loss_scale: float, fl) -> None:
         """search (no LM) -> exact scores -> weights -> ishara_loss_backward_nbest, all on the current stream; nothing waits"""
+        m, lib, st = self._mwer, self._lib, _stream()
+        N, T = m["key"][0], self.T
+        self._mwer_prepare(opts, logits, y, B)
+        _lib.check(lib.ishara_loss_backward_nbest(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf), _lib.ptr(self._nll_buf),
+                                                  C.c_float(loss_scale * opts["mwer_ctc_weight"]), _lib.ptr(fl), _lib.ptr(m["idx"]), _lib.ptr(m["len"]), N, T,
+                                                  m["max_len"], _lib.ptr(m["coef"]), C.c_float(loss_scale * opts["mwer_weight"]), _lib.ptr(m["grad_ws"]), st),
+                   "ishara_loss_backward_nbest")
+        m["B"] = B
+
+    def _mwer_prepare(self, opts: dict, logits, y, B: int) -> None:
+        """the n-best list of the step's logits, its exact scores and the weights coef, into the buffers of _mwer_begin_step"""
         from . import ctc_beam, mwer
         m, lib, st = self._mwer, self._lib, _stream()
         N, W = m["key"]
@@ -630,11 +677,6 @@ class Model(Handle):
         m["tgt"][:B] = torch.where(y == Cn - 1, torch.full_like(y, PAD_TOKEN_IDX), y).to(torch.int32)
         mwer.launch_weights(lib, m["idx"], m["len"], m["logp"], m["status"], B, N, T, m["tgt"], L, m["it"], 1 if opts["mwer_normalise"] else 0,
                             m["dist"], m["post"], m["risk"], m["coef"], m["tlen"], st)
-        _lib.check(lib.ishara_loss_backward_nbest(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf), _lib.ptr(self._nll_buf),
-                                                  C.c_float(loss_scale * opts["mwer_ctc_weight"]), _lib.ptr(fl), _lib.ptr(m["idx"]), _lib.ptr(m["len"]), N, T,
-                                                  m["max_len"], _lib.ptr(m["coef"]), C.c_float(loss_scale * opts["mwer_weight"]), _lib.ptr(m["grad_ws"]), st),
-                   "ishara_loss_backward_nbest")
-        m["B"] = B
 
     def mwer_stats(self) -> Dict[str, float]:
         """The last step that added the risk term, read on request (one device-to-host copy): risk, the mean expected distance of the
@@ -648,6 +690,115 @@ class Model(Handle):
         has, top = np.isfinite(risk), dist[:, 0] >= 0
         return dict(risk=float(risk[has].mean()) if has.any() else float("nan"), top_distance=float(dist[top, 0].mean()) if top.any() else float("nan"),
                     live_slots=int((dist >= 0).sum()), clips=int(has.sum()))
+
+    # ------------------------------------------------------------------ knowledge distillation from a teacher (ishara_amd/kd.py)
+    def set_teacher(self, teacher, weights=None, mode: str = "log-linear"):
+        """Attaches the teacher of optimizer.kd_weight > 0.  `teacher`: a Model with this model's T, C and input features (any width, depth
+        or dtype); a list of 1..8 such models, fused per batch by ensemble.combine_logits with `weights` (None: uniform) and `mode`
+        ("log-linear" or "linear"); or a callable (x [B,T,F] fp32 on the device, frame_lengths or None) -> fp32 [B,T,C] device tensor of
+        logits or log-probabilities.  None detaches.  The teacher is not part of save_state."""
+        if teacher is None:
+            self._teacher = None
+            return self
+        if isinstance(teacher, Model) or (isinstance(teacher, (list, tuple)) and all(isinstance(t, Model) for t in teacher)):
+            from . import ensemble
+            models = [teacher] if isinstance(teacher, Model) else list(teacher)
+            if not 1 <= len(models) <= ensemble.MAX_MODELS:
+                raise ValueError(f"{len(models)} teacher models: the fusion takes 1..{ensemble.MAX_MODELS}")
+            for i, t in enumerate(models):
+                if (t.T, t.C, t.F) != (self.T, self.C, self.F):
+                    raise ValueError(f"teacher {i} has (T, C, F) = {(t.T, t.C, t.F)}, the student {(self.T, self.C, self.F)}: distillation needs the same "
+                                     "frames, alphabet and input features")
+                if getattr(t, "device", None) != getattr(self, "device", None):
+                    raise ValueError(f"teacher {i} lives on {getattr(t, 'device', None)}, the student on {getattr(self, 'device', None)}")
+            md = {"log-linear": "log_linear", "log_linear": "log_linear", "linear": "linear"}.get(mode)
+            if md is None:
+                raise ValueError(f"mode must be 'log-linear' or 'linear', got {mode!r}")
+            if len(models) == 1 and weights is not None:
+                ensemble.normalise_weights(weights, 1)
+            w = ensemble.normalise_weights(weights, len(models)) if len(models) > 1 else None
+            self._teacher = ("models", models, w, md)
+        elif callable(teacher):
+            if weights is not None:
+                raise ValueError("weights belong to a list of teacher models, not to a callable")
+            self._teacher = ("callable", teacher)
+        else:
+            raise ValueError(f"teacher must be a Model, a list of Models, a callable or None, got {type(teacher).__name__}")
+        return self
+
+    def _kd_begin_step(self):
+        """The checked kd_* options when this step adds the distillation term (optimizer.kd_weight > 0 and optimizer.iterations has reached
+        kd_start_step), else None (and then nothing of it is touched, allocated or launched).  The first such step allocates kl_frame
+        and kl_clip for max_batch clips."""
+        o = self.optimizer
+        if not o.kd_weight:
+            return None
+        opts = o.kd_options()
+        if opts["kd_weight"] == 0 or o.iterations < opts["kd_start_step"]:
+            return None
+        if self._kd is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self._kd = dict(kl_frame=torch.empty((self.max_batch, self.T), **f32), kl_clip=torch.empty((self.max_batch,), **f32), B=0, mean=False)
+        return opts
+
+    def _teacher_rows(self, x, frame_lengths, teacher_logits) -> torch.Tensor:
+        """The teacher's rows [B,T,C] fp32 of this (micro)batch on the current stream, in inference mode: teacher_logits when given, else
+        one forward of every attached model (fused by combine_logits when there are several), or one call of the callable."""
+        x = self._as_input(x)
+        B = x.shape[0]
+        want = (B, self.T, self.C)
+        if teacher_logits is None and self._teacher is None:
+            raise _lib.IsharaError("distillation is on (optimizer.kd_weight > 0 and kd_start_step reached) but no teacher is attached: call "
+                                   "set_teacher(...) or pass teacher_logits= (a restored state holds the options, never the teacher)")
+        with torch.no_grad():
+            if teacher_logits is not None:
+                rows, what = teacher_logits, "teacher_logits"
+            elif self._teacher[0] == "callable":
+                rows, what = self._teacher[1](x, self._as_frame_lengths(frame_lengths, B)), "the teacher's output"
+            else:
+                _, models, w, md = self._teacher
+                outs = [t(x, training=False, **({} if frame_lengths is None or t._cfg.dtype == _lib.F16 else dict(frame_lengths=frame_lengths))) for t in models]
+                if len(outs) == 1:
+                    rows, what = outs[0], "the teacher's logits"
+                else:
+                    from . import ensemble
+                    rows, what = ensemble.combine_logits(outs, w, md), "the fused teachers' rows"
+        if not isinstance(rows, torch.Tensor) or tuple(rows.shape) != want or rows.dtype != torch.float32 or rows.device != self.device:
+            got = f"{tuple(rows.shape)} {rows.dtype} on {rows.device}" if isinstance(rows, torch.Tensor) else type(rows).__name__
+            raise ValueError(f"{what} must be a float32 {list(want)} tensor on {self.device}, got {got}")
+        return rows.detach().contiguous()
+
+    def _kd_loss_backward(self, opts: dict, mw: Optional[dict], rows, logits, y, B: int, loss_scale: float, fl) -> None:
+        """ishara_loss_backward_kd on the current stream: the CTC kernel, the n-best stage when minimum-risk training is active as well
+        (its search, scores and weights first), then the distillation stage; nothing waits"""
+        from . import kd as KD
+        k = self._kd
+        tau = opts["kd_temperature"]
+        ctc_scale = loss_scale * opts["kd_ctc_weight"]
+        stage = _lib.KdStage(rows.data_ptr(), KD.inverse_temperature(tau), 1 if opts["kd_normalise"] else 0, loss_scale * opts["kd_weight"] * tau,
+                             k["kl_frame"].data_ptr(), k["kl_clip"].data_ptr())
+        nb = None
+        if mw is not None:
+            m = self._mwer
+            self._mwer_prepare(mw, logits, y, B)
+            ctc_scale *= mw["mwer_ctc_weight"]
+            nb = C.byref(_lib.NbestStage(m["idx"].data_ptr(), m["len"].data_ptr(), m["key"][0], self.T, m["max_len"], m["coef"].data_ptr(),
+                                         loss_scale * mw["mwer_weight"], m["grad_ws"].data_ptr()))
+        _lib.check(self._lib.ishara_loss_backward_kd(self._h, _lib.ptr(logits), _lib.ptr(y), B, _lib.ptr(self._loss_buf), _lib.ptr(self._nll_buf),
+                                                     C.c_float(ctc_scale), _lib.ptr(fl), C.byref(stage), nb, _stream()), "ishara_loss_backward_kd")
+        if mw is not None:
+            self._mwer["B"] = B
+        k["B"], k["mean"] = B, bool(opts["kd_normalise"])
+
+    def kd_stats(self) -> Dict[str, float]:
+        """The last step that added the distillation term, read on request (one device-to-host copy): kl, the batch's mean of the clips'
+        KL(teacher || student) at the step's temperature (per frame with kd_normalise, summed over the T frames without); per_frame,
+        which of the two; clips, the batch size."""
+        if self._kd is None or not self._kd["B"]:
+            raise _lib.IsharaError("kd_stats: no step has run with distillation (optimizer.kd_weight > 0 and kd_start_step reached)")
+        B = self._kd["B"]
+        kl = self._kd["kl_clip"][:B].cpu().numpy().astype(np.float64)
+        return dict(kl=float(kl.mean()), per_frame=self._kd["mean"], clips=int(B))
 
     # ------------------------------------------------------------------ adversarial weight perturbation (csrc/awp.hip)
     def _awp_begin_step(self):
@@ -672,7 +823,7 @@ class Model(Handle):
             self._awp_backup = torch.empty(self.n_train, **f32)
         return opts
 
-    def _loss_and_gradients_step(self, x, y, seed, loss_scale: float, frame_lengths, ends_cycle: bool = True) -> torch.Tensor:
+    def _loss_and_gradients_step(self, x, y, seed, loss_scale: float, frame_lengths, ends_cycle: bool = True, teacher_logits=None) -> torch.Tensor:
         """The gradient of one (micro)batch of train_on_batch -> its loss tensor.  Without AWP: loss_and_gradients, as ever.  With it:
         pass 1 at loss scale 1 (the perturbation does not depend on the world size; no collective), ishara_awp_perturb on the trainable
         prefix by that gradient, pass 2 at the perturbed weights with the same seed (the dropout and drop-path masks the adversary was
@@ -681,6 +832,16 @@ class Model(Handle):
         perturbation, and behind the restore by the optimizer step that follows, or here when the microbatch does not end its cycle
         (ends_cycle False).  No host synchronise."""
         self._pg_begin_step()          # a change of the groups in the middle of a cycle is refused before any work
+        if self._kd_begin_step() is None:
+            return self._loss_and_gradients_passes(x, y, seed, loss_scale, frame_lengths, ends_cycle)
+        self._kd_rows = self._teacher_rows(x, frame_lengths, teacher_logits)      # once per (micro)batch: both of AWP's passes read these rows
+        try:
+            return self._loss_and_gradients_passes(x, y, seed, loss_scale, frame_lengths, ends_cycle)
+        finally:
+            self._kd_rows = None
+
+    def _loss_and_gradients_passes(self, x, y, seed, loss_scale: float, frame_lengths, ends_cycle: bool) -> torch.Tensor:
+        """the one pass, or AWP's two, of _loss_and_gradients_step"""
         awp = self._awp_begin_step()
         if awp is None:
             return self.loss_and_gradients(x, y, seed=seed, loss_scale=loss_scale, **_fl_kw(frame_lengths))[0]
@@ -830,7 +991,7 @@ class Model(Handle):
                            iterations=o.iterations, steps=self._steps, step_seed=self._step_seed, learning_rate=float(o.learning_rate),
                            weight_decay=float(o.weight_decay), apply_weight_decay=o.apply_weight_decay, global_clipnorm=o.global_clipnorm,
                            skip_nonfinite=o.skip_nonfinite, accumulate_steps=o.accumulate_steps, skipped=skipped, **self._ema_state_entries(), **self._awp_state_entries(),
-                           param_groups=o.group_options(), **self._mwer_state_entries())
+                           param_groups=o.group_options(), **self._mwer_state_entries(), **self._kd_state_entries())
         return TS.save_state_file(path, st)
 
     def _ema_state_entries(self) -> dict:
@@ -846,6 +1007,11 @@ class Model(Handle):
         opts = self.optimizer.mwer_options()
         return dict(mwer=opts) if opts["mwer_nbest"] > 0 else {}
 
+    def _kd_state_entries(self) -> dict:
+        """what save_state adds for distillation: its five options as one key when it is configured, nothing otherwise; never the teacher"""
+        opts = self.optimizer.kd_options()
+        return dict(kd=opts) if opts["kd_weight"] > 0 else {}
+
     def _awp_state_entries(self) -> dict:
         """what save_state adds for adversarial weight perturbation: its four options when it is configured (it has no device state
         beyond them), nothing otherwise"""
@@ -858,8 +1024,8 @@ class Model(Handle):
         """Restores what save_state wrote into this model (same architecture: the entry list is checked).  A file with a moving average
         restores it, its update count and the four ema settings; a file without one leaves the settings alone and, with optimizer.use_ema
         on, starts a fresh average at the loaded weights with 0 updates.  A file with the options of adversarial weight perturbation sets
-        them; a file without them leaves them alone, and so with the optimizer's parameter groups and the options of minimum-risk
-        training."""
+        them; a file without them leaves them alone, and so with the optimizer's parameter groups, the options of minimum-risk
+        training and those of distillation (whose teacher is never in the file: attach it again with set_teacher)."""
         from . import train_state as TS
         self._not_while_averaged("load_state")
         st = TS.load_state_file(path, self.entries)
@@ -878,6 +1044,9 @@ class Model(Handle):
             o.param_groups = st["param_groups"]
         if "mwer" in st:
             for k, v in st["mwer"].items():
+                setattr(o, k, v)
+        if "kd" in st:              # the options only: the teacher is attached again with set_teacher
+            for k, v in st["kd"].items():
                 setattr(o, k, v)
         if "awp_delta" in st:
             o.awp_delta, o.awp_eps, o.awp_start_step, o.awp_relative = st["awp_delta"], st["awp_eps"], st["awp_start_step"], st["awp_relative"]

@@ -9,32 +9,14 @@
 // the class row).  The other samples of the batch are computed exactly as if that sample were not there (one workgroup per sample, nothing
 // shared): their nll, dlogits and dlb are bit-identical.  The caller decides what an nll of 1e30 means (tf.nn.ctc_loss returns inf there).
 #include <type_traits>
-#include "kernels.h"
+#include "ctc_lattice.h"                                // the lattice arithmetic (lse3, the state set-up, the emission pipeline, the frame steps)
 
-
-static inline int ctc_ns(int L) { return (2 * L + 1 + 63) / 64; }            // lattice states per lane of the recursion wave
 // LDS of one workgroup: lse[T] and ext[64 NS] are requested at launch; cls (4 KiB), s_logp, s_len and s_bad are static.  The kernel is launched
 // without a raised dynamic-LDS attribute, so static + dynamic stay within the 64 KiB every HIP launch is granted.
 static constexpr size_t CTC_LDS_STATIC = 4 * 4 * 64 * sizeof(float) + 2 * sizeof(double), CTC_LDS_LAUNCH = 65536;
 size_t ctc_lds_bytes(int T, int L) { return (size_t)T * sizeof(float) + (size_t)64 * ctc_ns(L) * sizeof(int); }
 size_t ctc_lds_limit() { return CTC_LDS_LAUNCH - CTC_LDS_STATIC; }
 size_t ctc_workspace_floats(int B, int T, int L) { return 4 * (size_t)B * T * 64 * ctc_ns(L); }   // two fp64 lattices [B][T][64*NS]: alpha, beta sums
-
-#define CTC_NEG (-1e30)
-// log(e^a + e^b + e^c) with the running state in fp64 and the transcendentals in fp32: the lattice values reach ~-1700 at
-// T=384 where an fp32 ulp is 1.2e-4 and the drift over T frames reaches 1e-3 relative in the posteriors; fp64 add/max keeps
-// the drift at the 1e-6 level while exp/log only ever see small-magnitude differences.  (A scaled PROBABILITY-space
-// recursion is not an option: the state vector of one frame spans > 250 decades on random logits, tools/ notes in DESIGN.md.)
-DEVI double lse3(double a, double b, double c) {
-    // branch-free: with all three terms dead (m = CTC_NEG) the exponentials are exp(0) and the result is discarded by the select — an early
-    // return was an exec-mask branch on the recursions' dependency chain
-    const double m = fmax(a, fmax(b, c));
-    const float sum = __expf((float)(a - m)) + __expf((float)(b - m)) + __expf((float)(c - m));
-    const double r = m + (double)__logf(sum);
-    return m <= -1e29 ? CTC_NEG : r;
-}
-DEVI double shfl_up_d(double v, int d) { return __shfl_up(v, d, 64); }
-DEVI double shfl_down_d(double v, int d) { return __shfl_down(v, d, 64); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // One 256-thread workgroup per sample:
@@ -90,13 +72,7 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
         for (int i = 0; i < L; ++i) { const int64_t v = lab[i]; n += (v != blank) ? 1 : 0; bad |= (v < 0 || v >= C) ? 1 : 0; }
         s_len = n; s_bad = bad;
     }
-    for (int t = tid; t < Tn; t += 256) {
-        float m = -1e30f;
-        for (int c = 0; c < C; ++c) m = fmaxf(m, lg[(size_t)t * C + c]);
-        float a = 0.f;
-        for (int c = 0; c < C; ++c) a += expf(lg[(size_t)t * C + c] - m);
-        lse[t] = m + logf(a);
-    }
+    for (int t = tid; t < Tn; t += 256) lse[t] = ctc_row_lse(lg + (size_t)t * C, C);
     for (int s = tid; s < SP; s += 256) {
         const int64_t v = (s < 2 * L + 1 && (s & 1)) ? lab[s >> 1] : (int64_t)blank;
         ext[s] = (v < 0 || v >= C) ? blank : (int)v;
@@ -107,149 +83,10 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
     // The recursions, instantiated for a COMPILE-TIME number NK of occupied state registers per lane (1: labels of up to 31 symbols, 2: up to 63)
     // so that the per-k loops are straight-line code; NK = 0 keeps the run-time count (longer labels).  The block picks its instantiation below.
     auto recursions = [&](auto nkc) {
-        constexpr int NK = decltype(nkc)::value;
-        constexpr int KM = NK ? NK : NS;
-        const int wave = tid >> 6;
-        // state s = lane + 64 k (k < NS): a label of up to 31 symbols (S <= 63) occupies k = 0 only, and the recursion skips the
-        // other k (wave-uniform nk) -- a third of the work of NS consecutive states per lane; lattice rows are written as
-        // contiguous 512-byte pieces.  The s-1 / s-2 neighbours come from lanes l-1 / l-2 by a rotation; lanes 0 (and 1) take
-        // them from lanes 63 (and 62) of the previous k.
-        const int nk = NK ? NK : ((S + 63) >> 6);
-        bool act[NS], skip_bw[NS], skip_fw[NS];
-        int my[NS];
-#pragma unroll
-        for (int k = 0; k < KM; ++k) {
-            const int s = lane + 64 * k;
-            my[k] = ext[s];
-            act[k] = s < S;
-            skip_bw[k] = act[k] && s >= 2 && my[k] != blank && my[k] != ext[s - 2];                   // s-2 -> s
-            skip_fw[k] = s + 2 < S && ext[s + 2] != blank && ext[s + 2] != my[k];                     // s -> s+2
-        }
-        float em[8][NS], emn[8][NS];
-        // RAW logits of frames t0, t0 + dir, .., t0 + 7 dir (loads only: subtracting lse here made hipcc wait for the loads right
-        // after issuing them)
-        auto gather = [&](int t0, int dir, float (&dst)[8][NS]) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = min(max(t0 + dir * u, 0), Tn - 1);
-#pragma unroll
-                for (int k = 0; k < KM; ++k)
-                    if (NK != 0 || k < nk) dst[u][k] = lg[(size_t)t * C + my[k]];
-            }
-        };
-        // emission log-probabilities of a gathered group, one group later: the loads have landed by then (the empty asm keeps the
-        // subtraction from being scheduled up to the loads)
-        auto settle = [&](int t0, int dir, float (&src)[8][NS], float (&dst)[8][NS]) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float ls = lse[min(max(t0 + dir * u, 0), Tn - 1)];
-#pragma unroll
-                for (int k = 0; k < KM; ++k)
-                    if (NK != 0 || k < nk) { asm volatile("" : "+v"(src[u][k])); dst[u][k] = src[u][k] - ls; }
-            }
-        };
-      if (wave == 0) {
-        // ---- alpha ----
-        double a[NS];
-#pragma unroll
-        for (int k = 0; k < KM; ++k) {
-            const int s = lane + 64 * k;
-            a[k] = (act[k] && (s == 0 || (s == 1 && len > 0))) ? (double)(lg[my[k]] - lse[0]) : CTC_NEG;
-            if (NK != 0 || k < nk) Gw[s] = a[k];
-        }
-        gather(1, 1, emn);
-        settle(1, 1, emn, em);
-        for (int t0 = 1; t0 < Tn; t0 += 8) {
-            if (t0 + 8 < Tn) gather(t0 + 8, 1, emn);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = t0 + u;
-                if (t < Tn) {
-                    double r1[NS], r2[NS], n[NS];
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (NK != 0 || k < nk) { r1[k] = __shfl(a[k], (lane + 63) & 63, 64); r2[k] = __shfl(a[k], (lane + 62) & 63, 64); }
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (NK != 0 || k < nk) {
-                            const double a1 = lane >= 1 ? r1[k] : (k >= 1 ? r1[k >= 1 ? k - 1 : 0] : CTC_NEG);
-                            const double a2 = lane >= 2 ? r2[k] : (k >= 1 ? r2[k >= 1 ? k - 1 : 0] : CTC_NEG);
-                            double v = act[k] ? lse3(a[k], a1, skip_bw[k] ? a2 : CTC_NEG) : CTC_NEG;
-                            if (v > -1e29) v += (double)em[u][k];
-                            n[k] = v;
-                        }
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (NK != 0 || k < nk) { a[k] = n[k]; Gw[(size_t)t * SP + lane + 64 * k] = n[k]; }
-                }
-            }
-            if (t0 + 8 < Tn) settle(t0 + 8, 1, emn, em);
-        }
-        // log p(y | x) = logsumexp(alpha[S-1], alpha[S-2]): both live in (at most two) lanes; reduce max then sum over the wave
-        double logp;
-        {
-            double cand = CTC_NEG, cand2 = CTC_NEG;
-#pragma unroll
-            for (int k = 0; k < KM; ++k) {
-                const int s = lane + 64 * k;
-                if (s == S - 1) cand = a[k];
-                if (s == S - 2 && len > 0) cand2 = a[k];
-            }
-            double m = fmax(cand, cand2);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-            float e = 0.f;
-            if (m > -1e29) e = ((cand > -1e29) ? __expf((float)(cand - m)) : 0.f) + ((cand2 > -1e29) ? __expf((float)(cand2 - m)) : 0.f);
-            e = wave_sum(e);
-            logp = (m > -1e29 && !s_bad) ? m + (double)__logf(e) : CTC_NEG;
+        ctc_lattice_waves<NS, decltype(nkc)::value>(lg, lse, ext, S, len, Tn, C, blank, Gw, Hw, SP, lane, tid >> 6, [&](double lp) {
+            const double logp = s_bad ? CTC_NEG : lp;
             if (lane == 0) { nll[b] = (float)(-logp); s_logp = logp; }
-        }
-      } else {
-        // ---- beta (with emission): bt = beta_{t+1}; stores bsum_t[s] = logsumexp of the successors' betas ----
-        double bt[NS];
-#pragma unroll
-        for (int k = 0; k < KM; ++k) bt[k] = CTC_NEG;
-        gather(Tn - 1, -1, emn);
-        settle(Tn - 1, -1, emn, em);
-        for (int tb = Tn - 1; tb >= 0; tb -= 8) {
-            if (tb - 8 >= 0) gather(tb - 8, -1, emn);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = tb - u;
-                if (t >= 0) {
-                    double bsum[NS];
-                    if (t == Tn - 1) {
-#pragma unroll
-                        for (int k = 0; k < KM; ++k) {
-                            const int s = lane + 64 * k;
-                            bsum[k] = (act[k] && (s == S - 1 || (s == S - 2 && len > 0))) ? 0.0 : CTC_NEG;
-                        }
-                    } else {
-                        double d1[NS], d2[NS];
-#pragma unroll
-                        for (int k = 0; k < KM; ++k)
-                            if (NK != 0 || k < nk) { d1[k] = __shfl(bt[k], (lane + 1) & 63, 64); d2[k] = __shfl(bt[k], (lane + 2) & 63, 64); }
-#pragma unroll
-                        for (int k = 0; k < KM; ++k)
-                            if (NK != 0 || k < nk) {
-                                // successors s+1 / s+2: lanes 63 (and 62) take them from lanes 0 (and 1) of the next k (absent: no state)
-                                const bool nx = k + 1 < KM && k + 1 < nk;
-                                const double b1 = lane <= 62 ? d1[k] : (nx ? d1[k + 1 < KM ? k + 1 : k] : CTC_NEG);
-                                const double b2 = lane <= 61 ? d2[k] : (nx ? d2[k + 1 < KM ? k + 1 : k] : CTC_NEG);
-                                bsum[k] = act[k] ? lse3(bt[k], b1, skip_fw[k] ? b2 : CTC_NEG) : CTC_NEG;
-                            }
-                    }
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (NK != 0 || k < nk) {
-                            Hw[(size_t)t * SP + lane + 64 * k] = bsum[k];
-                            bt[k] = bsum[k] > -1e29 ? bsum[k] + (double)em[u][k] : CTC_NEG;
-                        }
-                }
-            }
-            if (tb - 8 >= 0) settle(tb - 8, -1, emn, em);
-        }
-      }
+        });
     };
     if (tid < 128) {
         const int nkb = (S + 63) >> 6;
@@ -259,8 +96,7 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
     }
     __threadfence_block();
     __syncthreads();
-    // ---- phase 3: state posteriors -> class posteriors by LDS scatter-add (one frame per wave at a time: O(T*S) work;
-    // a (frame, class) thread looping over the states was O(T*C*S) and took longer than both recursions), then the gradient
+    // ---- phase 3: state posteriors -> class posteriors by LDS scatter-add, then the gradient
     if (dlogits) {
         // four frames of a wave in flight together: the loop used to wait out one L2 round trip per frame (96 dependent trips per wave)
         constexpr int U = 4;
@@ -294,23 +130,14 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logi
             for (int u = 0; u < U; ++u) {
                 const int t = t0 + 4 * u;
                 if (t >= Tn) continue;                        // wave-uniform
-#pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    const int s = lane + 64 * k;
-                    if (s < S && al[u][k] > -1e29 && bs[u][k] > -1e29 && logp > -1e29) atomicAdd(&cls[wv][u][ext[s]], __expf((float)(al[u][k] + bs[u][k] - logp)));
-                }
+                ctc_post_add(cls[wv][u], [&](int k) { return ext[lane + 64 * k]; }, S, logp, al[u], bs[u], lane);
                 float gv = 0.f;
                 if (lane < C) {
                     const float sm = expf(lgv[u] - lse[t]);
                     gv = grad_scale * (sm - cls[wv][u][lane]);
                     dl[(size_t)t * C + lane] = gv;
                 }
-                if (dlb) {      // bf16 copy of the row, zero padded to 128 classes (MFMA operand of the classifier's dgrad / wgrad)
-                    const float lo = __shfl(gv, (2 * lane) & 63, 64), hi = __shfl(gv, (2 * lane + 1) & 63, 64);
-                    typedef __attribute__((ext_vector_type(2))) __bf16 ctc_bf2;
-                    ctc_bf2 pk; pk[0] = (__bf16)(lane < 32 ? lo : 0.f); pk[1] = (__bf16)(lane < 32 ? hi : 0.f);
-                    dlb[((size_t)b * Ts + t) * 64 + lane] = __builtin_bit_cast(uint32_t, pk);
-                }
+                if (dlb) store_dlb_row(dlb + ((size_t)b * Ts + t) * 64, gv, lane);
             }
         }
     }

@@ -19,15 +19,14 @@
 // Indices derived from data: the back-pointer is two bits, the state only ever decreases from S-1 and is clamped at 0, so frame_pos stays
 // in [-1, len); span bounds read back from memory are clamped to [0, T] before they index anything -- whatever the logits hold.
 #include <type_traits>
-#include "kernels.h"
+#include "ctc_lattice.h"                                // ctc_ns: the registers per lane of the lattice
 
 #define ALIGN_DEAD (-__builtin_huge_val())
-static inline int align_ns(int L) { return (2 * L + 1 + 63) / 64; }
 // LDS of one workgroup: (m_t, sum_t) [T] and ext [64 NS] always, the back-pointer rows [T][64] u16 on the fast path; the static part (label
 // length, reduction slots, the block-wide votes: 336 bytes) is below ALIGN_LDS_STATIC.  Above the 64 KiB every launch is granted the
 // kernel's limit is raised, up to the CU's 160 KiB.
 static constexpr size_t ALIGN_LDS_STATIC = 512, ALIGN_LDS_DEFAULT = 65536, ALIGN_LDS_MAX = 163840;
-static size_t align_lds_bytes(int T, int L, bool bp) { return (size_t)T * 8 + (size_t)256 * align_ns(L) + (bp ? (size_t)T * 128 : 0); }
+static size_t align_lds_bytes(int T, int L, bool bp) { return (size_t)T * 8 + (size_t)256 * ctc_ns(L) + (bp ? (size_t)T * 128 : 0); }
 bool ctc_align_bp_in_lds(int T, int L) { return align_lds_bytes(T, L, true) + ALIGN_LDS_STATIC <= ALIGN_LDS_MAX; }
 size_t ctc_align_workspace_bytes(int B, int T, int L) { return B == 0 ? 0 : (ctc_align_bp_in_lds(T, L) ? 128 : (size_t)B * T * 128); }
 
@@ -248,7 +247,7 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict_
 template <bool VL>
 static int launch_ctc_align_t(const float* logits, const int64_t* labels, int B, int T, int C, int L, int blank, void* ws, int* frame_pos, int* start,
                               int* end, float* conf, float* score, const int* frame_len, hipStream_t s) {
-    const int ns = align_ns(L);
+    const int ns = ctc_ns(L);
     if (ns < 1 || ns > 8 || C > 64) { ishara_set_error("ctc_align: L=%d (max 255) or C=%d (max 64) unsupported", L, C); return -1; }
     const bool fast = ctc_align_bp_in_lds(T, L);
     const size_t shmem = align_lds_bytes(T, L, fast);

@@ -2,9 +2,8 @@
 // definition in ishara_amd/mwer.py): G[b, t, k] = grad_scale * sum_n coef[b, n] * (softmax(logits[b, t])[k] - post_n[b, t, k]), post_n the CTC
 // class posterior of hypothesis n.  It is what minimum-risk (MWER) training adds to the CTC gradient.
 //
-// The device functions below are copies of ctc.hip's ctc_kernel (lse3, the lse[t] loop, the gather / settle pipeline, the alpha wave, the beta
-// wave that stores bsum, the LDS scatter-add of the state posteriors), as ctc_score.hip copied its alpha chain, so that N = 1, coef = 1 gives
-// that kernel's dlogits and dlb bit for bit; ctc.hip itself is untouched.
+// The lattice arithmetic is ctc_lattice.h's, as it is for ctc.hip's ctc_kernel, so N = 1, coef = 1 gives that kernel's dlogits and dlb bit
+// for bit.
 //
 // Two kernels, nothing shared between slots, no atomics on global memory:
 //   ng_lattice_kernel  grid (N, B), two waves: one slot's status (ishara_ctc_score_nbest's rule, plus bit 3 for a length above max_len), then
@@ -14,28 +13,16 @@
 //                      logp (fp64) and the slot's participation flag in the workspace's head.
 //   ng_grad_kernel     grid (ceil(T / 16), B), four waves, a frame per wave at a time, four frames in flight: for n ascending over the
 //                      participating slots the state posteriors exp(alpha + bsum - logp) are scatter-added to classes in LDS (ctc_kernel's
-//                      phase 3: the same instructions in the same order), acc = acc + coef * (softmax - post) in unfused fp32, then
+//                      phase 3: ctc_lattice.h's ctc_post_add), acc = acc + coef * (softmax - post) in unfused fp32, then
 //                      dlogits (= or +=) grad_scale * acc and the padded bf16 copy of the final row.
 // Workspace: 16 B * N (head, rounded up to 16) + 16 B * N * T * 64 * ceil((2 max_len + 1) / 64) bytes; every byte that is read was written by
 // the same call.  DESIGN.md §4 has the figures at the training shapes.
 #include <type_traits>
-#include "kernels.h"
+#include "ctc_lattice.h"
 
-#define NG_NEG (-1e30)
-// ctc.hip's lse3: fp64 state, fp32 transcendentals, branch-free
-DEVI double ng_lse3(double a, double b, double c) {
-    const double m = fmax(a, fmax(b, c));
-    const float sum = __expf((float)(a - m)) + __expf((float)(b - m)) + __expf((float)(c - m));
-    const double r = m + (double)__logf(sum);
-    return m <= -1e29 ? NG_NEG : r;
-}
-
-enum { NG_DEAD = 1, NG_NOALIGN = 2, NG_SYMBOL = 4, NG_LONG = 8 };
-
-static inline int ng_nsr(int max_len) { return (2 * max_len + 1 + 63) / 64; }           // occupied state registers of the longest slot
 static inline size_t ng_head_bytes(int B, int N) { return (((size_t)B * N * 12) + 15) / 16 * 16; }      // logp fp64 [B N], then part int32 [B N]
 size_t ctc_nbest_grad_lds_bytes(int T, int max_len) {
-    const int nsr = ng_nsr(max_len), ns = nsr <= 1 ? 1 : nsr <= 2 ? 2 : nsr <= 4 ? 4 : 8;
+    const int nsr = ctc_ns(max_len), ns = nsr <= 1 ? 1 : nsr <= 2 ? 2 : nsr <= 4 ? 4 : 8;
     return (size_t)T * sizeof(float) + (size_t)64 * ns * sizeof(int);
 }
 
@@ -60,32 +47,16 @@ __global__ __launch_bounds__(128) void ng_lattice_kernel(const float* __restrict
     const float cf = coef[slot];
     const bool skip = cf == 0.f;                        // +0 and -0: the slot takes no part
     if (skip && !logp_out && !status_out) {             // nobody asks for its score either: its row is not read
-        if (tid == 0) { ws_part[slot] = 0; ws_logp[slot] = NG_NEG; }
+        if (tid == 0) { ws_part[slot] = 0; ws_logp[slot] = CTC_NEG; }
         return;
     }
     const int len = hyp_len[slot];
     const int* hyp = hyp_idx + slot * Th;
-    // ishara_ctc_score_nbest's status, the first bit that applies (both waves compute it: nothing is shared before the barrier)
-    int st = 0;
-    if (len < 0) st = NG_DEAD;
-    else if (len > Th || len > 255 || len > max_len) st = NG_LONG;
-    else {
-        int bad = 0, rep = 0;
-        for (int i0 = 0; i0 < len; i0 += 64) {
-            const int i = i0 + lane;
-            const int v = i < len ? hyp[i] : 0;
-            const bool ok = v >= 0 && v < C && v != blank;
-            bad |= (i < len && !ok) ? 1 : 0;
-            rep += (i < len && i > 0 && v == hyp[i - 1]) ? 1 : 0;
-        }
-        bad = __any(bad);
-        rep = __popcll(__ballot(rep & 1)) + 2 * __popcll(__ballot(rep & 2)) + 4 * __popcll(__ballot(rep & 4));      // rep <= 4 per lane
-        if (bad) st = NG_SYMBOL;
-        else if (Tn < 1 || Tn < len + rep) st = NG_NOALIGN;
-    }
+    // ishara_ctc_score_nbest's status plus the max_len limit (both waves compute it: nothing is shared before the barrier)
+    const int st = ctc_hyp_status(hyp, len, Th, C, blank, Tn, lane, max_len);
     if (st) {                                           // workgroup-uniform
         if (tid == 0) {
-            ws_part[slot] = 0; ws_logp[slot] = NG_NEG;
+            ws_part[slot] = 0; ws_logp[slot] = CTC_NEG;
             if (logp_out) logp_out[slot] = -INFINITY;
             if (status_out) status_out[slot] = st;
         }
@@ -94,154 +65,21 @@ __global__ __launch_bounds__(128) void ng_lattice_kernel(const float* __restrict
     const float* lg = logits + (size_t)b * Ts * C;
     double* Gw = ws_lat + slot * 2 * (size_t)Ts * SPr;  // [Ts][SPr] alpha
     double* Hw = Gw + (size_t)Ts * SPr;                 // [Ts][SPr] bsum
-    for (int t = tid; t < Tn; t += 128) {               // ctc_kernel's loop: the same operations in the same order
-        float m = -1e30f;
-        for (int c = 0; c < C; ++c) m = fmaxf(m, lg[(size_t)t * C + c]);
-        float a = 0.f;
-        for (int c = 0; c < C; ++c) a += expf(lg[(size_t)t * C + c] - m);
-        lse[t] = m + logf(a);
-    }
+    for (int t = tid; t < Tn; t += 128) lse[t] = ctc_row_lse(lg + (size_t)t * C, C);
     const int S = 2 * len + 1;
-    for (int s = tid; s < SP; s += 128) ext[s] = (s < S && (s & 1)) ? hyp[s >> 1] : blank;      // the symbols passed the check above
+    for (int s = tid; s < SP; s += 128) ext[s] = ctc_hyp_symbol(hyp, S, blank, s);      // the symbols passed the check above
     __syncthreads();
 
     auto recursions = [&](auto nkc) {
-        constexpr int NK = decltype(nkc)::value;
-        constexpr int KM = NK ? NK : NS;
-        const int nk = NK ? NK : ((S + 63) >> 6);
-        bool act[NS], skip_bw[NS], skip_fw[NS];
-        int my[NS];
-#pragma unroll
-        for (int k = 0; k < KM; ++k) {
-            const int s = lane + 64 * k;
-            my[k] = ext[s];
-            act[k] = s < S;
-            skip_bw[k] = act[k] && s >= 2 && my[k] != blank && my[k] != ext[s >= 2 ? s - 2 : 0];       // s-2 -> s
-            skip_fw[k] = s + 2 < S && ext[s + 2 < SP ? s + 2 : s] != blank && ext[s + 2 < SP ? s + 2 : s] != my[k];      // s -> s+2
-        }
-        float em[8][NS], emn[8][NS];
-        auto gather = [&](int t0, int dir, float (&dst)[8][NS]) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = min(max(t0 + dir * u, 0), Tn - 1);
-#pragma unroll
-                for (int k = 0; k < KM; ++k)
-                    if (NK != 0 || k < nk) dst[u][k] = lg[(size_t)t * C + my[k]];
+        ctc_lattice_waves<NS, decltype(nkc)::value>(lg, lse, ext, S, len, Tn, C, blank, Gw, Hw, SPr, lane, wave, [&](double logp) {
+            if (lane == 0) {
+                const bool ok = logp > -1e29;
+                ws_logp[slot] = logp;
+                ws_part[slot] = (ok && !skip) ? 1 : 0;
+                if (logp_out) logp_out[slot] = ok ? -(float)(-logp) : -INFINITY;      // the loss writes (float)(-logp)
+                if (status_out) status_out[slot] = ok ? 0 : CTC_HYP_NOALIGN;
             }
-        };
-        auto settle = [&](int t0, int dir, float (&src)[8][NS], float (&dst)[8][NS]) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float ls = lse[min(max(t0 + dir * u, 0), Tn - 1)];
-#pragma unroll
-                for (int k = 0; k < KM; ++k)
-                    if (NK != 0 || k < nk) { asm volatile("" : "+v"(src[u][k])); dst[u][k] = src[u][k] - ls; }
-            }
-        };
-      if (wave == 0) {
-        // ---- alpha ----
-        double a[NS];
-#pragma unroll
-        for (int k = 0; k < KM; ++k) {
-            const int s = lane + 64 * k;
-            a[k] = (act[k] && (s == 0 || (s == 1 && len > 0))) ? (double)(lg[my[k]] - lse[0]) : NG_NEG;
-            if (NK != 0 || k < nk) Gw[s] = a[k];
-        }
-        gather(1, 1, emn);
-        settle(1, 1, emn, em);
-        for (int t0 = 1; t0 < Tn; t0 += 8) {
-            if (t0 + 8 < Tn) gather(t0 + 8, 1, emn);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = t0 + u;
-                if (t < Tn) {
-                    double r1[NS], r2[NS], nw[NS];
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (NK != 0 || k < nk) { r1[k] = __shfl(a[k], (lane + 63) & 63, 64); r2[k] = __shfl(a[k], (lane + 62) & 63, 64); }
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (NK != 0 || k < nk) {
-                            const double a1 = lane >= 1 ? r1[k] : (k >= 1 ? r1[k >= 1 ? k - 1 : 0] : NG_NEG);
-                            const double a2 = lane >= 2 ? r2[k] : (k >= 1 ? r2[k >= 1 ? k - 1 : 0] : NG_NEG);
-                            double v = act[k] ? ng_lse3(a[k], a1, skip_bw[k] ? a2 : NG_NEG) : NG_NEG;
-                            if (v > -1e29) v += (double)em[u][k];
-                            nw[k] = v;
-                        }
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (NK != 0 || k < nk) { a[k] = nw[k]; Gw[(size_t)t * SPr + lane + 64 * k] = nw[k]; }
-                }
-            }
-            if (t0 + 8 < Tn) settle(t0 + 8, 1, emn, em);
-        }
-        // log p(y | x) = logsumexp(alpha[S-1], alpha[S-2])
-        double cand = NG_NEG, cand2 = NG_NEG;
-#pragma unroll
-        for (int k = 0; k < KM; ++k) {
-            const int s = lane + 64 * k;
-            if (s == S - 1) cand = a[k];
-            if (s == S - 2 && len > 0) cand2 = a[k];
-        }
-        double m = fmax(cand, cand2);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-        float e = 0.f;
-        if (m > -1e29) e = ((cand > -1e29) ? __expf((float)(cand - m)) : 0.f) + ((cand2 > -1e29) ? __expf((float)(cand2 - m)) : 0.f);
-        e = wave_sum(e);
-        const double logp = m > -1e29 ? m + (double)__logf(e) : NG_NEG;
-        if (lane == 0) {
-            const bool ok = logp > -1e29;
-            ws_logp[slot] = logp;
-            ws_part[slot] = (ok && !skip) ? 1 : 0;
-            if (logp_out) logp_out[slot] = ok ? -(float)(-logp) : -INFINITY;      // the loss writes (float)(-logp)
-            if (status_out) status_out[slot] = ok ? 0 : NG_NOALIGN;
-        }
-      } else {
-        // ---- beta (with emission): bt = beta_{t+1}; stores bsum_t[s] = logsumexp of the successors' betas ----
-        double bt[NS];
-#pragma unroll
-        for (int k = 0; k < KM; ++k) bt[k] = NG_NEG;
-        gather(Tn - 1, -1, emn);
-        settle(Tn - 1, -1, emn, em);
-        for (int tb = Tn - 1; tb >= 0; tb -= 8) {
-            if (tb - 8 >= 0) gather(tb - 8, -1, emn);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = tb - u;
-                if (t >= 0) {
-                    double bsum[NS];
-                    if (t == Tn - 1) {
-#pragma unroll
-                        for (int k = 0; k < KM; ++k) {
-                            const int s = lane + 64 * k;
-                            bsum[k] = (act[k] && (s == S - 1 || (s == S - 2 && len > 0))) ? 0.0 : NG_NEG;
-                        }
-                    } else {
-                        double d1[NS], d2[NS];
-#pragma unroll
-                        for (int k = 0; k < KM; ++k)
-                            if (NK != 0 || k < nk) { d1[k] = __shfl(bt[k], (lane + 1) & 63, 64); d2[k] = __shfl(bt[k], (lane + 2) & 63, 64); }
-#pragma unroll
-                        for (int k = 0; k < KM; ++k)
-                            if (NK != 0 || k < nk) {
-                                const bool nx = k + 1 < KM && k + 1 < nk;
-                                const double b1 = lane <= 62 ? d1[k] : (nx ? d1[k + 1 < KM ? k + 1 : k] : NG_NEG);
-                                const double b2 = lane <= 61 ? d2[k] : (nx ? d2[k + 1 < KM ? k + 1 : k] : NG_NEG);
-                                bsum[k] = act[k] ? ng_lse3(bt[k], b1, skip_fw[k] ? b2 : NG_NEG) : NG_NEG;
-                            }
-                    }
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (NK != 0 || k < nk) {
-                            Hw[(size_t)t * SPr + lane + 64 * k] = bsum[k];
-                            bt[k] = bsum[k] > -1e29 ? bsum[k] + (double)em[u][k] : NG_NEG;
-                        }
-                }
-            }
-            if (tb - 8 >= 0) settle(tb - 8, -1, emn, em);
-        }
-      }
+        });
     };
     const int nkb = (S + 63) >> 6;
     if (NS >= 2 && nkb == 1) recursions(std::integral_constant<int, 1>{});
@@ -283,14 +121,7 @@ __global__ __launch_bounds__(256) void ng_grad_kernel(const float* __restrict__ 
     if (Tn < 1 || Tn > Ts) Tn = 0;
     const float* lg = logits + (size_t)b * Ts * C;
     float* dl = dlogits + (size_t)b * Ts * C;
-    if (tid < 4 * NG_U && tc + tid < Tn) {              // ctc_kernel's lse[t]: one thread per frame, the same operations in the same order
-        const int t = tc + tid;
-        float m = -1e30f;
-        for (int c = 0; c < C; ++c) m = fmaxf(m, lg[(size_t)t * C + c]);
-        float a = 0.f;
-        for (int c = 0; c < C; ++c) a += expf(lg[(size_t)t * C + c] - m);
-        s_lse[tid] = m + logf(a);
-    }
+    if (tid < 4 * NG_U && tc + tid < Tn) s_lse[tid] = ctc_row_lse(lg + (size_t)(tc + tid) * C, C);      // one thread per frame
     __syncthreads();
     float acc[NG_U], sm[NG_U];
 #pragma unroll
@@ -311,10 +142,7 @@ __global__ __launch_bounds__(256) void ng_grad_kernel(const float* __restrict__ 
             const double* Hw = Gw + (size_t)Ts * SPr;
             int exs[NS];
 #pragma unroll
-            for (int k = 0; k < NS; ++k) {
-                const int s = lane + 64 * k;
-                exs[k] = (s < S && (s & 1)) ? hyp[s >> 1] : blank;
-            }
+            for (int k = 0; k < NS; ++k) exs[k] = ctc_hyp_symbol(hyp, S, blank, lane + 64 * k);
             double al[NG_U][NS], bs[NG_U][NS];
 #pragma unroll
             for (int u = 0; u < NG_U; ++u) {
@@ -325,18 +153,14 @@ __global__ __launch_bounds__(256) void ng_grad_kernel(const float* __restrict__ 
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
                     const int s = lane + 64 * k;              // strided: coalesced 512-byte reads of the lattice rows
-                    al[u][k] = s < S ? ga[s] : NG_NEG; bs[u][k] = s < S ? gb[s] : NG_NEG;
+                    al[u][k] = s < S ? ga[s] : CTC_NEG; bs[u][k] = s < S ? gb[s] : CTC_NEG;
                 }
             }
 #pragma unroll
             for (int u = 0; u < NG_U; ++u) {
                 const int t = tc + wv + 4 * u;
                 if (t >= Tn) continue;                        // wave-uniform
-#pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    const int s = lane + 64 * k;
-                    if (s < S && al[u][k] > -1e29 && bs[u][k] > -1e29 && logp > -1e29) atomicAdd(&cls[wv][u][exs[k]], __expf((float)(al[u][k] + bs[u][k] - logp)));
-                }
+                ctc_post_add(cls[wv][u], [&](int k) { return exs[k]; }, S, logp, al[u], bs[u], lane);
                 // the class sums were added by OTHER lanes of this wave: without the fence the compiler may hand a lane that added nothing
                 // the 0 it stored itself (it did, at one register per lane)
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -359,25 +183,20 @@ __global__ __launch_bounds__(256) void ng_grad_kernel(const float* __restrict__ 
             } else if (accumulate) gv = dl[(size_t)t * C + lane];      // rows past the clip's end stay as they are
             else dl[(size_t)t * C + lane] = 0.f;
         }
-        if (dlb) {      // bf16 copy of the final row, zero padded to 128 classes (MFMA operand of the classifier's dgrad / wgrad)
-            const float lo = __shfl(gv, (2 * lane) & 63, 64), hi = __shfl(gv, (2 * lane + 1) & 63, 64);
-            typedef __attribute__((ext_vector_type(2))) __bf16 ng_bf2;
-            ng_bf2 pk; pk[0] = (__bf16)(lane < 32 ? lo : 0.f); pk[1] = (__bf16)(lane < 32 ? hi : 0.f);
-            dlb[((size_t)b * Ts + t) * 64 + lane] = __builtin_bit_cast(uint32_t, pk);
-        }
+        if (dlb) store_dlb_row(dlb + ((size_t)b * Ts + t) * 64, gv, lane);      // of the final row
     }
 }
 
 int64_t ctc_nbest_grad_workspace_bytes(int B, int T, int N, int max_len) {
     if (B < 0 || B > 65535 || T < 1 || T > 4096 || N < 1 || N > 64 || max_len < 1 || max_len > 255) return -1;
-    return (int64_t)ng_head_bytes(B, N) + (int64_t)16 * B * N * T * 64 * ng_nsr(max_len);
+    return (int64_t)ng_head_bytes(B, N) + (int64_t)16 * B * N * T * 64 * ctc_ns(max_len);
 }
 
 // arguments checked by the callers (ishara_ctc_nbest_grad below, ishara_loss_backward_nbest in keras_hybrid.hip)
 int launch_ctc_nbest_grad(const float* logits, int B, int T, int C, int blank, const int* hyp_idx, const int* hyp_len, int N, int Th, int max_len,
                           const int* frame_len, const float* coef, float grad_scale, float* dlogits, int accumulate, void* dlb, float* logp,
                           int* status, void* ws, hipStream_t s) {
-    const int nsr = ng_nsr(max_len), SPr = 64 * nsr;
+    const int nsr = ctc_ns(max_len), SPr = 64 * nsr;
     double* ws_logp = reinterpret_cast<double*>(ws);
     int* ws_part = reinterpret_cast<int*>(ws_logp + (size_t)B * N);
     double* ws_lat = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + ng_head_bytes(B, N));
@@ -396,11 +215,6 @@ int launch_ctc_nbest_grad(const float* logits, int B, int T, int C, int blank, c
     else NG_LAUNCH(8);
 #undef NG_LAUNCH
     return launch_rc();
-}
-
-static bool ng_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
 }
 
 extern "C" int64_t ishara_ctc_nbest_grad_workspace_bytes(int32_t B, int32_t T, int32_t N, int32_t max_len) {
@@ -428,7 +242,7 @@ int ctc_nbest_grad_check(const char* me, const float* logits, int B, int T, int 
         ishara_set_error("%s: misaligned buffer: every buffer must be 4-byte aligned", me); return -1;
     }
     if ((uintptr_t)ws % 16) { ishara_set_error("%s: misaligned workspace: it must be 16-byte aligned", me); return -1; }
-    if (ng_overlap(dlogits, (size_t)B * T * C * 4, logits, (size_t)B * T * C * 4)) { ishara_set_error("%s: dlogits overlaps logits", me); return -1; }
+    if (bytes_overlap(dlogits, (size_t)B * T * C * 4, logits, (size_t)B * T * C * 4)) { ishara_set_error("%s: dlogits overlaps logits", me); return -1; }
     return 0;
 }
 

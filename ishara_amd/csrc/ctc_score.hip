@@ -2,8 +2,7 @@
 // host twin in ishara_amd/rescore.py): logp[b, n] = log sum over the alignments of hypothesis n of prod_t softmax(logits[b, t])[path_t].
 //
 // It is the alpha chain of ctc.hip's ctc_kernel and nothing else: no lattice in memory, no beta wave, no gradient phase, no workspace.  The
-// device functions below are copies of that kernel's (lse3, the lse[t] loop, the gather / settle pipeline, the final log-sum over states
-// S-1 and S-2), so that logp == float32(-nll) of ishara_ctc_loss_ex bit for bit; ctc.hip itself is untouched.
+// chain's arithmetic is ctc_lattice.h's, as it is for that kernel, so logp == float32(-nll) of ishara_ctc_loss_ex bit for bit.
 //
 // One workgroup of CS_WAVES waves takes one clip and a group of `hpw` * CS_WAVES consecutive slots of its list:
 //   phase 0 (all threads)  lse[t] = logsumexp(logits[b, t]) for t < Tn into LDS, once per workgroup
@@ -15,115 +14,39 @@
 // larger hpw shares lse among more slots and serialises their chains.  DESIGN.md §3 has the measurement that picked the default.
 // LDS: lse[T] floats requested at launch (16 KiB at T = 4096), no static LDS: within the 64 KiB every launch is granted.
 #include <type_traits>
-#include "kernels.h"
+#include "ctc_lattice.h"
 
 static constexpr int CS_WAVES = 4;
 static int g_cs_hpw = 0;                                // 0: the default below
 extern "C" int ishara_debug_set_score_group(int32_t hyps_per_wave) { g_cs_hpw = hyps_per_wave < 0 ? 0 : (hyps_per_wave > 16 ? 16 : hyps_per_wave); return 0; }
 
-#define CS_NEG (-1e30)
-// ctc.hip's lse3: fp64 state, fp32 transcendentals, branch-free
-DEVI double cs_lse3(double a, double b, double c) {
-    const double m = fmax(a, fmax(b, c));
-    const float sum = __expf((float)(a - m)) + __expf((float)(b - m)) + __expf((float)(c - m));
-    const double r = m + (double)__logf(sum);
-    return m <= -1e29 ? CS_NEG : r;
-}
-
-enum { CS_DEAD = 1, CS_NOALIGN = 2, CS_SYMBOL = 4, CS_LONG = 8 };
-
 // the alpha chain of one hypothesis by one wave; NK: compile-time count of occupied state registers (0: run-time), as in ctc_kernel.
-// Two arrangements differ from ctc_kernel's and change no value: the k loop of a frame runs from the top register down and writes a[k] in
-// place (a[k]'s rotations are taken before it is overwritten and handed down to k - 1's step, so the r1 / r2 / n arrays are four scalars),
-// and the run-time path gathers U = 4 frames ahead instead of 8.  Both keep the NS = 8 instantiation, the one every list in the beam
-// search's layout at T > 127 gets, at half the registers, so that the short hypotheses of such a list run at a useful occupancy.
+// One arrangement differs from ctc_kernel's and changes no value: the run-time path gathers U = 4 frames ahead instead of 8.  With the
+// in-place frame step it keeps the NS = 8 instantiation, the one every list in the beam search's layout at T > 127 gets, at 164 registers,
+// so that the short hypotheses of such a list run at a useful occupancy.
 template <int NS, int NK>
 DEVI double cs_alpha(const float* __restrict__ lg, const float* __restrict__ lse, const int* __restrict__ hyp, int len, int Tn, int C, int blank,
                      int lane) {
-    constexpr int KM = NK ? NK : NS;
     constexpr int U = (NK || NS <= 2) ? 8 : 4;
     const int S = 2 * len + 1;
     const int nk = NK ? NK : ((S + 63) >> 6);
     bool act[NS], skip_bw[NS];
     int my[NS];
-#pragma unroll
-    for (int k = 0; k < KM; ++k) {
-        const int s = lane + 64 * k;
-        act[k] = s < S;
-        const bool sym = act[k] && (s & 1);             // odd states carry symbol s >> 1 (< len), the others the blank
-        my[k] = sym ? hyp[s >> 1] : blank;
-        const int prev = (sym && s >= 3) ? hyp[(s >> 1) - 1] : blank;
-        skip_bw[k] = act[k] && s >= 2 && my[k] != blank && my[k] != prev;                             // s-2 -> s
-    }
+    // the extended label sequence is read from the hypothesis row itself, no LDS copy
+    ctc_states<NK>([&](int i) { return hyp[i]; }, S, blank, lane, my, act, skip_bw);
     float em[U][NS], emn[U][NS];
-    auto gather = [&](int t0, float (&dst)[U][NS]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = min(max(t0 + u, 0), Tn - 1);
-#pragma unroll
-            for (int k = 0; k < KM; ++k)
-                if (NK != 0 || k < nk) dst[u][k] = lg[(size_t)t * C + my[k]];
-        }
-    };
-    auto settle = [&](int t0, float (&src)[U][NS], float (&dst)[U][NS]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float ls = lse[min(max(t0 + u, 0), Tn - 1)];
-#pragma unroll
-            for (int k = 0; k < KM; ++k)
-                if (NK != 0 || k < nk) { asm volatile("" : "+v"(src[u][k])); dst[u][k] = src[u][k] - ls; }
-        }
-    };
     double a[NS];
-#pragma unroll
-    for (int k = 0; k < KM; ++k) {
-        const int s = lane + 64 * k;
-        a[k] = (act[k] && (s == 0 || (s == 1 && len > 0))) ? (double)(lg[my[k]] - lse[0]) : CS_NEG;
-    }
-    gather(1, emn);
-    settle(1, emn, em);
+    ctc_alpha_init<NK>(lg, lse, len, lane, my, act, a);
+    ctc_gather<NK>(lg, C, Tn, nk, my, 1, 1, emn);
+    ctc_settle<NK>(lse, Tn, nk, 1, 1, emn, em);
     for (int t0 = 1; t0 < Tn; t0 += U) {
-        if (t0 + U < Tn) gather(t0 + U, emn);
+        if (t0 + U < Tn) ctc_gather<NK>(lg, C, Tn, nk, my, t0 + U, 1, emn);
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = t0 + u;
-            if (t < Tn) {
-                double top = a[0];
-#pragma unroll
-                for (int k = 1; k < KM; ++k)
-                    if (NK != 0 || k < nk) top = a[k];
-                double up1 = __shfl(top, (lane + 63) & 63, 64), up2 = __shfl(top, (lane + 62) & 63, 64);      // the rotations of the top register
-#pragma unroll
-                for (int k = KM - 1; k >= 0; --k)
-                    if (NK != 0 || k < nk) {
-                        double lo1 = CS_NEG, lo2 = CS_NEG;                                                     // the rotations of register k - 1
-                        if (k >= 1) { lo1 = __shfl(a[k >= 1 ? k - 1 : 0], (lane + 63) & 63, 64); lo2 = __shfl(a[k >= 1 ? k - 1 : 0], (lane + 62) & 63, 64); }
-                        const double a1 = lane >= 1 ? up1 : lo1;
-                        const double a2 = lane >= 2 ? up2 : lo2;
-                        double v = act[k] ? cs_lse3(a[k], a1, skip_bw[k] ? a2 : CS_NEG) : CS_NEG;
-                        if (v > -1e29) v += (double)em[u][k];
-                        a[k] = v;
-                        up1 = lo1; up2 = lo2;
-                    }
-            }
-        }
-        if (t0 + U < Tn) settle(t0 + U, emn, em);
+        for (int u = 0; u < U; ++u)
+            if (t0 + u < Tn) ctc_alpha_step_inplace<NK>(a, act, skip_bw, em[u], nk, lane);
+        if (t0 + U < Tn) ctc_settle<NK>(lse, Tn, nk, t0 + U, 1, emn, em);
     }
-    // log p(y | x) = logsumexp(alpha[S-1], alpha[S-2])
-    double cand = CS_NEG, cand2 = CS_NEG;
-#pragma unroll
-    for (int k = 0; k < KM; ++k) {
-        const int s = lane + 64 * k;
-        if (s == S - 1) cand = a[k];
-        if (s == S - 2 && len > 0) cand2 = a[k];
-    }
-    double m = fmax(cand, cand2);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-    float e = 0.f;
-    if (m > -1e29) e = ((cand > -1e29) ? __expf((float)(cand - m)) : 0.f) + ((cand2 > -1e29) ? __expf((float)(cand2 - m)) : 0.f);
-    e = wave_sum(e);
-    return m > -1e29 ? m + (double)__logf(e) : CS_NEG;
+    return ctc_alpha_final<NK>(a, S, len, lane);
 }
 
 template <int NS>
@@ -138,13 +61,7 @@ __global__ __launch_bounds__(CS_WAVES * 64) void ctc_score_kernel(const float* _
     if (frame_len) Tn = frame_len[b];
     if (Tn < 1 || Tn > Ts) Tn = 0;                      // no frames: never an index or a bound
     const float* lg = logits + (size_t)b * Ts * C;
-    for (int t = tid; t < Tn; t += CS_WAVES * 64) {     // ctc_kernel's loop: the same operations in the same order
-        float m = -1e30f;
-        for (int c = 0; c < C; ++c) m = fmaxf(m, lg[(size_t)t * C + c]);
-        float a = 0.f;
-        for (int c = 0; c < C; ++c) a += expf(lg[(size_t)t * C + c] - m);
-        cs_lse[t] = m + logf(a);
-    }
+    for (int t = tid; t < Tn; t += CS_WAVES * 64) cs_lse[t] = ctc_row_lse(lg + (size_t)t * C, C);
     __syncthreads();
     for (int j = 0; j < hpw; ++j) {
         const int n = n0 + j * CS_WAVES + wave;         // wave-uniform
@@ -152,30 +69,14 @@ __global__ __launch_bounds__(CS_WAVES * 64) void ctc_score_kernel(const float* _
         const size_t slot = (size_t)b * N + n;
         const int len = hyp_len[slot];
         const int* hyp = hyp_idx + slot * Th;
-        int st = 0;
-        if (len < 0) st = CS_DEAD;
-        else if (len > Th || len > 255) st = CS_LONG;
-        else {
-            int bad = 0, rep = 0;
-            for (int i0 = 0; i0 < len; i0 += 64) {
-                const int i = i0 + lane;
-                const int v = i < len ? hyp[i] : 0;
-                const bool ok = v >= 0 && v < C && v != blank;
-                bad |= (i < len && !ok) ? 1 : 0;
-                rep += (i < len && i > 0 && v == hyp[i - 1]) ? 1 : 0;
-            }
-            bad = __any(bad);
-            rep = __popcll(__ballot(rep & 1)) + 2 * __popcll(__ballot(rep & 2)) + 4 * __popcll(__ballot(rep & 4));      // rep <= 4 per lane
-            if (bad) st = CS_SYMBOL;
-            else if (Tn < 1 || Tn < len + rep) st = CS_NOALIGN;          // Tn = 0: no frames, not even for the empty hypothesis
-        }
-        double lp = CS_NEG;
+        int st = ctc_hyp_status(hyp, len, Th, C, blank, Tn, lane);
+        double lp = CTC_NEG;
         if (st == 0) {
             const int nkb = (2 * len + 1 + 63) >> 6;
             if (NS >= 2 && nkb == 1) lp = cs_alpha<NS, 1>(lg, cs_lse, hyp, len, Tn, C, blank, lane);
             else if (NS >= 3 && nkb == 2) lp = cs_alpha<NS, 2>(lg, cs_lse, hyp, len, Tn, C, blank, lane);
             else lp = cs_alpha<NS, 0>(lg, cs_lse, hyp, len, Tn, C, blank, lane);
-            if (!(lp > -1e29)) st = CS_NOALIGN;
+            if (!(lp > -1e29)) st = CTC_HYP_NOALIGN;
         }
         if (lane == 0) {
             logp_out[slot] = st ? -INFINITY : -(float)(-lp);      // the loss writes (float)(-logp)

@@ -17,6 +17,7 @@
 // kl_frame leaves through LDS so that a workgroup stores its 16 values as one run; kl_clip is a second, tiny kernel (one wave per clip) that
 // adds the clip's kl_frame values in ascending t from +0: a sum in that order cannot be spread over the frames' workgroups without atomics.
 #include "model_types.h"
+#include "ctc_lattice.h"                                // store_dlb_row
 
 static constexpr int KD_WAVES = 4;                      // waves of a workgroup
 static constexpr int KD_U = 4;                          // frames of a wave in flight together
@@ -97,12 +98,7 @@ __global__ __launch_bounds__(KD_WAVES * 64) void kd_grad_kernel(const float* log
         } else if (accumulate) gv = old[k];             // rows past the clip's end stay as they are
         else if (on) dlogits[at] = 0.f;
         if (lane == 0) s_kl[wv + KD_WAVES * k] = kl;
-        if (dlb) {      // bf16 copy of the final row, zero padded to 128 classes (MFMA operand of the classifier's dgrad / wgrad)
-            const float lo = __shfl(gv, (2 * lane) & 63, 64), hi = __shfl(gv, (2 * lane + 1) & 63, 64);
-            typedef __attribute__((ext_vector_type(2))) __bf16 kd_bf2;
-            kd_bf2 pk; pk[0] = (__bf16)(lane < 32 ? lo : 0.f); pk[1] = (__bf16)(lane < 32 ? hi : 0.f);
-            dlb[(row0 + t) * 64 + lane] = __builtin_bit_cast(uint32_t, pk);
-        }
+        if (dlb) store_dlb_row(dlb + (row0 + t) * 64, gv, lane);      // of the final row
     }
     if (kl_frame) {                                     // kernel-uniform
         __syncthreads();
@@ -140,11 +136,6 @@ int launch_kd_grad(const float* logits, const float* teacher, int B, int T, int 
     return launch_rc();
 }
 
-static bool kd_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 // the refusals the two entries share (me: the caller's name); 0 when the launch may go ahead (B == 0 passes and launches nothing)
 int kd_grad_check(const char* me, const float* logits, const float* teacher, int B, int T, int C, float inv_temp, int mode, const int* frame_len,
                   float grad_scale, const float* dlogits, int accumulate, const void* dlb, const float* kl_frame, const float* kl_clip) {
@@ -170,9 +161,9 @@ int kd_grad_check(const char* me, const float* logits, const float* teacher, int
     const Buf out[4] = {{"dlogits", dlogits, nin}, {"dlb", dlb, rows * 256}, {"kl_frame", kl_frame, rows * 4}, {"kl_clip", kl_clip, (size_t)B * 4}};
     for (const Buf& o : out) {
         for (const Buf& i : in)
-            if (kd_overlap(o.p, o.n, i.p, i.n)) { ishara_set_error("%s: %s overlaps %s", me, o.name, i.name); return -1; }
+            if (bytes_overlap(o.p, o.n, i.p, i.n)) { ishara_set_error("%s: %s overlaps %s", me, o.name, i.name); return -1; }
         for (const Buf& o2 : out)
-            if (&o2 != &o && kd_overlap(o.p, o.n, o2.p, o2.n)) { ishara_set_error("%s: %s overlaps %s", me, o.name, o2.name); return -1; }
+            if (&o2 != &o && bytes_overlap(o.p, o.n, o2.p, o2.n)) { ishara_set_error("%s: %s overlaps %s", me, o.name, o2.name); return -1; }
     }
     return 0;
 }

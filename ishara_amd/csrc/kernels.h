@@ -7,6 +7,11 @@
 enum DType : int { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };       // DT_F16: forward (inference) kernels only
 static inline size_t dt_size(int dt) { return dt == DT_F32 ? 4 : 2; }
 static inline bool dt_is16(int dt) { return dt != DT_F32; }
+// the byte ranges [a, a + na) and [b, b + nb) share a byte (the launchers' refusals); a NULL buffer overlaps nothing
+static inline bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
 
 // ---- operand transforms applied while staging a GEMM operand -------------------
 enum : int { OP_NONE = 0, OP_SWISH = 1, OP_COLAFFINE = 2, OP_ROWSCALE = 3, OP_DROPMASK = 4 };

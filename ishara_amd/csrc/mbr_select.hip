@@ -6,7 +6,7 @@
 //   1. stage    wave w takes the hypotheses w, w + MB_WAVES, ...: lane k loads symbol k (k < min(len, T, 64), nothing else is read), checks it
 //               against [0, C), stores it as a byte and, by one ballot per class, builds the match masks peq[n][c] (bit k: symbol k is c).
 //   2. pairs    the N (N - 1) / 2 pairs i < j are spread over the lanes (the strict upper triangle folded into N / 2 rows of N, so that no
-//               lane idles on the lower half): Hyyro's bit-vector form of Myers' algorithm, pattern i in one 64-bit word, len_j steps of
+//               lane idles on the lower half): edit_distance.h's myers (Hyyro's bit-vector form), pattern i in one 64-bit word, len_j steps of
 //               integer operations, global (not substring) distance.  d goes to LDS as a byte, both halves.
 //   3. votes    wave 0, lane = slot: the maximum over the finite scores by the xor butterfly (a maximum does not depend on its tree),
 //               x = (s - max) * inv_temp in two roundings, expf.
@@ -16,33 +16,11 @@
 // LDS: peq 64 x 64 x 8 = 32 KB, symbols and distances 4 KB each as bytes, under 41 KB in all (static; three clips per CU).  A clip with a
 // hypothesis longer than 64 symbols or a symbol outside [0, C) is not ranked (status, contract); such a symbol never becomes an index.
 // Integer distances, fixed summation order, no atomics: bit-identical from run to run.
-#include "kernels.h"
+#include "edit_distance.h"
 
 static constexpr int MB_WAVES = 4;
 static constexpr int MB_MAXN = 64;
 static constexpr int MB_MAXL = 64;                      // MAX_PHRASE_LENGTH: one 64-bit word per pattern
-
-// unit-cost Levenshtein distance of pattern (match masks peq, m symbols, 1 <= m <= 64) and text (n bytes), Hyyro 2001 fig. 3 with the
-// horizontal delta of the first row set (the `| 1`): the global distance, not the best substring match
-DEVI int mb_myers(const uint64_t* __restrict__ peq, int m, const uint8_t* __restrict__ text, int n) {
-    uint64_t pv = ~0ull, mv = 0ull;
-    const uint64_t top = 1ull << (m - 1);
-    int score = m;
-    for (int k = 0; k < n; ++k) {
-        const uint64_t eq = peq[text[k]];
-        const uint64_t xv = eq | mv;
-        const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
-        uint64_t ph = mv | ~(xh | pv);
-        uint64_t mh = pv & xh;
-        score += (ph & top) ? 1 : 0;
-        score -= (mh & top) ? 1 : 0;
-        ph = (ph << 1) | 1ull;
-        mh <<= 1;
-        pv = mh | ~(xv | ph);
-        mv = ph & xv;
-    }
-    return score;
-}
 
 // r + w * c, c = d or d / max(len_j, 1): the division, the multiplication and the addition each rounded on its own.  hipcc contracts
 // a * b + c into an FMA by default, and __fmul_rn / __fadd_rn are plain operators in its headers that carry the same permission into the
@@ -110,7 +88,9 @@ __global__ __launch_bounds__(MB_WAVES * 64) void mbr_select_kernel(const int* __
             else { i = N - 2 - r; j = i + 1 + (c - (N - 1 - r)); if (i == r) continue; }      // the middle row of an odd triangle folds onto itself
             const int li = s_len[i], lj = s_len[j];
             if (li < 0 || lj < 0) continue;
-            const int d = li == 0 ? lj : mb_myers(s_peq[i], li, s_sym[j], lj);
+            const uint64_t* peq = s_peq[i];
+            const uint8_t* text = s_sym[j];             // bytes < C <= 64: every symbol has its row of the table
+            const int d = myers(li, [&](int k) { return peq[text[k]]; }, lj);
             s_dist[i][j] = (uint8_t)d;
             s_dist[j][i] = (uint8_t)d;
         }
@@ -192,8 +172,7 @@ extern "C" int ishara_mbr_select(const int32_t* hyp_idx, const int32_t* hyp_len,
     const uintptr_t bits = (uintptr_t)hyp_idx | (uintptr_t)hyp_len | (uintptr_t)hyp_score | (uintptr_t)weights | (uintptr_t)inv_temp | (uintptr_t)out_idx |
                            (uintptr_t)out_len | (uintptr_t)best | (uintptr_t)risk | (uintptr_t)w_out | (uintptr_t)dist | (uintptr_t)status;
     if (bits % 4) { ishara_set_error("%s: misaligned buffer: every buffer must be 4-byte aligned", me); return -1; }
-    const uintptr_t i0 = (uintptr_t)hyp_idx, ib = (uintptr_t)B * N * T * 4, o0 = (uintptr_t)out_idx, ob = (uintptr_t)B * T * 4;
-    if (o0 < i0 + ib && i0 < o0 + ob) { ishara_set_error("%s: out_idx overlaps hyp_idx", me); return -1; }
+    if (bytes_overlap(out_idx, (size_t)B * T * 4, hyp_idx, (size_t)B * N * T * 4)) { ishara_set_error("%s: out_idx overlaps hyp_idx", me); return -1; }
     hipLaunchKernelGGL(mbr_select_kernel, dim3((unsigned)B), dim3(MB_WAVES * 64), 0, (hipStream_t)st, hyp_idx, hyp_len, hyp_score, weights, inv_temp,
                        N, T, C, mode, out_idx, out_len, best, risk, w_out, dist, status);
     return launch_rc();

@@ -2,41 +2,11 @@
 // ishara_amd/mwer.py): every slot's edit distance to the target, the posterior of the list renormalised over its live slots, the expected
 // distance (the risk) and coef[b, n] = d risk / d nll_n, which ishara_ctc_nbest_grad takes as it is.
 //
-// One wave per clip, lane = slot.  The distance is rescore_sweep.hip's: Hyyro's bit-vector form of Myers' algorithm, one 64-bit word, the
+// One wave per clip, lane = slot.  The distance is edit_distance.h's myers: Hyyro's bit-vector form of Myers' algorithm, one 64-bit word, the
 // TARGET as the pattern (<= 64 symbols), the hypothesis as the text; the match masks peq[c] by one ballot per class.  No fallback phrase.
 // The sums run over the slots in ascending order from +0 in every lane, each step one fp32 operation without FMA contraction.
 // Duplicate strings are not merged: the prefix beam search emits distinct prefixes.  No workspace, no atomics, graph-capturable.
-#include "kernels.h"
-
-static constexpr int MW_PAD = 59;                       // PAD_TOKEN_IDX: the targets' padding
-
-DEVI uint64_t mw_eq(const uint64_t* __restrict__ peq, const int* __restrict__ tgt, int m, int c) {
-    if (c >= 0 && c < 64) return peq[c];
-    uint64_t e = 0;
-    for (int j = 0; j < m; ++j) e |= (uint64_t)(tgt[j] == c) << j;
-    return e;
-}
-// unit-cost Levenshtein distance of the target (pattern, m symbols, 0 <= m <= 64) and text[0..n): rescore_sweep.hip's rs_myers
-DEVI int mw_myers(const uint64_t* __restrict__ peq, const int* __restrict__ tgt, int m, const int* __restrict__ text, int n) {
-    if (m == 0) return n;
-    uint64_t pv = ~0ull, mv = 0ull;
-    const uint64_t top = 1ull << (m - 1);
-    int score = m;
-    for (int k = 0; k < n; ++k) {
-        const uint64_t eq = mw_eq(peq, tgt, m, text[k]);
-        const uint64_t xv = eq | mv;
-        const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
-        uint64_t ph = mv | ~(xh | pv);
-        uint64_t mh = pv & xh;
-        score += (ph & top) ? 1 : 0;
-        score -= (mh & top) ? 1 : 0;
-        ph = (ph << 1) | 1ull;
-        mh <<= 1;
-        pv = mh | ~(xv | ph);
-        mv = ph & xv;
-    }
-    return score;
-}
+#include "edit_distance.h"
 
 __global__ __launch_bounds__(64) void mwer_weights_kernel(const int* __restrict__ hyp_idx, const int* __restrict__ hyp_len, const float* __restrict__ logp,
                                                           const int* __restrict__ status, int N, int Th, const int* __restrict__ targets, int L,
@@ -49,16 +19,7 @@ __global__ __launch_bounds__(64) void mwer_weights_kernel(const int* __restrict_
     __shared__ int s_tgt[64];
     const int b = blockIdx.x, lane = threadIdx.x;
     // ---- the target: the symbols before the first 59, its match masks
-    const int bj = lane < L ? targets[(size_t)b * L + lane] : MW_PAD;
-    const unsigned long long pads = __ballot(bj == MW_PAD);
-    const int nb = pads ? (int)__builtin_ctzll(pads) : 64;
-    s_tgt[lane] = bj;
-    uint64_t mine = 0;
-    for (int c = 0; c < 64; ++c) {
-        const uint64_t m = __ballot(lane < nb && bj == c);
-        if (lane == c) mine = m;
-    }
-    s_peq[lane] = mine;
+    const int nb = target_prep(targets + (size_t)b * L, L, lane, s_tgt, s_peq);
     __syncthreads();
     // ---- the slot of this lane
     const size_t slot = (size_t)b * N + (lane < N ? lane : 0);
@@ -67,7 +28,8 @@ __global__ __launch_bounds__(64) void mwer_weights_kernel(const int* __restrict_
     const float lp = lane < N ? logp[slot] : 0.f;
     const int stv = (lane < N && status) ? status[slot] : 0;
     const bool live = lane < N && len >= 0 && stv == 0 && fabsf(lp) < INFINITY;       // a NaN compares false
-    const int d = live ? mw_myers(s_peq, s_tgt, nb, hyp_idx + slot * Th, len) : -1;
+    const int* text = hyp_idx + slot * Th;
+    const int d = live ? myers(nb, [&](int k) { return match_mask(s_peq, s_tgt, nb, text[k]); }, len) : -1;
     const float it = inv_temp ? inv_temp[0] : 1.f;
     float W = (float)d;
     if (mode == 1) W = W / (float)(nb > 1 ? nb : 1);

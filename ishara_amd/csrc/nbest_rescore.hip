@@ -171,10 +171,10 @@ static int nr_run(const char* me, const int32_t* hyp_idx, const int32_t* hyp_len
     const size_t osz[5] = {bnt, bn, bn, bn, bn};
     const char* onm[5] = {"out_idx", "out_len", "out_score", "posterior", "perm"};
     for (int o = 0; o < 5; ++o) {
-        if (nr_overlap(outs[o], osz[o], hyp_idx, bnt)) { ishara_set_error("%s: %s overlaps hyp_idx", me, onm[o]); return -1; }
-        if (nr_overlap(outs[o], osz[o], hyp_len, bn)) { ishara_set_error("%s: %s overlaps hyp_len", me, onm[o]); return -1; }
+        if (bytes_overlap(outs[o], osz[o], hyp_idx, bnt)) { ishara_set_error("%s: %s overlaps hyp_idx", me, onm[o]); return -1; }
+        if (bytes_overlap(outs[o], osz[o], hyp_len, bn)) { ishara_set_error("%s: %s overlaps hyp_len", me, onm[o]); return -1; }
         for (int m = 0; m < M; ++m)
-            if (nr_overlap(outs[o], osz[o], logp[m], bn)) { ishara_set_error("%s: %s overlaps logp[%d]", me, onm[o], m); return -1; }
+            if (bytes_overlap(outs[o], osz[o], logp[m], bn)) { ishara_set_error("%s: %s overlaps logp[%d]", me, onm[o], m); return -1; }
     }
     NrPtrs in;
     for (int m = 0; m < NR_MAX_M; ++m) in.p[m] = m < M ? logp[m] : nullptr;

@@ -20,21 +20,17 @@
 // every row is taken exactly once, so D = nb - diagonals and I = na - diagonals.  Confusions go to a per-workgroup LDS histogram in vector
 // steps (the diagonal / deletion entries of a clip at its end, the insertions of a chunk when the walk leaves it) and only its non-zero
 // entries are added to the matrix: integer atomics, deterministic.
-#include "kernels.h"
+#include "edit_distance.h"
 
-#define SA_PAD 59                  // PAD_TOKEN_IDX: the targets' padding, and the matrix's "nothing" row / column
-#define SA_NSYM 60
-#define SA_FALLBACK_LEN 11
+#define SA_NSYM 60                 // the matrix's side: the symbols 0..58 and PAD_TOKEN, its "nothing" row / column
 #define SA_WAVES 4
-// the constant prediction the wrapper returns for a decode shorter than 3 (score.hip sc_fallback; ishara_amd/tflite_model.py FALLBACK_PHRASE)
-static __device__ __constant__ int sa_fallback[SA_FALLBACK_LEN] = {17, 0, 32, 12, 36, 0, 12, 32, 49, 46, 36};
 
 // mask rows per clip: the fallback phrase may be longer than T
-__host__ __device__ static inline int sa_rows(int T) { return T > SA_FALLBACK_LEN ? T : SA_FALLBACK_LEN; }
+__host__ __device__ static inline int sa_rows(int T) { return T > FALLBACK_LEN ? T : FALLBACK_LEN; }
 size_t edit_alignment_workspace_bytes(int B, int T) { return (size_t)B * sa_rows(T) * 16; }
 
 // a symbol as a matrix index: anything outside 0..58 is "nothing"
-__device__ __forceinline__ int sa_col(int s) { return (unsigned)s < (unsigned)SA_PAD ? s : SA_PAD; }
+__device__ __forceinline__ int sa_col(int s) { return (unsigned)s < (unsigned)PAD_TOKEN ? s : PAD_TOKEN; }
 
 // the number of consecutive set bits of x from bit p downwards (bit p is set): 1 .. p + 1
 __device__ __forceinline__ int sa_run(unsigned long long x, int p) {
@@ -47,13 +43,12 @@ __device__ __forceinline__ void sa_align_clip(const int* __restrict__ out_idx, c
                                               int L, int b, int lane, int fallback, int* __restrict__ ops, int* __restrict__ aligned,
                                               int* __restrict__ inserted, int* hist, bool want, ulonglong2* ws) {
     const int j = lane + 1;
-    const int bj = lane < L ? targets[(size_t)b * L + lane] : SA_PAD;
-    const unsigned long long pads = __ballot(bj == SA_PAD);
-    const int nb = __builtin_amdgcn_readfirstlane(pads ? (int)__builtin_ctzll(pads) : 64);
+    const int bj = lane < L ? targets[(size_t)b * L + lane] : PAD_TOKEN;
+    const int nb = __builtin_amdgcn_readfirstlane(target_length(bj));
     int na = out_len[b];
     na = na < 0 ? 0 : (na > Tn ? Tn : na);
     const bool fb = fallback != 0 && na < 3;
-    if (fb) na = SA_FALLBACK_LEN;
+    if (fb) na = FALLBACK_LEN;
     na = __builtin_amdgcn_readfirstlane(na);
     const int* a = out_idx + (size_t)b * Tn;
     ulonglong2* rows = ws + (size_t)b * sa_rows(Tn);       // row i of the table at rows[i - 1], i <= na <= sa_rows(Tn)
@@ -64,7 +59,7 @@ __device__ __forceinline__ void sa_align_clip(const int* __restrict__ out_idx, c
     unsigned long long um = 0, lm = 0;
     for (int i0 = 0; i0 < na; i0 += WAVE) {
         const int r_end = na - i0 < WAVE ? na - i0 : WAVE;
-        a_lane = lane < r_end ? (fb ? sa_fallback[i0 + lane] : a[i0 + lane]) : -1;
+        a_lane = lane < r_end ? (fb ? fallback_phrase[i0 + lane] : a[i0 + lane]) : -1;
         um = 0; lm = 0;
         for (int r = 0; r < r_end; ++r) {
             const int i = i0 + r + 1;
@@ -96,11 +91,11 @@ __device__ __forceinline__ void sa_align_clip(const int* __restrict__ out_idx, c
     int ali = 0;                                           // lane l: the row whose diagonal move took target position l + 1; 0: none, it was deleted
     int ins = 0, ins_row = 0, trail = 0;                   // lane l: inserted[l]; this lane's row of the chunk was an insertion; slot nb
     auto enter_chunk = [&](int c) {                        // c < the last chunk: all of its 64 rows exist
-        if (want && ins_row) atomicAdd(&hist[SA_PAD * SA_NSYM + sa_col(a_lane)], 1);
+        if (want && ins_row) atomicAdd(&hist[PAD_TOKEN * SA_NSYM + sa_col(a_lane)], 1);
         ins_row = 0;
         const ulonglong2 m = rows[c * WAVE + lane];
         um = m.x; lm = m.y;
-        a_lane = fb ? sa_fallback[c * WAVE + lane] : a[c * WAVE + lane];
+        a_lane = fb ? fallback_phrase[c * WAVE + lane] : a[c * WAVE + lane];
         chunk = c;
     };
     while (i > 0 && jj > 0) {
@@ -146,12 +141,12 @@ __device__ __forceinline__ void sa_align_clip(const int* __restrict__ out_idx, c
     const bool mine = lane < nb;
     const bool hit = mine && ali > 0;
     int sym = -1;
-    if (hit) sym = fb ? sa_fallback[ali - 1] : a[ali - 1];             // ali <= na
+    if (hit) sym = fb ? fallback_phrase[ali - 1] : a[ali - 1];             // ali <= na
     const int n_diag = (int)__popcll(__ballot(hit)), n_match = (int)__popcll(__ballot(hit && sym == bj));
     const int n_del = nb - n_diag, n_ins = na - n_diag;                // every target position and every row is taken exactly once
     if (want) {
-        if (ins_row) atomicAdd(&hist[SA_PAD * SA_NSYM + sa_col(a_lane)], 1);
-        if (mine) atomicAdd(&hist[sa_col(bj) * SA_NSYM + (hit ? sa_col(sym) : SA_PAD)], 1);
+        if (ins_row) atomicAdd(&hist[PAD_TOKEN * SA_NSYM + sa_col(a_lane)], 1);
+        if (mine) atomicAdd(&hist[sa_col(bj) * SA_NSYM + (hit ? sa_col(sym) : PAD_TOKEN)], 1);
     }
     if (lane < 4) ops[(size_t)b * 4 + lane] = lane == 0 ? n_match : (lane == 1 ? n_diag - n_match : (lane == 2 ? n_del : n_ins));
     if (lane < L) aligned[(size_t)b * L + lane] = mine ? (hit ? sym : -1) : -2;

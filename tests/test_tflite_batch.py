@@ -89,11 +89,17 @@ def test_fallback_rule_and_one_hot():
 
 
 def test_fallback_constant_in_kernel_equals_wrapper():
-    src = open(os.path.join(ROOT, "ishara_amd", "csrc", "score.hip")).read()
-    m = re.search(r"__constant__ int sc_fallback\[SC_FALLBACK_LEN\] = \{([^}]*)\}", src)
-    assert m, "score.hip: sc_fallback not found"
+    csrc = os.path.join(ROOT, "ishara_amd", "csrc")
+    src = open(os.path.join(csrc, "edit_distance.h")).read()
+    m = re.search(r"__constant__ int fallback_phrase\[FALLBACK_LEN\] = \{([^}]*)\}", src)
+    assert m, "edit_distance.h: fallback_phrase not found"
     assert [int(v) for v in m.group(1).split(",")] == FALLBACK_PHRASE.tolist()
-    assert int(re.search(r"#define SC_FALLBACK_LEN (\d+)", src).group(1)) == len(FALLBACK_PHRASE)
+    assert int(re.search(r"constexpr int FALLBACK_LEN = (\d+);", src).group(1)) == len(FALLBACK_PHRASE)
+    # every kernel takes the phrase from that header: no .hip file keeps an array of its own
+    hips = [f for f in sorted(os.listdir(csrc)) if f.endswith(".hip")]
+    assert hips
+    for f in hips:
+        assert not re.search(r"\{\s*17\s*,\s*0\s*,\s*32\s*,", open(os.path.join(csrc, f)).read()), f"{f}: a fallback phrase of its own"
 
 
 def test_normalized_scores_equal_host_mean_score():
